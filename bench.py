@@ -302,6 +302,26 @@ def launch_plan(first, count, per_launch, gather_every):
     return plan
 
 
+DUMP_FULL_MAX_BYTES = 48 << 20     # --dump-outputs: larger images are sampled (the dump stays under 64 MB)
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, accum, c):
+    """--dump-outputs: the accumulated image of the timed run and its counters as float32 / float64 .npy files.  An image
+    above DUMP_FULL_MAX_BYTES is reduced to DUMP_SAMPLE_PIXELS pixels drawn by a fixed seed (accum_index.npy holds their
+    flat pixel indices), so two builds of the same command dump the same pixels."""
+    os.makedirs(out_dir, exist_ok=True)
+    accum = np.ascontiguousarray(accum, dtype=np.float32)
+    if accum.nbytes > DUMP_FULL_MAX_BYTES:
+        h, w, ch = accum.shape
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=DUMP_SAMPLE_PIXELS, replace=False))
+        np.save(os.path.join(out_dir, "accum_index.npy"), idx.astype(np.float64))
+        accum = accum.reshape(h * w, ch)[idx]
+    np.save(os.path.join(out_dir, "accum.npy"), accum)
+    np.save(os.path.join(out_dir, "counters.npy"),
+            np.array([c.samples, c.tf_samples, c.frames, c.pixels], dtype=np.float64))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher around it: start the N ranks the way the driver does
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`)
@@ -369,6 +389,10 @@ def main():
                          "gathered image (config.image_sha256: equal to a 1-rank --force-gather run of the same frames)")
     ap.add_argument("--no-balance", action="store_true",
                     help="N>1: keep the default round-robin dealing of the 64x64 tiles instead of the cost-balanced order")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (rank 0): accum.npy = the "
+                         "accumulated RGBA32F image (a fixed seeded sample of its pixels when the image exceeds 48 MB, "
+                         "with accum_index.npy), counters.npy = rank 0's samples, tf_samples, frames, pixels of the timed run")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -575,6 +599,12 @@ def main():
         if rank == 0 and (rehearse or a.force_gather):
             import hashlib
             image_sha = hashlib.sha256(image.cpu().numpy().tobytes()).hexdigest()
+
+    if rank == 0 and a.dump_outputs:
+        # before the side measurements below render more frames into the accumulator
+        # N > 1 (or --force-gather): the de-tiled image of the last gather, which the timed run ends with (need_image)
+        accum = image.cpu().numpy().reshape(a.height, a.width, 4) if use_dist else r.read_accum()
+        dump_outputs(a.dump_outputs, accum, c)
 
     if rank == 0:
         name, cus, mem = r.device_info()

@@ -70,3 +70,30 @@ def test_world_size_must_match_gpus():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"], env=env, capture_output=True,
                        text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE=1" in p.stderr and p.stdout.strip() == ""
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: a 1080p image goes out whole; a 4K image as a fixed pixel sample (the same pixels on every run),
+    float32 / float64 only and under 64 MB in all"""
+    import types
+
+    import numpy as np
+    b = _bench()
+    c = types.SimpleNamespace(samples=123456789, tf_samples=4567, frames=96, pixels=96 * 1920 * 1080)
+    small = np.random.default_rng(1).random((1080, 1920, 4), dtype=np.float32)
+    b.dump_outputs(str(tmp_path / "a"), small, c)
+    assert np.array_equal(np.load(tmp_path / "a" / "accum.npy"), small)
+    assert not (tmp_path / "a" / "accum_index.npy").exists()
+    assert np.load(tmp_path / "a" / "counters.npy").tolist() == [123456789, 4567, 96, 96 * 1920 * 1080]
+
+    big = np.random.default_rng(2).random((2160, 3840, 4), dtype=np.float32)
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), big, c)
+    files = sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert files == ["accum.npy", "accum_index.npy", "counters.npy"]
+    for name in files:
+        x, y = np.load(tmp_path / "b" / name), np.load(tmp_path / "c" / name)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y)
+    idx = np.load(tmp_path / "b" / "accum_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "accum.npy"), big.reshape(-1, 4)[idx])
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) < 64 << 20

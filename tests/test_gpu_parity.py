@@ -1530,3 +1530,33 @@ def test_bench_two_ranks_rehearsal_gathers_the_one_rank_image():
     assert two["config"]["frames_per_launch"] == 64 and one["config"]["frames_per_launch"] == 32
     assert two["config"]["gathers"] >= 2 and "image-tiles x2" in two["config"]["parallelism"]
     assert two["cpu_baseline"] is None and two["scaling"] == "strong"
+
+
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """`bench.py --dump-outputs DIR` on a small scene, twice with the same arguments: exactly --steps timed steps, a
+    ms_per_step in the line, and the dumped image and counters of the timed run identical from run to run (the inputs
+    are seeded); the image is the accumulated mean of the warm-up and timed frames, finite and not blank."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--frames-per-step", "8", "--volume", "64", "--width", "320",
+            "--height", "192", "--no-cpu-baseline", "--no-mode-variants", "--no-skip-variant", "--no-side-measurements"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *args, "--dump-outputs", str(out)], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-500:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["config"]["frames_timed"] == 24 and line["ms_per_step"] > 0
+        dumps.append({f.name: np.load(f) for f in out.iterdir()})
+    assert sorted(dumps[0]) == ["accum.npy", "counters.npy"]
+    img, cnt = dumps[0]["accum.npy"], dumps[0]["counters.npy"]
+    assert img.shape == (192, 320, 4) and img.dtype == np.float32 and np.isfinite(img).all() and img.max() > 0
+    assert cnt[2] == 24 and cnt[0] > 0                       # the counters cover the 24 timed frames
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name
