@@ -162,6 +162,8 @@ typedef struct VxCounters {
   uint64_t active_lane_slots; /* of lane_slots, the slots whose lane did work -- counted by the event-batched path
                             kernels (default / no_dda), whose lanes may wait for an event pass; 0 elsewhere
                             (for the DVR kernels samples / lane_slots is the lane utilisation)          */
+  uint64_t merge_launches; /* running-mean blend kernels (merge_results) launched: one per multi-frame launch
+                            whose render kernel did not fold the running mean itself                        */
 } VxCounters;
 
 typedef struct VxContext VxContext;

@@ -550,11 +550,7 @@ def test_empty_space_skipping_is_exact(oracle, layout):
         assert np.abs(img - want).max() <= 2e-6
         assert c.samples == oc.samples
         imgs.append(img); counts.append(c.samples)
-    if os.environ.get("VX_DVR_DP") == "1" and layout == 1:
-        # the depth-parallel experiment re-associates the colour sum when a jump regroups the steps
-        assert np.abs(imgs[0] - imgs[1]).max() <= 5e-7
-    else:
-        assert np.array_equal(imgs[0], imgs[1])
+    assert np.array_equal(imgs[0], imgs[1])
     assert counts[0] < counts[1]
 
 
@@ -885,7 +881,7 @@ def test_counters_report_the_launches_that_ran(oracle):
     r.render(frames=20, rebind=False, in_flight=64); r.finish()
     c = r.counters()
     assert (c.launches, c.frames, c.min_launch_frames, c.max_launch_frames) == (1, 20, 20, 20)
-    assert c.merge_ms > 0 and c.kernel_ms > 0
+    assert c.merge_ms > 0 and c.kernel_ms > 0 and c.merge_launches == 1
     # 2 gathers per march step, issued in batches of 4 steps: between 2 per wave step and that plus one batch per wave
     steps = c.lane_slots // 64
     waves = 20 * (192 // 8) * (128 // 8)
@@ -1345,14 +1341,22 @@ def test_running_mean_in_the_render_kernel_is_bit_identical(oracle, monkeypatch,
         r.render(frames=2)                                  # the two frames that build the launch order
         r.render(frames=64 + 64 + 7, in_flight=fpl)         # frames 2 .. 136: launches with zero weights, without, and a partial one
         c = r.counters()
-        res[key] = (r.read_accum(), c.samples, c.tf_samples, c.merge_ms, c.max_launch_frames)
+        res[key] = (r.read_accum(), c.samples, c.tf_samples, c.merge_ms, c.max_launch_frames, c.merge_launches)
         r.close()
-    assert res["merge32"][3] > 0.0 and res["merge32"][4] == 32          # the blend kernel ran there ...
+    assert res["merge32"][3] > 0.0 and res["merge32"][4] == 32
     assert res["fused64"][4] == 64
     for key in ("merge32", "fused32", "fused64", "fused8", "fused16"):
         assert np.array_equal(res[key][0], res["serial"][0]) and res[key][1:3] == res["serial"][1:3], key
-    # ... and only for the partial launch here (7 frames): a fraction of the time
-    assert 0.0 < res["fused32"][3] < 0.5 * res["merge32"][3]
+    # blend kernels launched (VxCounters.merge_launches).  The 135 frames go as 4x32+7, 2x64+7, 16x8+7 or 8x16+7 frames per
+    # launch; in_flight=1 renders them frame by frame, without a blend.  DVR / Phong: both preamble frames go one by one (they
+    # build the launch order) and every full launch folds, so only the 7-frame launch blends.  The reference's modes fold
+    # only launches of exactly 32 frames, and the second frame of their preamble (in_flight=32 in every run) is already a
+    # 1-frame multi-frame launch: one blend more in every run, `serial` included.
+    if mode in ("dvr", "dvr_phong"):
+        want = {"serial": 0, "merge32": 5, "fused32": 1, "fused64": 1, "fused8": 1, "fused16": 1}
+    else:
+        want = {"serial": 1, "merge32": 6, "fused32": 2, "fused64": 4, "fused8": 18, "fused16": 10}
+    assert {key: res[key][5] for key in want} == want
 
 
 def test_shared_window_kernel_is_bit_identical(oracle, monkeypatch):

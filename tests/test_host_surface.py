@@ -191,3 +191,16 @@ console.log(JSON.stringify(out));
     assert out["unsynced"] == [1, 0, 0]
     p = np.asarray(out["pos"])
     assert np.allclose(out["synced"], p / np.linalg.norm(p), atol=1e-15)
+
+
+def test_merge_launches_is_the_last_counter():
+    """VxCounters.merge_launches (the running-mean blend kernels launched) is the struct's last field as _abi parses it from
+    include/volxel_hip.h -- every earlier field keeps its offset -- and the JavaScript host reports it as mergeLaunches"""
+    import ctypes
+    from volxel_amd import _abi
+    fields = _abi.VxCounters._fields_
+    assert [f[0] for f in fields[-2:]] == ["active_lane_slots", "merge_launches"]
+    assert fields[-1][1] is ctypes.c_uint64
+    assert _abi.VxCounters.merge_launches.offset + 8 == ctypes.sizeof(_abi.VxCounters)
+    assert 'PUT("mergeLaunches", k.merge_launches)' in open(os.path.join(NAPI, "volxel_napi.c")).read()
+    assert "mergeLaunches: number" in open(os.path.join(NAPI, "index.d.ts")).read()

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -25,8 +26,21 @@ thread_local std::string g_create_error;
 
 struct EventPair {
   hipEvent_t a, b;
-  uint32_t launches = 1;   // frames covered by this interval (pipelined batches cover several)
   bool merge = false;      // interval of a merge_results launch (reported apart, VxCounters.merge_ms)
+};
+
+// The diagnostic switches of the environment, read once by vx_create (none changes a result bit).
+struct Switches {
+  int dvr_variant = -1;            // VX_DVR_KERNEL=generic: 0, the DVR modes on render_generic; -1: the tuned kernels
+  int paths_variant = 0;           // VX_PATHS_KERNEL: 0 / 2 (generic): one pixel per lane (render_generic); 1 (packed): path
+                                   // segments re-packed through LDS (vx_paths.hpp) -- same bits, measured 3-11 % slower; 3 (events):
+                                   // wave-persistent, event-batched (vx_events.hpp) -- same bits, denser lanes, measured 1.4-1.8x slower
+  bool dvr_fuse = true;            // VX_DVR_FUSE=0: no kernel folds the running mean; merge_results blends every multi-frame launch
+  bool dvr_shared_window = false;  // VX_DVR_WG=1: one LDS window per workgroup in launches of a multiple of 32 frames (vx_dvr_lds.hpp, WG)
+  bool use_order = true;           // VX_DVR_ORDER=0: the tuned DVR kernels run their blocks in launch order
+  bool ray_shortcuts = true;       // VX_RAY_SHORTCUTS=0: the per-ray divisions themselves (DevVolume::ray_flags = 0)
+  std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
+  int dvr_unroll = 4;              // VX_DVR_UNROLL=1|2|4: march steps per loop iteration of the cellquad DVR kernel
 };
 
 }  // namespace
@@ -47,7 +61,7 @@ struct VxContext {
   void* bu_alloc = nullptr;    // bricku8 codes (+ one zero unit)
   void* bur_alloc = nullptr;   // bricku8 per-brick {min, max - min} (+ the {0, 0} entry of the zero unit)
   int layout = VX_LAYOUT_AUTO;       // what the host asked for (vx_set_layout); eff_layout() is what a launch samples
-  bool auto_no_cq = false;           // AUTO: the volume is too large for the cellquad layout (path modes use REFERENCE)
+  bool auto_no_cq = false;           // AUTO: no cellquad layout (index range or memory budget): `default` / `no_dda` take primary_layout
   bool auto_no_bf = false;           // AUTO: too large for brickf32 as well (everything uses REFERENCE)
 
   // transfer function
@@ -93,16 +107,14 @@ struct VxContext {
   DevCounters* dc = nullptr;   // one record per wave of the largest launch grid
   size_t dc_waves = 0;
   uint32_t* order = nullptr;   // launch permutation of the DVR kernel (build_order), dc_waves/4 entries
-  bool use_order = true;
   int tex_checked_res[2] = {-1, -1};  // DevVolume::ray_flags: the resolution (pixel + 0.5) / res was last tried against its reciprocal form
   bool tex_by_reciprocal[2] = {false, false};
-  bool dvr_fuse = true;              // VX_DVR_FUSE=0: multi-frame DVR launches write per-frame results and merge_results blends them
-  bool dvr_shared_window = false;    // VX_DVR_WG=1: one LDS window per workgroup in launches of a multiple of 32 frames (vx_dvr_lds.hpp, WG)
+  Switches sw;
   int order_builds_left = 2;   // rebuild the order after the first frames that follow a change
   VxCounters base{};           // totals folded in when the record array is reallocated
   std::vector<EventPair> free_events, pending_events;
   double kernel_ms = 0.0, last_kernel_ms = 0.0, merge_ms = 0.0;
-  uint64_t launches = 0, frames = 0;
+  uint64_t launches = 0, frames = 0, merge_launches = 0;
   uint32_t min_launch_frames = 0, max_launch_frames = 0;   // what the launches since the last reset covered
   hipStream_t aux_stream = nullptr;   // layout builds of an upload, overlapped with the atlas copy
   double upload_seconds = 0.0;        // wall time of the last vx_upload_volume (copies + layout build)
@@ -114,31 +126,12 @@ struct VxContext {
     min_launch_frames = (min_launch_frames == 0 || n < min_launch_frames) ? n : min_launch_frames;
     max_launch_frames = n > max_launch_frames ? n : max_launch_frames;
   }
-  int dvr_variant = -1;  // -1: tuned kernel; 0: generic
-  int paths_variant = 0;   // 0 / 2: one pixel per lane (render_generic); 1: path segments re-packed through LDS
-                           // (vx_paths.hpp, VX_PATHS_KERNEL=packed) -- same bits, measured 3-11 % slower; 3: the
-                           // wave-persistent event-batched form (vx_events.hpp, VX_PATHS_KERNEL=events) -- same
-                           // bits, denser lanes, measured 1.4-1.8x slower
-
-  // frame pipelining (vx_render_frames): independent accumulation frames in flight on their own
-  // streams, each into its own result slab + counter records; blended in order afterwards
-  struct Pipe {
-    hipStream_t stream = nullptr;
-    float4* result = nullptr;
-    DevCounters* dc = nullptr;
-    hipEvent_t done = nullptr;
-    hipEvent_t merged = nullptr;  // recorded on the main stream after this slot's result was blended
-    bool has_merged = false;
-  };
-  std::vector<Pipe> pipes;
-  // the result slabs and counter records of all slots are ONE allocation each (slot i at i * pipe_quads /
-  // i * pipe_waves): the event kernel addresses a frame slot by base + stride instead of by a pointer table
+  // per-frame result slabs and counter records of multi-frame launches (vx_render_frames), pipe_slots of each in ONE
+  // allocation (slot i at i * pipe_quads / i * pipe_waves): the event kernel addresses a frame slot by base + stride
   float4* pipe_result_pool = nullptr;
   DevCounters* pipe_dc_pool = nullptr;
   size_t pipe_quads = 0, pipe_waves = 0;
-  uint32_t pipe_next = 0;
-  int dp_env = -1;       // VX_DVR_DP=1: depth-parallel waves (experiment, see vx_dvr.hpp)
-  bool dp_active() const { return dp_env == 1; }
+  uint32_t pipe_slots = 0;
 };
 
 #define VX_FAIL(ctx, code, ...)                       \
@@ -187,7 +180,7 @@ static void drain_events(VxContext* c) {
         c->merge_ms += ms;
       } else {
         c->kernel_ms += ms;
-        c->last_kernel_ms = ms / (float)(e.launches ? e.launches : 1u);
+        c->last_kernel_ms = ms;
       }
     }
     e.merge = false;
@@ -383,7 +376,7 @@ static int rebuild_skip_mask(VxContext* c) {
 }
 
 
-// fold every record array (accumulator slot and pipeline slots) into c->base on the device and zero it
+// fold every record array (accumulator slot and the multi-frame slots) into c->base on the device and zero it
 static int fold_counters(VxContext* c) {
   if (!c->dc || !c->dc_waves) return VX_OK;
   if (!c->fold_dev) VX_HIP(c, hipMalloc(&c->fold_dev, 10 * sizeof(unsigned long long)));
@@ -393,11 +386,7 @@ static int fold_counters(VxContext* c) {
     hipLaunchKernelGGL(fold_records, dim3(blocks), dim3(256), 0, c->stream, recs, n, c->fold_dev);
   };
   fold(c->dc, c->dc_waves);
-  for (auto& p : c->pipes) {
-    if (!p.dc) continue;
-    if (p.stream) VX_HIP(c, hipStreamSynchronize(p.stream));
-    fold(p.dc, c->pipe_waves);
-  }
+  if (c->pipe_dc_pool) fold(c->pipe_dc_pool, c->pipe_slots * c->pipe_waves);
   VX_HIP(c, hipGetLastError());
   VX_HIP(c, hipStreamSynchronize(c->stream));
   unsigned long long h[10];
@@ -462,101 +451,155 @@ static int eff_layout(const VxContext* c) {
   return c->auto_no_cq ? primary_layout(c) : VX_LAYOUT_CELLQUAD;
 }
 
-template <int MODE>
-static void launch_generic(VxContext* c, const MultiOut& mo, float weight, dim3 grid, size_t lds, hipStream_t stream) {
-  grid.x *= mo.count ? mo.count : 1u;
-  const int lay = eff_layout(c);
-  if (lay == VX_LAYOUT_BRICKF32)
-    hipLaunchKernelGGL((render_generic<MODE, LAYOUT_BF>), grid, dim3(256), lds, stream, c->params,
-                       c->dv, c->tf, c->tf_len, mo, weight, c->tm);
-  else if (lay == VX_LAYOUT_CELLQUAD)
-    hipLaunchKernelGGL((render_generic<MODE, LAYOUT_CQ>), grid, dim3(256), lds, stream, c->params,
-                       c->dv, c->tf, c->tf_len, mo, weight, c->tm);
-  else
-    hipLaunchKernelGGL((render_generic<MODE, LAYOUT_REF>), grid, dim3(256), lds, stream, c->params,
-                       c->dv, c->tf, c->tf_len, mo, weight, c->tm);
+// calls f(std::integral_constant<int, LAYOUT_*>) for the device layout `lay` (the path kernels and the tile-cost probe
+// sample brickf32, cellquad, or -- for every other layout -- the reference textures)
+template <class F>
+static void with_layout(int lay, F&& f) {
+  if (lay == VX_LAYOUT_BRICKF32) f(std::integral_constant<int, LAYOUT_BF>{});
+  else if (lay == VX_LAYOUT_CELLQUAD) f(std::integral_constant<int, LAYOUT_CQ>{});
+  else f(std::integral_constant<int, LAYOUT_REF>{});
 }
 
-// the three reference modes with the path segments re-packed through LDS (vx_paths.hpp)
-template <int MODE>
-static void launch_paths(VxContext* c, const MultiOut& mo, float weight, dim3 grid, size_t lds, hipStream_t stream) {
-  grid.x *= mo.count ? mo.count : 1u;
-  const int lay = eff_layout(c);
-  if (lay == VX_LAYOUT_BRICKF32)
-    hipLaunchKernelGGL((render_paths<MODE, LAYOUT_BF>), grid, dim3(256), lds, stream, c->params, c->dv, c->tf, c->tf_len,
-                       mo, weight, c->tm);
-  else if (lay == VX_LAYOUT_CELLQUAD)
-    hipLaunchKernelGGL((render_paths<MODE, LAYOUT_CQ>), grid, dim3(256), lds, stream, c->params, c->dv, c->tf, c->tf_len,
-                       mo, weight, c->tm);
-  else
-    hipLaunchKernelGGL((render_paths<MODE, LAYOUT_REF>), grid, dim3(256), lds, stream, c->params, c->dv, c->tf, c->tf_len,
-                       mo, weight, c->tm);
-}
+// ---- the launch plan: which kernel a render launch runs, and whether it folds the running mean itself ----------------
 
-// default / no_dda as the wave-persistent, event-batched path tracer (vx_events.hpp).  The frame slots of `mo` must be
-// consecutive frames at constant strides (vx_render_frames allocates them that way).
-template <int MODE>
-static void launch_events(VxContext* c, const MultiOut& mo, float weight, dim3 grid, hipStream_t stream) {
-  const uint32_t n = mo.count ? mo.count : 1u;
-  const uint64_t out_stride = n > 1 ? (uint64_t)(mo.out[1] - mo.out[0]) : 0u, dc_stride = n > 1 ? (uint64_t)(mo.dc[1] - mo.dc[0]) : 0u;
-  const uint32_t groups = (n + VX_EV_FRAMES - 1u) / VX_EV_FRAMES;
-  grid.x *= groups;
-  const size_t lds = (size_t)c->tf_len * sizeof(float4) + 4u * PF_COUNT * 64u * sizeof(float);
-  const int lay = eff_layout(c);
-#define VX_LAUNCH_EV(LAY) \
-  hipLaunchKernelGGL((render_events<MODE, LAY>), grid, dim3(256), lds, stream, c->params, c->dv, c->tf, c->tf_len, mo.out[0], \
-                     out_stride, mo.dc[0], dc_stride, mo.frame[0], n, weight, c->tm)
-  if (lay == VX_LAYOUT_BRICKF32) VX_LAUNCH_EV(LAYOUT_BF);
-  else if (lay == VX_LAYOUT_CELLQUAD) VX_LAUNCH_EV(LAYOUT_CQ);
-  else VX_LAUNCH_EV(LAYOUT_REF);
-#undef VX_LAUNCH_EV
+enum class Kernel {
+  DVR_LDS,   // LDS-window DVR / Phong (vx_dvr_lds.hpp), the shared-window form under VX_DVR_WG=1
+  DVR_CQ,    // tuned DVR on the cellquad layout (vx_dvr.hpp)
+  EVENTS,    // `default` / `no_dda` wave-persistent and event-batched (vx_events.hpp, VX_PATHS_KERNEL=events)
+  PATHS,     // the three reference modes with path segments re-packed through LDS (vx_paths.hpp, VX_PATHS_KERNEL=packed)
+  GENERIC,   // render_generic<MODE> (vx_kernels.hpp)
+};
+struct LaunchPlan {
+  Kernel kernel = Kernel::GENERIC;
+  int layout = VX_LAYOUT_REFERENCE;   // what the path kernels sample (eff_layout; the DVR launchers pick their own form)
+  size_t lds = 0;                     // dynamic LDS bytes of the path kernels (the DVR launchers size their windows)
+  bool fuse = false;                  // the kernel folds the running mean of the launch itself (MultiOut::fuse)
+  bool ordered = false;               // the kernel runs its blocks in c->order, and single frames refresh it (build_order)
+};
+
+static bool tuned_possible(const VxContext* c) {
+  // (an early-termination threshold <= 0 -- an epsilon >= 1: every ray ends at its first contributing sample -- is
+  // served by render_generic, whose Frame::dvr spells the test as the oracle does; the tuned kernels assume tau >= ert
+  // implies a contributing sample)
+  return c->sw.dvr_variant != 0 && !c->params.debug_hits && c->tf_len <= TF_LDS_MAX && c->params.dvr_ert_tau > 0.0f;
 }
+// the LDS-window kernel (vx_dvr_lds.hpp): DVR on the brickf32 layout, Phong wherever brickf32 data is resident
+static bool use_lds_kernel(const VxContext* c) {
+  if (!tuned_possible(c)) return false;
+  if (eff_layout(c) == VX_LAYOUT_BRICKU8)   // the same kernel, staging from the 8-bit bricks
+    return (c->params.render_mode == VX_MODE_DVR || c->params.render_mode == VX_MODE_DVR_PHONG) && c->dv.bu != nullptr;
+  if (c->params.render_mode == VX_MODE_DVR) return eff_layout(c) == VX_LAYOUT_BRICKF32;
+  return c->params.render_mode == VX_MODE_DVR_PHONG && c->dv.bf != nullptr;
+}
+static bool is_tuned(const VxContext* c) {
+  const bool dvr_cq = c->params.render_mode == VX_MODE_DVR && eff_layout(c) == VX_LAYOUT_CELLQUAD;
+  return tuned_possible(c) && (dvr_cq || use_lds_kernel(c));
+}
+// the event kernel addresses its frame slots by base + stride: consecutive frames at constant strides (vx_render_frames
+// allocates them that way), slab slots below 2^26
 static bool events_possible(const VxContext* c, const MultiOut& mo) {
-  if (c->paths_variant != 3 || c->params.debug_hits || c->tf_len > TF_LDS_MAX) return false;
+  if (c->sw.paths_variant != 3 || c->params.debug_hits || c->tf_len > TF_LDS_MAX) return false;
   if (c->params.render_mode != VX_MODE_DEFAULT && c->params.render_mode != VX_MODE_NO_DDA) return false;
-  const uint32_t n = mo.count ? mo.count : 1u;
-  for (uint32_t i = 1; i < n; ++i)   // consecutive frames, constant strides, slab slots below 2^26
+  const uint32_t n = mo.count;
+  for (uint32_t i = 1; i < n; ++i)
     if (mo.frame[i] != mo.frame[0] + i || mo.out[i] - mo.out[0] != (ptrdiff_t)i * (mo.out[1] - mo.out[0]) ||
         mo.dc[i] - mo.dc[0] != (ptrdiff_t)i * (mo.dc[1] - mo.dc[0]))
       return false;
   return c->slab_quads < (1u << 26) && n <= 64u;
 }
 
-static void launch_generic_mode(VxContext* c, const MultiOut& mo, float weight, dim3 grid, hipStream_t stream) {
-  if (events_possible(c, mo)) {
-    if (c->params.render_mode == VX_MODE_DEFAULT) launch_events<VX_MODE_DEFAULT>(c, mo, weight, grid, stream);
-    else launch_events<VX_MODE_NO_DDA>(c, mo, weight, grid, stream);
-    return;
+// The one place that decides what a render launch of the mo.count frame slots of `mo` runs.  The fuse rule: while
+// VX_DVR_FUSE is on, the kernel folds the running mean of the launch into the accumulator itself when
+//   * it is the LDS-window DVR / Phong kernel without the shared window (VX_DVR_WG) and the launch has 8, 16, 32 or 64
+//     frames (a wave holds every frame of its 8, 4, 2 or 1 pixels), or
+//   * it is render_generic for `default`, `no_dda` or `raymarch` and the launch has exactly 32 frames (2 pixels x 32
+//     frames per wave).
+// Every other multi-frame launch writes per-frame result slabs that merge_results blends in frame order.
+static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo) {
+  const VxParams& p = c->params;
+  const uint32_t n = mo.count;
+  LaunchPlan lp;
+  lp.layout = eff_layout(c);
+  if (is_tuned(c)) {
+    lp.kernel = use_lds_kernel(c) ? Kernel::DVR_LDS : Kernel::DVR_CQ;
+    lp.ordered = c->sw.use_order;
+    lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && !c->sw.dvr_shared_window &&
+              (n == 8u || n == 16u || n == 32u || n == 64u);
+    return lp;
   }
-  size_t lds = c->tf_len <= TF_LDS_MAX ? (size_t)c->tf_len * sizeof(float4) : 0;
-  if (mo.fuse) lds += 4u * 320u * sizeof(float);   // fold_frames' scratch, one per wave (generic_fusable)
+  if (events_possible(c, mo)) {
+    lp.kernel = Kernel::EVENTS;
+    lp.lds = (size_t)c->tf_len * sizeof(float4) + 4u * PF_COUNT * 64u * sizeof(float);
+    return lp;
+  }
+  lp.lds = c->tf_len <= TF_LDS_MAX ? (size_t)c->tf_len * sizeof(float4) : 0;
   // (bounces < 1: fragment.frag:86-101 still traces the primary segment and one light sample before it tests the
   // count; render_paths loops on `n_paths < bounces` and would leave the slab unwritten -- render_generic serves it)
-  if (c->paths_variant == 1 && !c->params.debug_hits && c->params.render_mode <= VX_MODE_RAYMARCH && c->params.bounces >= 1) {
-    switch (c->params.render_mode) {
-      case VX_MODE_DEFAULT: launch_paths<VX_MODE_DEFAULT>(c, mo, weight, grid, lds, stream); break;
-      case VX_MODE_NO_DDA: launch_paths<VX_MODE_NO_DDA>(c, mo, weight, grid, lds, stream); break;
-      default: launch_paths<VX_MODE_RAYMARCH>(c, mo, weight, grid, lds, stream); break;
-    }
-    return;
+  if (c->sw.paths_variant == 1 && !p.debug_hits && p.render_mode <= VX_MODE_RAYMARCH && p.bounces >= 1) {
+    lp.kernel = Kernel::PATHS;
+    return lp;
   }
-  switch (c->params.render_mode) {
-    case VX_MODE_DEFAULT: launch_generic<VX_MODE_DEFAULT>(c, mo, weight, grid, lds, stream); break;
-    case VX_MODE_NO_DDA: launch_generic<VX_MODE_NO_DDA>(c, mo, weight, grid, lds, stream); break;
-    case VX_MODE_RAYMARCH: launch_generic<VX_MODE_RAYMARCH>(c, mo, weight, grid, lds, stream); break;
-    case VX_MODE_DVR: launch_generic<VX_MODE_DVR>(c, mo, weight, grid, lds, stream); break;
-    default: launch_generic<VX_MODE_DVR_PHONG>(c, mo, weight, grid, lds, stream); break;
-  }
+  lp.kernel = Kernel::GENERIC;
+  lp.fuse = c->sw.dvr_fuse && p.render_mode <= VX_MODE_RAYMARCH && n == 32u;
+  if (lp.fuse) lp.lds += 4u * 320u * sizeof(float);   // fold_frames' scratch, one per wave
+  return lp;
 }
 
-// will launch_generic_mode run render_generic<MODE <= RAYMARCH> for this context?  (Only that kernel applies the running mean of
-// a 32-frame launch itself, MultiOut::fuse; the re-packed and event-batched path kernels and the DVR modes on the generic
-// kernel keep the result slabs and merge_results.)
-static bool generic_fusable(const VxContext* c, const MultiOut& mo) {
-  if (c->params.render_mode > VX_MODE_RAYMARCH) return false;
-  if (events_possible(c, mo)) return false;
-  if (c->paths_variant == 1 && !c->params.debug_hits && c->params.bounces >= 1) return false;
-  return true;
+// the path kernels of render mode MODE: event-batched, re-packed or render_generic, on the plan's layout
+template <int MODE>
+static void launch_mode(const VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
+  with_layout(lp.layout, [&](auto tag) {
+    constexpr int LAY = decltype(tag)::value;
+    if constexpr (MODE == VX_MODE_DEFAULT || MODE == VX_MODE_NO_DDA) {
+      if (lp.kernel == Kernel::EVENTS) {
+        const uint32_t n = mo.count;
+        const uint64_t out_stride = n > 1 ? (uint64_t)(mo.out[1] - mo.out[0]) : 0u,
+                       dc_stride = n > 1 ? (uint64_t)(mo.dc[1] - mo.dc[0]) : 0u;
+        grid.x *= (n + VX_EV_FRAMES - 1u) / VX_EV_FRAMES;
+        hipLaunchKernelGGL((render_events<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
+                           mo.out[0], out_stride, mo.dc[0], dc_stride, mo.frame[0], n, weight, c->tm);
+        return;
+      }
+    }
+    grid.x *= mo.count;
+    if constexpr (MODE <= VX_MODE_RAYMARCH) {
+      if (lp.kernel == Kernel::PATHS) {
+        hipLaunchKernelGGL((render_paths<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
+                           mo, weight, c->tm);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((render_generic<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
+                       mo, weight, c->tm);
+  });
+}
+
+// The one launch switch: runs what `lp` names for the frame slots of `mo` on the context's stream.  Fails closed: a
+// kernel that does not fold the running mean refuses a launch with mo.fuse set -- its frames would reach no accumulator.
+static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
+  const bool folds = (lp.kernel == Kernel::DVR_LDS && !c->sw.dvr_shared_window) ||
+                     (lp.kernel == Kernel::GENERIC && c->params.render_mode <= VX_MODE_RAYMARCH);
+  if (mo.fuse && !folds)
+    VX_FAIL(c, VX_ERR_INVALID, "render launch: running mean to fold (MultiOut::fuse) for a kernel that does not fold it");
+  const uint32_t* order = lp.ordered ? c->order : nullptr;
+  switch (lp.kernel) {
+    case Kernel::DVR_LDS:
+      launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_shared_window);
+      break;
+    case Kernel::DVR_CQ:
+      launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_unroll);
+      break;
+    default:
+      switch (c->params.render_mode) {
+        case VX_MODE_DEFAULT: launch_mode<VX_MODE_DEFAULT>(c, lp, mo, weight, grid); break;
+        case VX_MODE_NO_DDA: launch_mode<VX_MODE_NO_DDA>(c, lp, mo, weight, grid); break;
+        case VX_MODE_RAYMARCH: launch_mode<VX_MODE_RAYMARCH>(c, lp, mo, weight, grid); break;
+        case VX_MODE_DVR: launch_mode<VX_MODE_DVR>(c, lp, mo, weight, grid); break;
+        default: launch_mode<VX_MODE_DVR_PHONG>(c, lp, mo, weight, grid); break;
+      }
+  }
+  VX_HIP(c, hipGetLastError());
+  return VX_OK;
 }
 
 extern "C" {
@@ -616,20 +659,20 @@ int vx_create(int device_id, VxContext** out) {
       return VX_ERR_DEVICE;
     }
   }
-  const char* v = getenv("VX_DVR_KERNEL");
-  if (v && !strcmp(v, "generic")) c->dvr_variant = 0;
-  const char* pk = getenv("VX_PATHS_KERNEL");
-  if (pk && !strcmp(pk, "packed")) c->paths_variant = 1;     // path segments re-packed through LDS (vx_paths.hpp)
-  if (pk && !strcmp(pk, "generic")) c->paths_variant = 2;    // one pixel per lane for the whole path (render_generic): the default
-  if (pk && !strcmp(pk, "events")) c->paths_variant = 3;     // wave-persistent, event-batched (vx_events.hpp): measured slower
-  const char* dpe = getenv("VX_DVR_DP");
-  if (dpe) c->dp_env = atoi(dpe);
-  const char* fu = getenv("VX_DVR_FUSE");
-  if (fu) c->dvr_fuse = atoi(fu) != 0;
-  const char* wg = getenv("VX_DVR_WG");
-  if (wg) c->dvr_shared_window = atoi(wg) != 0;
-  const char* o = getenv("VX_DVR_ORDER");
-  if (o && !strcmp(o, "0")) c->use_order = false;
+  // the diagnostic switches (struct Switches): the only place that reads the environment
+  Switches& sw = c->sw;
+  if (const char* v = getenv("VX_DVR_KERNEL"); v && !strcmp(v, "generic")) sw.dvr_variant = 0;
+  if (const char* v = getenv("VX_PATHS_KERNEL")) {
+    if (!strcmp(v, "packed")) sw.paths_variant = 1;
+    if (!strcmp(v, "generic")) sw.paths_variant = 2;
+    if (!strcmp(v, "events")) sw.paths_variant = 3;
+  }
+  if (const char* v = getenv("VX_DVR_FUSE")) sw.dvr_fuse = atoi(v) != 0;
+  if (const char* v = getenv("VX_DVR_WG")) sw.dvr_shared_window = atoi(v) != 0;
+  if (const char* v = getenv("VX_DVR_ORDER"); v && !strcmp(v, "0")) sw.use_order = false;
+  if (const char* v = getenv("VX_RAY_SHORTCUTS"); v && atoi(v) == 0) sw.ray_shortcuts = false;
+  if (const char* v = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) sw.cellquad_max_bytes = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VX_DVR_UNROLL")) sw.dvr_unroll = atoi(v);
   *out = c;
   return VX_OK;
 }
@@ -656,11 +699,6 @@ void vx_destroy(VxContext* c) {
   if (c->tile_perm) (void)hipFree(c->tile_perm);
   if (c->dc) (void)hipFree(c->dc);
   if (c->order) (void)hipFree(c->order);
-  for (auto& p : c->pipes) {
-    if (p.stream) { (void)hipStreamSynchronize(p.stream); (void)hipStreamDestroy(p.stream); }
-    if (p.done) (void)hipEventDestroy(p.done);
-    if (p.merged) (void)hipEventDestroy(p.merged);
-  }
   if (c->pipe_result_pool) (void)hipFree(c->pipe_result_pool);
   if (c->pipe_dc_pool) (void)hipFree(c->pipe_dc_pool);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
@@ -814,11 +852,10 @@ static int ensure_cellquad(VxContext* c) {
     // AUTO builds this layout on demand, beside what is resident: only when it leaves half of the free device memory to
     // the rest of the process (19.8 GB for 1024^3 on a 288 GB MI355X: always; a volume near the layout's 64 GiB index limit
     // on a device that other contexts share: not necessarily).  Otherwise `default` / `no_dda` take the resident bricks.
-    // VX_AUTO_CELLQUAD_MAX_BYTES (environment, read here) overrides the budget -- 0 keeps AUTO off this layout.
+    // VX_AUTO_CELLQUAD_MAX_BYTES (Switches) overrides the budget -- 0 keeps AUTO off this layout.
     size_t free_b = 0, total_b = 0;
     VX_HIP(c, hipMemGetInfo(&free_b, &total_b));
-    uint64_t budget = (uint64_t)free_b / 2u;
-    if (const char* e = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) budget = strtoull(e, nullptr, 10);
+    const uint64_t budget = c->sw.cellquad_max_bytes.value_or((uint64_t)free_b / 2u);
     if (n_quads * sizeof(float4) > budget) {
       c->auto_no_cq = true;
       return VX_OK;
@@ -1082,8 +1119,6 @@ int vx_upload_environment(VxContext* c, const float* rgba, uint32_t w, uint32_t 
   if (!c) return VX_ERR_INVALID;
   VX_HIP(c, hipSetDevice(c->device));
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  for (auto& p : c->pipes)
-    if (p.stream) VX_HIP(c, hipStreamSynchronize(p.stream));
   if (c->env_tex) (void)hipFree(c->env_tex);
   if (c->env_imp) (void)hipFree(c->env_imp);
   if (c->env_impq) (void)hipFree(c->env_impq);
@@ -1175,25 +1210,6 @@ int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
   return alloc_framebuffers(c);
 }
 
-static bool tuned_possible(const VxContext* c) {
-  // (an early-termination threshold <= 0 -- an epsilon >= 1: every ray ends at its first contributing sample -- is
-  // served by render_generic, whose Frame::dvr spells the test as the oracle does; the tuned kernels assume tau >= ert
-  // implies a contributing sample)
-  return c->dvr_variant != 0 && !c->params.debug_hits && c->tf_len <= TF_LDS_MAX && c->params.dvr_ert_tau > 0.0f;
-}
-// the LDS-window kernel (vx_dvr_lds.hpp): DVR on the brickf32 layout, Phong wherever brickf32 data is resident
-static bool use_lds_kernel(const VxContext* c) {
-  if (!tuned_possible(c)) return false;
-  if (eff_layout(c) == VX_LAYOUT_BRICKU8)   // the same kernel, staging from the 8-bit bricks
-    return (c->params.render_mode == VX_MODE_DVR || c->params.render_mode == VX_MODE_DVR_PHONG) && c->dv.bu != nullptr;
-  if (c->params.render_mode == VX_MODE_DVR) return eff_layout(c) == VX_LAYOUT_BRICKF32;
-  return c->params.render_mode == VX_MODE_DVR_PHONG && c->dv.bf != nullptr;
-}
-static bool is_tuned(const VxContext* c) {
-  const bool dvr_cq = c->params.render_mode == VX_MODE_DVR && eff_layout(c) == VX_LAYOUT_CELLQUAD;
-  return tuned_possible(c) && (dvr_cq || use_lds_kernel(c));
-}
-
 static int prepare_render(VxContext* c, dim3& grid) {
   if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
   if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
@@ -1260,7 +1276,7 @@ static int prepare_render(VxContext* c, dim3& grid) {
       }
       if (c->tex_by_reciprocal[axis]) flags |= (axis == 0 ? RAY_TEX_BY_RECIPROCAL_X : RAY_TEX_BY_RECIPROCAL_Y);
     }
-    if (getenv("VX_RAY_SHORTCUTS") && atoi(getenv("VX_RAY_SHORTCUTS")) == 0) flags = 0;   // diagnostic: the divisions themselves
+    if (!c->sw.ray_shortcuts) flags = 0;   // diagnostic: the divisions themselves
     c->dv.ray_flags = flags;
   }
   {
@@ -1296,32 +1312,7 @@ static int prepare_render(VxContext* c, dim3& grid) {
   }
   uint32_t groups = (c->tm.tiles_per_shard + 7u) / 8u;
   grid = dim3(groups * 128u);
-  return ensure_counters(c, (size_t)grid.x * 4u * 8u);  // x8: the depth-parallel DVR grid
-}
-
-// one render-kernel launch into `out` (accumulator or a pipeline result slab)
-static hipError_t launch_render(VxContext* c, uint32_t frame_index, float weight, dim3 grid, float4* out,
-                                DevCounters* dc, hipStream_t stream) {
-  bool tuned = is_tuned(c);
-  if (tuned && use_lds_kernel(c)) {
-    MultiOut mo{};
-    mo.count = 1;
-    mo.out[0] = out;
-    mo.dc[0] = dc;
-    mo.frame[0] = frame_index;
-    launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, stream, c->use_order ? c->order : nullptr);
-  } else if (tuned) {
-    launch_dvr_cq(c->params, c->dv, c->tf, c->tf_len, out, frame_index, weight, c->tm, dc, stream,
-                  (c->use_order && !c->dp_active()) ? c->order : nullptr);
-  } else {
-    MultiOut mo{};
-    mo.count = 1;
-    mo.out[0] = out;
-    mo.dc[0] = dc;
-    mo.frame[0] = frame_index;
-    launch_generic_mode(c, mo, weight, grid, stream);
-  }
-  return hipGetLastError();
+  return ensure_counters(c, (size_t)grid.x * 4u);  // one record per wave of the grid
 }
 
 static int take_events(VxContext* c, EventPair& ev) {
@@ -1330,13 +1321,11 @@ static int take_events(VxContext* c, EventPair& ev) {
     if (c->free_events.empty()) {
       VX_HIP(c, hipEventCreate(&ev.a));
       VX_HIP(c, hipEventCreate(&ev.b));
-      ev.launches = 1;
       return VX_OK;
     }
   }
   ev = c->free_events.back();
   c->free_events.pop_back();
-  ev.launches = 1;
   return VX_OK;
 }
 
@@ -1346,67 +1335,58 @@ int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
   dim3 grid;
   int rc = prepare_render(c, grid);
   if (rc) return rc;
+  MultiOut mo{};
+  mo.count = 1;
+  mo.out[0] = c->slab;
+  mo.dc[0] = c->dc;
+  mo.frame[0] = frame_index;
+  const LaunchPlan lp = plan_launch(c, mo);
   EventPair ev;
   if ((rc = take_events(c, ev))) return rc;
   VX_HIP(c, hipEventRecord(ev.a, c->stream));
-  hipError_t le = launch_render(c, frame_index, sample_weight, grid, c->slab, c->dc, c->stream);
+  rc = launch_planned(c, lp, mo, sample_weight, grid);
   VX_HIP(c, hipEventRecord(ev.b, c->stream));
-  const bool ordered = is_tuned(c) && c->use_order && !(c->dp_active() && !use_lds_kernel(c));
-  if (!ordered) c->order_builds_left = 0;
-  if (ordered && le == hipSuccess && c->order_builds_left > 0) {
+  c->pending_events.push_back(ev);
+  if (rc) return rc;
+  if (!lp.ordered) c->order_builds_left = 0;
+  if (lp.ordered && c->order_builds_left > 0) {
     c->order_builds_left--;
     hipLaunchKernelGGL(build_order, dim3(1), dim3(1024), 0, c->stream, c->dc, c->order, grid.x);
-    le = hipGetLastError();
+    VX_HIP(c, hipGetLastError());
   }
-  c->pending_events.push_back(ev);
   c->note_launch(1);
-  if (le != hipSuccess) VX_FAIL(c, VX_ERR_DEVICE, "render kernel launch: %s", hipGetErrorString(le));
   return VX_OK;
 }
 
-static int ensure_pipes(VxContext* c, int n) {
-  size_t waves = c->dc_waves;
-  if ((int)c->pipes.size() >= n && c->pipe_quads == c->slab_quads && c->pipe_waves == waves) return VX_OK;
+// at least n slots of per-frame result slabs and counter records for the current framebuffer and grid (grow-only)
+static int ensure_pipes(VxContext* c, uint32_t n) {
+  if (c->pipe_slots >= n && c->pipe_quads == c->slab_quads && c->pipe_waves == c->dc_waves) return VX_OK;
   VX_HIP(c, hipStreamSynchronize(c->stream));
   {
     int rc = fold_counters(c);   // keep what the records of the old slots have counted
     if (rc) return rc;
   }
-  for (auto& p : c->pipes) {
-    if (p.stream) (void)hipStreamSynchronize(p.stream);
-    p.result = nullptr;
-    p.dc = nullptr;
-  }
+  const size_t ns = std::max(n, c->pipe_slots), waves = c->dc_waves;
   if (c->pipe_result_pool) (void)hipFree(c->pipe_result_pool);
   if (c->pipe_dc_pool) (void)hipFree(c->pipe_dc_pool);
   c->pipe_result_pool = nullptr;
   c->pipe_dc_pool = nullptr;
-  if ((int)c->pipes.size() < n) c->pipes.resize(n);
-  const size_t ns = c->pipes.size();
+  c->pipe_slots = 0;
   VX_HIP(c, hipMalloc(&c->pipe_result_pool, ns * c->slab_quads * sizeof(float4)));
   VX_HIP(c, hipMalloc(&c->pipe_dc_pool, ns * waves * sizeof(DevCounters)));
   VX_HIP(c, hipMemsetAsync(c->pipe_dc_pool, 0, ns * waves * sizeof(DevCounters), c->stream));   // ordered with the launches
-  for (size_t i = 0; i < ns; ++i) {
-    auto& p = c->pipes[i];
-    // streams only for the rolling-window path of the depth-parallel experiment (<= 8 slots); the multi-frame kernels
-    // need none
-    if (i < 8 && !p.stream && c->dp_active()) VX_HIP(c, hipStreamCreateWithFlags(&p.stream, hipStreamNonBlocking));
-    if (!p.done) VX_HIP(c, hipEventCreateWithFlags(&p.done, hipEventDisableTiming));
-    if (!p.merged) VX_HIP(c, hipEventCreateWithFlags(&p.merged, hipEventDisableTiming));
-    p.has_merged = false;
-    p.result = c->pipe_result_pool + i * c->slab_quads;
-    p.dc = c->pipe_dc_pool + i * waves;
-  }
-  VX_HIP(c, hipStreamSynchronize(c->stream));   // the fills are done before any stream launches into the new slots
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  c->pipe_slots = (uint32_t)ns;
   c->pipe_quads = c->slab_quads;
   c->pipe_waves = waves;
   return VX_OK;
 }
 
-// `count` accumulation frames first_frame.. with their sample weights, up to `in_flight` of them
-// concurrently (frames are independent given their index; only the running mean is ordered, and
-// it is applied afterwards, in order, by merge_results -> bit-identical to count vx_render_frame
-// calls).  Hides the latency-bound tail of one frame behind the bulk of the next ones.
+// `count` accumulation frames first_frame.. with their sample weights, up to `in_flight` of them in one launch (frames
+// are independent given their index; only the running mean is ordered).  A launch either folds the running mean of its
+// frames itself (plan_launch's fuse rule) or writes per-frame result slabs that merge_results then blends in frame
+// order -- bit-identical to count vx_render_frame calls either way.  Hides the latency-bound tail of one frame behind
+// the bulk of the next ones.
 int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const float* weights, int in_flight) {
   if (!c || (!weights && count)) return VX_ERR_INVALID;
   VX_DEV(c);
@@ -1422,103 +1402,52 @@ int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const f
   dim3 grid;
   int rc = prepare_render(c, grid);
   if (rc) return rc;
-  if ((rc = ensure_pipes(c, in_flight))) return rc;
-  EventPair ev;
-  if ((rc = take_events(c, ev))) return rc;
-  ev.launches = count - done;
-  hipError_t le = hipSuccess;
-  const bool tuned_lds = is_tuned(c) && use_lds_kernel(c);
-  const bool tuned_cq = is_tuned(c) && !tuned_lds && !c->dp_active();
-  if (tuned_cq || tuned_lds || !is_tuned(c)) {
-    // several frames per launch (see MultiOut): one kernel for up to in_flight frames, then the
-    // ordered blend of their results (the tuned cellquad DVR kernel and every render_generic mode)
-    const uint32_t nqm = (uint32_t)c->slab_quads;
-    c->free_events.push_back(ev);   // per-launch intervals instead of one batch interval
-    while (done < count && le == hipSuccess) {
-      uint32_t n = count - done < (uint32_t)in_flight ? count - done : (uint32_t)in_flight;
-      MultiOut mo{};
-      MergeArgs ma{};
-      mo.count = n;
-      ma.count = n;
-      for (uint32_t i = 0; i < n; ++i) {
-        mo.out[i] = c->pipes[i].result;
-        mo.dc[i] = c->pipes[i].dc;
-        mo.frame[i] = first_frame + done + i;
-        ma.result[i] = c->pipes[i].result;
-        ma.weight[i] = weights[done + i];
-      }
-      // the LDS-window kernel applies the running mean itself when one wave holds every frame of its pixels: a launch of
-      // exactly 8, 16, 32 or 64 frames (MultiOut::fuse; VX_DVR_FUSE=0 keeps the result slabs and the blend kernel)
-      const bool fused = c->dvr_fuse &&
-                         ((tuned_lds && !c->dvr_shared_window && (n == 8u || n == 16u || n == 32u || n == 64u)) ||
-                          (!is_tuned(c) && n == 32u && generic_fusable(c, mo)));
-      if (fused) {
-        bool zero = false;
-        for (uint32_t i = 0; i < n; ++i) {
-          mo.weight[i] = ma.weight[i];
-          zero = zero || ma.weight[i] == 0.0f;
-        }
-        mo.fuse = zero ? 2u : 1u;
-        mo.accum = c->slab;
-      }
-      EventPair e2;
-      if ((rc = take_events(c, e2))) return rc;
-      VX_HIP(c, hipEventRecord(e2.a, c->stream));
-      if (tuned_cq)
-        launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream,
-                            c->use_order ? c->order : nullptr);
-      else if (tuned_lds)
-        launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream,
-                       c->use_order ? c->order : nullptr, c->dvr_shared_window);
-      else
-        launch_generic_mode(c, mo, 0.0f, grid, c->stream);
-      le = hipGetLastError();
-      VX_HIP(c, hipEventRecord(e2.b, c->stream));   // the render kernel alone; the blend is outside
-      c->pending_events.push_back(e2);
-      if (le == hipSuccess && !fused) {
-        EventPair e3;
-        if ((rc = take_events(c, e3))) return rc;
-        e3.merge = true;
-        VX_HIP(c, hipEventRecord(e3.a, c->stream));
-        hipLaunchKernelGGL(merge_results, dim3((nqm + 255) / 256), dim3(256), 0, c->stream, c->slab, ma, nqm);
-        le = hipGetLastError();
-        VX_HIP(c, hipEventRecord(e3.b, c->stream));
-        c->pending_events.push_back(e3);
-      }
-      done += n;
-      c->note_launch(n);
-    }
-    if (le != hipSuccess) VX_FAIL(c, VX_ERR_DEVICE, "render kernel launch: %s", hipGetErrorString(le));
-    return VX_OK;
-  }
-  // the depth-parallel experiment: rolling window of frames on separate streams
-  VX_HIP(c, hipEventRecord(ev.a, c->stream));
-  // rolling window: frame f renders on slot f % in_flight as soon as that slot's previous result has
-  // been blended; the blends happen on the main stream, in frame order
-  const uint32_t P = (uint32_t)(in_flight > 8 ? 8 : in_flight);  // streams; more only costs queue slots
+  if ((rc = ensure_pipes(c, (uint32_t)in_flight))) return rc;
   const uint32_t nq = (uint32_t)c->slab_quads;
-  for (; done < count && le == hipSuccess; ++done) {
-    auto& p = c->pipes[c->pipe_next % P];
-    c->pipe_next = (c->pipe_next + 1) % P;
-    if (p.has_merged) VX_HIP(c, hipStreamWaitEvent(p.stream, p.merged, 0));
-    le = launch_render(c, first_frame + done, 0.0f, grid, p.result, p.dc, p.stream);  // weight 0: raw result
-    VX_HIP(c, hipEventRecord(p.done, p.stream));
-    VX_HIP(c, hipStreamWaitEvent(c->stream, p.done, 0));
-    if (le == hipSuccess) {
-      MergeArgs ma{};
-      ma.count = 1;
-      ma.result[0] = p.result;
-      ma.weight[0] = weights[done];
-      hipLaunchKernelGGL(merge_results, dim3((nq + 255) / 256), dim3(256), 0, c->stream, c->slab, ma, nq);
-      le = hipGetLastError();
+  while (done < count) {
+    const uint32_t n = std::min(count - done, (uint32_t)in_flight);
+    MultiOut mo{};
+    MergeArgs ma{};
+    mo.count = n;
+    ma.count = n;
+    for (uint32_t i = 0; i < n; ++i) {
+      mo.out[i] = c->pipe_result_pool + i * c->pipe_quads;
+      mo.dc[i] = c->pipe_dc_pool + i * c->pipe_waves;
+      mo.frame[i] = first_frame + done + i;
+      ma.result[i] = mo.out[i];
+      ma.weight[i] = weights[done + i];
     }
-    VX_HIP(c, hipEventRecord(p.merged, c->stream));
-    p.has_merged = true;
-    c->note_launch(1);
+    const LaunchPlan lp = plan_launch(c, mo);
+    if (lp.fuse) {
+      bool zero = false;
+      for (uint32_t i = 0; i < n; ++i) {
+        mo.weight[i] = ma.weight[i];
+        zero = zero || ma.weight[i] == 0.0f;
+      }
+      mo.fuse = zero ? 2u : 1u;
+      mo.accum = c->slab;
+    }
+    EventPair ev;
+    if ((rc = take_events(c, ev))) return rc;
+    VX_HIP(c, hipEventRecord(ev.a, c->stream));
+    rc = launch_planned(c, lp, mo, 0.0f, grid);
+    VX_HIP(c, hipEventRecord(ev.b, c->stream));   // the render kernel alone; the blend is timed apart
+    c->pending_events.push_back(ev);
+    if (rc) return rc;
+    if (!lp.fuse) {
+      EventPair em;
+      if ((rc = take_events(c, em))) return rc;
+      em.merge = true;
+      VX_HIP(c, hipEventRecord(em.a, c->stream));
+      hipLaunchKernelGGL(merge_results, dim3((nq + 255) / 256), dim3(256), 0, c->stream, c->slab, ma, nq);
+      VX_HIP(c, hipGetLastError());
+      VX_HIP(c, hipEventRecord(em.b, c->stream));
+      c->pending_events.push_back(em);
+      c->merge_launches += 1;
+    }
+    done += n;
+    c->note_launch(n);
   }
-  VX_HIP(c, hipEventRecord(ev.b, c->stream));
-  c->pending_events.push_back(ev);
-  if (le != hipSuccess) VX_FAIL(c, VX_ERR_DEVICE, "render kernel launch: %s", hipGetErrorString(le));
   return VX_OK;
 }
 
@@ -1606,13 +1535,10 @@ int vx_probe_tile_costs(VxContext* c, uint32_t* costs, uint32_t n) {
   if (rc) return rc;
   uint32_t* d = nullptr;
   VX_HIP(c, hipMalloc(&d, (size_t)n * 4));
-  const int lay = eff_layout(c);
-  if (lay == VX_LAYOUT_BRICKF32)
-    hipLaunchKernelGGL((probe_tile_costs<LAYOUT_BF>), dim3(n), dim3(64), 0, c->stream, c->params, c->dv, c->tf, c->tf_len, c->tm, d);
-  else if (lay == VX_LAYOUT_CELLQUAD)
-    hipLaunchKernelGGL((probe_tile_costs<LAYOUT_CQ>), dim3(n), dim3(64), 0, c->stream, c->params, c->dv, c->tf, c->tf_len, c->tm, d);
-  else
-    hipLaunchKernelGGL((probe_tile_costs<LAYOUT_REF>), dim3(n), dim3(64), 0, c->stream, c->params, c->dv, c->tf, c->tf_len, c->tm, d);
+  with_layout(eff_layout(c), [&](auto tag) {
+    hipLaunchKernelGGL((probe_tile_costs<decltype(tag)::value>), dim3(n), dim3(64), 0, c->stream, c->params, c->dv, c->tf, c->tf_len,
+                       c->tm, d);
+  });
   hipError_t le = hipGetLastError();
   if (le == hipSuccess) le = hipMemcpyAsync(costs, d, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
   if (le == hipSuccess) le = hipStreamSynchronize(c->stream);
@@ -1626,8 +1552,6 @@ int vx_set_tile_order(VxContext* c, const uint32_t* perm, uint32_t n) {
   VX_DEV(c);
   if (!c->W) VX_FAIL(c, VX_ERR_INVALID, "vx_set_tile_order: vx_resize first");
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  for (auto& p : c->pipes)
-    if (p.stream) VX_HIP(c, hipStreamSynchronize(p.stream));
   if (perm) {
     if (n != c->tm.n_tiles) VX_FAIL(c, VX_ERR_INVALID, "vx_set_tile_order: the image has %u tiles, not %u", c->tm.n_tiles, n);
     std::vector<uint32_t> both(2 * (size_t)n, 0xffffffffu);
@@ -1698,6 +1622,7 @@ int vx_get_counters(VxContext* c, VxCounters* out) {
   out->max_launch_frames = c->max_launch_frames;
   out->tf_samples = c->base.tf_samples;
   out->active_lane_slots = c->base.active_lane_slots;
+  out->merge_launches = c->merge_launches;
   return VX_OK;
 }
 
@@ -1707,13 +1632,14 @@ int vx_reset_counters(VxContext* c) {
   VX_HIP(c, hipStreamSynchronize(c->stream));
   drain_events(c);
   {
-    int rc = fold_counters(c);   // zeroes every record array (accumulator and pipeline slots)
+    int rc = fold_counters(c);   // zeroes every record array (accumulator and multi-frame slots)
     if (rc) return rc;
   }
   c->base = VxCounters{};
   c->kernel_ms = c->last_kernel_ms = c->merge_ms = 0.0;
   c->launches = 0;
   c->frames = 0;
+  c->merge_launches = 0;
   c->min_launch_frames = c->max_launch_frames = 0;
   return VX_OK;
 }
@@ -1840,19 +1766,19 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
   dim3 grid;
   int rc = prepare_render(c, grid);
   if (rc) return rc;
-  if (!(is_tuned(c) && eff_layout(c) == VX_LAYOUT_CELLQUAD && c->params.render_mode == VX_MODE_DVR))
+  MultiOut mo{};
+  mo.count = 1;
+  mo.out[0] = c->slab;   // never written by the probe build
+  mo.frame[0] = frame_index;
+  if (plan_launch(c, mo).kernel != Kernel::DVR_CQ)
     VX_FAIL(c, VX_ERR_INVALID, "vx_probe_gather_spread: needs render_mode dvr on the cellquad layout");
   const size_t waves = (size_t)grid.x * 4u;
   DevCounters* d = nullptr;
   VX_HIP(c, hipMalloc(&d, waves * sizeof(DevCounters)));
   hipError_t e = hipMemsetAsync(d, 0, waves * sizeof(DevCounters), c->stream);
-  MultiOut mo{};
-  mo.count = 1;
-  mo.out[0] = c->slab;   // never written by the probe build
   mo.dc[0] = d;
-  mo.frame[0] = frame_index;
   if (e == hipSuccess) {
-    launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream, nullptr, true);
+    launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream, nullptr, c->sw.dvr_unroll, true);
     e = hipGetLastError();
   }
   std::vector<DevCounters> h(waves);

@@ -162,8 +162,8 @@ struct MultiOut {
   uint32_t frame[MERGE_MAX];
   uint32_t count;
   // Round 4, behind the fields lane_frame_slot addresses (their offsets do not move): the running mean applied IN the render
-  // kernel.  fuse != 0 (the launcher sets it for a launch of exactly 8, 16, 32 or 64 frames of the LDS-window DVR kernel, of 32
-  // frames of render_generic): a wave holds every frame of its 8, 4, 2 (or 1) pixels, so it folds their results in frame order into `accum` itself -- fragment.frag:158
+  // kernel.  fuse != 0 (vx_api.hip plan_launch's fuse rule: a launch of exactly 8, 16, 32 or 64 frames of the LDS-window DVR
+  // kernel, of 32 frames of render_generic): a wave holds every frame of its 8, 4, 2 (or 1) pixels, so it folds their results in frame order into `accum` itself -- fragment.frag:158
   // with weight[k] for frame slot k, exactly what merge_results does -- and neither the per-frame result slabs nor the blend
   // kernel are touched.  fuse == 2: some weight of the launch is 0 (the previous value is then dropped: merge_results'
   // `w != 0 ? acc : 0`), the fold tests each weight; fuse == 1: none is.
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(generic_min
   // Path-traced modes in a multi-frame launch: lanes = pixels x frames (frame_group above), 8 pixels x 8 frames per wave.
   // The free-flight samples of one wave then fall along a beam 8 pixels wide instead of 64, and the vector L1 -- whose
   // misses in flight bound these modes -- serves more of them: no_dda 0.684 -> 0.622 ms per frame.
-  const uint32_t fuse = (MODE <= VX_MODE_RAYMARCH) ? mo.fuse : 0u;   // wave uniform; the launcher sets it for 32-frame launches only
+  const uint32_t fuse = (MODE <= VX_MODE_RAYMARCH) ? mo.fuse : 0u;   // wave uniform; plan_launch sets it for 32-frame launches only
   if (fuse != 0u) {
     // the running mean applied here (MultiOut::fuse): the workgroup at slot r of the 32 takes wave tile r >> 3 of its block
     // position and pixel octet r & 7 as below, but each of its waves takes 2 of the 8 pixels for ALL 32 frames -- the
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(generic_min
       const float4 r = f.template shade_pixel<MODE>(px, py, my_frame);
       L = v3(r.x, r.y, r.z);
     }
-    // wave-private scratch behind the transfer function (launch_generic adds it to the LDS size of a fused launch)
+    // wave-private scratch behind the transfer function (plan_launch adds it to the LDS size of a fused launch)
     float* const fold = reinterpret_cast<float*>(tf_lds + (tf_len <= TF_LDS_MAX ? tf_len : 0u)) + (threadIdx.x >> 6) * 320u;
     fold_frames(fold, threadIdx.x & 63u, L, active, si, mo.accum, fuse, 5u);
     flush_counts(dc, c, active ? 1u : 0u, blk);

@@ -418,7 +418,7 @@ static napi_value n_get_counters(napi_env env, napi_callback_info info) {
   PUT("gradSamples", k.grad_samples) PUT("tfSamples", k.tf_samples) PUT("activeLaneSlots", k.active_lane_slots) PUT("laneSlots", k.lane_slots) PUT("launches", k.launches) PUT("frames", k.frames)
   PUT("kernelMs", k.kernel_ms) PUT("lastKernelMs", k.last_kernel_ms) PUT("gathers", k.gathers)
   PUT("ldsReads", k.lds_reads) PUT("mergeMs", k.merge_ms) PUT("minLaunchFrames", k.min_launch_frames)
-  PUT("maxLaunchFrames", k.max_launch_frames)
+  PUT("maxLaunchFrames", k.max_launch_frames) PUT("mergeLaunches", k.merge_launches)
 #undef PUT
   return o;
 }
