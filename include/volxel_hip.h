@@ -174,18 +174,35 @@ typedef struct VxContext VxContext;
  *      (viewer.ts:221-414).  device_id = HIP ordinal.  Fails with VX_ERR_NO_DEVICE
  *      when no GPU is present.  */
 int vx_create(int device_id, VxContext** out_ctx);
+
+/* ---- device group (no counterpart in the reference): one image rendered on several GPUs from one process.
+ * One VxContext per entry of device_ids (a HIP ordinal may repeat), member i renders shard i of n.
+ * The returned handle is accepted by the existing entry points; the note "group:" beside each one says what it does
+ * with a group.  Fan-out calls run on every member in order (hipSetDevice per member) and stop at the first member
+ * that fails; renders are enqueued on every member's stream before anything waits, so distinct devices run
+ * concurrently.  The vx_read_* calls gather: one de-tile on the display device (device_ids[0]) reads every member's
+ * slab in place -- over xGMI for another device -- after its stream has waited on an event recorded behind each
+ * member's last render.  A member's error is reported on the group handle: vx_last_error(group) starts with
+ * "member <i> (device <d>): ".  vx_destroy(group) releases every member.
+ * Distinct devices: peer access from device_ids[0] to each other device is enabled here; a device it cannot reach
+ * fails with VX_ERR_NO_DEVICE (there is no staging-copy fallback).  Repeated ids need no peer access.
+ * 1 <= n <= VX_GROUP_MAX, else VX_ERR_INVALID before any device is touched (also for NULL device_ids / out_ctx). */
+#define VX_GROUP_MAX 64
+int vx_create_group(const int* device_ids, int n, VxContext** out_ctx);
+
 void vx_destroy(VxContext* ctx);
-/* message of the last failed call on ctx (ctx may be NULL for vx_create failures) */
+/* message of the last failed call on ctx (ctx may be NULL for vx_create / vx_create_group failures) */
 const char* vx_last_error(const VxContext* ctx);
 
 /* run all work of this context on an existing HIP stream (hipStream_t passed as void*);
- * NULL = the context's own stream.  Lets a torch/RCCL host order copies and collectives. */
+ * NULL = the context's own stream.  Lets a torch/RCCL host order copies and collectives.
+ * group: refused (VX_ERR_INVALID), every member owns its stream. */
 int vx_set_stream(VxContext* ctx, void* hip_stream);
 
 /* ---- volume upload: replaces setupFromGrid's four texImage3D groups
  *      (viewer.ts:1106-1142); arguments are field-for-field WasmWorkerMessageDicomReturn
  *      (common.ts:37-55).  `range` and the mips are the LE u16 stream [max,min] per brick
- *      (brick.rs:19-23,357-359).  n_mips must be 3 (brick.rs:13).  */
+ *      (brick.rs:19-23,357-359).  n_mips must be 3 (brick.rs:13).  group: fan out.  */
 int vx_upload_volume(VxContext* ctx,
                      const uint32_t* indirection, const uint32_t indirection_size[3],
                      const uint16_t* range, const uint32_t range_size[3],
@@ -197,45 +214,47 @@ int vx_upload_volume(VxContext* ctx,
  * both inside the call), host bytes moved over PCIe, and whether the atlas could be pinned in place
  * (hipHostRegister) so that the copy engine read it directly -- the "pin/upload volumes to HBM" step.
  * The atlas goes in chunks of whole 8-slice layers and the layout of the brick layers a chunk completes is
- * built behind it on a second stream.  Any out pointer may be NULL. */
+ * built behind it on a second stream.  Any out pointer may be NULL.  group: member 0's upload. */
 int vx_upload_stats(VxContext* ctx, double* seconds, uint64_t* host_bytes, int* pinned);
 
 /* the same straight from a native brick grid (volxel_brick.h): a C / Rust host that built the grid
  * with vxb_read_dicoms_to_grid or vxb_build_from_u16 uploads it without the copy-out of
- * worker.ts:19-58.  The grid stays owned by the caller (vxb_free afterwards). */
+ * worker.ts:19-58.  The grid stays owned by the caller (vxb_free afterwards).  group: fan out. */
 struct VxBrickGrid;
 int vx_upload_brick_grid(VxContext* ctx, const struct VxBrickGrid* grid);
 
 /* select the device layout the trilinear modes sample from (default VX_LAYOUT_AUTO);
- * takes effect at the next vx_upload_volume or immediately if a volume is resident. */
+ * takes effect at the next vx_upload_volume or immediately if a volume is resident.  group: fan out. */
 int vx_set_layout(VxContext* ctx, int layout);
 
 /* ---- transfer function: replaces changeTransferFunc's texImage2D (viewer.ts:1147-1153);
- *      rgba = length x 4 floats, sampled NEAREST + CLAMP_TO_EDGE (viewer.ts:386-389). */
+ *      rgba = length x 4 floats, sampled NEAREST + CLAMP_TO_EDGE (viewer.ts:386-389).
+ *      group: fan out. */
 int vx_upload_transfer(VxContext* ctx, const float* rgba, uint32_t length);
 
 /* ---- environment map: replaces `new Environment(gl, env)` (representation/environment.ts:15-61,
  *      viewer.ts:1076-1077): rgba = width*height*4 floats with row 0 = TOP, exactly the `floats` of
  *      WasmWorkerMessageEnvReturn (the library applies the UNPACK_FLIP_Y_WEBGL of environment.ts:30-32);
  *      builds the 512x512 importance map (shaders/envSetup.frag, 8x8 taps per texel) and its mip
- *      chain on the device.  Needed before VxParams.use_env = 1.  Passing rgba = NULL removes it. */
+ *      chain on the device.  Needed before VxParams.use_env = 1.  Passing rgba = NULL removes it.  group: fan out. */
 int vx_upload_environment(VxContext* ctx, const float* rgba, uint32_t width, uint32_t height);
-/* test hook: the importance pyramid, 349525 floats (levels 0..9 of the 512^2 map back to back) */
+/* test hook: the importance pyramid, 349525 floats (levels 0..9 of the 512^2 map back to back).  group: member 0. */
 int vx_debug_read_importance(VxContext* ctx, float* out);
 
 /* ---- uniforms: replaces bindUniforms + Camera.bindAsUniforms (viewer.ts:1295-1357,
- *      scene.ts:53-56). */
+ *      scene.ts:53-56).
+ *      group: fan out; member i gets shard_rank = i, shard_count = n.  Params with shard_count != 1 are refused. */
 int vx_set_params(VxContext* ctx, const VxParams* params);
 
 /* ---- framebuffers: replaces resizeFramebuffersToCanvas / the two RGBA32F ping-pong
- *      FBOs (viewer.ts:294-324).  Clears the accumulation. */
+ *      FBOs (viewer.ts:294-324).  Clears the accumulation.  group: fan out. */
 int vx_resize(VxContext* ctx, uint32_t width, uint32_t height);
 
 /* ---- one accumulation sample: replaces gl.drawArrays(TRIANGLE_STRIP,0,4) of the
  *      path-tracing program (viewer.ts:1208-1211) including the running-mean blend
  *      out = w*prev + (1-w)*result (fragment.frag:158); frame_index = u_frame_index,
  *      sample_weight = u_sample_weight (viewer.ts:1351,1356).  Asynchronous on the
- *      context's stream. */
+ *      context's stream.  group: fan out. */
 int vx_render_frame(VxContext* ctx, uint32_t frame_index, float sample_weight);
 
 /* The same for `count` consecutive accumulation frames (weights[i] = u_sample_weight of frame
@@ -243,7 +262,7 @@ int vx_render_frame(VxContext* ctx, uint32_t frame_index, float sample_weight);
  * own result buffer.  Accumulation frames are independent given their index; only the running mean is
  * ordered and it is applied afterwards, in order -- the accumulator is bit-identical to `count` calls of
  * vx_render_frame.  Needs in_flight x (framebuffer + counters) of extra device memory.
- * [build] no reference counterpart: WebGL2 draws are serialised. */
+ * [build] no reference counterpart: WebGL2 draws are serialised.  group: fan out. */
 int vx_render_frames(VxContext* ctx, uint32_t first_frame, uint32_t count, const float* weights, int in_flight);
 
 /* ---- multi-GPU load balance (no counterpart in the reference).  By default tile t of the 64x64 tile grid
@@ -254,18 +273,20 @@ int vx_render_frames(VxContext* ctx, uint32_t first_frame, uint32_t count, const
  *      restart the accumulation (frame 0) afterwards.  vx_probe_tile_costs fills costs[t] with a cost
  *      estimate of every tile of the image (DVR samples of 64 probe rays per tile, current volume /
  *      transfer function / params) -- the same numbers on every rank, so sorting them gives every rank the
- *      same order without communication. */
+ *      same order without communication.
+ *      group: vx_probe_tile_costs runs on member 0 (every member derives the same costs); vx_set_tile_order fans out. */
 int vx_probe_tile_costs(VxContext* ctx, uint32_t* costs, uint32_t n_tiles);
 int vx_set_tile_order(VxContext* ctx, const uint32_t* perm, uint32_t n_tiles);
 
-/* current framebuffer size (what vx_read_accum / vx_read_display will write) */
+/* current framebuffer size (what vx_read_accum / vx_read_display will write).  group: member 0's (all are equal). */
 int vx_render_size(VxContext* ctx, uint32_t* width, uint32_t* height);
 
-/* ---- synchronise: replaces gl.finish() (viewer.ts:1214,1289) */
+/* ---- synchronise: replaces gl.finish() (viewer.ts:1214,1289).  group: fan out. */
 int vx_finish(VxContext* ctx);
 
 /* ---- readback of the accumulation buffer (what blit.frag samples as u_result),
- *      width*height*4 floats, row 0 = bottom.  Synchronises. */
+ *      width*height*4 floats, row 0 = bottom.  Synchronises.
+ *      group (also the two display calls): gather every member's shard, then act like one context. */
 int vx_read_accum(VxContext* ctx, float* rgba_out);
 /* ---- display pass: replaces the blit program (blit.frag:17-35, viewer.ts:1259-1265):
  *      Hable tonemap + gamma, RGBA8, width*height*4 bytes.  Synchronises. */
@@ -278,7 +299,8 @@ int vx_read_display_scaled(VxContext* ctx, uint8_t* rgba8_out, uint32_t out_w, u
                            float exposure, float gamma);
 
 /* device-side views for a zero-copy host (torch / RCCL gather): the tile-major slab this
- * shard owns (floats = vx_slab_floats) and a de-tiling pass from a gathered set of slabs. */
+ * shard owns (floats = vx_slab_floats) and a de-tiling pass from a gathered set of slabs.
+ * group: all three refused (VX_ERR_INVALID): a group has no single slab. */
 int vx_slab_info(VxContext* ctx, uint64_t* slab_floats, uint32_t* tiles_per_shard);
 int vx_slab_device_ptr(VxContext* ctx, void** dev_ptr);
 /* gathered = shard_count slabs back to back (device pointer); writes row-major W*H*4 floats
@@ -286,11 +308,17 @@ int vx_slab_device_ptr(VxContext* ctx, void** dev_ptr);
 int vx_detile(VxContext* ctx, const void* gathered_dev, void* image_out_dev);
 
 /* ---- counters: the benchmark harness of viewer.ts:1213-1252 measures wall time around
- *      gl.finish(); here the kernel is bracketed by HIP events on its own stream. */
+ *      gl.finish(); here the kernel is bracketed by HIP events on its own stream.
+ *      group: vx_reset_counters fans out.  vx_get_counters combines the members': the work counters samples, rays,
+ *      pixels, skip_steps, grad_samples, tf_samples, lane_slots, active_lane_slots, gathers, lds_reads, launches and
+ *      merge_launches are summed; frames, min_launch_frames and max_launch_frames are member 0's (every member renders
+ *      the same frames); kernel_ms, last_kernel_ms and merge_ms are the maximum over the members (the slowest device
+ *      bounds the wall time). */
 int vx_get_counters(VxContext* ctx, VxCounters* out);
 int vx_reset_counters(VxContext* ctx);
 
-/* library / device facts for logs (viewer.ts:225-242 device record) */
+/* library / device facts for logs (viewer.ts:225-242 device record).  group: member 0 (the display device).
+ * The test and measurement hooks below (vx_debug_*, vx_probe_*) also run on member 0 of a group. */
 int vx_device_info(VxContext* ctx, char* name_out, uint32_t name_cap, uint32_t* cu_count,
                    uint64_t* hbm_bytes);
 const char* vx_version(void);

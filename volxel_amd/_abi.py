@@ -92,6 +92,7 @@ def load_library():
     P = C.POINTER
     sig = {
         "vx_create": ([i32, P(vp)], i32),
+        "vx_create_group": ([P(i32), i32, P(vp)], i32),
         "vx_destroy": ([vp], None),
         "vx_last_error": ([vp], C.c_char_p),
         "vx_set_stream": ([vp, vp], i32),

@@ -132,7 +132,16 @@ struct VxContext {
   DevCounters* pipe_dc_pool = nullptr;
   size_t pipe_quads = 0, pipe_waves = 0;
   uint32_t pipe_slots = 0;
+  // the slab table the detile kernel reads (one entry per shard, on this device); slab_table_host is what it holds
+  const float4** slab_table = nullptr;
+  size_t slab_table_cap = 0;
+  std::vector<const float4*> slab_table_host;
+  // device group (vx_create_group): member i renders shard i of members.size(); empty for a plain context
+  std::vector<VxContext*> members;
+  hipEvent_t done = nullptr;   // a member's: recorded after its last render, waited on by the display stream
 };
+
+static bool is_group(const VxContext* c) { return !c->members.empty(); }
 
 #define VX_FAIL(ctx, code, ...)                       \
   do {                                                \
@@ -602,6 +611,86 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
   return VX_OK;
 }
 
+// ---- device groups (vx_create_group): the entry points fan out to the members, read member 0, or gather --------
+// a member's failure, reported on the group handle with the member's index and device
+static int member_fail(VxContext* g, size_t i, int rc) {
+  char head[64];
+  snprintf(head, sizeof head, "member %zu (device %d): ", i, g->members[i]->device);
+  g->err = head + g->members[i]->err;
+  return rc;
+}
+template <class F>
+static int fan_out(VxContext* g, F&& f) {
+  for (size_t i = 0; i < g->members.size(); ++i)
+    if (int rc = f(g->members[i], i)) return member_fail(g, i, rc);
+  return VX_OK;
+}
+static int on_member0(VxContext* g, int rc) { return rc ? member_fail(g, 0, rc) : VX_OK; }
+static int refuse_group(VxContext* g, const char* fn, const char* why) {
+  VX_FAIL(g, VX_ERR_INVALID, "%s: not for a device group (%s)", fn, why);
+}
+
+// point the detile kernel's table at these slabs (entries in stream order: rewritten only when they change)
+static int set_slab_table(VxContext* c, const std::vector<const float4*>& t) {
+  if (t == c->slab_table_host) return VX_OK;
+  c->slab_table_host.clear();
+  VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued de-tile still reads the old table
+  if (t.size() > c->slab_table_cap) {
+    if (c->slab_table) (void)hipFree(c->slab_table);
+    c->slab_table = nullptr;
+    c->slab_table_cap = 0;
+    VX_HIP(c, hipMalloc(&c->slab_table, t.size() * sizeof(float4*)));
+    c->slab_table_cap = t.size();
+  }
+  VX_HIP(c, hipMemcpy(c->slab_table, t.data(), t.size() * sizeof(float4*), hipMemcpyHostToDevice));
+  c->slab_table_host = t;
+  return VX_OK;
+}
+
+// the slabs of the table -> row-major image (W x H float4) on the context's stream
+static int launch_detile(VxContext* c, float4* image) {
+  if (c->slab_table_host.size() != c->tm.shard_count)
+    VX_FAIL(c, VX_ERR_INVALID, "detile: %zu slabs for %u shards", c->slab_table_host.size(), c->tm.shard_count);
+  dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
+  hipLaunchKernelGGL(detile, grid, dim3(256), 0, c->stream, (const float4* const*)c->slab_table, image, c->tm);
+  VX_HIP(c, hipGetLastError());
+  return VX_OK;
+}
+
+// The row-major image the vx_read_* calls read, de-tiled into the image of the context returned through d.  A plain
+// context: its own slab, the tiles of other shards reading as zero.  A group: every member's slab read in place by one
+// de-tile on the display device (member 0), whose stream first waits for each member's last render.
+static int compose_image(VxContext* c, VxContext*& d) {
+  if (!is_group(c)) {
+    d = c;
+    if (!c->slab) VX_FAIL(c, VX_ERR_INVALID, "no framebuffer (vx_resize not called)");
+    std::vector<const float4*> t(c->tm.shard_count, nullptr);
+    t[c->tm.shard_rank] = c->slab;
+    int rc = set_slab_table(c, t);
+    return rc ? rc : launch_detile(c, c->image);
+  }
+  d = c->members[0];
+  if (!d->has_params) VX_FAIL(c, VX_ERR_INVALID, "a device group is read after vx_set_params (which deals the shards)");
+  std::vector<const float4*> t(c->members.size());
+  for (size_t i = 0; i < t.size(); ++i) {
+    VxContext* m = c->members[i];
+    if (!m->slab) VX_FAIL(c, VX_ERR_INVALID, "member %zu (device %d): no framebuffer (vx_resize not called)", i, m->device);
+    if (m->W != d->W || m->H != d->H || m->tm.shard_count != t.size())
+      VX_FAIL(c, VX_ERR_INVALID, "member %zu (device %d): framebuffer differs from member 0's", i, m->device);
+    t[i] = m->slab;
+  }
+  VX_HIP(c, hipSetDevice(d->device));
+  if (int rc = set_slab_table(d, t)) return member_fail(c, 0, rc);
+  for (size_t i = 1; i < t.size(); ++i) {
+    VxContext* m = c->members[i];
+    VX_HIP(c, hipSetDevice(m->device));
+    VX_HIP(c, hipEventRecord(m->done, m->stream));
+  }
+  VX_HIP(c, hipSetDevice(d->device));
+  for (size_t i = 1; i < t.size(); ++i) VX_HIP(c, hipStreamWaitEvent(d->stream, c->members[i]->done, 0));
+  return on_member0(c, launch_detile(d, d->image));
+}
+
 extern "C" {
 
 const char* vx_version(void) { return "volxel_hip 0.1 (gfx950)"; }
@@ -677,8 +766,76 @@ int vx_create(int device_id, VxContext** out) {
   return VX_OK;
 }
 
+int vx_create_group(const int* device_ids, int n, VxContext** out) {
+  if (out) *out = nullptr;
+  if (!device_ids || !out || n < 1 || n > VX_GROUP_MAX) {
+    g_create_error = "vx_create_group: need device_ids, 1 <= n <= 64 and out_ctx";
+    return VX_ERR_INVALID;
+  }
+  VxContext* g = new VxContext();
+  g->device = device_ids[0];
+  auto drop = [g] {   // the members made so far (a group without members is not a context yet)
+    for (VxContext* m : g->members) vx_destroy(m);
+    delete g;
+  };
+  for (int i = 0; i < n; ++i) {
+    VxContext* m = nullptr;
+    int rc = vx_create(device_ids[i], &m);
+    if (rc == VX_OK && hipEventCreateWithFlags(&m->done, hipEventDisableTiming) != hipSuccess) {
+      vx_destroy(m);
+      g_create_error = "event creation failed";
+      rc = VX_ERR_DEVICE;
+    }
+    if (rc) {
+      char head[80];
+      snprintf(head, sizeof head, "vx_create_group: member %d (device %d): ", i, device_ids[i]);
+      g_create_error = head + g_create_error;
+      drop();
+      return rc;
+    }
+    g->members.push_back(m);
+  }
+  // the gather runs on device_ids[0] and reads every other device's slab in place: peer access, no staging copy
+  const int d0 = device_ids[0];
+  for (int i = 1; i < n; ++i) {
+    const int d = device_ids[i];
+    if (d == d0 || std::find(device_ids + 1, device_ids + i, d) != device_ids + i) continue;
+    int can = 0;
+    hipError_t e = hipDeviceCanAccessPeer(&can, d0, d);
+    if (e == hipSuccess && !can) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "vx_create_group: device %d cannot access device %d as a peer", d0, d);
+      g_create_error = buf;
+      drop();
+      return VX_ERR_NO_DEVICE;
+    }
+    if (e == hipSuccess) e = hipSetDevice(d0);
+    if (e == hipSuccess) {
+      e = hipDeviceEnablePeerAccess(d, 0);
+      if (e == hipErrorPeerAccessAlreadyEnabled) {
+        (void)hipGetLastError();
+        e = hipSuccess;
+      }
+    }
+    if (e != hipSuccess) {
+      g_create_error = std::string("vx_create_group: peer access from device ") + std::to_string(d0) + " to " +
+                       std::to_string(d) + ": " + hipGetErrorString(e);
+      drop();
+      return VX_ERR_DEVICE;
+    }
+  }
+  g->prop = g->members[0]->prop;
+  *out = g;
+  return VX_OK;
+}
+
 void vx_destroy(VxContext* c) {
   if (!c) return;
+  if (is_group(c)) {
+    for (VxContext* m : c->members) vx_destroy(m);
+    delete c;
+    return;
+  }
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   drain_events(c);
@@ -701,6 +858,8 @@ void vx_destroy(VxContext* c) {
   if (c->order) (void)hipFree(c->order);
   if (c->pipe_result_pool) (void)hipFree(c->pipe_result_pool);
   if (c->pipe_dc_pool) (void)hipFree(c->pipe_dc_pool);
+  if (c->slab_table) (void)hipFree(c->slab_table);
+  if (c->done) (void)hipEventDestroy(c->done);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -710,6 +869,7 @@ const char* vx_last_error(const VxContext* c) { return c ? c->err.c_str() : g_cr
 
 int vx_set_stream(VxContext* c, void* s) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_set_stream", "each member owns its stream");
   VX_DEV(c);
   (void)hipStreamSynchronize(c->stream);
   c->stream = s ? (hipStream_t)s : c->own_stream;
@@ -904,6 +1064,11 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
                      const uint32_t atlas_size[3], int n_mips, const uint16_t* const* mip_data,
                      const uint32_t (*mip_size)[3], const uint32_t index_extent[3]) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c))
+    return fan_out(c, [&](VxContext* m, size_t) {
+      return vx_upload_volume(m, indirection, ind_size, range, range_size, atlas, atlas_size, n_mips, mip_data, mip_size,
+                              index_extent);
+    });
   VX_DEV(c);
   if (!indirection || !range || !ind_size || !range_size || !atlas_size || !index_extent)
     VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: null argument");
@@ -1051,6 +1216,7 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
 
 int vx_upload_stats(VxContext* c, double* seconds, uint64_t* host_bytes, int* pinned) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_upload_stats(c->members[0], seconds, host_bytes, pinned));
   if (seconds) *seconds = c->upload_seconds;
   if (host_bytes) *host_bytes = c->upload_host_bytes;
   if (pinned) *pinned = c->upload_pinned;
@@ -1078,6 +1244,7 @@ int vx_upload_brick_grid(VxContext* c, const VxBrickGrid* g) {
 
 int vx_set_layout(VxContext* c, int layout) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_set_layout(m, layout); });
   VX_DEV(c);
   if (layout != VX_LAYOUT_REFERENCE && layout != VX_LAYOUT_CELLQUAD && layout != VX_LAYOUT_BRICKF32 &&
       layout != VX_LAYOUT_AUTO && layout != VX_LAYOUT_BRICKU8)
@@ -1095,6 +1262,7 @@ int vx_set_layout(VxContext* c, int layout) {
 
 int vx_upload_transfer(VxContext* c, const float* rgba, uint32_t length) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_upload_transfer(m, rgba, length); });
   VX_DEV(c);
   if (!rgba || length == 0) VX_FAIL(c, VX_ERR_INVALID, "vx_upload_transfer: empty transfer function");
   // the DVR composite runs straight-line for every lane of a wave step (a lane that does not contribute adds
@@ -1117,6 +1285,7 @@ int vx_upload_transfer(VxContext* c, const float* rgba, uint32_t length) {
 
 int vx_upload_environment(VxContext* c, const float* rgba, uint32_t w, uint32_t h) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_upload_environment(m, rgba, w, h); });
   VX_HIP(c, hipSetDevice(c->device));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   if (c->env_tex) (void)hipFree(c->env_tex);
@@ -1158,6 +1327,7 @@ int vx_upload_environment(VxContext* c, const float* rgba, uint32_t w, uint32_t 
 
 int vx_debug_read_importance(VxContext* c, float* out) {
   if (!c || !out) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_debug_read_importance(c->members[0], out));
   VX_DEV(c);
   if (!c->env_imp) VX_FAIL(c, VX_ERR_INVALID, "vx_debug_read_importance: no environment uploaded");
   VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -1167,6 +1337,16 @@ int vx_debug_read_importance(VxContext* c, float* out) {
 
 int vx_set_params(VxContext* c, const VxParams* p) {
   if (!c || !p) return VX_ERR_INVALID;
+  if (is_group(c)) {   // the group deals the shards: member i renders shard i of n
+    if (p->shard_count != 1)
+      VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: a device group shards itself; pass shard_count 1, not %d", p->shard_count);
+    return fan_out(c, [&](VxContext* m, size_t i) {
+      VxParams q = *p;
+      q.shard_rank = (int32_t)i;
+      q.shard_count = (int32_t)c->members.size();
+      return vx_set_params(m, &q);
+    });
+  }
   VX_DEV(c);
   if (p->render_mode < VX_MODE_DEFAULT || p->render_mode > VX_MODE_DVR_PHONG)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: unknown render mode %d", p->render_mode);
@@ -1197,6 +1377,7 @@ int vx_set_params(VxContext* c, const VxParams* p) {
 
 int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_resize(m, w, h); });
   if (w == 0 || h == 0 || w > 16384 || h > 16384) VX_FAIL(c, VX_ERR_INVALID, "vx_resize: bad size %ux%u", w, h);
   VX_HIP(c, hipSetDevice(c->device));
   VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -1331,6 +1512,7 @@ static int take_events(VxContext* c, EventPair& ev) {
 
 int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_render_frame(m, frame_index, sample_weight); });
   VX_DEV(c);
   dim3 grid;
   int rc = prepare_render(c, grid);
@@ -1389,6 +1571,8 @@ static int ensure_pipes(VxContext* c, uint32_t n) {
 // the bulk of the next ones.
 int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const float* weights, int in_flight) {
   if (!c || (!weights && count)) return VX_ERR_INVALID;
+  if (is_group(c))   // enqueued on every member's stream, no wait: distinct devices render concurrently
+    return fan_out(c, [&](VxContext* m, size_t) { return vx_render_frames(m, first_frame, count, weights, in_flight); });
   VX_DEV(c);
   if (in_flight > MERGE_MAX) in_flight = MERGE_MAX;
   uint32_t done = 0;
@@ -1453,6 +1637,7 @@ int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const f
 
 int vx_finish(VxContext* c) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_finish(m); });
   VX_DEV(c);
   VX_HIP(c, hipStreamSynchronize(c->stream));
   return VX_OK;
@@ -1460,37 +1645,22 @@ int vx_finish(VxContext* c) {
 
 int vx_detile(VxContext* c, const void* gathered, void* image_out) {
   if (!c || !gathered || !image_out) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_detile", "it has no single slab; vx_read_* gather the members");
   VX_DEV(c);
-  dim3 grid((c->W + 15) / 16, (c->H + 15) / 16);
-  hipLaunchKernelGGL(detile, grid, dim3(256), 0, c->stream, (const float4*)gathered, (float4*)image_out, c->tm);
-  VX_HIP(c, hipGetLastError());
-  return VX_OK;
-}
-
-// own slab -> row-major image; for a sharded context the tiles of other shards read as zero
-static int own_image(VxContext* c) {
-  if (!c->slab) VX_FAIL(c, VX_ERR_INVALID, "no framebuffer (vx_resize not called)");
-  if (c->tm.shard_count == 1) return vx_detile(c, c->slab, c->image);
-  // build a temporary gathered buffer with only this shard's slab filled
-  size_t slab_bytes = c->slab_quads * sizeof(float4);
-  void* tmp = nullptr;
-  VX_HIP(c, hipMalloc(&tmp, slab_bytes * c->tm.shard_count));
-  VX_HIP(c, hipMemsetAsync(tmp, 0, slab_bytes * c->tm.shard_count, c->stream));
-  VX_HIP(c, hipMemcpyAsync((char*)tmp + slab_bytes * c->tm.shard_rank, c->slab, slab_bytes,
-                           hipMemcpyDeviceToDevice, c->stream));
-  int rc = vx_detile(c, tmp, c->image);
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  return rc;
+  std::vector<const float4*> t(c->tm.shard_count);
+  for (size_t s = 0; s < t.size(); ++s) t[s] = (const float4*)gathered + s * c->slab_quads;
+  int rc = set_slab_table(c, t);
+  return rc ? rc : launch_detile(c, (float4*)image_out);
 }
 
 int vx_read_accum(VxContext* c, float* out) {
   if (!c || !out) return VX_ERR_INVALID;
   VX_DEV(c);
-  int rc = own_image(c);
+  VxContext* d = nullptr;
+  int rc = compose_image(c, d);
   if (rc) return rc;
-  VX_HIP(c, hipMemcpyAsync(out, c->image, (size_t)c->W * c->H * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
+  VX_HIP(c, hipMemcpyAsync(out, d->image, (size_t)d->W * d->H * sizeof(float4), hipMemcpyDeviceToHost, d->stream));
+  VX_HIP(c, hipStreamSynchronize(d->stream));
   return VX_OK;
 }
 
@@ -1501,31 +1671,34 @@ int vx_read_display_scaled(VxContext* c, uint8_t* out, uint32_t ow, uint32_t oh,
     c->err = "vx_read_display_scaled: bad canvas size";
     return VX_ERR_INVALID;
   }
-  int rc = own_image(c);
+  VxContext* d = nullptr;
+  int rc = compose_image(c, d);
   if (rc) return rc;
   uint32_t n = ow * oh;
-  if (n > c->display_cap) {
-    if (c->display) (void)hipFree(c->display);
-    c->display = nullptr;
-    c->display_cap = 0;
-    VX_HIP(c, hipMalloc(&c->display, (size_t)n * sizeof(uchar4)));
-    c->display_cap = n;
+  if (n > d->display_cap) {
+    if (d->display) (void)hipFree(d->display);
+    d->display = nullptr;
+    d->display_cap = 0;
+    VX_HIP(c, hipMalloc(&d->display, (size_t)n * sizeof(uchar4)));
+    d->display_cap = n;
   }
-  hipLaunchKernelGGL(blit_rgba8, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->image, c->display, c->W, c->H,
+  hipLaunchKernelGGL(blit_rgba8, dim3((n + 255) / 256), dim3(256), 0, d->stream, d->image, d->display, d->W, d->H,
                      ow, oh, exposure, gamma);
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipMemcpyAsync(out, c->display, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
+  VX_HIP(c, hipMemcpyAsync(out, d->display, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+  VX_HIP(c, hipStreamSynchronize(d->stream));
   return VX_OK;
 }
 
 int vx_read_display(VxContext* c, uint8_t* out, float exposure, float gamma) {
   if (!c) return VX_ERR_INVALID;
-  return vx_read_display_scaled(c, out, c->W, c->H, exposure, gamma);
+  const VxContext* d = is_group(c) ? c->members[0] : c;
+  return vx_read_display_scaled(c, out, d->W, d->H, exposure, gamma);
 }
 
 int vx_probe_tile_costs(VxContext* c, uint32_t* costs, uint32_t n) {
   if (!c || !costs) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_probe_tile_costs(c->members[0], costs, n));   // every member derives the same costs
   VX_DEV(c);
   if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_probe_tile_costs: no volume uploaded");
   if (!c->has_params || !c->tf || !c->W) VX_FAIL(c, VX_ERR_INVALID, "vx_probe_tile_costs: params, transfer function and size first");
@@ -1549,6 +1722,7 @@ int vx_probe_tile_costs(VxContext* c, uint32_t* costs, uint32_t n) {
 
 int vx_set_tile_order(VxContext* c, const uint32_t* perm, uint32_t n) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_set_tile_order(m, perm, n); });
   VX_DEV(c);
   if (!c->W) VX_FAIL(c, VX_ERR_INVALID, "vx_set_tile_order: vx_resize first");
   VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -1580,6 +1754,7 @@ int vx_set_tile_order(VxContext* c, const uint32_t* perm, uint32_t n) {
 
 int vx_render_size(VxContext* c, uint32_t* w, uint32_t* h) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) c = c->members[0];
   if (w) *w = c->W;
   if (h) *h = c->H;
   return VX_OK;
@@ -1587,6 +1762,7 @@ int vx_render_size(VxContext* c, uint32_t* w, uint32_t* h) {
 
 int vx_slab_info(VxContext* c, uint64_t* slab_floats, uint32_t* tiles_per_shard) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_slab_info", "it has no single slab");
   if (slab_floats) *slab_floats = (uint64_t)c->slab_quads * 4u;
   if (tiles_per_shard) *tiles_per_shard = c->tm.tiles_per_shard;
   return VX_OK;
@@ -1594,12 +1770,41 @@ int vx_slab_info(VxContext* c, uint64_t* slab_floats, uint32_t* tiles_per_shard)
 
 int vx_slab_device_ptr(VxContext* c, void** p) {
   if (!c || !p) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_slab_device_ptr", "it has no single slab");
   *p = c->slab;
   return VX_OK;
 }
 
 int vx_get_counters(VxContext* c, VxCounters* out) {
   if (!c || !out) return VX_ERR_INVALID;
+  if (is_group(c)) {   // work summed; frames from member 0 (all render the same frames); times: the slowest member
+    VxCounters t{};
+    return fan_out(c, [&](VxContext* m, size_t i) {
+      VxCounters k{};
+      if (int rc = vx_get_counters(m, &k)) return rc;
+      if (i == 0) {
+        t = k;
+      } else {
+        t.samples += k.samples;
+        t.rays += k.rays;
+        t.pixels += k.pixels;
+        t.skip_steps += k.skip_steps;
+        t.grad_samples += k.grad_samples;
+        t.tf_samples += k.tf_samples;
+        t.lane_slots += k.lane_slots;
+        t.active_lane_slots += k.active_lane_slots;
+        t.gathers += k.gathers;
+        t.lds_reads += k.lds_reads;
+        t.launches += k.launches;
+        t.merge_launches += k.merge_launches;
+        t.kernel_ms = std::max(t.kernel_ms, k.kernel_ms);
+        t.last_kernel_ms = std::max(t.last_kernel_ms, k.last_kernel_ms);
+        t.merge_ms = std::max(t.merge_ms, k.merge_ms);
+      }
+      if (i + 1 == c->members.size()) *out = t;
+      return VX_OK;
+    });
+  }
   VX_DEV(c);
   VX_HIP(c, hipStreamSynchronize(c->stream));
   drain_events(c);
@@ -1628,6 +1833,7 @@ int vx_get_counters(VxContext* c, VxCounters* out) {
 
 int vx_reset_counters(VxContext* c) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_reset_counters(m); });
   VX_DEV(c);
   VX_HIP(c, hipStreamSynchronize(c->stream));
   drain_events(c);
@@ -1646,6 +1852,7 @@ int vx_reset_counters(VxContext* c) {
 
 int vx_device_info(VxContext* c, char* name, uint32_t cap, uint32_t* cus, uint64_t* hbm) {
   if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) c = c->members[0];
   if (name && cap) {
     snprintf(name, cap, "%s (%s)", c->prop.name, c->prop.gcnArchName);
   }
@@ -1674,6 +1881,7 @@ int vx_debug_build_skip_mask(const uint32_t* range_packed, const uint32_t brick_
 // test hook: random.glsl on the device
 int vx_debug_rng(VxContext* c, int op, const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* out) {
   if (!c || !a || !out || n == 0 || n > 65536u || op < 0 || op > 4 || (op == 0 && !b)) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_debug_rng(c->members[0], op, a, b, n, out));
   VX_DEV(c);
   const uint32_t n_in = op < 2 ? n : 1u;
   uint32_t *da = nullptr, *db = nullptr, *dout = nullptr;
@@ -1698,6 +1906,7 @@ int vx_debug_rng(VxContext* c, int op, const uint32_t* a, const uint32_t* b, uin
 // measurement hook: what the vector ALUs of this device sustain -- clocks (nominal) per wave64 VALU instruction per SIMD
 int vx_probe_valu_rate(VxContext* c, double* clk_out, uint32_t* clock_khz_out) {
   if (!c || !clk_out) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_probe_valu_rate(c->members[0], clk_out, clock_khz_out));
   VX_DEV(c);
   float* sink = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1728,6 +1937,7 @@ int vx_probe_valu_rate(VxContext* c, double* clk_out, uint32_t* clock_khz_out) {
 // measurement hook: L1 gather rate for a given number of distinct lines per gather instruction
 int vx_probe_gather_rate(VxContext* c, uint32_t lines, uint32_t distinct, double* clk_out, uint32_t* clock_khz_out) {
   if (!c || !clk_out || lines < 1u || lines > 64u || distinct < 1u || distinct > lines) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_probe_gather_rate(c->members[0], lines, distinct, clk_out, clock_khz_out));
   VX_DEV(c);
   float4* table = nullptr;
   float* sink = nullptr;
@@ -1762,6 +1972,7 @@ int vx_probe_gather_rate(VxContext* c, uint32_t lines, uint32_t distinct, double
 // measurement hook: distinct lines per gather of the tuned cellquad DVR march (one frame, nothing is stored)
 int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3]) {
   if (!c || !out3) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_probe_gather_spread(c->members[0], frame_index, out3));
   VX_DEV(c);
   dim3 grid;
   int rc = prepare_render(c, grid);
@@ -1798,6 +2009,7 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
 // test hook (not part of the reference boundary): the device's unorm8 decode table
 int vx_debug_unorm_table(VxContext* c, float* out256) {
   if (!c || !out256) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_debug_unorm_table(c->members[0], out256));
   VX_DEV(c);
   float* d = nullptr;
   VX_HIP(c, hipMalloc(&d, 256 * sizeof(float)));

@@ -556,21 +556,28 @@ __global__ __launch_bounds__(256) void merge_results(float4* __restrict__ slab, 
 }
 
 // ---- slab(s) -> row-major image --------------------------------------------------------
-// gathered = shard_count slabs back to back (each tiles_per_shard*4096 float4)
-__global__ __launch_bounds__(256) void detile(const float4* __restrict__ gathered,
+// table[s] = the slab of shard s (tiles_per_shard*4096 float4), in this device's HBM or in a peer's over xGMI; a null
+// entry reads as zero.  A 256-thread block covers a 16x16 pixel square as four 8x8 wave blocks: the wave block is 64
+// consecutive float4 of one slab (lane = (y & 7) * 8 + (x & 7)), so each lane reads one 16-byte element and the wave one
+// contiguous 1 KiB run.  The square lies inside one 64x64 tile, so the tile, its shard and the table entry are the
+// same for the whole block: scalar loads, and a scalar branch on a null entry.
+__global__ __launch_bounds__(256) void detile(const float4* const* __restrict__ table,
                                                float4* __restrict__ image, const TileMap tm) {
-  uint32_t x = blockIdx.x * 16u + (threadIdx.x & 15u);
-  uint32_t y = blockIdx.y * 16u + (threadIdx.x >> 4);
+  const uint32_t t = (blockIdx.y >> 2) * tm.tiles_x + (blockIdx.x >> 2);
+  const uint32_t pos = tm.inv ? tm.inv[t] : t;
+  const uint32_t shard = pos % tm.shard_count, lt = pos / tm.shard_count;
+  const float4* __restrict__ src = table[shard];
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t wx = ((blockIdx.x & 3u) << 1) | (w & 1u), wy = ((blockIdx.y & 3u) << 1) | (w >> 1);
+  const uint32_t x = wx * 8u + (blockIdx.x >> 2) * 64u + (lane & 7u), y = wy * 8u + (blockIdx.y >> 2) * 64u + (lane >> 3);
   if (x >= tm.W || y >= tm.H) return;
-  uint32_t t = (y >> 6) * tm.tiles_x + (x >> 6);
-  uint32_t pos = tm.inv ? tm.inv[t] : t;
-  uint32_t shard = pos % tm.shard_count, lt = pos / tm.shard_count;
-  uint32_t wx = (x >> 3) & 7u, wy = (y >> 3) & 7u;
-  uint32_t wt = (wx & 1u) | ((wy & 1u) << 1) | ((wx & 2u) << 1) | ((wy & 2u) << 2) |
-                ((wx & 4u) << 2) | ((wy & 4u) << 3);
-  uint32_t lane = (y & 7u) * 8u + (x & 7u);
-  size_t si = ((size_t)shard * tm.tiles_per_shard + lt) * 4096u + wt * 64u + lane;
-  image[(size_t)y * tm.W + x] = gathered[si];
+  const uint32_t wt = (wx & 1u) | ((wy & 1u) << 1) | ((wx & 2u) << 1) | ((wy & 2u) << 2) |
+                      ((wx & 4u) << 2) | ((wy & 4u) << 3);
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+  // a table entry is a plain device pointer: say so (address space 1), or the read goes out as a flat load
+  if (src) v = ((const __attribute__((address_space(1))) f4*)src)[((size_t)lt * 4096u + wt * 64u) + lane];
+  image[(size_t)y * tm.W + x] = make_float4(v.x, v.y, v.z, v.w);
 }
 
 // ---- display pass: blit.frag:17-35 -------------------------------------------------------

@@ -26,8 +26,11 @@ export declare class Environment {          // representation/environment.ts; ro
   static default(): Environment;
 }
 export declare class Volxel3DDicomRenderer {
-  /** layout: 0 reference textures, 1 cellquad, 2 brickf32, 3 (default) per render mode, 4 bricku8 (8-bit bricks decoded at staging) -- include/volxel_hip.h VxLayout */
-  constructor(opts?: { width?: number; height?: number; device?: number; layout?: number; lowResPreview?: boolean });
+  /** layout: 0 reference textures, 1 cellquad, 2 brickf32, 3 (default) per render mode, 4 bricku8 (8-bit bricks decoded at staging) -- include/volxel_hip.h VxLayout.
+   *  device: one GPU (HIP ordinal, default 0).  devices: one image on several GPUs (member i renders shard i, an id
+   *  may repeat); excludes device. */
+  constructor(opts?: { width?: number; height?: number; device?: number; devices?: number[]; layout?: number; lowResPreview?: boolean });
+  readonly devices: number[] | null;
   environment: Environment | null;
   setEnvironment(env: Environment | null): void;
   settings: Record<string, any>; camera: Camera; envStrength: number; frameIndex: number;

@@ -280,9 +280,14 @@ function registerVolxelComponents(worker) {
 
 class Volxel3DDicomRenderer {
   /** width, height: the canvas.  lowResPreview reproduces the viewer's interactive sizing
-   *  (settings.resolutionFactor and the 0.33 ramp of viewer.ts:1167-1188); off = full-size frames. */
-  constructor({ width = 1920, height = 1080, device = 0, layout, lowResPreview = false } = {}) {
-    this.ctx = native.create(device);            // throws when no GPU is visible
+   *  (settings.resolutionFactor and the 0.33 ramp of viewer.ts:1167-1188); off = full-size frames.
+   *  devices: render one image on several GPUs (a device group, member i renders shard i; an id may repeat) in
+   *  place of the one `device`; every other call is the same. */
+  constructor({ width = 1920, height = 1080, device, devices, layout, lowResPreview = false } = {}) {
+    if (devices !== undefined && device !== undefined) throw new Error('pass either device or devices, not both');
+    // throws when no GPU is visible
+    this.ctx = devices !== undefined ? native.createGroup(devices) : native.create(device === undefined ? 0 : device);
+    this.devices = devices !== undefined ? devices.slice() : null;
     this.canvasWidth = width; this.canvasHeight = height;
     this.width = width; this.height = height;    // current render size
     this.lowResPreview = lowResPreview; this.resolutionFactor = 1.0; // viewer.ts:131

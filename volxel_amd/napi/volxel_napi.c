@@ -101,14 +101,8 @@ static void ctx_finalize(napi_env env, void* data, void* hint) {
   free(h);
 }
 
-/* create(deviceId) -> handle */
-static napi_value n_create(napi_env env, napi_callback_info info) {
-  napi_value a[1];
-  if (!get_args(env, info, 1, a)) return NULL;
-  int32_t dev = 0;
-  NAPI_OK(napi_get_value_int32(env, a[0], &dev));
-  VxContext* c = NULL;
-  if (vx_create(dev, &c) != VX_OK) return throw_msg(env, vx_last_error(NULL));
+/* a created context -> JS handle (the context is destroyed if wrapping fails) */
+static napi_value wrap_ctx(napi_env env, VxContext* c) {
   Handle* box = (Handle*)malloc(sizeof(Handle));
   if (!box) {
     vx_destroy(c);
@@ -122,6 +116,43 @@ static napi_value n_create(napi_env env, napi_callback_info info) {
     return throw_msg(env, "volxel_napi: napi_create_external failed");
   }
   return h;
+}
+
+/* create(deviceId) -> handle */
+static napi_value n_create(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  int32_t dev = 0;
+  NAPI_OK(napi_get_value_int32(env, a[0], &dev));
+  VxContext* c = NULL;
+  if (vx_create(dev, &c) != VX_OK) return throw_msg(env, vx_last_error(NULL));
+  return wrap_ctx(env, c);
+}
+
+/* createGroup([deviceId, ...]) -> handle of a device group (vx_create_group: member i renders shard i) */
+static napi_value n_create_group(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  bool is_array = false;
+  uint32_t n = 0;
+  if (napi_is_array(env, a[0], &is_array) != napi_ok || !is_array || napi_get_array_length(env, a[0], &n) != napi_ok ||
+      n < 1 || n > VX_GROUP_MAX) {
+    napi_throw_type_error(env, NULL, "volxel_napi: createGroup expects an array of 1 to 64 device ids");
+    return NULL;
+  }
+  int ids[VX_GROUP_MAX];
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value e;
+    int32_t d = 0;
+    if (napi_get_element(env, a[0], i, &e) != napi_ok || napi_get_value_int32(env, e, &d) != napi_ok) {
+      napi_throw_type_error(env, NULL, "volxel_napi: createGroup expects integer device ids");
+      return NULL;
+    }
+    ids[i] = d;
+  }
+  VxContext* c = NULL;
+  if (vx_create_group(ids, (int)n, &c) != VX_OK) return throw_msg(env, vx_last_error(NULL));
+  return wrap_ctx(env, c);
 }
 
 /* destroy(handle): idempotent */
@@ -581,7 +612,7 @@ static napi_value grid_to_object(napi_env env, VxBrickGrid* g) {
 
 static napi_value init(napi_env env, napi_value exports) {
   static const struct { const char* name; napi_callback fn; } fns[] = {
-      {"create", n_create}, {"destroy", n_destroy}, {"uploadVolume", n_upload_volume},
+      {"create", n_create}, {"createGroup", n_create_group}, {"destroy", n_destroy}, {"uploadVolume", n_upload_volume},
       {"uploadTransfer", n_upload_transfer}, {"uploadEnvironment", n_upload_environment}, {"setParams", n_set_params}, {"sizeofParams", n_sizeof_params},
       {"resize", n_resize}, {"setLayout", n_set_layout}, {"renderFrame", n_render_frame}, {"renderFrames", n_render_frames},
       {"probeTileCosts", n_probe_tile_costs}, {"setTileOrder", n_set_tile_order}, {"deviceInfo", n_device_info}, {"finish", n_finish},

@@ -126,20 +126,36 @@ def register_volxel_components(worker_factory=None):
 class Volxel3DRenderer:
     """Headless counterpart of the `<volxel-3d-viewer>` element's render core."""
 
-    def __init__(self, width: int = 1920, height: int = 1080, device: int = 0,
+    def __init__(self, width: int = 1920, height: int = 1080, device: int | None = None,
                  shard_rank: int = 0, shard_count: int = 1, layout: int | None = None,
-                 low_res_preview: bool = False):
+                 low_res_preview: bool = False, devices=None):
         """width, height: the canvas.  low_res_preview=True reproduces the viewer's interactive
         ramp (viewer.ts:1167-1188): after every restart the first `low_resolution_duration` frames
         are rendered at 0.33 x the canvas and shown NEAREST-magnified; a headless caller that wants
-        full-size frames from frame 0 (tests, bench.py) leaves it off."""
+        full-size frames from frame 0 (tests, bench.py) leaves it off.
+        device: the HIP ordinal (None = 0).  devices: render one image on several GPUs of this process instead
+        (vx_create_group: member i renders shard i, a device may repeat); excludes `device` and shard_count != 1."""
+        self._ctx = None
+        if devices is not None:
+            devices = [int(d) for d in devices]
+            if device is not None:
+                raise ValueError("pass either device or devices, not both")
+            if shard_count != 1 or shard_rank != 0:
+                raise ValueError("a device group deals the shards itself: devices excludes shard_rank / shard_count")
+            if not 1 <= len(devices) <= 64:
+                raise ValueError(f"devices must name 1 to 64 GPUs, not {len(devices)}")
         self._lib = _abi.load_library()
-        self._ctx = C.c_void_p()
-        rc = self._lib.vx_create(int(device), C.byref(self._ctx))
+        ctx = C.c_void_p()
+        if devices is None:
+            rc = self._lib.vx_create(0 if device is None else int(device), C.byref(ctx))
+        else:
+            ids = (C.c_int * len(devices))(*devices)
+            rc = self._lib.vx_create_group(ids, len(devices), C.byref(ctx))
         if rc != 0:
             msg = self._lib.vx_last_error(None)
-            self._ctx = None
             raise VolxelError(msg.decode() if msg else f"vx_create failed ({rc})")
+        self._ctx = ctx
+        self.devices = devices                        # None: one context on one device
         self.settings = ViewerSettings()
         self.camera = Camera(1)                       # viewer.ts:418
         self.volume: Volume | None = None
@@ -599,7 +615,7 @@ class Volxel3DRenderer:
     def balance_tiles(self):
         """probe the tile costs and deal the tiles so that every shard gets an equal share of the work"""
         from .tiles import balanced_order
-        perm = balanced_order(self.probe_tile_costs(), self.shard_count)
+        perm = balanced_order(self.probe_tile_costs(), len(self.devices) if self.devices else self.shard_count)
         self.set_tile_order(perm)
         return perm
 
