@@ -135,6 +135,13 @@ typedef struct VxParams {
      t with t % shard_count == shard_rank, tile = shard_tile x shard_tile pixels        */
   int32_t shard_rank;
   int32_t shard_count;
+
+  /* [build] shadowed DVR ("light grid"): 0 = off (plain DVR, zero-initialised hosts keep it);
+     1, 2 or 4 = stride in voxels of the light grid -- transmittance toward the directional light, built on the device
+     and looked up at every contributing DVR sample (w = dT * T_L).  vx_set_params refuses other values, a non-zero
+     stride with VX_MODE_DVR_PHONG, and a non-zero stride with VX_MODE_DVR and use_env = 1 (an environment map has no
+     single light direction).  The path-traced modes and debug_hits ignore it: they trace real shadows.          */
+  int32_t dvr_shadow_stride;
 } VxParams;
 
 /* exact work counters of the launches since the last vx_reset_counters */
@@ -350,6 +357,18 @@ int vx_probe_valu_rate(VxContext* ctx, double* clk_per_instruction_out, uint32_t
  * (whole wave) and the line look-ups of its 16 groups of 4 consecutive lanes (what the L1 tag pipe sees).
  * Nothing is written to the accumulator.  out3 = {gather instructions, distinct lines, quad look-ups}. */
 int vx_probe_gather_spread(VxContext* ctx, uint32_t frame_index, uint64_t out3[3]);
+
+/* ---- shadowed DVR (VxParams.dvr_shadow_stride != 0, no reference counterpart): the light grid is rebuilt lazily before
+ *      a shadowed DVR launch whenever one of its inputs differs bitwise from the last build (volume or TF upload, light_dir,
+ *      density_transform_inv, the clip box, volume_maj / inv_maj / density_scale, sample_range, dvr_step_voxels,
+ *      dvr_ert_tau, dvr_max_steps, the stride); a camera move does not rebuild.
+ * vx_shadow_stats: light-grid builds since vx_create, light-march samples of the last build and its HIP-event time
+ * (synchronises).  Any out pointer may be NULL.  group: member 0 (every member builds its own grid, replicated like the volume). */
+int vx_shadow_stats(VxContext* ctx, uint64_t* builds, uint64_t* light_samples, double* last_build_ms);
+/* test hook: the last light grid built, dims_out[0] * dims_out[1] * dims_out[2] floats, x fastest (node (i, j, k) at
+ * ((k * dims[1]) + j) * dims[0] + i); out = NULL queries the dimensions only.  VX_ERR_INVALID before the first build.
+ * Synchronises.  group: member 0. */
+int vx_debug_read_shadow_grid(VxContext* ctx, float* out, uint32_t dims_out[3]);
 
 /* test hook (no reference counterpart): the device's R8-unorm decode table, 256 floats */
 int vx_debug_unorm_table(VxContext* ctx, float* out256);

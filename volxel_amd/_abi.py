@@ -127,6 +127,8 @@ def load_library():
         "vx_probe_valu_rate": ([vp, P(C.c_double), P(u32)], i32),
         "vx_upload_stats": ([vp, P(C.c_double), P(u64), P(i32)], i32),
         "vx_debug_build_skip_mask": ([vp, P(u32), vp, u32, P(VxParams), vp, P(u32), P(u32)], i32),
+        "vx_shadow_stats": ([vp, P(u64), P(u64), P(C.c_double)], i32),
+        "vx_debug_read_shadow_grid": ([vp, vp, P(u32)], i32),
         # preprocessor
         "vxb_build_from_u16": ([vp, P(u32), P(C.c_float), C.c_uint16, i32, P(vp)], i32),
         "vxb_read_dicoms_to_grid": ([P(vp), P(u64), u32, i32, P(vp)], i32),

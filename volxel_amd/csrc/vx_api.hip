@@ -17,6 +17,7 @@
 #include "vx_kernels.hpp"
 #include "vx_paths.hpp"
 #include "vx_events.hpp"
+#include "vx_shadow.hpp"
 
 using namespace vx;
 
@@ -81,6 +82,16 @@ struct VxContext {
   float lmaj_key[5] = {0, 0, 0, 0, 0};   // density_scale, inv_maj, maj, sample_range
 
   unsigned long long* fold_dev = nullptr;   // eight totals of fold_records
+
+  // shadowed DVR: the light grid (vx_shadow.hpp), rebuilt when its inputs differ bitwise from the last build (ShadowKey)
+  float* shadow_dev = nullptr;
+  size_t shadow_cap = 0;                     // floats allocated
+  ShadowGrid shadow{};                       // what the last build made (t == nullptr: none since the last upload)
+  bool shadow_dirty = true;                  // volume or TF uploaded since the last build
+  float shadow_key[34] = {};                 // shadow_key() of the last build (SHADOW_KEY floats)
+  unsigned long long* shadow_count_dev = nullptr;   // light-march samples of the last build
+  hipEvent_t shadow_ev[2] = {nullptr, nullptr};
+  uint64_t shadow_builds = 0;
 
   // params
   VxParams params{};
@@ -178,6 +189,11 @@ static void free_volume(VxContext* c) {
   if (c->lmaj_dev) (void)hipFree(c->lmaj_dev);
   c->lmaj_dev = nullptr;
   c->lmaj_dirty = true;
+  if (c->shadow_dev) (void)hipFree(c->shadow_dev);
+  c->shadow_dev = nullptr;
+  c->shadow_cap = 0;
+  c->shadow = ShadowGrid{};
+  c->shadow_dirty = true;
 }
 
 static void drain_events(VxContext* c) {
@@ -469,6 +485,108 @@ static void with_layout(int lay, F&& f) {
   else f(std::integral_constant<int, LAYOUT_REF>{});
 }
 
+// ---- shadowed DVR: the light grid (vx_shadow.hpp) ---------------------------------------------------
+static bool shadow_on(const VxContext* c) {
+  const VxParams& p = c->params;
+  return p.render_mode == VX_MODE_DVR && p.dvr_shadow_stride != 0 && !p.debug_hits;
+}
+// the inputs of a light-grid build besides the volume and TF uploads, bit for bit
+constexpr int SHADOW_KEY = 34;
+static void shadow_key(const VxParams& p, float k[SHADOW_KEY]) {
+  float* o = k;
+  auto put = [&](const void* src, size_t n) { memcpy(o, src, n * 4); o += n; };
+  put(p.light_dir, 3);
+  put(p.density_transform_inv, 16);
+  put(p.volume_aabb_min, 3);
+  put(p.volume_aabb_max, 3);
+  put(&p.volume_maj, 1);
+  put(&p.volume_inv_maj, 1);
+  put(&p.volume_density_scale, 1);
+  put(p.sample_range, 2);
+  put(&p.dvr_step_voxels, 1);
+  put(&p.dvr_ert_tau, 1);
+  put(&p.dvr_max_steps, 1);
+  put(&p.dvr_shadow_stride, 1);
+}
+// the light march of every node, with fp32 operations a NumPy restatement repeats (tests/shadow_ref.py)
+static LightMarch light_march(const VxContext* c) {
+  const VxParams& p = c->params;
+  const float* m = p.density_transform_inv;
+  LightMarch lm{};
+  const float lx = -p.light_dir[0], ly = -p.light_dir[1], lz = -p.light_dir[2];
+  for (int i = 0; i < 3; ++i) lm.idir[i] = fmaf(m[8 + i], lz, fmaf(m[4 + i], ly, m[i] * lx));   // mat3(dti) * (-light_dir)
+  lm.dt = p.dvr_step_voxels / sqrtf(fmaf(lm.idir[2], lm.idir[2], fmaf(lm.idir[1], lm.idir[1], lm.idir[0] * lm.idir[0])));
+  // the clip box in index space: the bounds of its eight corners mapped as prepare_render maps them
+  for (int i = 0; i < 3; ++i) {
+    lm.box_lo[i] = INFINITY;
+    lm.box_hi[i] = -INFINITY;
+  }
+  for (int corner = 0; corner < 8; ++corner) {
+    const float w[3] = {(corner & 1) ? p.volume_aabb_max[0] : p.volume_aabb_min[0],
+                        (corner & 2) ? p.volume_aabb_max[1] : p.volume_aabb_min[1],
+                        (corner & 4) ? p.volume_aabb_max[2] : p.volume_aabb_min[2]};
+    for (int i = 0; i < 3; ++i) {
+      const float q = fmaf(m[12 + i], 1.0f, fmaf(m[8 + i], w[2], fmaf(m[4 + i], w[1], m[i] * w[0])));
+      lm.box_lo[i] = std::min(lm.box_lo[i], q);
+      lm.box_hi[i] = std::max(lm.box_hi[i], q);
+    }
+  }
+  const uint32_t s = (uint32_t)p.dvr_shadow_stride;
+  lm.stride = s;
+  for (int i = 0; i < 3; ++i) {
+    lm.n[i] = (c->dv.extent[i] - 1u + s - 1u) / s + 1u;   // ceil((extent - 1) / s) + 1
+    // nodes inside the box: box_lo <= s * i + 1/2 <= box_hi (prepare_render keeps the box within the volume)
+    const double lo = std::ceil(((double)lm.box_lo[i] - 0.5) / s), hi = std::floor(((double)lm.box_hi[i] - 0.5) / s);
+    lm.ilo[i] = (uint32_t)std::min(std::max(lo, 0.0), (double)(lm.n[i] - 1u));
+    lm.ihi[i] = (uint32_t)std::min(std::max(hi, (double)lm.ilo[i]), (double)(lm.n[i] - 1u));
+  }
+  return lm;
+}
+// build the light grid on the context's stream (after the layouts of the launch are in place)
+static int rebuild_light_grid(VxContext* c) {
+  const LightMarch lm = light_march(c);
+  const uint64_t nodes = (uint64_t)lm.n[0] * lm.n[1] * lm.n[2];
+  if (nodes >= (1ull << 31))
+    VX_FAIL(c, VX_ERR_INVALID, "shadowed DVR: a light grid of %llu nodes (stride %u) is beyond the look-up's index range; "
+            "use a larger dvr_shadow_stride", (unsigned long long)nodes, lm.stride);
+  if (nodes > c->shadow_cap) {
+    VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued launch still reads the old grid
+    if (c->shadow_dev) (void)hipFree(c->shadow_dev);
+    c->shadow_dev = nullptr;
+    c->shadow_cap = 0;
+    c->shadow = ShadowGrid{};
+    VX_HIP(c, hipMalloc(&c->shadow_dev, nodes * sizeof(float)));
+    c->shadow_cap = nodes;
+  }
+  if (!c->shadow_count_dev) VX_HIP(c, hipMalloc(&c->shadow_count_dev, sizeof(unsigned long long)));
+  for (hipEvent_t& e : c->shadow_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  VX_HIP(c, hipMemsetAsync(c->shadow_count_dev, 0, sizeof(unsigned long long), c->stream));
+  const dim3 grid((lm.n[0] + 7u) / 8u, (lm.n[1] + 7u) / 8u, (lm.n[2] + 3u) / 4u);
+  const size_t lds = c->tf_len <= TF_LDS_MAX ? (size_t)c->tf_len * sizeof(float4) : 0u;
+  VX_HIP(c, hipEventRecord(c->shadow_ev[0], c->stream));
+  with_layout(eff_layout(c), [&](auto tag) {
+    constexpr int LAY = decltype(tag)::value;
+    hipLaunchKernelGGL((build_light_grid<LAY>), grid, dim3(256), lds, c->stream, c->params, c->dv, c->tf, c->tf_len, lm,
+                       c->shadow_dev, c->shadow_count_dev);
+  });
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->shadow_ev[1], c->stream));
+  ShadowGrid& g = c->shadow;
+  g.t = c->shadow_dev;
+  g.inv_s = 1.0f / (float)lm.stride;
+  for (int i = 0; i < 3; ++i) {
+    g.n[i] = lm.n[i];
+    g.glo[i] = (float)lm.ilo[i];
+    g.ghi[i] = (float)lm.ihi[i];
+    g.gmax[i] = (float)(lm.n[i] - 1u);
+  }
+  shadow_key(c->params, c->shadow_key);
+  c->shadow_dirty = false;
+  c->shadow_builds += 1;
+  return VX_OK;
+}
+
 // ---- the launch plan: which kernel a render launch runs, and whether it folds the running mean itself ----------------
 
 enum class Kernel {
@@ -529,7 +647,8 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo) {
   const uint32_t n = mo.count;
   LaunchPlan lp;
   lp.layout = eff_layout(c);
-  if (is_tuned(c)) {
+  // shadowed DVR: the LDS-window kernel's shadowed form, or render_generic's -- never the cellquad DVR kernel
+  if (is_tuned(c) && (!shadow_on(c) || use_lds_kernel(c))) {
     lp.kernel = use_lds_kernel(c) ? Kernel::DVR_LDS : Kernel::DVR_CQ;
     lp.ordered = c->sw.use_order;
     lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && !c->sw.dvr_shared_window &&
@@ -578,6 +697,13 @@ static void launch_mode(const VxContext* c, const LaunchPlan& lp, const MultiOut
         return;
       }
     }
+    if constexpr (MODE == VX_MODE_DVR) {
+      if (shadow_on(c)) {
+        hipLaunchKernelGGL((render_generic_shadow<LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
+                           mo, weight, c->tm, c->shadow);
+        return;
+      }
+    }
     hipLaunchKernelGGL((render_generic<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
                        mo, weight, c->tm);
   });
@@ -593,7 +719,8 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
   const uint32_t* order = lp.ordered ? c->order : nullptr;
   switch (lp.kernel) {
     case Kernel::DVR_LDS:
-      launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_shared_window);
+      launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_shared_window,
+                     shadow_on(c) ? &c->shadow : nullptr);
       break;
     case Kernel::DVR_CQ:
       launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_unroll);
@@ -850,6 +977,9 @@ void vx_destroy(VxContext* c) {
   if (c->env_impq) (void)hipFree(c->env_impq);
   if (c->skip_dev) (void)hipFree(c->skip_dev);
   if (c->fold_dev) (void)hipFree(c->fold_dev);
+  if (c->shadow_count_dev) (void)hipFree(c->shadow_count_dev);
+  for (hipEvent_t e : c->shadow_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->slab) (void)hipFree(c->slab);
   if (c->image) (void)hipFree(c->image);
   if (c->display) (void)hipFree(c->display);
@@ -1279,6 +1409,7 @@ int vx_upload_transfer(VxContext* c, const float* rgba, uint32_t length) {
   c->tf_host.assign(rgba, rgba + (size_t)length * 4);
   c->skip_dirty = true;
   c->lmaj_dirty = true;
+  c->shadow_dirty = true;
   c->order_builds_left = 2;
   return VX_OK;
 }
@@ -1363,6 +1494,14 @@ int vx_set_params(VxContext* c, const VxParams* p) {
   if ((p->render_mode == VX_MODE_DVR || p->render_mode == VX_MODE_DVR_PHONG) &&
       (p->dvr_max_steps < 0 || p->dvr_max_steps > (1 << 24)))
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_max_steps %d outside [0, 2^24]", p->dvr_max_steps);
+  if (p->dvr_shadow_stride != 0 && p->dvr_shadow_stride != 1 && p->dvr_shadow_stride != 2 && p->dvr_shadow_stride != 4)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride must be 0, 1, 2 or 4, not %d", p->dvr_shadow_stride);
+  if (p->dvr_shadow_stride != 0 && p->render_mode == VX_MODE_DVR_PHONG)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride %d with VX_MODE_DVR_PHONG (shadows serve plain DVR)",
+            p->dvr_shadow_stride);
+  if (p->dvr_shadow_stride != 0 && p->render_mode == VX_MODE_DVR && p->use_env != 0)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride %d with use_env = 1 (an environment map has no single light "
+            "direction)", p->dvr_shadow_stride);
   bool reshard = !c->has_params || p->shard_count != c->params.shard_count ||
                  p->shard_rank != c->params.shard_rank;
   if (!c->has_params || memcmp(&c->params, p, sizeof(VxParams)) != 0) c->order_builds_left = 2;
@@ -1490,6 +1629,14 @@ static int prepare_render(VxContext* c, dim3& grid) {
                 (c->params.render_mode == VX_MODE_DVR_PHONG && lay == VX_LAYOUT_CELLQUAD && tuned_possible(c))))
       rc = ensure_brickf32(c);
     if (rc) return rc;
+  }
+  if (shadow_on(c)) {   // the light grid, rebuilt when an input differs bitwise from the last build (a camera move does not)
+    float key[SHADOW_KEY];
+    shadow_key(c->params, key);
+    if (c->shadow_dirty || !c->shadow.t || memcmp(key, c->shadow_key, sizeof key) != 0) {
+      int rc = rebuild_light_grid(c);
+      if (rc) return rc;
+    }
   }
   uint32_t groups = (c->tm.tiles_per_shard + 7u) / 8u;
   grid = dim3(groups * 128u);
@@ -2007,6 +2154,37 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
 }
 
 // test hook (not part of the reference boundary): the device's unorm8 decode table
+int vx_shadow_stats(VxContext* c, uint64_t* builds, uint64_t* light_samples, double* last_build_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_shadow_stats(c->members[0], builds, light_samples, last_build_ms));
+  VX_DEV(c);
+  unsigned long long n = 0;
+  float ms = 0.0f;
+  if (c->shadow_builds) {
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    VX_HIP(c, hipMemcpy(&n, c->shadow_count_dev, sizeof n, hipMemcpyDeviceToHost));
+    VX_HIP(c, hipEventElapsedTime(&ms, c->shadow_ev[0], c->shadow_ev[1]));
+  }
+  if (builds) *builds = c->shadow_builds;
+  if (light_samples) *light_samples = n;
+  if (last_build_ms) *last_build_ms = ms;
+  return VX_OK;
+}
+
+int vx_debug_read_shadow_grid(VxContext* c, float* out, uint32_t dims_out[3]) {
+  if (!c || !dims_out) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_debug_read_shadow_grid(c->members[0], out, dims_out));
+  VX_DEV(c);
+  if (!c->shadow.t) VX_FAIL(c, VX_ERR_INVALID, "vx_debug_read_shadow_grid: no light grid built since the last upload");
+  for (int i = 0; i < 3; ++i) dims_out[i] = c->shadow.n[i];
+  if (out) {
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    VX_HIP(c, hipMemcpy(out, c->shadow.t, (size_t)c->shadow.n[0] * c->shadow.n[1] * c->shadow.n[2] * sizeof(float),
+                        hipMemcpyDeviceToHost));
+  }
+  return VX_OK;
+}
+
 int vx_debug_unorm_table(VxContext* c, float* out256) {
   if (!c || !out256) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_debug_unorm_table(c->members[0], out256));

@@ -389,6 +389,35 @@ VXD float trilinear_cell(const DevVolume& v, float density_scale, int ix, int iy
   return density_scale * gl_mix(gl_mix(lx0, lx1, fy), gl_mix(hx0, hx1, fy), fz);
 }
 
+// [build] the light grid of shadowed DVR: transmittance toward the directional light at the nodes of a
+// lattice of stride s voxels, node (i, j, k) at cell-frame position s * (i, j, k), x fastest
+struct ShadowGrid {
+  const float* t;   // n[0] * n[1] * n[2] node values
+  uint32_t n[3];    // nodes per axis: ceil((extent - 1) / s) + 1
+  float inv_s;      // 1 / s (s = 1, 2 or 4: q * inv_s is q / s exactly)
+  float glo[3];     // the first and last node per axis whose position lies inside the clip box (vx_api.hip light_march)
+  float ghi[3];
+  float gmax[3];    // n - 1
+};
+// T_L at cell-frame position q: g = q / s clamped to [glo, ghi] per axis -- a sample within a node spacing of a clip-box face
+// takes the outermost node inside the box, never one outside it (whose march misses the box) -- cell i = min(floor(g), n - 2)
+// (n >= 2: extents are multiples of 8), fractions g - i, the eight nodes mixed x -> y -> z in common.glsl:62-68's order.
+// A NaN position clamps to glo.
+VXD float shadow_lookup(const ShadowGrid& g, float qx, float qy, float qz) {
+  const float gx = fminf(fmaxf(qx * g.inv_s, g.glo[0]), g.ghi[0]), gy = fminf(fmaxf(qy * g.inv_s, g.glo[1]), g.ghi[1]),
+              gz = fminf(fmaxf(qz * g.inv_s, g.glo[2]), g.ghi[2]);
+  const float ix = fminf(floorf(gx), g.gmax[0] - 1.0f), iy = fminf(floorf(gy), g.gmax[1] - 1.0f),
+              iz = fminf(floorf(gz), g.gmax[2] - 1.0f);
+  const float fx = gx - ix, fy = gy - iy, fz = gz - iz;
+  const uint32_t nx = g.n[0], nxy = g.n[0] * g.n[1];
+  const float* b = g.t + (((uint32_t)iz * g.n[1] + (uint32_t)iy) * nx + (uint32_t)ix);   // below 2^31 nodes (vx_api.hip)
+  const float v000 = b[0], v100 = b[1], v010 = b[nx], v110 = b[nx + 1];
+  const float v001 = b[nxy], v101 = b[nxy + 1], v011 = b[nxy + nx], v111 = b[nxy + nx + 1];
+  const float lx0 = gl_mix(v000, v100, fx), lx1 = gl_mix(v010, v110, fx);
+  const float hx0 = gl_mix(v001, v101, fx), hx1 = gl_mix(v011, v111, fx);
+  return gl_mix(gl_mix(lx0, lx1, fy), gl_mix(hx0, hx1, fy), fz);
+}
+
 // A5: lookup_density_trilinear, common.glsl:61-69
 template <int LAYOUT, bool IN_LATTICE = false>
 VXD float lookup_density_trilinear(const DevVolume& v, float density_scale, V3 p) {

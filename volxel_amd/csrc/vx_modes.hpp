@@ -12,6 +12,7 @@ struct Frame {
   const DevVolume& v;
   TfView tf;
   Counts& c;
+  ShadowGrid sg{};   // shadowed DVR (dvr<PHONG, true>): the light grid
 
   VXD float transfer_alpha(float d) const {   // the .a of transfer(d), counted the same
     if (!(d < p.sample_range[0] || d > p.sample_range[1])) c.tf++;
@@ -358,7 +359,8 @@ struct Frame {
   }
 
   // ---- A12 [build] deterministic DVR (generic form; the tuned kernel is vx_dvr.hpp) ------
-  template <bool PHONG>
+  // SHADOW: a contributing sample adds w = dT * T_L (the light grid sg at its position) instead of dT
+  template <bool PHONG, bool SHADOW = false>
   VXD float4 dvr(const Ray& ray, float start_offset) const {
     float near, far;
     V3 C = v3(0, 0, 0);
@@ -414,6 +416,7 @@ struct Frame {
           tau = fma_(rgba.w * p.volume_maj, dt, tau);
           float Tn = expf(-tau);
           float dT = T - Tn;
+          if (SHADOW) dT = dT * shadow_lookup(sg, qx, qy, qz);
           C.x = fma_(dT, rgba.x, C.x);
           C.y = fma_(dT, rgba.y, C.y);
           C.z = fma_(dT, rgba.z, C.z);
@@ -433,7 +436,7 @@ struct Frame {
   }
 
   // ---- fragment.frag:128-158 for one pixel (without the running-mean blend) -------------
-  template <int MODE>
+  template <int MODE, bool SHADOW = false>
   VXD float4 shade_pixel(int px, int py, uint32_t frame) const {
     Rng s = seed_xoshiro(tea32(42u * (uint32_t)(py * p.res[0] + px), frame));  // :143-144
     float tex_x = tex_coord(px, p.res[0], &v, 0);
@@ -461,7 +464,7 @@ struct Frame {
     if (DVR) {
       (void)rng(s);  // tau_target slot of raymarch.glsl:28
       float u_start = rng(s);
-      r = dvr<MODE == VX_MODE_DVR_PHONG>(ray, p.dvr_jitter ? u_start : 0.5f);
+      r = dvr<MODE == VX_MODE_DVR_PHONG, SHADOW>(ray, p.dvr_jitter ? u_start : 0.5f);
     } else {
       float near, far;
       if (slab(ray, near, far)) c.rays++;

@@ -69,6 +69,11 @@ export declare class Volxel3DDicomRenderer {
                 kernelMs: number; lastKernelMs: number; gathers: number; ldsReads: number; mergeMs: number; minLaunchFrames: number; maxLaunchFrames: number;
                 mergeLaunches: number };
   resetCounters(): void;
+  /** shadowed DVR (settings.dvrShadowStride = 1, 2 or 4; include/volxel_hip.h vx_shadow_stats): light-grid builds since
+   *  creation, light-march samples and HIP-event time of the last build */
+  shadowStats(): { builds: number; lightSamples: number; lastBuildMs: number };
+  /** the last light grid built (vx_debug_read_shadow_grid): transmittance toward the light per node, x fastest */
+  readShadowGrid(): { dims: [number, number, number]; data: Float32Array };
   dispose(): void;
 }
 /** viewer.ts:1455-1462: keeps the worker factory, returns the element-name -> class table ("volxel-3d-viewer") */

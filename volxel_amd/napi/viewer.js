@@ -296,6 +296,7 @@ class Volxel3DDicomRenderer {
       showEnvironment: true, useEnv: true, lightDir: [-1, -1, -1].map(v => v / Math.sqrt(3)), syncLightDir: false,
       bounces: 3, gamma: 2.2, exposure: 5.5, sampleRange: [0, 1], renderMode: 'default', resolutionFactor: 1,
       dvrStepVoxels: 0.5, dvrErtEpsilon: 1e-4, dvrJitter: false, dvrMaxSteps: 1 << 20, dvrSkipEmpty: true, phong: [0.3, 0.7, 0.4, 32],
+      dvrShadowStride: 0,   // shadowed DVR: 0 off, 1 / 2 / 4 light-grid stride (volxel_hip.h VxParams.dvr_shadow_stride)
     };
     this.camera = new Camera(1);                  // viewer.ts:418
     this.environment = null;
@@ -441,6 +442,7 @@ class Volxel3DDicomRenderer {
     p.set('render_mode', RenderMode[s.renderMode]);
     p.set('dvr_step_voxels', s.dvrStepVoxels); p.set('dvr_ert_tau', -Math.log(s.dvrErtEpsilon));
     p.set('dvr_jitter', s.dvrJitter ? 1 : 0); p.set('dvr_max_steps', s.dvrMaxSteps); p.set('dvr_skip_empty', s.dvrSkipEmpty ? 1 : 0);
+    p.set('dvr_shadow_stride', s.dvrShadowStride | 0);
     const f = Math.fround;
     const fp = f(f(1) / f(f(4) * f(Math.PI)));                         // utils.glsl:121-124, g = 0
     const mis = s.showEnvironment ? f(f(1) / f(f(1) + f(fp * fp))) : f(1); // utils.glsl:104
@@ -534,6 +536,10 @@ class Volxel3DDicomRenderer {
     return o;
   }
   counters() { return native.getCounters(this.ctx); }
+  /** shadowed DVR (settings.dvrShadowStride): light-grid builds, light-march samples and time of the last build */
+  shadowStats() { return native.shadowStats(this.ctx); }
+  /** the last light grid built: node transmittances, x fastest */
+  readShadowGrid() { return native.readShadowGrid(this.ctx); }
   resetCounters() { native.resetCounters(this.ctx); }
 }
 

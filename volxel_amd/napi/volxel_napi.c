@@ -454,6 +454,48 @@ static napi_value n_get_counters(napi_env env, napi_callback_info info) {
   return o;
 }
 
+static napi_value make_u32x3(napi_env env, const uint32_t s[3]);
+
+/* shadowStats(ctx) -> { builds, lightSamples, lastBuildMs } (vx_shadow_stats) */
+static napi_value n_shadow_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint64_t builds = 0, samples = 0;
+  double ms = 0.0;
+  if (vx_shadow_stats(c, &builds, &samples, &ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o, v;
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_double(env, (double)builds, &v));
+  NAPI_OK(napi_set_named_property(env, o, "builds", v));
+  NAPI_OK(napi_create_double(env, (double)samples, &v));
+  NAPI_OK(napi_set_named_property(env, o, "lightSamples", v));
+  NAPI_OK(napi_create_double(env, ms, &v));
+  NAPI_OK(napi_set_named_property(env, o, "lastBuildMs", v));
+  return o;
+}
+
+/* readShadowGrid(ctx) -> { dims: [nx, ny, nz], data: Float32Array } (vx_debug_read_shadow_grid) */
+static napi_value n_read_shadow_grid(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t dims[3];
+  if (vx_debug_read_shadow_grid(c, NULL, dims) != VX_OK) return throw_msg(env, vx_last_error(c));
+  const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+  napi_value ab, arr, o;
+  void* data = NULL;
+  NAPI_OK(napi_create_arraybuffer(env, n * sizeof(float), &data, &ab));
+  if (vx_debug_read_shadow_grid(c, (float*)data, dims) != VX_OK) return throw_msg(env, vx_last_error(c));
+  NAPI_OK(napi_create_typedarray(env, napi_float32_array, n, ab, 0, &arr));
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_set_named_property(env, o, "dims", make_u32x3(env, dims)));
+  NAPI_OK(napi_set_named_property(env, o, "data", arr));
+  return o;
+}
+
 static napi_value n_reset_counters(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (!get_args(env, info, 1, a)) return NULL;
@@ -618,7 +660,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"probeTileCosts", n_probe_tile_costs}, {"setTileOrder", n_set_tile_order}, {"deviceInfo", n_device_info}, {"finish", n_finish},
       {"readAccum", n_read_accum}, {"readDisplay", n_read_display},
       {"readDisplayScaled", n_read_display_scaled}, {"getCounters", n_get_counters},
-      {"resetCounters", n_reset_counters}, {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
+      {"resetCounters", n_reset_counters}, {"shadowStats", n_shadow_stats}, {"readShadowGrid", n_read_shadow_grid},
+      {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {
     napi_value f;

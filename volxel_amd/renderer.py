@@ -93,6 +93,7 @@ def compute_params(settings: ViewerSettings, camera: Camera, volume: Volume, den
     p.dvr_jitter = 1 if settings.dvr_jitter else 0
     p.dvr_max_steps = int(settings.dvr_max_steps)
     p.dvr_skip_empty = 1 if settings.dvr_skip_empty else 0
+    p.dvr_shadow_stride = int(settings.dvr_shadow_stride)
     # K = albedo * mis * f_p * Le / pdf for the directional light (fragment.frag:94-97,
     # environment.glsl:30-33, utils.glsl:104,121-124), in float32 like the shader
     f32 = np.float32
@@ -561,6 +562,22 @@ class Volxel3DRenderer:
         s, b, pin = C.c_double(), C.c_uint64(), C.c_int()
         self._check(self._lib.vx_upload_stats(self._ctx, C.byref(s), C.byref(b), C.byref(pin)))
         return s.value, b.value, bool(pin.value)
+
+    def shadow_stats(self):
+        """(builds, light_samples, last_build_ms) of the light grid of shadowed DVR (settings.dvr_shadow_stride): builds since
+        the renderer was created, light-march samples and HIP-event time of the last build"""
+        b, n, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+        self._check(self._lib.vx_shadow_stats(self._ctx, C.byref(b), C.byref(n), C.byref(ms)))
+        return b.value, n.value, ms.value
+
+    def read_shadow_grid(self) -> np.ndarray:
+        """the last light grid built, shape (nz, ny, nx): transmittance toward the light at node (i, j, k), cell-frame
+        position stride * (i, j, k)"""
+        dims = (C.c_uint32 * 3)()
+        self._check(self._lib.vx_debug_read_shadow_grid(self._ctx, None, dims))
+        out = np.empty((dims[2], dims[1], dims[0]), dtype=np.float32)
+        self._check(self._lib.vx_debug_read_shadow_grid(self._ctx, out.ctypes.data, dims))
+        return out
 
     def probe_gather_rate(self, lines: int, distinct: int | None = None):
         """clocks per 16-byte-per-lane gather instruction per CU (nominal clock) when the 64 lanes form `lines` groups of

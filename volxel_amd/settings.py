@@ -35,6 +35,7 @@ class ViewerSettings:  # settings.ts:45-61, defaults viewer.ts:147-163
     dvr_max_steps: int = 1 << 20
     dvr_skip_empty: bool = True   # exact empty-space skipping (samples with alpha == 0 for sure)
     phong: tuple = (0.3, 0.7, 0.4, 32.0)  # ka, kd, ks, shininess
+    dvr_shadow_stride: int = 0    # shadowed DVR: 0 off, 1 / 2 / 4 light-grid stride in voxels (needs use_env off)
 
 
     def to_viewer_dict(self) -> dict:
@@ -51,6 +52,7 @@ class ViewerSettings:  # settings.ts:45-61, defaults viewer.ts:147-163
             "dvrStepVoxels": self.dvr_step_voxels, "dvrErtEpsilon": self.dvr_ert_epsilon,
             "dvrJitter": self.dvr_jitter, "dvrMaxSteps": self.dvr_max_steps,
             "dvrSkipEmpty": self.dvr_skip_empty, "phong": list(self.phong),
+            "dvrShadowStride": self.dvr_shadow_stride,
         }
 
 
