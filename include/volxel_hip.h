@@ -41,7 +41,17 @@ enum VxRenderMode {
   VX_MODE_RAYMARCH = 2, /* 64-step stochastic march             sampling/raymarch.glsl   */
   VX_MODE_DVR = 3,      /* [build] deterministic front-to-back compositing = E[RAYMARCH],
                            SURVEY.md section 8 row A12 -- the BASELINE.json headline loop */
-  VX_MODE_DVR_PHONG = 4 /* [build] DVR + central-difference gradient + Phong (config 4)  */
+  VX_MODE_DVR_PHONG = 4, /* [build] DVR + central-difference gradient + Phong (config 4) */
+  /* [build] intensity projections ("projections"): the samples of VX_MODE_DVR (ray set-up, jitter
+     draws, dvr_step_voxels, dvr_max_steps, clip box, march contract), density d_k = trilinear(q_k) * volume_inv_maj; a ray
+     with n >= 1 samples reduces them to m = max_k d_k (MIP) or m = min_k d_k (MinIP) and shows rgba = TF(m) (0 outside
+     sample_range) as (r*a, g*a, b*a, 1); a ray that misses or has n = 0 gives (0, 0, 0, 1).  dvr_ert_tau, dvr_gain, the
+     Phong terms, bounces, use_env and show_environment have no effect; debug_hits acts as for DVR; the running mean is
+     fragment.frag:158's.  dvr_skip_empty = 1: range skipping -- the LDS-window kernel flies over a macro cell whose
+     density bound (from the per-brick ranges, widened against rounding) cannot change m: upper bound <= m for MIP, lower
+     bound >= m for MinIP.  Exact: the image is bit-identical with skipping on or off.  dvr_shadow_stride must be 0. */
+  VX_MODE_MIP = 5,     /* maximum-intensity projection (CT angiography, bone)                                     */
+  VX_MODE_MINIP = 6    /* minimum-intensity projection (airways, lung)                                            */
 };
 
 /* device layout of the brick grid the trilinear look-ups sample (vx_set_layout) */
@@ -126,7 +136,8 @@ typedef struct VxParams {
                             t_k = fma(k, dt, t0)); vx_set_params refuses more            */
   int32_t dvr_skip_empty; /* 1: exact empty-space skipping -- samples whose macro cell (16..64
                              voxels) can only see TF-transparent bricks are
-                             not evaluated (their alpha is exactly 0) and not counted          */
+                             not evaluated (their alpha is exactly 0) and not counted; for
+                             VX_MODE_MIP / VX_MODE_MINIP: range skipping (see VxRenderMode) */
   float dvr_gain[3];     /* albedo * mis * f_p * Le / pdf  (fragment.frag:94-97), host-computed */
   /* Phong terms of VX_MODE_DVR_PHONG */
   float phong_ka, phong_kd, phong_ks, phong_shininess;
@@ -149,7 +160,8 @@ typedef struct VxCounters {
   uint64_t samples;      /* volume sample evaluations (density lookup + TF + accumulate)  */
   uint64_t rays;         /* primary rays that hit the clipped AABB                        */
   uint64_t pixels;       /* pixels written                                                */
-  uint64_t skip_steps;   /* DDA / empty-space steps (not samples)                         */
+  uint64_t skip_steps;   /* DDA / empty-space steps (not samples).  VX_MODE_MIP / VX_MODE_MINIP: the SAMPLES flown over
+                            by range skipping; there samples + skip_steps is exactly the sum of n over the rays */
   uint64_t grad_samples; /* samples that also evaluated the 6-tap gradient (DVR_PHONG)    */
   uint64_t lane_slots;   /* 64 x wave iterations of the DVR march loop (samples / lane_slots
                             = SIMD lane utilisation); 0 for kernels that do not count it   */
@@ -165,7 +177,8 @@ typedef struct VxCounters {
   uint32_t min_launch_frames; /* smallest / largest number of accumulation frames one launch  */
   uint32_t max_launch_frames; /* actually covered (what ran, not what was requested)           */
   uint64_t tf_samples;   /* samples whose density lay inside the sample range: the ones that fetch a
-                            transfer-function entry (common.glsl:78-83) and enter the composite  */
+                            transfer-function entry (common.glsl:78-83) and enter the composite.
+                            VX_MODE_MIP / VX_MODE_MINIP: one per ray that has a sample (the TF fetch of m)  */
   uint64_t active_lane_slots; /* of lane_slots, the slots whose lane did work -- counted by the event-batched path
                             kernels (default / no_dda), whose lanes may wait for an event pass; 0 elsewhere
                             (for the DVR kernels samples / lane_slots is the lane utilisation)          */
@@ -376,6 +389,13 @@ int vx_debug_unorm_table(VxContext* ctx, float* out256);
 int vx_debug_build_skip_mask(const uint32_t* range_packed, const uint32_t brick_count[3], const float* tf_rgba,
                              uint32_t tf_len, const VxParams* params, uint32_t* bits_out, uint32_t* level_out,
                              uint32_t dims_out[3]);
+/* test hook: the host-built density bounds of range skipping (VX_MODE_MIP / VX_MODE_MINIP; pure CPU, no context).  Per
+ * macro cell of the empty-space grid (the level and dims vx_debug_build_skip_mask reports for the same brick grid), two
+ * floats {lo, hi}: every density d = trilinear(q) * volume_inv_maj that a sample q of the cell can produce on the device lies
+ * in [lo, hi].  With volume_density_scale <= 0 or volume_inv_maj <= 0 (or either not finite) the bounds are {-inf, +inf}:
+ * nothing is skipped.  bounds_out holds 2 * dims[0] * dims[1] * dims[2] floats, or is NULL to query level / dims. */
+int vx_debug_build_projection_bounds(const uint32_t* range_packed, const uint32_t brick_count[3], const VxParams* params,
+                                     float* bounds_out, uint32_t* level_out, uint32_t dims_out[3]);
 
 #ifdef __cplusplus
 }

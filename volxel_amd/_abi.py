@@ -48,10 +48,10 @@ def struct_from_header(header: str, name: str):
 VxParams = struct_from_header("volxel_hip.h", "VxParams")
 VxCounters = struct_from_header("volxel_hip.h", "VxCounters")
 
-MODE_DEFAULT, MODE_NO_DDA, MODE_RAYMARCH, MODE_DVR, MODE_DVR_PHONG = range(5)
+MODE_DEFAULT, MODE_NO_DDA, MODE_RAYMARCH, MODE_DVR, MODE_DVR_PHONG, MODE_MIP, MODE_MINIP = range(7)
 LAYOUT_REFERENCE, LAYOUT_CELLQUAD, LAYOUT_BRICKF32, LAYOUT_AUTO = 0, 1, 2, 3
 RENDER_MODES = {"default": MODE_DEFAULT, "no_dda": MODE_NO_DDA, "raymarch": MODE_RAYMARCH,
-                "dvr": MODE_DVR, "dvr_phong": MODE_DVR_PHONG}
+                "dvr": MODE_DVR, "dvr_phong": MODE_DVR_PHONG, "mip": MODE_MIP, "minip": MODE_MINIP}
 SHARD_TILE = 64
 
 
@@ -127,6 +127,7 @@ def load_library():
         "vx_probe_valu_rate": ([vp, P(C.c_double), P(u32)], i32),
         "vx_upload_stats": ([vp, P(C.c_double), P(u64), P(i32)], i32),
         "vx_debug_build_skip_mask": ([vp, P(u32), vp, u32, P(VxParams), vp, P(u32), P(u32)], i32),
+        "vx_debug_build_projection_bounds": ([vp, P(u32), P(VxParams), vp, P(u32), P(u32)], i32),
         "vx_shadow_stats": ([vp, P(u64), P(u64), P(C.c_double)], i32),
         "vx_debug_read_shadow_grid": ([vp, vp, P(u32)], i32),
         # preprocessor

@@ -18,6 +18,7 @@
 #include "vx_paths.hpp"
 #include "vx_events.hpp"
 #include "vx_shadow.hpp"
+#include "vx_projection.hpp"
 
 using namespace vx;
 
@@ -75,6 +76,12 @@ struct VxContext {
   uint32_t* skip_dev = nullptr;
   bool skip_dirty = true;
   float skip_key[4] = {0, 0, 0, 0};   // density_scale, inv_maj, sample_range
+  // range skipping of the intensity projections: one density bound per macro cell (vx_projection.hpp), rebuilt when the
+  // volume, volume_density_scale, volume_inv_maj or the mode changes
+  float* proj_dev = nullptr;
+  bool proj_dirty = true;
+  float proj_key[2] = {0, 0};         // density_scale, inv_maj
+  int proj_mode = -1;
 
   // default mode: local-majorant table (DevVolume::lmaj), rebuilt when its inputs change
   float* lmaj_dev = nullptr;
@@ -186,6 +193,7 @@ static void free_volume(VxContext* c) {
   c->dv = DevVolume{};
   c->has_volume = false;
   c->skip_dirty = true;
+  c->proj_dirty = true;
   if (c->lmaj_dev) (void)hipFree(c->lmaj_dev);
   c->lmaj_dev = nullptr;
   c->lmaj_dirty = true;
@@ -356,6 +364,110 @@ static void compute_skip_mask(const VxParams& p, const uint32_t* range_packed, c
       }
 }
 
+// ---- range skipping of the intensity projections: host-side construction of the density bounds ----------------------
+// Per macro cell of the empty-space grid above (level, dims), {lo, hi} with lo <= d <= hi for every density
+// d = (density_scale * mix) * inv_maj the device can compute at a sample of the cell.  Such a sample (mask index
+// floor(q) + 1 in the cell) takes its eight taps from the w + 1 bricks per axis m*w-1 .. m*w+w-1 that compute_skip_mask
+// ORs (a tap outside the grid reads 0), and a tap of brick b is decoded inside b's own range [min, max] (the f16 pair).
+// Rounding, argued against a relative margin of 2^-16 and an absolute one of 2^-100:
+//   * a decoded voxel, fma(c/255, max - min, min), lands at most an ulp or two beyond [min, max] (relative 2^-22);
+//   * a mix fma(b, t, a * (1 - t)): 1 - t and the product round once each, the fma once: with weights t, 1 - t in [0, 1] the
+//     result is within 3 rounding errors (2^-24 each, of the larger operand) of a convex combination, and the trilinear is
+//     three nested mixes -- at most ~10 rounding errors of max(|lo|, |hi|) in all, below 2^-20 relative;
+//   * the products by density_scale and inv_maj add one rounding each, and a device that flushes a denormal moves a value by
+//     less than 2^-126.
+// Bounds widened by 2^-16 of the magnitude and by 2^-100 hold with a margin of more than 16x.  A density_scale or inv_maj
+// that is <= 0 or not finite turns the map around or breaks it: then the bounds are {-inf, +inf} and nothing is skipped.
+static void compute_projection_bounds(const VxParams& p, const uint32_t* range_packed, const uint32_t bc[3],
+                                      const uint32_t extent[3], std::vector<float>& lohi, int& level_out, uint32_t md[3]) {
+  const int level = skip_level_for(extent);
+  level_out = level;
+  const int w = 1 << level;
+  for (int a = 0; a < 3; ++a) md[a] = (extent[a] >> (3 + level)) + 1u;
+  const size_t n = (size_t)md[0] * md[1] * md[2];
+  lohi.assign(2 * n, 0.0f);
+  const float s = p.volume_density_scale, im = p.volume_inv_maj;
+  if (!(s > 0.0f) || !(im > 0.0f) || !std::isfinite(s) || !std::isfinite(im)) {
+    for (size_t i = 0; i < n; ++i) { lohi[2 * i] = -INFINITY; lohi[2 * i + 1] = INFINITY; }
+    return;
+  }
+  // per-brick ranges, then separable min / max over the window [m*w-1, m*w+w-1] per axis (out-of-grid bricks read 0)
+  const size_t nb = (size_t)bc[0] * bc[1] * bc[2];
+  std::vector<float> bmin(nb), bmax(nb);
+  for (size_t i = 0; i < nb; ++i) {
+    const uint32_t pk = range_packed[i];
+    const float a = f16_bits_to_float((uint16_t)(pk >> 16)), b = f16_bits_to_float((uint16_t)pk);
+    bmin[i] = std::min(a, b);
+    bmax[i] = std::max(a, b);
+  }
+  auto reduce = [&](const std::vector<float>& src, uint32_t sx, uint32_t sy, uint32_t sz, int axis, bool hi) {
+    const uint32_t dims_in[3] = {sx, sy, sz};
+    uint32_t d[3] = {sx, sy, sz};
+    d[axis] = md[axis];
+    std::vector<float> out((size_t)d[0] * d[1] * d[2]);
+    for (uint32_t z = 0; z < d[2]; ++z)
+      for (uint32_t y = 0; y < d[1]; ++y)
+        for (uint32_t x = 0; x < d[0]; ++x) {
+          uint32_t at[3] = {x, y, z};
+          const int m = (int)at[axis];
+          float r = 0.0f;
+          bool first = true;
+          for (int b = m * w - 1; b <= m * w + w - 1; ++b) {
+            float v = 0.0f;
+            if (b >= 0 && (uint32_t)b < dims_in[axis]) {
+              at[axis] = (uint32_t)b;
+              v = src[((size_t)at[2] * dims_in[1] + at[1]) * dims_in[0] + at[0]];
+            }
+            r = first ? v : (hi ? std::max(r, v) : std::min(r, v));
+            first = false;
+          }
+          out[((size_t)z * d[1] + y) * d[0] + x] = r;
+        }
+    return out;
+  };
+  for (int hi = 0; hi < 2; ++hi) {
+    const std::vector<float>& b0 = hi ? bmax : bmin;
+    std::vector<float> rx = reduce(b0, bc[0], bc[1], bc[2], 0, hi);
+    std::vector<float> ry = reduce(rx, md[0], bc[1], bc[2], 1, hi);
+    std::vector<float> rz = reduce(ry, md[0], md[1], bc[2], 2, hi);
+    for (size_t i = 0; i < n; ++i) {
+      const double v = rz[i];   // voxel units
+      const double d = v * (double)s * (double)im;
+      const double widened = hi ? d + std::fabs(d) * 0x1p-16 + 0x1p-100 : d - std::fabs(d) * 0x1p-16 - 0x1p-100;
+      float f = (float)widened;   // then one more step outwards against the conversion's rounding
+      f = std::nextafter(f, hi ? INFINITY : -INFINITY);
+      lohi[2 * i + hi] = f;
+    }
+  }
+}
+static bool proj_mode(int m) { return m == VX_MODE_MIP || m == VX_MODE_MINIP; }
+// the device table: the bound the mode tests (hi for MIP, lo for MinIP), one float per macro cell
+static int rebuild_projection_bounds(VxContext* c) {
+  const VxParams& p = c->params;
+  std::vector<float> lohi;
+  int level = 1;
+  uint32_t md[3];
+  compute_projection_bounds(p, c->range_host.data(), c->dv.bc, c->dv.extent, lohi, level, md);
+  const size_t n = lohi.size() / 2;
+  std::vector<float> one(n);
+  const int which = p.render_mode == VX_MODE_MINIP ? 0 : 1;
+  for (size_t i = 0; i < n; ++i) one[i] = lohi[2 * i + which];
+  if (c->proj_dev) (void)hipFree(c->proj_dev);
+  c->proj_dev = nullptr;
+  VX_HIP(c, hipMalloc(&c->proj_dev, n * sizeof(float)));
+  VX_HIP(c, hipMemcpyAsync(c->proj_dev, one.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  // the macro-cell grid the kernel indexes: the empty-space grid's level and dims (a function of the extent alone, so the
+  // same values rebuild_skip_mask sets for this volume)
+  c->dv.skip_level = (uint32_t)level;
+  for (int a = 0; a < 3; ++a) c->dv.skip_dims[a] = md[a];
+  c->proj_dirty = false;
+  c->proj_key[0] = p.volume_density_scale;
+  c->proj_key[1] = p.volume_inv_maj;
+  c->proj_mode = p.render_mode;
+  return VX_OK;
+}
+
 // the local majorants of the default mode, tabulated on the device with the operations of Frame::local_majorant
 static int rebuild_local_majorants(VxContext* c) {
   const VxParams& p = c->params;
@@ -468,7 +580,7 @@ static int eff_layout(const VxContext* c) {
   const int m = c->has_params ? c->params.render_mode : VX_MODE_DVR;
   // raymarch takes ONE nearest tap per sample (common.glsl:72-76): the 4-byte-per-voxel bricks serve it better than
   // the 18-byte-per-voxel quads, and the layout is resident already
-  if (m == VX_MODE_DVR || m == VX_MODE_DVR_PHONG || m == VX_MODE_RAYMARCH) return primary_layout(c);
+  if (m == VX_MODE_DVR || m == VX_MODE_DVR_PHONG || m == VX_MODE_RAYMARCH || proj_mode(m)) return primary_layout(c);
   // `default` / `no_dda`: cellquad (18 B / voxel) while the volume is inside its index range and the build fits the device
   // memory budget (ensure_cellquad); beyond that the fp32 bricks that are resident anyway -- eight taps per look-up, measured
   // 1.4x / 2.0x slower than cellquad and 2.0x / 2.2x faster than the reference textures on the 1024^3 volume at 3840x2160
@@ -608,11 +720,16 @@ static bool tuned_possible(const VxContext* c) {
   // (an early-termination threshold <= 0 -- an epsilon >= 1: every ray ends at its first contributing sample -- is
   // served by render_generic, whose Frame::dvr spells the test as the oracle does; the tuned kernels assume tau >= ert
   // implies a contributing sample)
-  return c->sw.dvr_variant != 0 && !c->params.debug_hits && c->tf_len <= TF_LDS_MAX && c->params.dvr_ert_tau > 0.0f;
+  // (the projections have no early termination: dvr_ert_tau does not matter to them)
+  return c->sw.dvr_variant != 0 && !c->params.debug_hits && c->tf_len <= TF_LDS_MAX &&
+         (c->params.dvr_ert_tau > 0.0f || proj_mode(c->params.render_mode));
 }
-// the LDS-window kernel (vx_dvr_lds.hpp): DVR on the brickf32 layout, Phong wherever brickf32 data is resident
+// the LDS-window kernel (vx_dvr_lds.hpp): DVR on the brickf32 layout, Phong wherever brickf32 data is resident; the
+// projections' form of it (vx_projection.hpp) on brickf32 and bricku8
 static bool use_lds_kernel(const VxContext* c) {
   if (!tuned_possible(c)) return false;
+  if (proj_mode(c->params.render_mode))
+    return eff_layout(c) == VX_LAYOUT_BRICKF32 || (eff_layout(c) == VX_LAYOUT_BRICKU8 && c->dv.bu != nullptr);
   if (eff_layout(c) == VX_LAYOUT_BRICKU8)   // the same kernel, staging from the 8-bit bricks
     return (c->params.render_mode == VX_MODE_DVR || c->params.render_mode == VX_MODE_DVR_PHONG) && c->dv.bu != nullptr;
   if (c->params.render_mode == VX_MODE_DVR) return eff_layout(c) == VX_LAYOUT_BRICKF32;
@@ -637,8 +754,9 @@ static bool events_possible(const VxContext* c, const MultiOut& mo) {
 
 // The one place that decides what a render launch of the mo.count frame slots of `mo` runs.  The fuse rule: while
 // VX_DVR_FUSE is on, the kernel folds the running mean of the launch into the accumulator itself when
-//   * it is the LDS-window DVR / Phong kernel without the shared window (VX_DVR_WG) and the launch has 8, 16, 32 or 64
-//     frames (a wave holds every frame of its 8, 4, 2 or 1 pixels), or
+//   * it is the LDS-window DVR / Phong kernel without the shared window (VX_DVR_WG), or the projections' LDS-window kernel
+//     (which never takes the shared window), and the launch has 8, 16, 32 or 64 frames (a wave holds every frame of its
+//     8, 4, 2 or 1 pixels), or
 //   * it is render_generic for `default`, `no_dda` or `raymarch` and the launch has exactly 32 frames (2 pixels x 32
 //     frames per wave).
 // Every other multi-frame launch writes per-frame result slabs that merge_results blends in frame order.
@@ -651,7 +769,7 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo) {
   if (is_tuned(c) && (!shadow_on(c) || use_lds_kernel(c))) {
     lp.kernel = use_lds_kernel(c) ? Kernel::DVR_LDS : Kernel::DVR_CQ;
     lp.ordered = c->sw.use_order;
-    lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && !c->sw.dvr_shared_window &&
+    lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && (!c->sw.dvr_shared_window || proj_mode(p.render_mode)) &&
               (n == 8u || n == 16u || n == 32u || n == 64u);
     return lp;
   }
@@ -712,13 +830,18 @@ static void launch_mode(const VxContext* c, const LaunchPlan& lp, const MultiOut
 // The one launch switch: runs what `lp` names for the frame slots of `mo` on the context's stream.  Fails closed: a
 // kernel that does not fold the running mean refuses a launch with mo.fuse set -- its frames would reach no accumulator.
 static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
-  const bool folds = (lp.kernel == Kernel::DVR_LDS && !c->sw.dvr_shared_window) ||
+  const bool folds = (lp.kernel == Kernel::DVR_LDS && (!c->sw.dvr_shared_window || proj_mode(c->params.render_mode))) ||
                      (lp.kernel == Kernel::GENERIC && c->params.render_mode <= VX_MODE_RAYMARCH);
   if (mo.fuse && !folds)
     VX_FAIL(c, VX_ERR_INVALID, "render launch: running mean to fold (MultiOut::fuse) for a kernel that does not fold it");
   const uint32_t* order = lp.ordered ? c->order : nullptr;
   switch (lp.kernel) {
     case Kernel::DVR_LDS:
+      if (proj_mode(c->params.render_mode)) {
+        const bool skip = c->params.dvr_skip_empty && c->proj_dev && !c->proj_dirty;
+        launch_proj_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, skip ? c->proj_dev : nullptr);
+        break;
+      }
       launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_shared_window,
                      shadow_on(c) ? &c->shadow : nullptr);
       break;
@@ -731,6 +854,8 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
         case VX_MODE_NO_DDA: launch_mode<VX_MODE_NO_DDA>(c, lp, mo, weight, grid); break;
         case VX_MODE_RAYMARCH: launch_mode<VX_MODE_RAYMARCH>(c, lp, mo, weight, grid); break;
         case VX_MODE_DVR: launch_mode<VX_MODE_DVR>(c, lp, mo, weight, grid); break;
+        case VX_MODE_MIP: launch_mode<VX_MODE_MIP>(c, lp, mo, weight, grid); break;
+        case VX_MODE_MINIP: launch_mode<VX_MODE_MINIP>(c, lp, mo, weight, grid); break;
         default: launch_mode<VX_MODE_DVR_PHONG>(c, lp, mo, weight, grid); break;
       }
   }
@@ -976,6 +1101,7 @@ void vx_destroy(VxContext* c) {
   if (c->env_imp) (void)hipFree(c->env_imp);
   if (c->env_impq) (void)hipFree(c->env_impq);
   if (c->skip_dev) (void)hipFree(c->skip_dev);
+  if (c->proj_dev) (void)hipFree(c->proj_dev);
   if (c->fold_dev) (void)hipFree(c->fold_dev);
   if (c->shadow_count_dev) (void)hipFree(c->shadow_count_dev);
   for (hipEvent_t e : c->shadow_ev)
@@ -1274,6 +1400,7 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
   }
   c->range_host.assign((const uint32_t*)range, (const uint32_t*)range + nb);
   c->skip_dirty = true;
+  c->proj_dirty = true;
   c->order_builds_left = 2;
   uint32_t n_layers = 0;
   if ((rc = alloc_layout(c, n_layers))) { free_volume(c); return rc; }
@@ -1479,7 +1606,7 @@ int vx_set_params(VxContext* c, const VxParams* p) {
     });
   }
   VX_DEV(c);
-  if (p->render_mode < VX_MODE_DEFAULT || p->render_mode > VX_MODE_DVR_PHONG)
+  if (p->render_mode < VX_MODE_DEFAULT || p->render_mode > VX_MODE_MINIP)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: unknown render mode %d", p->render_mode);
   if (p->shard_count < 1 || p->shard_rank < 0 || p->shard_rank >= p->shard_count)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: bad shard %d/%d", p->shard_rank, p->shard_count);
@@ -1487,17 +1614,20 @@ int vx_set_params(VxContext* c, const VxParams* p) {
   if (c->W && ((uint32_t)p->res[0] != c->W || (uint32_t)p->res[1] != c->H))
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: res %dx%d differs from vx_resize %ux%u", p->res[0],
             p->res[1], c->W, c->H);
-  if ((p->render_mode == VX_MODE_DVR || p->render_mode == VX_MODE_DVR_PHONG) &&
-      !(p->dvr_step_voxels > 0.0f))
+  // the projections sample as DVR does: the same checks
+  const bool marches = p->render_mode == VX_MODE_DVR || p->render_mode == VX_MODE_DVR_PHONG || proj_mode(p->render_mode);
+  if (marches && !(p->dvr_step_voxels > 0.0f))
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_step_voxels must be > 0");
   // the kernels count steps in fp32 (t_k = fma(k, dt, t0)): beyond 2^24 the count stops advancing
-  if ((p->render_mode == VX_MODE_DVR || p->render_mode == VX_MODE_DVR_PHONG) &&
-      (p->dvr_max_steps < 0 || p->dvr_max_steps > (1 << 24)))
+  if (marches && (p->dvr_max_steps < 0 || p->dvr_max_steps > (1 << 24)))
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_max_steps %d outside [0, 2^24]", p->dvr_max_steps);
   if (p->dvr_shadow_stride != 0 && p->dvr_shadow_stride != 1 && p->dvr_shadow_stride != 2 && p->dvr_shadow_stride != 4)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride must be 0, 1, 2 or 4, not %d", p->dvr_shadow_stride);
   if (p->dvr_shadow_stride != 0 && p->render_mode == VX_MODE_DVR_PHONG)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride %d with VX_MODE_DVR_PHONG (shadows serve plain DVR)",
+            p->dvr_shadow_stride);
+  if (p->dvr_shadow_stride != 0 && proj_mode(p->render_mode))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride %d with an intensity projection (shadows serve plain DVR)",
             p->dvr_shadow_stride);
   if (p->dvr_shadow_stride != 0 && p->render_mode == VX_MODE_DVR && p->use_env != 0)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_params: dvr_shadow_stride %d with use_env = 1 (an environment map has no single light "
@@ -1609,6 +1739,12 @@ static int prepare_render(VxContext* c, dim3& grid) {
         int rc = rebuild_skip_mask(c);
         if (rc) return rc;
       }
+    }
+    if (proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits &&
+        (c->proj_dirty || !c->proj_dev || c->proj_mode != p.render_mode || c->proj_key[0] != p.volume_density_scale ||
+         c->proj_key[1] != p.volume_inv_maj)) {
+      int rc = rebuild_projection_bounds(c);
+      if (rc) return rc;
     }
     if (p.render_mode == VX_MODE_DEFAULT && !p.debug_hits &&
         (c->lmaj_dirty || !c->dv.lmaj || c->lmaj_key[0] != p.volume_density_scale || c->lmaj_key[1] != p.volume_inv_maj ||
@@ -2022,6 +2158,21 @@ int vx_debug_build_skip_mask(const uint32_t* range_packed, const uint32_t brick_
   if (level_out) *level_out = (uint32_t)level;
   if (dims_out) { dims_out[0] = md[0]; dims_out[1] = md[1]; dims_out[2] = md[2]; }
   if (bits_out) memcpy(bits_out, bits.data(), bits.size() * 4);
+  return VX_OK;
+}
+
+// test hook: the host-built density bounds of range skipping (pure CPU, no context), {lo, hi} per macro cell
+int vx_debug_build_projection_bounds(const uint32_t* range_packed, const uint32_t brick_count[3], const VxParams* p,
+                                     float* bounds_out, uint32_t* level_out, uint32_t dims_out[3]) {
+  if (!range_packed || !brick_count || !p) return VX_ERR_INVALID;
+  uint32_t extent[3] = {brick_count[0] * 8u, brick_count[1] * 8u, brick_count[2] * 8u};
+  std::vector<float> lohi;
+  int level = 1;
+  uint32_t md[3];
+  compute_projection_bounds(*p, range_packed, brick_count, extent, lohi, level, md);
+  if (level_out) *level_out = (uint32_t)level;
+  if (dims_out) { dims_out[0] = md[0]; dims_out[1] = md[1]; dims_out[2] = md[2]; }
+  if (bounds_out) memcpy(bounds_out, lohi.data(), lohi.size() * sizeof(float));
   return VX_OK;
 }
 

@@ -76,6 +76,19 @@ VXD void dvr_store(const VxParams& p, const DevVolume& dv, const DvrRay& r, floa
   slab[si] = o;
 }
 
+// fragment.frag:158 for one pixel's radiance L: out = w * prev + (1 - w) * L, alpha 1 (render_generic's blend, operation for
+// operation); the intensity projections' LDS-window kernel (vx_projection.hpp) stores with it
+VXD void store_blend(V3 L, float weight, float4* __restrict__ slab, uint32_t si) {
+  float4 prev = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (weight != 0.0f) prev = slab[si];
+  float4 o;
+  o.x = fma_(1.0f - weight, L.x, weight * prev.x);
+  o.y = fma_(1.0f - weight, L.y, weight * prev.y);
+  o.z = fma_(1.0f - weight, L.z, weight * prev.z);
+  o.w = 1.0f;
+  slab[si] = o;
+}
+
 // U = march steps per loop iteration: the 2*U gathers of a batch are issued back to back before
 // any of them is consumed, so a wave keeps 2*U loads in flight instead of 2 (the march is
 // latency-bound on the longest rays: tools/tail_probe.py).

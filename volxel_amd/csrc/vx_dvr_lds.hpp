@@ -162,7 +162,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PHONG ? (SK
                                                        const uint32_t* __restrict__ order) {
   static_assert(!WG || (!SKIP && !PHONG), "the shared window serves the plain DVR march");
   constexpr bool SHADOW = false;
+  constexpr int PROJ = 0;
   const ShadowGrid sg{};
+  const float* const pbound = nullptr;
 #include "vx_dvr_lds_march.inc"
 }
 // Shadowed DVR (VxParams::dvr_shadow_stride): the same march, and a contributing sample adds w = dT * T_L,
@@ -175,6 +177,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W
     const TileMap tm, const uint32_t* __restrict__ order, const ShadowGrid sg) {
   constexpr bool PHONG = false, WG = false;
   constexpr bool SHADOW = true;
+  constexpr int PROJ = 0;
+  const float* const pbound = nullptr;
 #include "vx_dvr_lds_march.inc"
 }
 

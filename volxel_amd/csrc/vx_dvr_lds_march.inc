@@ -1,21 +1,25 @@
 // vx_dvr_lds_march.inc -- the body of the LDS-window DVR / Phong kernels (vx_dvr_lds.hpp), included INSIDE each __global__
-// function that runs it: render_dvr_lds<S, PHONG, SKIP, U8, WG> and render_dvr_lds_shadow<S, SKIP, U8>.  Textual, not a device
+// function that runs it: render_dvr_lds<S, PHONG, SKIP, U8, WG>, render_dvr_lds_shadow<S, SKIP, U8> and the intensity projections
+// render_proj_lds<S, MINIP, SKIP, U8> (vx_projection.hpp).  Textual, not a device
 // function: a function inlined into the kernel is first optimised on its own (flat pointers, its own inlining order), and the
 // unshadowed kernels then came out with other registers and instructions.  Included this way they compile to exactly what
 // they were before the shadowed form existed.
-// In scope at the point of inclusion: the template parameters S, PHONG, SKIP, U8, WG and `constexpr bool SHADOW`, the kernel
-// arguments p, v, tf_global, tf_len, mo, weight, tm, order, and `sg` (the light grid; unused unless SHADOW).
+// In scope at the point of inclusion: the template parameters S, PHONG, SKIP, U8, WG, `constexpr bool SHADOW` and `constexpr int
+// PROJ` (0: DVR / Phong; 1: MIP, 2: MinIP), the kernel arguments p, v, tf_global, tf_len, mo, weight, tm, order, `sg` (the light
+// grid; unused unless SHADOW) and `pbound` (the density bounds of range skipping per macro cell; unused unless PROJ and SKIP).
+// PROJ: the march evaluates the same samples, keeps their largest (smallest) density instead of compositing, has no early ray
+// termination, and SKIP means range skipping: a lane flies over a macro cell whose bound cannot change its m.
   using TL = LdsTile<PHONG, WG>;
   constexpr int DX = TL::X, DY = TL::Y, DZ = TL::Z, RS = TL::RS, SS = TL::SS;
   extern __shared__ float4 lds_raw[];
   float4* tf_lds = lds_raw;
   uint32_t* mask_lds = reinterpret_cast<uint32_t*>(lds_raw + tf_len);
-  float* tile = reinterpret_cast<float*>(mask_lds + (SKIP ? ((v.skip_words + 3u) & ~3u) : 0u)) + (WG ? 0u : (threadIdx.x >> 6) * TL::FLOATS);
+  float* tile = reinterpret_cast<float*>(mask_lds + (SKIP && !PROJ ? ((v.skip_words + 3u) & ~3u) : 0u)) + (WG ? 0u : (threadIdx.x >> 6) * TL::FLOATS);
   // WG: behind the shared tile, per wave {min x, min y, min z, first live lane's cell x, y, z, live | direction bits, -}
   int* const wg_box = reinterpret_cast<int*>(tile + TL::FLOATS);
   const uint32_t wave = threadIdx.x >> 6;
   for (uint32_t i = threadIdx.x; i < tf_len; i += blockDim.x) tf_lds[i] = tf_global[i];
-  if (SKIP)
+  if (SKIP && !PROJ)
     for (uint32_t i = threadIdx.x; i < v.skip_words; i += blockDim.x) mask_lds[i] = v.skip_bits[i];
   __syncthreads();
   uint32_t fslot, bslot;
@@ -90,6 +94,8 @@
   const float ivz = r.dq.z != 0.0f ? __builtin_amdgcn_rcpf(r.dq.z) : 3.0e38f;
 
   float Cx = 0.f, Cy = 0.f, Cz = 0.f, T = 1.0f, tau = 0.0f, kf = 0.0f;   // kf: per-lane step index
+  // PROJ: the running maximum (minimum) of the lane's densities, and the samples range skipping flew over (exact integers)
+  [[maybe_unused]] float pm = PROJ == 2 ? __builtin_inff() : -__builtin_inff(), pskip = 0.0f;
   uint32_t n_samples = 0, n_slots = 0, n_skipped = 0, n_grads = 0, n_loads = 0, n_reads = 0, n_tf = 0;   // wave-uniform
 
   // cell-frame position of the lane's next sample and its floor (the cell), as floats: the march needs no integer
@@ -396,9 +402,28 @@
   // that windows are only staged where something can be seen.  Bounded: a lane still in empty space after FLY rounds
   // goes on inside the next window (the march tests the mask per step wherever the window touches an empty cell).
   constexpr int FLY = 48;
+  // PROJ: the bound of the lane's macro cell (global memory, through the caches) cannot change m -- every sample passed over
+  // lies in that cell, and m does not move while the lane flies
+  [[maybe_unused]] auto cannot_change_m = [&]() {
+    uint32_t cx = (uint32_t)((int)flx + 1), cy = (uint32_t)((int)fly + 1), cz = (uint32_t)((int)flz + 1);
+    cx = cx < cmaxx ? cx : cmaxx; cy = cy < cmaxy ? cy : cmaxy; cz = cz < cmaxz ? cz : cmaxz;
+    const float b = pbound[mad24(mad24(cz >> sh, md1, cy >> sh), md0, cx >> sh)];
+    return PROJ == 2 ? b >= pm : b <= pm;
+  };
   auto free_flight = [&]() {
 #pragma unroll 1
     for (int it = 0; it < FLY; ++it) {
+      if constexpr (PROJ != 0) {   // counts the samples flown over; a jump never passes the ray's last sample
+        const bool emp = is_alive() & cannot_change_m();   // (every lane loads: the clamps keep the index in the table)
+        const unsigned long long em = ballot(emp);
+        if (em == 0ull) break;
+        n_slots += 64u;
+        const float kn = emp ? fminf(kf + 1.0f + jump_of(emp), nray) : kf;
+        pskip += kn - kf;
+        kf = kn;
+        next_sample();
+        continue;
+      }
       const bool emp = is_alive() & in_empty_cell();
       const unsigned long long em = ballot(emp);
       if (em == 0ull) break;
@@ -429,7 +454,7 @@
     }
     const bool now = exact_window(live);
     if (WG && !wg_any) return false;   // workgroup uniform: no wave has a live ray left
-    if (SKIP) wtest = touches_empty();
+    if (SKIP && !PROJ) wtest = touches_empty();
     set_limits(now);
     float4 vals[TL::PASSES][NC];
     issue_loads(LOx, LOy, LOz, vals);
@@ -475,7 +500,7 @@
         if (em != 0ull) jump = jump_of(emp);      // wave uniform
       }
       // (without skipping a lane evaluates one sample per step it takes: its count is kf after the march)
-      if (SKIP) n_samples += (uint32_t)__builtin_popcountll(ballot(eval));
+      if (SKIP && !PROJ) n_samples += (uint32_t)__builtin_popcountll(ballot(eval));
       // byte address of the sample's cell in the tile: (z * SS + y * RS + x) * 4 + tile_base, every partial sum an
       // integer below 2^23, exact in fp32 (cells are below 2^13, the byte strides below 2^11).  A lane that does not step (its pending sample
       // lies outside this window) reads the tile's first cell instead: every read stays inside the wave's tile.
@@ -501,7 +526,11 @@
       // and a second compare, two half-rate vector instructions per step -- profiles/r03_op_rates.txt)
       // (the upper bound is only tested where the lower one holds for some lane: on this kind of data the lower bound
       // alone turns 80 % of the wave steps away)
-      const unsigned long long rlo = (TEST ? ballot(eval) : gom) & ballot(!(dn < sr0));
+      if constexpr (PROJ != 0) {   // one v_max_f32 / v_min_f32; no TF, no composite, no termination
+        const float mv = PROJ == 2 ? fminf(pm, dn) : fmaxf(pm, dn);
+        pm = ALL ? mv : (go ? mv : pm);
+      }
+      const unsigned long long rlo = PROJ != 0 ? 0ull : (TEST ? ballot(eval) : gom) & ballot(!(dn < sr0));
       if (rlo != 0ull) {
         const unsigned long long rm = rlo & ballot(!(dn > sr1));
         n_tf += (uint32_t)__builtin_popcountll(rm);
@@ -614,7 +643,7 @@
     if (!WG && ballot(is_alive()) == 0ull) break;
     if (SKIP && wtest) march(std::integral_constant<bool, SKIP>{});
     else march(std::false_type{});
-    nray = tau >= ert ? -1.0f : nray;   // the rays the march terminated
+    if (!PROJ) nray = tau >= ert ? -1.0f : nray;   // the rays the march terminated
     // ---- next window ------------------------------------------------------------------------------------------------
     const unsigned long long live = ballot(is_alive());
     if (!WG && live == 0ull) break;
@@ -622,10 +651,24 @@
   }
 
   // (kf counts the samples of a lane: without skipping every step it takes evaluates one; a terminated ray stopped at kf)
-  if (!SKIP) n_samples = wave_sum((uint32_t)kf);   // kf <= 2^24: exact; lane 0 holds the sum (add_counts reads it there)
+  if (!SKIP && !PROJ) n_samples = wave_sum((uint32_t)kf);   // kf <= 2^24: exact; lane 0 holds the sum (add_counts reads it there)
+  if (PROJ) {   // a lane ends at kf = n: each of its samples was evaluated or flown over
+    n_samples = wave_sum((uint32_t)(kf - pskip));
+    n_skipped = wave_sum((uint32_t)pskip);
+    n_tf = (uint32_t)__builtin_popcountll(ballot(hit0 && r.n > 0.0f));   // the TF fetch of m, once per ray with a sample
+  }
   // a ray that terminated early is opaque: T = 0 (vx_modes.hpp Frame::dvr)
   if (nray < 0.0f) T = 0.0f;
-  if (!WG && fuse != 0u) {
+  if (PROJ) {
+    V3 L = v3(0.f, 0.f, 0.f);
+    if (in_image && hit0 && r.n > 0.0f) {
+      const TfView tv{tf_lds, tf_len, lenf, true};
+      const float4 px4 = projection_pixel(tv, sr0, sr1, pm);
+      L = v3(sanitize1(px4.x), sanitize1(px4.y), sanitize1(px4.z));   // as Frame::shade_pixel
+    }
+    if (fuse != 0u) fold_frames(tile, lane, L, in_image, si, mo.accum, fuse, 31u - (uint32_t)__builtin_clz(mo.count));
+    else if (in_image) store_blend(L, weight, slab, si);
+  } else if (!WG && fuse != 0u) {
     // ---- the running mean of the launch, in the wave that holds every frame of its pixels (MultiOut::fuse) -------------
     // lane l holds frame slot l >> psh of pixel l & (npx - 1); its result goes to the wave's tile (the march is over); lanes
     // 0 .. 3 npx - 1 then each fold one colour channel of one pixel through the frame slots in order:

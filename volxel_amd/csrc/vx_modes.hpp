@@ -6,6 +6,13 @@ namespace vx {
 
 constexpr uint32_t LOOP_GUARD = 1u << 20;
 
+// the pixel of an intensity projection (VX_MODE_MIP / VX_MODE_MINIP) whose ray has a sample: rgba = TF(m) with DVR's TF rule
+// (0 outside the sample range), shown as (r a, g a, b a, 1).  Shared by Frame::project and the LDS-window kernel.
+VXD float4 projection_pixel(const TfView& tf, float sr0, float sr1, float m) {
+  const float4 rgba = lookup_transfer(tf, sr0, sr1, m);
+  return make_float4(rgba.x * rgba.w, rgba.y * rgba.w, rgba.z * rgba.w, 1.0f);
+}
+
 template <int LAYOUT>
 struct Frame {
   const VxParams& p;
@@ -435,6 +442,39 @@ struct Frame {
     return make_float4(L.x, L.y, L.z, hit ? 1.0f : 0.0f);
   }
 
+  // ---- [build] intensity projections (VX_MODE_MIP / VX_MODE_MINIP): DVR's samples, reduced to their
+  // largest (smallest) density m; the pixel is TF(m) premultiplied by its alpha.  No range skipping here: render_generic has
+  // no argument for the bound table, and every sample is evaluated (the LDS-window kernel, vx_projection.hpp, skips).
+  template <bool MINIP>
+  VXD float4 project(const Ray& ray, float start_offset) const {
+    float near, far;
+    float m = MINIP ? __builtin_inff() : -__builtin_inff();
+    float nf = 0.0f;
+    if (slab(ray, near, far)) {
+      c.rays++;
+      V3 ipos, idir;
+      to_index(p, ray, ipos, idir);
+      const float dt = p.dvr_step_voxels / sqrtf(dot3(idir, idir));
+      const float t0 = fma_(start_offset, dt, near);
+      const float xq = (far - t0) / dt;   // the march contract, as Frame::dvr
+      nf = (xq > 0.0f) ? fminf(ceilf(xq), (float)p.dvr_max_steps) : 0.0f;
+      const V3 dq = v3(dt * idir.x, dt * idir.y, dt * idir.z);
+      const V3 q0 = v3(fma_(t0, idir.x, ipos.x) - 0.5f, fma_(t0, idir.y, ipos.y) - 0.5f, fma_(t0, idir.z, ipos.z) - 0.5f);
+      for (float kf = 0.0f; kf < nf; kf += 1.0f) {
+        const float qx = fma_(kf, dq.x, q0.x), qy = fma_(kf, dq.y, q0.y), qz = fma_(kf, dq.z, q0.z);
+        const float flx = floorf(qx), fly = floorf(qy), flz = floorf(qz);
+        const float dens = trilinear_cell<LAYOUT>(v, p.volume_density_scale, f2i(flx), f2i(fly), f2i(flz), qx - flx, qy - fly,
+                                                  qz - flz);
+        const float dn = dens * p.volume_inv_maj;
+        m = MINIP ? fminf(m, dn) : fmaxf(m, dn);
+        c.samples++;
+      }
+    }
+    if (!(nf > 0.0f)) return make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    c.tf++;
+    return projection_pixel(tf, p.sample_range[0], p.sample_range[1], m);
+  }
+
   // ---- fragment.frag:128-158 for one pixel (without the running-mean blend) -------------
   template <int MODE, bool SHADOW = false>
   VXD float4 shade_pixel(int px, int py, uint32_t frame) const {
@@ -444,7 +484,8 @@ struct Frame {
     float a0 = rng(s), a1 = rng(s), b0 = rng(s), b1 = rng(s);  // :146
     float jx = (a0 + b0) / 2.0f, jy = (a1 + b1) / 2.0f;
     constexpr bool DVR = (MODE == VX_MODE_DVR || MODE == VX_MODE_DVR_PHONG);
-    if (DVR && !p.dvr_jitter) { jx = 0.5f; jy = 0.5f; }
+    constexpr bool PROJ = (MODE == VX_MODE_MIP || MODE == VX_MODE_MINIP);   // DVR's rays and draws
+    if ((DVR || PROJ) && !p.dvr_jitter) { jx = 0.5f; jy = 0.5f; }
     Ray ray = setup_world_ray(p, tex_x, tex_y, jx, jy, &v);   // uniform terms from the host (DevVolume::cam_o)
     float4 r;
     if (p.debug_hits) {  // :147-153
@@ -461,7 +502,11 @@ struct Frame {
       }
       return r;
     }
-    if (DVR) {
+    if constexpr (PROJ) {
+      (void)rng(s);  // the draws of the DVR branch below
+      float u_start = rng(s);
+      r = project<MODE == VX_MODE_MINIP>(ray, p.dvr_jitter ? u_start : 0.5f);
+    } else if (DVR) {
       (void)rng(s);  // tau_target slot of raymarch.glsl:28
       float u_start = rng(s);
       r = dvr<MODE == VX_MODE_DVR_PHONG, SHADOW>(ray, p.dvr_jitter ? u_start : 0.5f);

@@ -1,0 +1,51 @@
+// vx_projection.hpp -- maximum- and minimum-intensity projection (VX_MODE_MIP / VX_MODE_MINIP) on the
+// brickf32 / bricku8 layouts: the LDS-window march of vx_dvr_lds_march.inc with `PROJ` set.  The window is staged exactly as
+// render_dvr_lds stages it and every tap comes from LDS; per sample the kernel keeps one v_max_f32 / v_min_f32 instead of the TF
+// look-up and the composite, has no early ray termination, and reads the TF once per pixel after the march.  The other layouts,
+// debug_hits, VX_DVR_KERNEL=generic and TFs too long for LDS go to render_generic<VX_MODE_MIP / VX_MODE_MINIP> (Frame::project).
+#pragma once
+#include "vx_dvr_lds.hpp"
+
+namespace vx {
+
+// Range skipping (SKIP): `pbound` holds ONE float per macro cell of the empty-space grid (v.skip_level / v.skip_dims), the upper
+// density bound for MIP and the lower one for MinIP (vx_api.hip compute_projection_bounds).  It stays in global memory and is
+// read through the caches: 65 536 cells x 4 B does not fit beside the TF and the tiles in a CU's 160 KB of LDS, a table rounded
+// to 8 or 16 bits would skip less, and the bound is only read in free flight -- once per lane and flight round before a window
+// is placed, not per march step -- where one cached load per lane is small against the window it saves.
+template <int S, bool MINIP, bool SKIP, bool U8>
+// Occupancy asked of the register allocator: 8 waves per SIMD, as the DVR build; the SKIP builds on brickf32 came out with a
+// 36-byte stack frame under that budget, so they are asked for VX_W_LDS_SKIP like the DVR SKIP builds (see the resource report
+// in NOTEBOOK.md).
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W_LDS_SKIP : VX_W_LDS, 8))) void render_proj_lds(
+    const VxParams p, const DevVolume v, const float4* __restrict__ tf_global, uint32_t tf_len, const MultiOut mo, float weight,
+    const TileMap tm, const uint32_t* __restrict__ order, const float* __restrict__ pbound) {
+  constexpr bool PHONG = false, WG = false;
+  constexpr bool SHADOW = false;
+  constexpr int PROJ = MINIP ? 2 : 1;
+  const ShadowGrid sg{};
+#include "vx_dvr_lds_march.inc"
+}
+
+// bounds: the table of range skipping, nullptr without it
+inline void launch_proj_lds(const VxParams& p, const DevVolume& v, const float4* tf, uint32_t tf_len, const MultiOut& mo,
+                            float weight, const TileMap& tm, hipStream_t stream, const uint32_t* order, const float* bounds) {
+  const uint32_t groups = (tm.tiles_per_shard + 7u) / 8u;
+  const dim3 grid(groups * 128u * (mo.count ? mo.count : 1u)), block(256);
+  const bool skip = bounds != nullptr;
+  const bool minip = p.render_mode == VX_MODE_MINIP;
+  const bool u8 = v.bu_active != 0u;
+  const size_t lds = (size_t)tf_len * sizeof(float4) + 4u * (size_t)LdsTile<false>::FLOATS * sizeof(float);
+#define VX_LAUNCH_PR(MI, SK, U) \
+  hipLaunchKernelGGL((render_proj_lds<VX_LDS_S, MI, SK, U>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order, bounds)
+  if (minip) {
+    if (skip) { if (u8) VX_LAUNCH_PR(true, true, true); else VX_LAUNCH_PR(true, true, false); }
+    else      { if (u8) VX_LAUNCH_PR(true, false, true); else VX_LAUNCH_PR(true, false, false); }
+  } else {
+    if (skip) { if (u8) VX_LAUNCH_PR(false, true, true); else VX_LAUNCH_PR(false, true, false); }
+    else      { if (u8) VX_LAUNCH_PR(false, false, true); else VX_LAUNCH_PR(false, false, false); }
+  }
+#undef VX_LAUNCH_PR
+}
+
+}  // namespace vx

@@ -8,7 +8,7 @@ export type BrickGridMessage = {            // WasmWorkerMessageDicomReturn, com
   rangeMipmaps: { mipmap: Uint16Array; stride: [number, number, number] }[];
   indirection: Uint32Array; range: Uint16Array; atlas: Uint8Array; brickCounter: number;
 };
-export declare const VolxelRenderMode: { default: 0; no_dda: 1; raymarch: 2; dvr: 3; dvr_phong: 4 };
+export declare const VolxelRenderMode: { default: 0; no_dda: 1; raymarch: 2; dvr: 3; dvr_phong: 4; mip: 5; minip: 6 };
 export declare function generateTransferFunction(colors: ColorStop[], generatedSteps?: number): { data: Float32Array; length: number };
 export declare class Camera {
   pos: number[]; view: number[];

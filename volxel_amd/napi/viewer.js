@@ -13,7 +13,7 @@ const fs = require('fs');
 const path = require('path');
 const native = require('./volxel_napi.node');
 
-const RenderMode = Object.freeze({ default: 0, no_dda: 1, raymarch: 2, dvr: 3, dvr_phong: 4 });
+const RenderMode = Object.freeze({ default: 0, no_dda: 1, raymarch: 2, dvr: 3, dvr_phong: 4, mip: 5, minip: 6 });
 const LOW_RES_DURATION = 5; // viewer.ts:132
 
 // ---- VxParams field table, parsed from the C header (single source of truth) --------------

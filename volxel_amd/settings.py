@@ -80,11 +80,15 @@ def verify_transfer_settings(s):  # settings.ts:75-92
     return s
 
 
+# the render modes a settings export may carry: the reference's three, and the intensity projections ([build])
+DISPLAY_RENDER_MODES = ("default", "no_dda", "raymarch", "mip", "minip")
+
+
 def verify_display_settings(s):  # settings.ts:94-105
     if not (_is_num(s.get("samples")) and _is_num(s.get("bounces")) and _is_num(s.get("gamma"))
             and _is_num(s.get("exposure")) and isinstance(s.get("debugHits"), bool)
             and isinstance(s.get("renderMode"), str)
-            and s["renderMode"] in ("default", "no_dda", "raymarch")
+            and s["renderMode"] in DISPLAY_RENDER_MODES
             and _is_num(s.get("resolutionFactor"))):
         raise ValueError("Malformed Display Settings detected.")
 
