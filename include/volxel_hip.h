@@ -179,9 +179,9 @@ typedef struct VxCounters {
   uint64_t tf_samples;   /* samples whose density lay inside the sample range: the ones that fetch a
                             transfer-function entry (common.glsl:78-83) and enter the composite.
                             VX_MODE_MIP / VX_MODE_MINIP: one per ray that has a sample (the TF fetch of m)  */
-  uint64_t active_lane_slots; /* of lane_slots, the slots whose lane did work -- counted by the event-batched path
-                            kernels (default / no_dda), whose lanes may wait for an event pass; 0 elsewhere
-                            (for the DVR kernels samples / lane_slots is the lane utilisation)          */
+  uint64_t active_lane_slots; /* of lane_slots, the slots whose lane did work -- counted by the path-traced modes
+                            (default / no_dda / raymarch), whose lanes wait for the slowest lane of their wave;
+                            0 elsewhere (for the DVR kernels samples / lane_slots is the lane utilisation)  */
   uint64_t merge_launches; /* running-mean blend kernels (merge_results) launched: one per multi-frame launch
                             whose render kernel did not fold the running mean itself                        */
 } VxCounters;

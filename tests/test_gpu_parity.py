@@ -213,39 +213,29 @@ def test_converged_mean_matches_oracle(oracle, mode, env):
 
 # ---- row N3: environment-map lighting (environment.ts, envSetup.frag, environment.glsl) ----------
 @pytest.mark.parametrize("mode,bounces", [("default", 1), ("default", 3), ("no_dda", 2), ("raymarch", 1), ("default", 0)])
-def test_repacked_path_kernel_is_bit_identical(oracle, mode, bounces, monkeypatch):
-    """vx_paths.hpp (VX_PATHS_KERNEL=packed): the collided paths of a 16x16-pixel workgroup are re-packed through LDS
-    between the primary and the shadow segments.  A path record carries its pixel's xoshiro state, so every pixel
-    draws exactly the stream of fragment.frag:79-124 whichever lane runs it: same image bits, same sample counts as
-    the one-pixel-per-lane kernel, on every layout, with and without the environment map, several frames per launch."""
-    from tests.common import make_scene, benchmark_tf, BENCH_CAM, small_noise
+def test_path_kernel_renders_every_layout_and_launch_size(oracle, mode, bounces):
+    """render_generic for the path-traced modes on every layout, with and without the environment map, on a ragged image
+    (partial workgroups) and in launches of 1, 1, 3 and 2 frames: every launch renders samples and a finite image."""
+    from tests.common import benchmark_tf, BENCH_CAM, small_noise
     from volxel_amd import Volxel3DRenderer
     vox, sp = small_noise(64, seed=9)
     g = oracle.BrickGrid(vox, sp)
     tf, L = benchmark_tf()
-    res = {}
-    for kern in ("generic", "packed", "events"):     # "generic" ships; "packed" (vx_paths.hpp) and "events" (vx_events.hpp) are opt-in
-        monkeypatch.setenv("VX_PATHS_KERNEL", kern)
-        for layout in (0, 1, 2):
-            r = Volxel3DRenderer(200, 136, layout=layout)       # not a multiple of 16: partial workgroups
-            r.setup_from_grid(g)
-            r.change_transfer_func(tf, L)
-            r.settings.render_mode, r.settings.bounces = mode, bounces
-            r.settings.sample_range = (0.05, 1.0)
-            r.settings.use_env = layout != 1                     # directional light on one layout, the map on the others
-            r.camera.pos = np.asarray(BENCH_CAM["cam_pos"], dtype=np.float64)
-            r.camera.view = np.asarray(BENCH_CAM["look_at"], dtype=np.float64)
-            r.reset_counters()
-            r.render(frames=7, in_flight=3)                      # frames 0..6: launches of 1, 1, 3 and 2 frames
-            c = r.counters()
-            res[(kern, layout)] = (r.read_accum(), c.samples, c.skip_steps, c.rays)
-            r.close()
     for layout in (0, 1, 2):
-        a = res[("generic", layout)]
-        for kern in ("packed", "events"):
-            b = res[(kern, layout)]
-            assert np.array_equal(a[0], b[0]) and a[1:] == b[1:], (mode, bounces, kern, layout)
-        assert a[1] > 0 and np.isfinite(a[0]).all()
+        r = Volxel3DRenderer(200, 136, layout=layout)       # not a multiple of 16: partial workgroups
+        r.setup_from_grid(g)
+        r.change_transfer_func(tf, L)
+        r.settings.render_mode, r.settings.bounces = mode, bounces
+        r.settings.sample_range = (0.05, 1.0)
+        r.settings.use_env = layout != 1                     # directional light on one layout, the map on the others
+        r.camera.pos = np.asarray(BENCH_CAM["cam_pos"], dtype=np.float64)
+        r.camera.view = np.asarray(BENCH_CAM["look_at"], dtype=np.float64)
+        r.reset_counters()
+        r.render(frames=7, in_flight=3)                      # frames 0..6: launches of 1, 1, 3 and 2 frames
+        c = r.counters()
+        accum, samples = r.read_accum(), c.samples
+        r.close()
+        assert samples > 0 and np.isfinite(accum).all(), (mode, bounces, layout)
 
 
 def test_transfer_function_must_be_finite():
@@ -1326,7 +1316,6 @@ def test_running_mean_in_the_render_kernel_is_bit_identical(oracle, monkeypatch,
     g = oracle.BrickGrid(vox, sp)
     tf, L = benchmark_tf()
     res = {}
-    monkeypatch.setenv("VX_DVR_WG", "0")     # (the shared-window kernel keeps the blend kernel: not what is under test here)
     for key, fuse, fpl in (("serial", "1", 1), ("merge32", "0", 32), ("fused32", "1", 32), ("fused64", "1", 64), ("fused8", "1", 8),
                            ("fused16", "1", 16)):
         monkeypatch.setenv("VX_DVR_FUSE", fuse)
@@ -1357,42 +1346,6 @@ def test_running_mean_in_the_render_kernel_is_bit_identical(oracle, monkeypatch,
     else:
         want = {"serial": 1, "merge32": 6, "fused32": 2, "fused64": 4, "fused8": 18, "fused16": 10}
     assert {key: res[key][5] for key in want} == want
-
-
-def test_shared_window_kernel_is_bit_identical(oracle, monkeypatch):
-    """VX_DVR_WG=1 (vx_dvr_lds.hpp, WG): in launches of a multiple of 32 frames the four waves of a workgroup take the same 8
-    pixels (8 frames each) and march through ONE window four times the volume, placed through an exchange in LDS and two
-    workgroup barriers per window -- the north star's "per-workgroup LDS staging of the active brick", literally.  Same
-    image bits and counters as the shipped wave-private windows: jittered frames, clip box, ERT, a ragged image (partial
-    tiles: waves without a live ray must still meet every barrier), 32 and 64 frames in flight, and a 40-frame request
-    (32 through the shared window, 8 through the wave-private one)."""
-    from tests.common import benchmark_tf, BENCH_CAM, small_noise
-    from volxel_amd import Volxel3DRenderer
-    vox, sp = small_noise(64, seed=11)
-    g = oracle.BrickGrid(vox, sp)
-    tf, L = benchmark_tf()
-    res = {}
-    for wg in ("0", "1"):
-        monkeypatch.setenv("VX_DVR_WG", wg)
-        out = []
-        for (W, H), frames, fpl in (((200, 136), 32, 32), ((333, 77), 64, 64), ((96, 64), 40, 32)):
-            r = Volxel3DRenderer(W, H)
-            r.setup_from_grid(g)
-            r.change_transfer_func(tf, L)
-            r.settings.render_mode, r.settings.dvr_jitter, r.settings.dvr_skip_empty = "dvr", True, False
-            r.settings.volume_clip_min, r.settings.volume_clip_max = (0.25, 0.0, 0.0), (1.0, 1.0, 0.75)
-            r.settings.sample_range = (0.05, 1.0)
-            r.camera.pos = np.asarray(BENCH_CAM["cam_pos"], dtype=np.float64)
-            r.camera.view = np.asarray(BENCH_CAM["look_at"], dtype=np.float64)
-            r.reset_counters()
-            r.render(frames=frames, in_flight=fpl); r.finish()
-            c = r.counters()
-            out.append((r.read_accum(), c.samples, c.tf_samples, c.rays, c.pixels))
-            r.close()
-        res[wg] = out
-    for a, b in zip(res["0"], res["1"]):
-        assert np.array_equal(a[0], b[0]) and a[1:] == b[1:]
-        assert a[1] > 0
 
 
 @pytest.mark.parametrize("res", [(1920, 1080), (333, 251), (1000, 7), (4096, 16)])

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """the render modes on BASELINE config 3 (1x MI355X): kernel ms per accumulation frame, lane utilisation where the kernel
-counts it.  usage: python tools/mode_probe.py [--modes a,b] [--fpl 16,32] [bounces ...]
-VX_PATHS_KERNEL=generic | packed selects the one-pixel-per-lane / segment re-packing kernels instead of the event-batched one"""
+counts it.  usage: python tools/mode_probe.py [--modes a,b] [--fpl 16,32] [bounces ...]"""
 import os
 import sys
 

@@ -15,8 +15,6 @@
 #include "vx_dvr.hpp"
 #include "vx_dvr_lds.hpp"
 #include "vx_kernels.hpp"
-#include "vx_paths.hpp"
-#include "vx_events.hpp"
 #include "vx_shadow.hpp"
 #include "vx_projection.hpp"
 
@@ -34,15 +32,9 @@ struct EventPair {
 // The diagnostic switches of the environment, read once by vx_create (none changes a result bit).
 struct Switches {
   int dvr_variant = -1;            // VX_DVR_KERNEL=generic: 0, the DVR modes on render_generic; -1: the tuned kernels
-  int paths_variant = 0;           // VX_PATHS_KERNEL: 0 / 2 (generic): one pixel per lane (render_generic); 1 (packed): path
-                                   // segments re-packed through LDS (vx_paths.hpp) -- same bits, measured 3-11 % slower; 3 (events):
-                                   // wave-persistent, event-batched (vx_events.hpp) -- same bits, denser lanes, measured 1.4-1.8x slower
   bool dvr_fuse = true;            // VX_DVR_FUSE=0: no kernel folds the running mean; merge_results blends every multi-frame launch
-  bool dvr_shared_window = false;  // VX_DVR_WG=1: one LDS window per workgroup in launches of a multiple of 32 frames (vx_dvr_lds.hpp, WG)
-  bool use_order = true;           // VX_DVR_ORDER=0: the tuned DVR kernels run their blocks in launch order
   bool ray_shortcuts = true;       // VX_RAY_SHORTCUTS=0: the per-ray divisions themselves (DevVolume::ray_flags = 0)
   std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
-  int dvr_unroll = 4;              // VX_DVR_UNROLL=1|2|4: march steps per loop iteration of the cellquad DVR kernel
 };
 
 }  // namespace
@@ -145,7 +137,7 @@ struct VxContext {
     max_launch_frames = n > max_launch_frames ? n : max_launch_frames;
   }
   // per-frame result slabs and counter records of multi-frame launches (vx_render_frames), pipe_slots of each in ONE
-  // allocation (slot i at i * pipe_quads / i * pipe_waves): the event kernel addresses a frame slot by base + stride
+  // allocation (slot i at i * pipe_quads / i * pipe_waves)
   float4* pipe_result_pool = nullptr;
   DevCounters* pipe_dc_pool = nullptr;
   size_t pipe_quads = 0, pipe_waves = 0;
@@ -702,18 +694,16 @@ static int rebuild_light_grid(VxContext* c) {
 // ---- the launch plan: which kernel a render launch runs, and whether it folds the running mean itself ----------------
 
 enum class Kernel {
-  DVR_LDS,   // LDS-window DVR / Phong (vx_dvr_lds.hpp), the shared-window form under VX_DVR_WG=1
+  DVR_LDS,   // LDS-window DVR / Phong (vx_dvr_lds.hpp)
   DVR_CQ,    // tuned DVR on the cellquad layout (vx_dvr.hpp)
-  EVENTS,    // `default` / `no_dda` wave-persistent and event-batched (vx_events.hpp, VX_PATHS_KERNEL=events)
-  PATHS,     // the three reference modes with path segments re-packed through LDS (vx_paths.hpp, VX_PATHS_KERNEL=packed)
   GENERIC,   // render_generic<MODE> (vx_kernels.hpp)
 };
+// The tuned DVR kernels (DVR_LDS, DVR_CQ) run their blocks in c->order, longest first, and single frames refresh it (build_order).
 struct LaunchPlan {
   Kernel kernel = Kernel::GENERIC;
-  int layout = VX_LAYOUT_REFERENCE;   // what the path kernels sample (eff_layout; the DVR launchers pick their own form)
-  size_t lds = 0;                     // dynamic LDS bytes of the path kernels (the DVR launchers size their windows)
+  int layout = VX_LAYOUT_REFERENCE;   // what render_generic samples (eff_layout; the DVR launchers pick their own form)
+  size_t lds = 0;                     // dynamic LDS bytes of render_generic (the DVR launchers size their windows)
   bool fuse = false;                  // the kernel folds the running mean of the launch itself (MultiOut::fuse)
-  bool ordered = false;               // the kernel runs its blocks in c->order, and single frames refresh it (build_order)
 };
 
 static bool tuned_possible(const VxContext* c) {
@@ -739,24 +729,10 @@ static bool is_tuned(const VxContext* c) {
   const bool dvr_cq = c->params.render_mode == VX_MODE_DVR && eff_layout(c) == VX_LAYOUT_CELLQUAD;
   return tuned_possible(c) && (dvr_cq || use_lds_kernel(c));
 }
-// the event kernel addresses its frame slots by base + stride: consecutive frames at constant strides (vx_render_frames
-// allocates them that way), slab slots below 2^26
-static bool events_possible(const VxContext* c, const MultiOut& mo) {
-  if (c->sw.paths_variant != 3 || c->params.debug_hits || c->tf_len > TF_LDS_MAX) return false;
-  if (c->params.render_mode != VX_MODE_DEFAULT && c->params.render_mode != VX_MODE_NO_DDA) return false;
-  const uint32_t n = mo.count;
-  for (uint32_t i = 1; i < n; ++i)
-    if (mo.frame[i] != mo.frame[0] + i || mo.out[i] - mo.out[0] != (ptrdiff_t)i * (mo.out[1] - mo.out[0]) ||
-        mo.dc[i] - mo.dc[0] != (ptrdiff_t)i * (mo.dc[1] - mo.dc[0]))
-      return false;
-  return c->slab_quads < (1u << 26) && n <= 64u;
-}
-
 // The one place that decides what a render launch of the mo.count frame slots of `mo` runs.  The fuse rule: while
 // VX_DVR_FUSE is on, the kernel folds the running mean of the launch into the accumulator itself when
-//   * it is the LDS-window DVR / Phong kernel without the shared window (VX_DVR_WG), or the projections' LDS-window kernel
-//     (which never takes the shared window), and the launch has 8, 16, 32 or 64 frames (a wave holds every frame of its
-//     8, 4, 2 or 1 pixels), or
+//   * it is the LDS-window DVR / Phong kernel or the projections' LDS-window kernel, and the launch has 8, 16, 32 or 64
+//     frames (a wave holds every frame of its 8, 4, 2 or 1 pixels), or
 //   * it is render_generic for `default`, `no_dda` or `raymarch` and the launch has exactly 32 frames (2 pixels x 32
 //     frames per wave).
 // Every other multi-frame launch writes per-frame result slabs that merge_results blends in frame order.
@@ -768,53 +744,21 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo) {
   // shadowed DVR: the LDS-window kernel's shadowed form, or render_generic's -- never the cellquad DVR kernel
   if (is_tuned(c) && (!shadow_on(c) || use_lds_kernel(c))) {
     lp.kernel = use_lds_kernel(c) ? Kernel::DVR_LDS : Kernel::DVR_CQ;
-    lp.ordered = c->sw.use_order;
-    lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && (!c->sw.dvr_shared_window || proj_mode(p.render_mode)) &&
-              (n == 8u || n == 16u || n == 32u || n == 64u);
-    return lp;
-  }
-  if (events_possible(c, mo)) {
-    lp.kernel = Kernel::EVENTS;
-    lp.lds = (size_t)c->tf_len * sizeof(float4) + 4u * PF_COUNT * 64u * sizeof(float);
+    lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && (n == 8u || n == 16u || n == 32u || n == 64u);
     return lp;
   }
   lp.lds = c->tf_len <= TF_LDS_MAX ? (size_t)c->tf_len * sizeof(float4) : 0;
-  // (bounces < 1: fragment.frag:86-101 still traces the primary segment and one light sample before it tests the
-  // count; render_paths loops on `n_paths < bounces` and would leave the slab unwritten -- render_generic serves it)
-  if (c->sw.paths_variant == 1 && !p.debug_hits && p.render_mode <= VX_MODE_RAYMARCH && p.bounces >= 1) {
-    lp.kernel = Kernel::PATHS;
-    return lp;
-  }
-  lp.kernel = Kernel::GENERIC;
   lp.fuse = c->sw.dvr_fuse && p.render_mode <= VX_MODE_RAYMARCH && n == 32u;
   if (lp.fuse) lp.lds += 4u * 320u * sizeof(float);   // fold_frames' scratch, one per wave
   return lp;
 }
 
-// the path kernels of render mode MODE: event-batched, re-packed or render_generic, on the plan's layout
+// render_generic of render mode MODE (render_generic_shadow for shadowed DVR), on the plan's layout
 template <int MODE>
 static void launch_mode(const VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
   with_layout(lp.layout, [&](auto tag) {
     constexpr int LAY = decltype(tag)::value;
-    if constexpr (MODE == VX_MODE_DEFAULT || MODE == VX_MODE_NO_DDA) {
-      if (lp.kernel == Kernel::EVENTS) {
-        const uint32_t n = mo.count;
-        const uint64_t out_stride = n > 1 ? (uint64_t)(mo.out[1] - mo.out[0]) : 0u,
-                       dc_stride = n > 1 ? (uint64_t)(mo.dc[1] - mo.dc[0]) : 0u;
-        grid.x *= (n + VX_EV_FRAMES - 1u) / VX_EV_FRAMES;
-        hipLaunchKernelGGL((render_events<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
-                           mo.out[0], out_stride, mo.dc[0], dc_stride, mo.frame[0], n, weight, c->tm);
-        return;
-      }
-    }
     grid.x *= mo.count;
-    if constexpr (MODE <= VX_MODE_RAYMARCH) {
-      if (lp.kernel == Kernel::PATHS) {
-        hipLaunchKernelGGL((render_paths<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
-                           mo, weight, c->tm);
-        return;
-      }
-    }
     if constexpr (MODE == VX_MODE_DVR) {
       if (shadow_on(c)) {
         hipLaunchKernelGGL((render_generic_shadow<LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
@@ -830,23 +774,20 @@ static void launch_mode(const VxContext* c, const LaunchPlan& lp, const MultiOut
 // The one launch switch: runs what `lp` names for the frame slots of `mo` on the context's stream.  Fails closed: a
 // kernel that does not fold the running mean refuses a launch with mo.fuse set -- its frames would reach no accumulator.
 static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
-  const bool folds = (lp.kernel == Kernel::DVR_LDS && (!c->sw.dvr_shared_window || proj_mode(c->params.render_mode))) ||
-                     (lp.kernel == Kernel::GENERIC && c->params.render_mode <= VX_MODE_RAYMARCH);
+  const bool folds = lp.kernel == Kernel::DVR_LDS || (lp.kernel == Kernel::GENERIC && c->params.render_mode <= VX_MODE_RAYMARCH);
   if (mo.fuse && !folds)
     VX_FAIL(c, VX_ERR_INVALID, "render launch: running mean to fold (MultiOut::fuse) for a kernel that does not fold it");
-  const uint32_t* order = lp.ordered ? c->order : nullptr;
   switch (lp.kernel) {
     case Kernel::DVR_LDS:
       if (proj_mode(c->params.render_mode)) {
         const bool skip = c->params.dvr_skip_empty && c->proj_dev && !c->proj_dirty;
-        launch_proj_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, skip ? c->proj_dev : nullptr);
+        launch_proj_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, c->order, skip ? c->proj_dev : nullptr);
         break;
       }
-      launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_shared_window,
-                     shadow_on(c) ? &c->shadow : nullptr);
+      launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, c->order, shadow_on(c) ? &c->shadow : nullptr);
       break;
     case Kernel::DVR_CQ:
-      launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, order, c->sw.dvr_unroll);
+      launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, c->order);
       break;
     default:
       switch (c->params.render_mode) {
@@ -1003,17 +944,9 @@ int vx_create(int device_id, VxContext** out) {
   // the diagnostic switches (struct Switches): the only place that reads the environment
   Switches& sw = c->sw;
   if (const char* v = getenv("VX_DVR_KERNEL"); v && !strcmp(v, "generic")) sw.dvr_variant = 0;
-  if (const char* v = getenv("VX_PATHS_KERNEL")) {
-    if (!strcmp(v, "packed")) sw.paths_variant = 1;
-    if (!strcmp(v, "generic")) sw.paths_variant = 2;
-    if (!strcmp(v, "events")) sw.paths_variant = 3;
-  }
   if (const char* v = getenv("VX_DVR_FUSE")) sw.dvr_fuse = atoi(v) != 0;
-  if (const char* v = getenv("VX_DVR_WG")) sw.dvr_shared_window = atoi(v) != 0;
-  if (const char* v = getenv("VX_DVR_ORDER"); v && !strcmp(v, "0")) sw.use_order = false;
   if (const char* v = getenv("VX_RAY_SHORTCUTS"); v && atoi(v) == 0) sw.ray_shortcuts = false;
   if (const char* v = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) sw.cellquad_max_bytes = strtoull(v, nullptr, 10);
-  if (const char* v = getenv("VX_DVR_UNROLL")) sw.dvr_unroll = atoi(v);
   *out = c;
   return VX_OK;
 }
@@ -1813,8 +1746,8 @@ int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
   VX_HIP(c, hipEventRecord(ev.b, c->stream));
   c->pending_events.push_back(ev);
   if (rc) return rc;
-  if (!lp.ordered) c->order_builds_left = 0;
-  if (lp.ordered && c->order_builds_left > 0) {
+  if (lp.kernel == Kernel::GENERIC) c->order_builds_left = 0;   // render_generic runs its blocks in launch order
+  else if (c->order_builds_left > 0) {
     c->order_builds_left--;
     hipLaunchKernelGGL(build_order, dim3(1), dim3(1024), 0, c->stream, c->dc, c->order, grid.x);
     VX_HIP(c, hipGetLastError());
@@ -2287,7 +2220,7 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
   hipError_t e = hipMemsetAsync(d, 0, waves * sizeof(DevCounters), c->stream);
   mo.dc[0] = d;
   if (e == hipSuccess) {
-    launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream, nullptr, c->sw.dvr_unroll, true);
+    launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream, nullptr, true);
     e = hipGetLastError();
   }
   std::vector<DevCounters> h(waves);

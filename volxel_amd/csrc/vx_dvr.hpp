@@ -276,35 +276,20 @@ __global__ __launch_bounds__(256) void render_dvr_cq(const VxParams p, const Dev
   const uint32_t n_px = (uint32_t)__builtin_popcountll(__ballot(in_image));
   add_counts(dc, n_samples, n_rays, n_px, n_skipped, 0u, n_slots, blk, n_batches * (uint32_t)(2 * U), 0u, n_tf);
 }
-// unroll = march steps per loop iteration (VX_DVR_UNROLL, read once by vx_create): 1, 2 or 4 (the default)
+// 4 march steps per batch (U); probe: the measurement build (PROBE, vx_probe_gather_spread)
 inline void launch_dvr_cq_multi(const VxParams& p, const DevVolume& v, const float4* tf, uint32_t tf_len,
                                 const MultiOut& mo, float weight, const TileMap& tm, hipStream_t stream,
-                                const uint32_t* order, int unroll, bool probe = false) {
+                                const uint32_t* order, bool probe = false) {
   uint32_t groups = (tm.tiles_per_shard + 7u) / 8u;
   dim3 grid(groups * 128u * mo.count), block(256);
   const bool skip = p.dvr_skip_empty && v.skip_bits;
   size_t lds = (size_t)tf_len * sizeof(float4) + (skip ? (size_t)v.skip_words * 4u : 0u);
-#define VX_LAUNCH(UU, SS) \
-  hipLaunchKernelGGL((render_dvr_cq<UU, SS>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order)
+#define VX_LAUNCH(SS, PR) \
+  hipLaunchKernelGGL((render_dvr_cq<4, SS, PR>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order)
   if (probe) {
-    if (skip)
-      hipLaunchKernelGGL((render_dvr_cq<4, true, true>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order);
-    else
-      hipLaunchKernelGGL((render_dvr_cq<4, false, true>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order);
-    return;
-  }
-  if (skip) {
-    switch (unroll) {
-      case 1: VX_LAUNCH(1, true); break;
-      case 2: VX_LAUNCH(2, true); break;
-      default: VX_LAUNCH(4, true); break;
-    }
+    if (skip) VX_LAUNCH(true, true); else VX_LAUNCH(false, true);
   } else {
-    switch (unroll) {
-      case 1: VX_LAUNCH(1, false); break;
-      case 2: VX_LAUNCH(2, false); break;
-      default: VX_LAUNCH(4, false); break;
-    }
+    if (skip) VX_LAUNCH(true, false); else VX_LAUNCH(false, false);
   }
 #undef VX_LAUNCH
 }

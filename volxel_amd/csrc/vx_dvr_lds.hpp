@@ -52,10 +52,7 @@ namespace vx {
 #ifndef VX_LDS_S_PHONG   // steps per window of the shading kernel: with one frame's 64 pixels per wave 12 / 16 / 20 / 24 gave
 #define VX_LDS_S_PHONG 16  // 0.365 / 0.370 / 0.375 / 0.377 ms per frame; with lanes = pixels x frames 12 / 16 / 20: 0.335 / 0.327 / 0.329
 #endif
-#ifndef VX_LDS_WGD   // y / z size of a window the four waves of a workgroup share (WG builds): 16 x 16 rows = 64 per wave
-#define VX_LDS_WGD 16
-#endif
-template <bool PHONG, bool WG = false>
+template <bool PHONG>
 struct LdsTile {
   static constexpr int X = VX_LDS_X;             // X / 4 chunks of 16 bytes per row
 #ifndef VX_LDS_DY   // windows that are not square in (y, z), with lanes = pixels x frames, config 3, ms per frame at 32 frames per
@@ -66,14 +63,13 @@ struct LdsTile {
 #ifndef VX_LDS_DZ
 #define VX_LDS_DZ VX_LDS_D
 #endif
-  static constexpr int Y = WG ? VX_LDS_WGD : (PHONG ? VX_LDS_DP : VX_LDS_DY);
-  static constexpr int Z = WG ? VX_LDS_WGD : (PHONG ? VX_LDS_DP : VX_LDS_DZ);
+  static constexpr int Y = PHONG ? VX_LDS_DP : VX_LDS_DY;
+  static constexpr int Z = PHONG ? VX_LDS_DP : VX_LDS_DZ;
   static constexpr int RS = (X % 8 == 4) ? X : X + 4;             // row stride in words, = 4 mod 8
   static constexpr int SS = (Y * RS + 31 - 28) / 32 * 32 + 28;    // slice stride in words: >= Y * RS, = 28 mod 32
   static constexpr int ROWS = Y * Z;
   static constexpr int FLOATS = SS * Z;          // 3968 B (DVR) / 4960 B (Phong) per wave
-  static constexpr int PASSES = WG ? 1 : (ROWS + 63) / 64;   // WG: wave w stages rows 64 w .. 64 w + 63
-  static_assert(!WG || ROWS == 256, "a shared window is staged by four waves, 64 rows each");
+  static constexpr int PASSES = (ROWS + 63) / 64;
   static constexpr int LO_MARGIN = PHONG ? 1 : 0;   // cells below the sample's cell that must be resident
   static constexpr int HI_MARGIN = PHONG ? 2 : 1;   // taps above it (x+1; x+2 for the gradient)
   static_assert(SS >= Y * RS && SS % 4 == 0 && RS % 4 == 0 && RS >= X && X % 4 == 0, "tile strides");
@@ -143,24 +139,11 @@ typedef const float __attribute__((address_space(3))) * LdsFloatPtr;
 // U8: the window is staged from the bricku8 layout (8-bit codes + a range per brick, decoded here with A4's fma) instead
 // of brickf32's fp32 voxels -- the dword index of a 4-voxel chunk is brickf32's 16-byte-unit index, so the row and chunk
 // arithmetic is shared; everything after the staging is the same code on the same values.
-// WG (round 4): ONE window per workgroup.  In a launch of a multiple of 32 frames the four waves of a workgroup take the SAME 8
-// pixels (8 frames each): 256 rays of one narrow beam.  They place one window four times the volume of a wave's (12 x 16 x 16),
-// each wave stages a quarter of its rows, and every lane marches in it -- 1.7x the steps per window for the same staging work
-// per wave.  The cost is two workgroup barriers per window (the anchor's minima go through LDS; nobody may restage a tile a
-// sister wave still reads).  Every barrier sits on a workgroup-uniform path: the loop ends for all four waves together, when
-// the minima in LDS say no wave has a live ray.  Which samples a ray evaluates is untouched: same bits
-// (tests/test_gpu_parity.py::test_shared_window_kernel_is_bit_identical).
-// MEASURED (profiles/r04_shared_window.txt), config 3, 32 frames per launch: wave-windows per frame 235 955 -> 146 521 (0.62x), lane
-// utilisation 0.936 -> 0.924 (a longer window has a longer tail of lanes that have left it), and 0.2040-0.2086 ms per frame against
-// 0.2045-0.2074 for the wave-private windows on the same boxes: the windows it saves (7 % of the vector work by the listing's
-// prices) go into the exchange through LDS (~100 clocks per window and wave), the idle lane slots and the barrier skew.
-// Not faster: it stays OPT-IN (VX_DVR_WG=1).
-template <int S, bool PHONG, bool SKIP, bool U8 = false, bool WG = false>
+template <int S, bool PHONG, bool SKIP, bool U8 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PHONG ? (SKIP ? 1 : VX_W_LDS_PHONG) : (SKIP ? VX_W_LDS_SKIP : VX_W_LDS), 8))) void render_dvr_lds(const VxParams p, const DevVolume v,
                                                        const float4* __restrict__ tf_global, uint32_t tf_len,
                                                        const MultiOut mo, float weight, const TileMap tm,
                                                        const uint32_t* __restrict__ order) {
-  static_assert(!WG || (!SKIP && !PHONG), "the shared window serves the plain DVR march");
   constexpr bool SHADOW = false;
   constexpr int PROJ = 0;
   const ShadowGrid sg{};
@@ -175,19 +158,16 @@ template <int S, bool SKIP, bool U8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W_LDS_SKIP : VX_W_LDS, 8))) void render_dvr_lds_shadow(
     const VxParams p, const DevVolume v, const float4* __restrict__ tf_global, uint32_t tf_len, const MultiOut mo, float weight,
     const TileMap tm, const uint32_t* __restrict__ order, const ShadowGrid sg) {
-  constexpr bool PHONG = false, WG = false;
+  constexpr bool PHONG = false;
   constexpr bool SHADOW = true;
   constexpr int PROJ = 0;
   const float* const pbound = nullptr;
 #include "vx_dvr_lds_march.inc"
 }
 
-#ifndef VX_LDS_S_WG   // steps per shared window (its geometry ends a lane's run long before)
-#define VX_LDS_S_WG 32   // 24 / 28 / 32 / 36 / 40 / 48 measured: 0.2070 / 0.2062 / 0.2040 / 0.2057 / 0.2075 / 0.2044 ms per frame (lane utilisation 0.939 ... 0.912)
-#endif
 // sg: the light grid of a shadowed DVR launch (nullptr: unshadowed)
 inline void launch_dvr_lds(const VxParams& p, const DevVolume& v, const float4* tf, uint32_t tf_len, const MultiOut& mo,
-                           float weight, const TileMap& tm, hipStream_t stream, const uint32_t* order, bool shared_window = false,
+                           float weight, const TileMap& tm, hipStream_t stream, const uint32_t* order,
                            const ShadowGrid* sg = nullptr) {
   const uint32_t groups = (tm.tiles_per_shard + 7u) / 8u;
   const dim3 grid(groups * 128u * (mo.count ? mo.count : 1u)), block(256);
@@ -202,13 +182,6 @@ inline void launch_dvr_lds(const VxParams& p, const DevVolume& v, const float4* 
     if (skip) { if (u8) VX_LAUNCH_SH(true, true); else VX_LAUNCH_SH(true, false); }
     else      { if (u8) VX_LAUNCH_SH(false, true); else VX_LAUNCH_SH(false, false); }
 #undef VX_LAUNCH_SH
-    return;
-  }
-  // one window per workgroup: the plain DVR march on brickf32 in a launch of a multiple of 32 frames (render_dvr_lds, WG)
-  if (shared_window && !skip && !phong && !u8 && mo.count >= 32u && (mo.count & 31u) == 0u) {
-    const size_t lds_wg = (size_t)tf_len * sizeof(float4) + (size_t)LdsTile<false, true>::FLOATS * sizeof(float) + 32u * sizeof(int);
-    hipLaunchKernelGGL((render_dvr_lds<VX_LDS_S_WG, false, false, false, true>), grid, block, lds_wg, stream, p, v, tf, tf_len, mo,
-                       weight, tm, order);
     return;
   }
   const size_t tile_bytes = 4u * (size_t)(phong ? LdsTile<true>::FLOATS : LdsTile<false>::FLOATS) * sizeof(float);

@@ -1,23 +1,20 @@
 // vx_dvr_lds_march.inc -- the body of the LDS-window DVR / Phong kernels (vx_dvr_lds.hpp), included INSIDE each __global__
-// function that runs it: render_dvr_lds<S, PHONG, SKIP, U8, WG>, render_dvr_lds_shadow<S, SKIP, U8> and the intensity projections
+// function that runs it: render_dvr_lds<S, PHONG, SKIP, U8>, render_dvr_lds_shadow<S, SKIP, U8> and the intensity projections
 // render_proj_lds<S, MINIP, SKIP, U8> (vx_projection.hpp).  Textual, not a device
 // function: a function inlined into the kernel is first optimised on its own (flat pointers, its own inlining order), and the
 // unshadowed kernels then came out with other registers and instructions.  Included this way they compile to exactly what
 // they were before the shadowed form existed.
-// In scope at the point of inclusion: the template parameters S, PHONG, SKIP, U8, WG, `constexpr bool SHADOW` and `constexpr int
+// In scope at the point of inclusion: the template parameters S, PHONG, SKIP, U8, `constexpr bool SHADOW` and `constexpr int
 // PROJ` (0: DVR / Phong; 1: MIP, 2: MinIP), the kernel arguments p, v, tf_global, tf_len, mo, weight, tm, order, `sg` (the light
 // grid; unused unless SHADOW) and `pbound` (the density bounds of range skipping per macro cell; unused unless PROJ and SKIP).
 // PROJ: the march evaluates the same samples, keeps their largest (smallest) density instead of compositing, has no early ray
 // termination, and SKIP means range skipping: a lane flies over a macro cell whose bound cannot change its m.
-  using TL = LdsTile<PHONG, WG>;
+  using TL = LdsTile<PHONG>;
   constexpr int DX = TL::X, DY = TL::Y, DZ = TL::Z, RS = TL::RS, SS = TL::SS;
   extern __shared__ float4 lds_raw[];
   float4* tf_lds = lds_raw;
   uint32_t* mask_lds = reinterpret_cast<uint32_t*>(lds_raw + tf_len);
-  float* tile = reinterpret_cast<float*>(mask_lds + (SKIP && !PROJ ? ((v.skip_words + 3u) & ~3u) : 0u)) + (WG ? 0u : (threadIdx.x >> 6) * TL::FLOATS);
-  // WG: behind the shared tile, per wave {min x, min y, min z, first live lane's cell x, y, z, live | direction bits, -}
-  int* const wg_box = reinterpret_cast<int*>(tile + TL::FLOATS);
-  const uint32_t wave = threadIdx.x >> 6;
+  float* tile = reinterpret_cast<float*>(mask_lds + (SKIP && !PROJ ? ((v.skip_words + 3u) & ~3u) : 0u)) + (threadIdx.x >> 6) * TL::FLOATS;
   for (uint32_t i = threadIdx.x; i < tf_len; i += blockDim.x) tf_lds[i] = tf_global[i];
   if (SKIP && !PROJ)
     for (uint32_t i = threadIdx.x; i < v.skip_words; i += blockDim.x) mask_lds[i] = v.skip_bits[i];
@@ -30,20 +27,14 @@
   const uint32_t frame = mo.frame[fslot];
   uint32_t lt, sub;
   if (!block_to_tile(blk, tm, lt, sub)) return;
-  uint32_t wt = sub * 4u + (threadIdx.x >> 6);
+  const uint32_t wt = sub * 4u + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63u;
   uint32_t plane = lane, my_frame = frame;
-  const uint32_t fuse = WG ? 0u : mo.fuse;   // the running mean of the launch's frames applied here (wave uniform)
+  const uint32_t fuse = mo.fuse;   // the running mean of the launch's frames applied here (wave uniform)
 #ifndef VX_DVR_FL_MAXSH   // groups of up to 2^3 frame slots: 8 pixels x 8 frames per wave (groups of 16 / 32 measured within 1 %:
 #define VX_DVR_FL_MAXSH 3 // ms per frame at 20 / 32 frames per launch 0.2244 / 0.2169 against 0.2216-0.2245 / 0.2150-0.2185)
 #endif
-  if (WG) {   // (the launcher only takes this build for a multiple of 32 frames) the workgroup at slot r of a group of 32 takes
-              // wave tile r >> 3 of its block position and pixel octet r & 7; its four waves take 8 frames of the group each
-    const uint32_t r = fslot & 31u;
-    wt = sub * 4u + (r >> 3);
-    plane = ((r & 7u) << 3) + (lane & 7u);
-    slab = lane_frame_slot((fslot - r) + wave * 8u + (lane >> 3), my_frame);
-  } else if (mo.count > 1u) {   // lanes = pixels x frames (vx_kernels.hpp frame_group)
+  if (mo.count > 1u) {   // lanes = pixels x frames (vx_kernels.hpp frame_group)
     uint32_t base;
     // fused running mean (MultiOut::fuse): ONE group of all 32 / 64 frames of the launch, 2 pixels / 1 pixel per wave
     const uint32_t sh = fuse ? frame_group<6>(fslot, mo.count, base) : frame_group<VX_DVR_FL_MAXSH>(fslot, mo.count, base);
@@ -120,14 +111,6 @@
       fwx = __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.dq.x), first) >= 0;   // sign bit clear
       fwy = __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.dq.y), first) >= 0;
       fwz = __builtin_amdgcn_readlane(__builtin_bit_cast(int, r.dq.z), first) >= 0;
-    }
-    if (WG) {   // one direction for the workgroup: that of the lowest wave with a live ray
-      if (lane == 0u) wg_box[wave * 8u + 6u] = live0 != 0ull ? (1 | (fwx ? 2 : 0) | (fwy ? 4 : 0) | (fwz ? 8 : 0)) : 0;
-      __syncthreads();
-      const int d0 = wg_box[6], d1 = wg_box[14], d2 = wg_box[22], d3 = wg_box[30];
-      const int d = __builtin_amdgcn_readfirstlane(d0 ? d0 : (d1 ? d1 : (d2 ? d2 : d3)));
-      fwx = (d & 2) != 0 || d == 0; fwy = (d & 4) != 0 || d == 0; fwz = (d & 8) != 0 || d == 0;
-      __syncthreads();   // the slots are written again by the first window
     }
   }
   int LOx = 0, LOy = 0, LOz = 0;   // origin of the resident window (wave uniform)
@@ -230,51 +213,9 @@
   // exact window for the lanes as they stand; lanes too far apart for one window (a wave astride two entry faces of
   // the clip box): serve the first live lane
   // returns, per lane: alive and the current sample's cell inside the window placed
-  bool wg_any = true;   // WG: some wave of the workgroup has a live ray (workgroup uniform, from the minima in LDS)
   auto exact_window = [&](unsigned long long live) -> bool {
     const bool alive = is_alive();
     const int cxi = (int)flx, cyi = (int)fly, czi = (int)flz;
-    if (WG) {
-      // the wave's extreme cells and its first live lane's cell go through LDS; the barrier behind the writes is also the
-      // point after which no wave reads the resident tile any more (every wave has left its march)
-      int ex_ = alive ? (fwx ? cxi : -cxi) : 0x7fffffff, ey_ = alive ? (fwy ? cyi : -cyi) : 0x7fffffff,
-          ez_ = alive ? (fwz ? czi : -czi) : 0x7fffffff;
-      wave_min3(ex_, ey_, ez_);
-      const int first = live != 0ull ? (int)__builtin_ctzll(live) : 0;
-      const int fx_ = __builtin_amdgcn_readlane(cxi, first), fy_ = __builtin_amdgcn_readlane(cyi, first),
-                fz_ = __builtin_amdgcn_readlane(czi, first);
-      if (lane == 0u) {
-        int* b = wg_box + wave * 8u;
-        b[0] = ex_; b[1] = ey_; b[2] = ez_; b[3] = fx_; b[4] = fy_; b[5] = fz_; b[6] = live != 0ull ? 1 : 0;
-      }
-      __syncthreads();
-      auto mn = [](int a, int b) { return a < b ? a : b; };
-      const int gx = __builtin_amdgcn_readfirstlane(mn(mn(wg_box[0], wg_box[8]), mn(wg_box[16], wg_box[24])));
-      const int gy = __builtin_amdgcn_readfirstlane(mn(mn(wg_box[1], wg_box[9]), mn(wg_box[17], wg_box[25])));
-      const int gz = __builtin_amdgcn_readfirstlane(mn(mn(wg_box[2], wg_box[10]), mn(wg_box[18], wg_box[26])));
-      const int l0 = wg_box[6], l1 = wg_box[14], l2 = wg_box[22], l3 = wg_box[30];
-      const int fw = __builtin_amdgcn_readfirstlane(l0 ? 0 : (l1 ? 1 : (l2 ? 2 : (l3 ? 3 : -1))));   // lowest wave with a live ray
-      wg_any = fw >= 0;
-      if (!wg_any) return false;
-      LOx = fwx ? gx - TL::LO_MARGIN : -gx + TL::HI_MARGIN - (DX - 1);
-      LOy = fwy ? gy - TL::LO_MARGIN : -gy + TL::HI_MARGIN - (DY - 1);
-      LOz = fwz ? gz - TL::LO_MARGIN : -gz + TL::HI_MARGIN - (DZ - 1);
-      LOx = fwx ? (LOx & ~3) : ((LOx + 3) & ~3);
-      // progress: the window must hold the first live lane of that wave (rays too far apart for one window -- a workgroup
-      // astride two entry faces of the clip box -- are served one neighbourhood at a time); every wave decides alike
-      const int ax = __builtin_amdgcn_readfirstlane(wg_box[fw * 8 + 3]), ay = __builtin_amdgcn_readfirstlane(wg_box[fw * 8 + 4]),
-                az = __builtin_amdgcn_readfirstlane(wg_box[fw * 8 + 5]);
-      const uint32_t rx = (uint32_t)(ax - LOx - TL::LO_MARGIN), ry = (uint32_t)(ay - LOy - TL::LO_MARGIN),
-                     rz = (uint32_t)(az - LOz - TL::LO_MARGIN);
-      if (!((rx < (uint32_t)(DX - TL::LO_MARGIN - TL::HI_MARGIN)) & (ry < (uint32_t)(DY - TL::LO_MARGIN - TL::HI_MARGIN)) &
-            (rz < (uint32_t)(DZ - TL::LO_MARGIN - TL::HI_MARGIN)))) {
-        LOx = ax - TL::LO_MARGIN - (fwx ? 0 : DX - 1 - TL::LO_MARGIN - TL::HI_MARGIN);
-        LOx = fwx ? (LOx & ~3) : ((LOx + 3) & ~3);
-        LOy = ay - TL::LO_MARGIN - (fwy ? 0 : DY - 1 - TL::LO_MARGIN - TL::HI_MARGIN);
-        LOz = az - TL::LO_MARGIN - (fwz ? 0 : DZ - 1 - TL::LO_MARGIN - TL::HI_MARGIN);
-      }
-      return (bool)(alive & inside_of(LOx, LOy, LOz, cxi, cyi, czi));
-    }
     anchor(alive, cxi, cyi, czi, 0, LOx, LOy, LOz);
     bool now = alive & inside_of(LOx, LOy, LOz, cxi, cyi, czi);
     if (ballot(now) == 0ull) {
@@ -301,7 +242,7 @@
     }
 #pragma unroll
     for (int ps = 0; ps < TL::PASSES; ++ps) {
-      const uint32_t row = lane + 64u * (WG ? wave : (uint32_t)ps);
+      const uint32_t row = lane + 64u * (uint32_t)ps;
       const uint32_t zz = row / (uint32_t)DY, yy = row - zz * (uint32_t)DY;
       const int gy = oy + (int)yy, gz = oz + (int)zz;
       const bool rin = row < (uint32_t)TL::ROWS && (uint32_t)gy < ey && (uint32_t)gz < ez;
@@ -342,13 +283,11 @@
   };
   // stage, part 2: the rows into the wave's tile
   auto write_tile = [&](float4 (&vals)[TL::PASSES][NC]) {
-    if (!WG) {   // (WG: the barrier of exact_window already separates the old tile's reads from these writes)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // earlier tile reads are done
-      __builtin_amdgcn_wave_barrier();
-    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // earlier tile reads are done
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int ps = 0; ps < TL::PASSES; ++ps) {
-      const uint32_t row = lane + 64u * (WG ? wave : (uint32_t)ps);
+      const uint32_t row = lane + 64u * (uint32_t)ps;
       if (row < (uint32_t)TL::ROWS) {
         const uint32_t zz = row / (uint32_t)DY, yy = row - zz * (uint32_t)DY;
         float4* dst = reinterpret_cast<float4*>(tile + zz * (uint32_t)SS + yy * (uint32_t)RS);
@@ -356,13 +295,9 @@
         for (int c = 0; c < NC; ++c) dst[c] = vals[ps][c];
       }
     }
-    if (WG) {
-      __syncthreads();   // the four quarters of the tile are in place
-    } else {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   };
 
   // ---- SKIP: exact empty-space skipping (A12 note: a sample in a macro cell that can only see TF-transparent bricks
@@ -453,7 +388,6 @@
       if (live == 0ull) return false;
     }
     const bool now = exact_window(live);
-    if (WG && !wg_any) return false;   // workgroup uniform: no wave has a live ray left
     if (SKIP && !PROJ) wtest = touches_empty();
     set_limits(now);
     float4 vals[TL::PASSES][NC];
@@ -462,11 +396,9 @@
     return true;
   };
 
-  bool wg_go = true;
   {
     const unsigned long long live = ballot(is_alive());
-    if (WG) wg_go = next_window(live);   // every wave takes part in every window of its workgroup
-    else if (live != 0ull) (void)next_window(live);
+    if (live != 0ull) (void)next_window(live);
   }
   // ---- 3. march: up to S steps out of LDS.  TEST (SKIP builds): the window touches an empty macro cell, the mask is
   // tested per step; in the other windows the test is compiled out.
@@ -639,15 +571,15 @@
       } while (more);
     }
   };
-  while (WG ? wg_go : true) {
-    if (!WG && ballot(is_alive()) == 0ull) break;
+  while (true) {
+    if (ballot(is_alive()) == 0ull) break;
     if (SKIP && wtest) march(std::integral_constant<bool, SKIP>{});
     else march(std::false_type{});
     if (!PROJ) nray = tau >= ert ? -1.0f : nray;   // the rays the march terminated
     // ---- next window ------------------------------------------------------------------------------------------------
     const unsigned long long live = ballot(is_alive());
-    if (!WG && live == 0ull) break;
-    if (!next_window(live)) break;      // WG: false for the four waves together
+    if (live == 0ull) break;
+    if (!next_window(live)) break;
   }
 
   // (kf counts the samples of a lane: without skipping every step it takes evaluates one; a terminated ray stopped at kf)
@@ -668,7 +600,7 @@
     }
     if (fuse != 0u) fold_frames(tile, lane, L, in_image, si, mo.accum, fuse, 31u - (uint32_t)__builtin_clz(mo.count));
     else if (in_image) store_blend(L, weight, slab, si);
-  } else if (!WG && fuse != 0u) {
+  } else if (fuse != 0u) {
     // ---- the running mean of the launch, in the wave that holds every frame of its pixels (MultiOut::fuse) -------------
     // lane l holds frame slot l >> psh of pixel l & (npx - 1); its result goes to the wave's tile (the march is over); lanes
     // 0 .. 3 npx - 1 then each fold one colour channel of one pixel through the frame slots in order:

@@ -76,7 +76,7 @@ struct DevCounters {
   uint32_t gathers;     // 16-byte-per-lane gather wave instructions issued (tuned DVR kernels)
   uint32_t lds_reads;   // LDS tap-read wave instructions (LDS-tile kernels)
   uint32_t tf;          // samples inside the sample range (LUT fetched)
-  uint32_t active;      // lane slots that did work (event-batched path kernels)
+  uint32_t active;      // lane slots that did work (path-traced modes, flush_counts)
   uint32_t pad;
 };
 

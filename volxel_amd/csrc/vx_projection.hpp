@@ -20,7 +20,7 @@ template <int S, bool MINIP, bool SKIP, bool U8>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W_LDS_SKIP : VX_W_LDS, 8))) void render_proj_lds(
     const VxParams p, const DevVolume v, const float4* __restrict__ tf_global, uint32_t tf_len, const MultiOut mo, float weight,
     const TileMap tm, const uint32_t* __restrict__ order, const float* __restrict__ pbound) {
-  constexpr bool PHONG = false, WG = false;
+  constexpr bool PHONG = false;
   constexpr bool SHADOW = false;
   constexpr int PROJ = MINIP ? 2 : 1;
   const ShadowGrid sg{};
