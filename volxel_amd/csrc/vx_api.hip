@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -37,6 +38,39 @@ struct Switches {
   std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
 };
 
+// ---- the tables a launch derives from the params and the uploads ---------------------------------------------------------
+// The skip mask, the projection bounds, the local majorants and the light grid share one cache rule: a table is rebuilt
+// before a launch that reads it when an upload marked it stale or when its key -- the bits of the params it is built from,
+// listed once in its key function -- differs from the key of the last build.  A camera move rebuilds none of them.
+
+// the bits of 4-byte params and param arrays, in order
+template <class... T>
+std::array<uint32_t, (sizeof(T) + ...) / 4> key_of(const T&... v) {
+  static_assert(((sizeof(T) % 4 == 0) && ...), "key fields are 4-byte values");
+  std::array<uint32_t, (sizeof(T) + ...) / 4> k{};
+  uint32_t* o = k.data();
+  ((memcpy(o, &v, sizeof v), o += sizeof v / 4), ...);
+  return k;
+}
+auto skip_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.sample_range); }
+auto proj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.render_mode); }
+auto lmaj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.volume_maj, p.sample_range); }
+auto shadow_key(const VxParams& p) {
+  return key_of(p.light_dir, p.density_transform_inv, p.volume_aabb_min, p.volume_aabb_max, p.volume_maj, p.volume_inv_maj,
+                p.volume_density_scale, p.sample_range, p.dvr_step_voxels, p.dvr_ert_tau, p.dvr_max_steps, p.dvr_shadow_stride);
+}
+
+template <auto KEY>
+struct DerivedTable {
+  bool stale = true;                      // never built, an upload since the last build, or a rebuild that failed
+  decltype(KEY(VxParams{})) key{};        // KEY of the params of the last build
+  bool current(const VxParams& p) const { return !stale && KEY(p) == key; }
+  void built(const VxParams& p) {
+    key = KEY(p);
+    stale = false;
+  }
+};
+
 }  // namespace
 
 struct VxContext {
@@ -63,31 +97,25 @@ struct VxContext {
   uint32_t tf_len = 0;
   std::vector<float> tf_host;
 
-  // exact empty-space skipping (DVR): macro-cell bitmask, rebuilt when its inputs change
+  // exact empty-space skipping (DVR): macro-cell bitmask
   std::vector<uint32_t> range_host;   // packed (min16<<16)|max16 per brick
   uint32_t* skip_dev = nullptr;
-  bool skip_dirty = true;
-  float skip_key[4] = {0, 0, 0, 0};   // density_scale, inv_maj, sample_range
-  // range skipping of the intensity projections: one density bound per macro cell (vx_projection.hpp), rebuilt when the
-  // volume, volume_density_scale, volume_inv_maj or the mode changes
+  DerivedTable<skip_key> skip_table;
+  // range skipping of the intensity projections: one density bound per macro cell (vx_projection.hpp)
   float* proj_dev = nullptr;
-  bool proj_dirty = true;
-  float proj_key[2] = {0, 0};         // density_scale, inv_maj
-  int proj_mode = -1;
+  DerivedTable<proj_key> proj_table;
 
-  // default mode: local-majorant table (DevVolume::lmaj), rebuilt when its inputs change
+  // default mode: local-majorant table (DevVolume::lmaj)
   float* lmaj_dev = nullptr;
-  bool lmaj_dirty = true;
-  float lmaj_key[5] = {0, 0, 0, 0, 0};   // density_scale, inv_maj, maj, sample_range
+  DerivedTable<lmaj_key> lmaj_table;
 
   unsigned long long* fold_dev = nullptr;   // eight totals of fold_records
 
-  // shadowed DVR: the light grid (vx_shadow.hpp), rebuilt when its inputs differ bitwise from the last build (ShadowKey)
+  // shadowed DVR: the light grid (vx_shadow.hpp)
   float* shadow_dev = nullptr;
   size_t shadow_cap = 0;                     // floats allocated
   ShadowGrid shadow{};                       // what the last build made (t == nullptr: none since the last upload)
-  bool shadow_dirty = true;                  // volume or TF uploaded since the last build
-  float shadow_key[34] = {};                 // shadow_key() of the last build (SHADOW_KEY floats)
+  DerivedTable<shadow_key> shadow_table;
   unsigned long long* shadow_count_dev = nullptr;   // light-march samples of the last build
   hipEvent_t shadow_ev[2] = {nullptr, nullptr};
   uint64_t shadow_builds = 0;
@@ -184,16 +212,13 @@ static void free_volume(VxContext* c) {
   c->bu_alloc = c->bur_alloc = nullptr;
   c->dv = DevVolume{};
   c->has_volume = false;
-  c->skip_dirty = true;
-  c->proj_dirty = true;
+  c->skip_table.stale = c->proj_table.stale = c->lmaj_table.stale = c->shadow_table.stale = true;
   if (c->lmaj_dev) (void)hipFree(c->lmaj_dev);
   c->lmaj_dev = nullptr;
-  c->lmaj_dirty = true;
   if (c->shadow_dev) (void)hipFree(c->shadow_dev);
   c->shadow_dev = nullptr;
   c->shadow_cap = 0;
   c->shadow = ShadowGrid{};
-  c->shadow_dirty = true;
 }
 
 static void drain_events(VxContext* c) {
@@ -436,6 +461,7 @@ static bool proj_mode(int m) { return m == VX_MODE_MIP || m == VX_MODE_MINIP; }
 // the device table: the bound the mode tests (hi for MIP, lo for MinIP), one float per macro cell
 static int rebuild_projection_bounds(VxContext* c) {
   const VxParams& p = c->params;
+  c->proj_table.stale = true;   // until this build is complete
   std::vector<float> lohi;
   int level = 1;
   uint32_t md[3];
@@ -453,16 +479,14 @@ static int rebuild_projection_bounds(VxContext* c) {
   // same values rebuild_skip_mask sets for this volume)
   c->dv.skip_level = (uint32_t)level;
   for (int a = 0; a < 3; ++a) c->dv.skip_dims[a] = md[a];
-  c->proj_dirty = false;
-  c->proj_key[0] = p.volume_density_scale;
-  c->proj_key[1] = p.volume_inv_maj;
-  c->proj_mode = p.render_mode;
+  c->proj_table.built(p);
   return VX_OK;
 }
 
 // the local majorants of the default mode, tabulated on the device with the operations of Frame::local_majorant
 static int rebuild_local_majorants(VxContext* c) {
   const VxParams& p = c->params;
+  c->lmaj_table.stale = true;   // until this build is complete
   const size_t n = 4 * (size_t)c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2] + 1;
   if (!c->lmaj_dev) VX_HIP(c, hipMalloc(&c->lmaj_dev, n * sizeof(float)));
   DevVolume dv = c->dv;
@@ -472,17 +496,13 @@ static int rebuild_local_majorants(VxContext* c) {
   VX_HIP(c, hipGetLastError());
   c->dv.lmaj = c->lmaj_dev;
   c->dv.lmaj_cells = (uint32_t)(n - 1);
-  c->lmaj_dirty = false;
-  c->lmaj_key[0] = p.volume_density_scale;
-  c->lmaj_key[1] = p.volume_inv_maj;
-  c->lmaj_key[2] = p.volume_maj;
-  c->lmaj_key[3] = p.sample_range[0];
-  c->lmaj_key[4] = p.sample_range[1];
+  c->lmaj_table.built(p);
   return VX_OK;
 }
 
 static int rebuild_skip_mask(VxContext* c) {
   const VxParams& p = c->params;
+  c->skip_table.stale = true;   // until this build is complete
   std::vector<uint32_t> bits;
   int level = 1;
   uint32_t md[3];
@@ -496,11 +516,7 @@ static int rebuild_skip_mask(VxContext* c) {
   c->dv.skip_level = (uint32_t)level;
   c->dv.skip_words = (uint32_t)bits.size();
   for (int a = 0; a < 3; ++a) c->dv.skip_dims[a] = md[a];
-  c->skip_dirty = false;
-  c->skip_key[0] = p.volume_density_scale;
-  c->skip_key[1] = p.volume_inv_maj;
-  c->skip_key[2] = p.sample_range[0];
-  c->skip_key[3] = p.sample_range[1];
+  c->skip_table.built(p);
   return VX_OK;
 }
 
@@ -594,24 +610,6 @@ static bool shadow_on(const VxContext* c) {
   const VxParams& p = c->params;
   return p.render_mode == VX_MODE_DVR && p.dvr_shadow_stride != 0 && !p.debug_hits;
 }
-// the inputs of a light-grid build besides the volume and TF uploads, bit for bit
-constexpr int SHADOW_KEY = 34;
-static void shadow_key(const VxParams& p, float k[SHADOW_KEY]) {
-  float* o = k;
-  auto put = [&](const void* src, size_t n) { memcpy(o, src, n * 4); o += n; };
-  put(p.light_dir, 3);
-  put(p.density_transform_inv, 16);
-  put(p.volume_aabb_min, 3);
-  put(p.volume_aabb_max, 3);
-  put(&p.volume_maj, 1);
-  put(&p.volume_inv_maj, 1);
-  put(&p.volume_density_scale, 1);
-  put(p.sample_range, 2);
-  put(&p.dvr_step_voxels, 1);
-  put(&p.dvr_ert_tau, 1);
-  put(&p.dvr_max_steps, 1);
-  put(&p.dvr_shadow_stride, 1);
-}
 // the light march of every node, with fp32 operations a NumPy restatement repeats (tests/shadow_ref.py)
 static LightMarch light_march(const VxContext* c) {
   const VxParams& p = c->params;
@@ -648,6 +646,7 @@ static LightMarch light_march(const VxContext* c) {
 }
 // build the light grid on the context's stream (after the layouts of the launch are in place)
 static int rebuild_light_grid(VxContext* c) {
+  c->shadow_table.stale = true;   // until this build is complete
   const LightMarch lm = light_march(c);
   const uint64_t nodes = (uint64_t)lm.n[0] * lm.n[1] * lm.n[2];
   if (nodes >= (1ull << 31))
@@ -685,24 +684,40 @@ static int rebuild_light_grid(VxContext* c) {
     g.ghi[i] = (float)lm.ihi[i];
     g.gmax[i] = (float)(lm.n[i] - 1u);
   }
-  shadow_key(c->params, c->shadow_key);
-  c->shadow_dirty = false;
+  c->shadow_table.built(c->params);
   c->shadow_builds += 1;
   return VX_OK;
 }
 
-// ---- the launch plan: which kernel a render launch runs, and whether it folds the running mean itself ----------------
+// the blocks of one frame slot of a render launch: 16 per 64x64 tile of the shard (4 waves of 8x8 pixels each), the tiles in
+// groups of 8
+static uint32_t frame_blocks(const VxContext* c) { return (c->tm.tiles_per_shard + 7u) / 8u * 128u; }
+
+// ---- the launch plan: the kernel instance a render launch runs, its launch shape, and whether it folds the running mean ---
 
 enum class Kernel {
-  DVR_LDS,   // LDS-window DVR / Phong (vx_dvr_lds.hpp)
-  DVR_CQ,    // tuned DVR on the cellquad layout (vx_dvr.hpp)
-  GENERIC,   // render_generic<MODE> (vx_kernels.hpp)
+  DVR_LDS,    // LDS-window DVR / Phong: render_dvr_lds, render_dvr_lds_shadow (vx_dvr_lds.hpp)
+  PROJ_LDS,   // LDS-window intensity projections: render_proj_lds (vx_projection.hpp)
+  DVR_CQ,     // tuned DVR on the cellquad layout: render_dvr_cq (vx_dvr.hpp)
+  GENERIC,    // render_generic<MODE, LAYOUT>, render_generic_shadow (vx_kernels.hpp, vx_shadow.hpp)
 };
-// The tuned DVR kernels (DVR_LDS, DVR_CQ) run their blocks in c->order, longest first, and single frames refresh it (build_order).
+// Everything a render launch needs besides the frame slots and the weight: the instance (kernel family and template
+// arguments), the launch shape, and the kernel's extra argument.
 struct LaunchPlan {
   Kernel kernel = Kernel::GENERIC;
-  int layout = VX_LAYOUT_REFERENCE;   // what render_generic samples (eff_layout; the DVR launchers pick their own form)
-  size_t lds = 0;                     // dynamic LDS bytes of render_generic (the DVR launchers size their windows)
+  int mode = VX_MODE_DVR;             // render_generic's MODE
+  int layout = VX_LAYOUT_REFERENCE;   // render_generic's LAYOUT (with_layout); the tuned kernels are each for one layout
+  bool phong = false;                 // DVR_LDS: PHONG
+  bool minip = false;                 // PROJ_LDS: MINIP
+  bool shadow = false;                // DVR_LDS, GENERIC: the shadowed kernel, with `light` as its extra argument
+  bool skip = false;                  // DVR_LDS, DVR_CQ: SKIP (the macro-cell mask); PROJ_LDS: SKIP, with `bounds`
+  bool u8 = false;                    // DVR_LDS, PROJ_LDS: U8 (staged from the bricku8 layout)
+  bool probe = false;                 // DVR_CQ: PROBE (vx_probe_gather_spread's measurement build)
+  ShadowGrid light{};                 // the light grid of a shadowed launch
+  const float* bounds = nullptr;      // PROJ_LDS: the table of range skipping, nullptr without SKIP
+  const uint32_t* order = nullptr;    // the tuned kernels' block order, longest first (build_order); nullptr: the probe's
+  dim3 grid, block{256};
+  size_t lds = 0;                     // dynamic LDS bytes
   bool fuse = false;                  // the kernel folds the running mean of the launch itself (MultiOut::fuse)
 };
 
@@ -729,76 +744,140 @@ static bool is_tuned(const VxContext* c) {
   const bool dvr_cq = c->params.render_mode == VX_MODE_DVR && eff_layout(c) == VX_LAYOUT_CELLQUAD;
   return tuned_possible(c) && (dvr_cq || use_lds_kernel(c));
 }
-// The one place that decides what a render launch of the mo.count frame slots of `mo` runs.  The fuse rule: while
-// VX_DVR_FUSE is on, the kernel folds the running mean of the launch into the accumulator itself when
-//   * it is the LDS-window DVR / Phong kernel or the projections' LDS-window kernel, and the launch has 8, 16, 32 or 64
-//     frames (a wave holds every frame of its 8, 4, 2 or 1 pixels), or
-//   * it is render_generic for `default`, `no_dda` or `raymarch` and the launch has exactly 32 frames (2 pixels x 32
-//     frames per wave).
-// Every other multi-frame launch writes per-frame result slabs that merge_results blends in frame order.
-static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo) {
-  const VxParams& p = c->params;
-  const uint32_t n = mo.count;
-  LaunchPlan lp;
-  lp.layout = eff_layout(c);
-  // shadowed DVR: the LDS-window kernel's shadowed form, or render_generic's -- never the cellquad DVR kernel
-  if (is_tuned(c) && (!shadow_on(c) || use_lds_kernel(c))) {
-    lp.kernel = use_lds_kernel(c) ? Kernel::DVR_LDS : Kernel::DVR_CQ;
-    lp.fuse = c->sw.dvr_fuse && lp.kernel == Kernel::DVR_LDS && (n == 8u || n == 16u || n == 32u || n == 64u);
-    return lp;
+// The fuse rule: whether `kernel` folds the running mean of an n-frame launch of render mode `mode` itself -- the LDS-window
+// kernels at 8, 16, 32 or 64 frames (a wave holds every frame of its 8, 4, 2 or 1 pixels), render_generic for `default`,
+// `no_dda` or `raymarch` at exactly 32 frames (2 pixels x 32 frames per wave).  Every other multi-frame launch writes
+// per-frame result slabs that merge_results blends in frame order.
+static bool folds(Kernel kernel, int mode, uint32_t n) {
+  switch (kernel) {
+    case Kernel::DVR_LDS:
+    case Kernel::PROJ_LDS: return n == 8u || n == 16u || n == 32u || n == 64u;
+    case Kernel::GENERIC: return mode <= VX_MODE_RAYMARCH && n == 32u;
+    default: return false;
   }
-  lp.lds = c->tf_len <= TF_LDS_MAX ? (size_t)c->tf_len * sizeof(float4) : 0;
-  lp.fuse = c->sw.dvr_fuse && p.render_mode <= VX_MODE_RAYMARCH && n == 32u;
-  if (lp.fuse) lp.lds += 4u * 320u * sizeof(float);   // fold_frames' scratch, one per wave
+}
+// the dynamic LDS of a launch: the TF, the mask of the empty-space grid where the kernel stages it, the wave tiles
+static size_t lds_bytes(const VxContext* c, const LaunchPlan& lp) {
+  const size_t tf = (size_t)c->tf_len * sizeof(float4);
+  const size_t mask = lp.skip ? (size_t)c->dv.skip_words * 4u : 0u;
+  const size_t tiles = 4u * (size_t)(lp.phong ? LdsTile<true>::FLOATS : LdsTile<false>::FLOATS) * sizeof(float);
+  switch (lp.kernel) {
+    case Kernel::DVR_LDS: return tf + ((mask + 15u) & ~(size_t)15u) + tiles;   // the mask in whole 16-byte rows
+    case Kernel::PROJ_LDS: return tf + tiles;                                   // the bounds stay in global memory
+    case Kernel::DVR_CQ: return tf + mask;
+    default: return (c->tf_len <= TF_LDS_MAX ? tf : 0u) + (lp.fuse ? 4u * 320u * sizeof(float) : 0u);   // + fold_frames' scratch
+  }
+}
+// The one place that decides what a render launch of the mo.count frame slots of `mo` runs (after prepare_render).  The
+// kernel folds the running mean of the launch itself while VX_DVR_FUSE is on and the fuse rule (folds) says it does.
+static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo, bool probe = false) {
+  const VxParams& p = c->params;
+  LaunchPlan lp;
+  lp.mode = p.render_mode;
+  lp.layout = eff_layout(c);
+  lp.shadow = shadow_on(c);
+  // shadowed DVR: the LDS-window kernel's shadowed form, or render_generic's -- never the cellquad DVR kernel
+  if (is_tuned(c) && (!lp.shadow || use_lds_kernel(c)))
+    lp.kernel = !use_lds_kernel(c) ? Kernel::DVR_CQ : proj_mode(p.render_mode) ? Kernel::PROJ_LDS : Kernel::DVR_LDS;
+  lp.phong = lp.kernel == Kernel::DVR_LDS && p.render_mode == VX_MODE_DVR_PHONG;
+  lp.minip = lp.kernel == Kernel::PROJ_LDS && p.render_mode == VX_MODE_MINIP;
+  if (lp.shadow) lp.light = c->shadow;
+  // SKIP: the DVR kernels test that a mask exists, the projections that their bounds are current
+  if (lp.kernel == Kernel::PROJ_LDS) {
+    lp.skip = p.dvr_skip_empty && c->proj_dev && !c->proj_table.stale;
+    lp.bounds = lp.skip ? c->proj_dev : nullptr;
+  } else {
+    lp.skip = p.dvr_skip_empty && c->dv.skip_bits;
+  }
+  lp.u8 = lp.layout == VX_LAYOUT_BRICKU8 && c->dv.bu;
+  lp.probe = probe;
+  lp.order = probe ? nullptr : c->order;
+  // a frame's blocks per frame slot (the LDS-window kernels take a count of 0 as 1)
+  const bool lds_window = lp.kernel == Kernel::DVR_LDS || lp.kernel == Kernel::PROJ_LDS;
+  lp.grid = dim3(frame_blocks(c) * (lds_window && mo.count == 0u ? 1u : mo.count));
+  lp.fuse = c->sw.dvr_fuse && folds(lp.kernel, lp.mode, mo.count);
+  lp.lds = lds_bytes(c, lp);
   return lp;
 }
 
-// render_generic of render mode MODE (render_generic_shadow for shadowed DVR), on the plan's layout
-template <int MODE>
-static void launch_mode(const VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
-  with_layout(lp.layout, [&](auto tag) {
-    constexpr int LAY = decltype(tag)::value;
-    grid.x *= mo.count;
-    if constexpr (MODE == VX_MODE_DVR) {
-      if (shadow_on(c)) {
-        hipLaunchKernelGGL((render_generic_shadow<LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
-                           mo, weight, c->tm, c->shadow);
-        return;
-      }
-    }
-    hipLaunchKernelGGL((render_generic<MODE, LAY>), grid, dim3(256), lp.lds, c->stream, c->params, c->dv, c->tf, c->tf_len,
-                       mo, weight, c->tm);
-  });
+// calls f(std::integral_constant<bool, b>)
+template <class F>
+static void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+// calls f(std::integral_constant<int, VX_MODE_*>) for render mode m
+template <class F>
+static void with_mode(int m, F&& f) {
+  switch (m) {
+    case VX_MODE_DEFAULT: f(std::integral_constant<int, VX_MODE_DEFAULT>{}); break;
+    case VX_MODE_NO_DDA: f(std::integral_constant<int, VX_MODE_NO_DDA>{}); break;
+    case VX_MODE_RAYMARCH: f(std::integral_constant<int, VX_MODE_RAYMARCH>{}); break;
+    case VX_MODE_DVR: f(std::integral_constant<int, VX_MODE_DVR>{}); break;
+    case VX_MODE_MIP: f(std::integral_constant<int, VX_MODE_MIP>{}); break;
+    case VX_MODE_MINIP: f(std::integral_constant<int, VX_MODE_MINIP>{}); break;
+    default: f(std::integral_constant<int, VX_MODE_DVR_PHONG>{}); break;
+  }
 }
 
-// The one launch switch: runs what `lp` names for the frame slots of `mo` on the context's stream.  Fails closed: a
-// kernel that does not fold the running mean refuses a launch with mo.fuse set -- its frames would reach no accumulator.
-static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight, dim3 grid) {
-  const bool folds = lp.kernel == Kernel::DVR_LDS || (lp.kernel == Kernel::GENERIC && c->params.render_mode <= VX_MODE_RAYMARCH);
-  if (mo.fuse && !folds)
+// The one launch switch: runs the instance `lp` names for the frame slots of `mo` on the context's stream.  Fails closed: a
+// launch with mo.fuse set that the fuse rule does not fold is refused -- its frames would reach no accumulator.
+static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo, float weight) {
+  if (mo.fuse && !folds(lp.kernel, lp.mode, mo.count))
     VX_FAIL(c, VX_ERR_INVALID, "render launch: running mean to fold (MultiOut::fuse) for a kernel that does not fold it");
+  const VxParams& p = c->params;
+  const DevVolume& v = c->dv;
+  const TileMap& tm = c->tm;
+  const float4* tf = c->tf;
+  const uint32_t n = c->tf_len;
+  const hipStream_t s = c->stream;
   switch (lp.kernel) {
     case Kernel::DVR_LDS:
-      if (proj_mode(c->params.render_mode)) {
-        const bool skip = c->params.dvr_skip_empty && c->proj_dev && !c->proj_dirty;
-        launch_proj_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, c->order, skip ? c->proj_dev : nullptr);
-        break;
-      }
-      launch_dvr_lds(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, c->order, shadow_on(c) ? &c->shadow : nullptr);
+      with_bool(lp.skip, [&](auto sk) {
+        with_bool(lp.u8, [&](auto u8) {
+          constexpr bool SK = decltype(sk)::value, U8 = decltype(u8)::value;
+          if (lp.shadow) {   // (vx_set_params refuses a stride with Phong)
+            hipLaunchKernelGGL((render_dvr_lds_shadow<VX_LDS_S, SK, U8>), lp.grid, lp.block, lp.lds, s, p, v, tf, n, mo, weight, tm,
+                               lp.order, lp.light);
+            return;
+          }
+          with_bool(lp.phong, [&](auto ph) {
+            constexpr bool PH = decltype(ph)::value;
+            hipLaunchKernelGGL((render_dvr_lds<(PH ? VX_LDS_S_PHONG : VX_LDS_S), PH, SK, U8>), lp.grid, lp.block, lp.lds, s, p, v, tf,
+                               n, mo, weight, tm, lp.order);
+          });
+        });
+      });
       break;
-    case Kernel::DVR_CQ:
-      launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, weight, c->tm, c->stream, c->order);
+    case Kernel::PROJ_LDS:
+      with_bool(lp.minip, [&](auto mi) {
+        with_bool(lp.skip, [&](auto sk) {
+          with_bool(lp.u8, [&](auto u8) {
+            hipLaunchKernelGGL((render_proj_lds<VX_LDS_S, decltype(mi)::value, decltype(sk)::value, decltype(u8)::value>), lp.grid,
+                               lp.block, lp.lds, s, p, v, tf, n, mo, weight, tm, lp.order, lp.bounds);
+          });
+        });
+      });
+      break;
+    case Kernel::DVR_CQ:   // 4 march steps per batch
+      with_bool(lp.skip, [&](auto sk) {
+        with_bool(lp.probe, [&](auto pr) {
+          hipLaunchKernelGGL((render_dvr_cq<4, decltype(sk)::value, decltype(pr)::value>), lp.grid, lp.block, lp.lds, s, p, v, tf, n,
+                             mo, weight, tm, lp.order);
+        });
+      });
       break;
     default:
-      switch (c->params.render_mode) {
-        case VX_MODE_DEFAULT: launch_mode<VX_MODE_DEFAULT>(c, lp, mo, weight, grid); break;
-        case VX_MODE_NO_DDA: launch_mode<VX_MODE_NO_DDA>(c, lp, mo, weight, grid); break;
-        case VX_MODE_RAYMARCH: launch_mode<VX_MODE_RAYMARCH>(c, lp, mo, weight, grid); break;
-        case VX_MODE_DVR: launch_mode<VX_MODE_DVR>(c, lp, mo, weight, grid); break;
-        case VX_MODE_MIP: launch_mode<VX_MODE_MIP>(c, lp, mo, weight, grid); break;
-        case VX_MODE_MINIP: launch_mode<VX_MODE_MINIP>(c, lp, mo, weight, grid); break;
-        default: launch_mode<VX_MODE_DVR_PHONG>(c, lp, mo, weight, grid); break;
-      }
+      with_layout(lp.layout, [&](auto lay) {
+        constexpr int LAY = decltype(lay)::value;
+        if (lp.shadow) {
+          hipLaunchKernelGGL((render_generic_shadow<LAY>), lp.grid, lp.block, lp.lds, s, p, v, tf, n, mo, weight, tm, lp.light);
+          return;
+        }
+        with_mode(lp.mode, [&](auto m) {
+          hipLaunchKernelGGL((render_generic<decltype(m)::value, LAY>), lp.grid, lp.block, lp.lds, s, p, v, tf, n, mo, weight, tm);
+        });
+      });
   }
   VX_HIP(c, hipGetLastError());
   return VX_OK;
@@ -1332,8 +1411,7 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
     c->dv.extent[i] = index_extent[i];
   }
   c->range_host.assign((const uint32_t*)range, (const uint32_t*)range + nb);
-  c->skip_dirty = true;
-  c->proj_dirty = true;
+  c->skip_table.stale = c->proj_table.stale = true;
   c->order_builds_left = 2;
   uint32_t n_layers = 0;
   if ((rc = alloc_layout(c, n_layers))) { free_volume(c); return rc; }
@@ -1467,9 +1545,7 @@ int vx_upload_transfer(VxContext* c, const float* rgba, uint32_t length) {
   VX_HIP(c, hipMemcpy(c->tf, rgba, (size_t)length * sizeof(float4), hipMemcpyHostToDevice));
   c->tf_len = length;
   c->tf_host.assign(rgba, rgba + (size_t)length * 4);
-  c->skip_dirty = true;
-  c->lmaj_dirty = true;
-  c->shadow_dirty = true;
+  c->skip_table.stale = c->lmaj_table.stale = c->shadow_table.stale = true;
   c->order_builds_left = 2;
   return VX_OK;
 }
@@ -1593,7 +1669,7 @@ int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
   return alloc_framebuffers(c);
 }
 
-static int prepare_render(VxContext* c, dim3& grid) {
+static int prepare_render(VxContext* c) {
   if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
   if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
   if (!c->tf) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: no transfer function");
@@ -1608,7 +1684,6 @@ static int prepare_render(VxContext* c, dim3& grid) {
   c->dv.env_avg_w = c->env_avg_w;
   c->dv.env_w = c->env_w;
   c->dv.env_h = c->env_h;
-  c->dv.bu_active = (eff_layout(c) == VX_LAYOUT_BRICKU8 && c->dv.bu) ? 1u : 0u;
   {
     // The box the rays are clipped to must lie inside the volume (volume.ts:32-37 clips the volume's own box, so the
     // viewer cannot ask for anything else): the trilinear look-up of the cellquad layout relies on every sample's cell
@@ -1664,27 +1739,13 @@ static int prepare_render(VxContext* c, dim3& grid) {
   }
   {
     const VxParams& p = c->params;
-    bool dvr = p.render_mode == VX_MODE_DVR || p.render_mode == VX_MODE_DVR_PHONG;
-    if (dvr && p.dvr_skip_empty && !p.debug_hits) {
-      if (c->skip_dirty || !c->dv.skip_bits || c->skip_key[0] != p.volume_density_scale ||
-          c->skip_key[1] != p.volume_inv_maj || c->skip_key[2] != p.sample_range[0] ||
-          c->skip_key[3] != p.sample_range[1]) {
-        int rc = rebuild_skip_mask(c);
-        if (rc) return rc;
-      }
-    }
-    if (proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits &&
-        (c->proj_dirty || !c->proj_dev || c->proj_mode != p.render_mode || c->proj_key[0] != p.volume_density_scale ||
-         c->proj_key[1] != p.volume_inv_maj)) {
-      int rc = rebuild_projection_bounds(c);
-      if (rc) return rc;
-    }
-    if (p.render_mode == VX_MODE_DEFAULT && !p.debug_hits &&
-        (c->lmaj_dirty || !c->dv.lmaj || c->lmaj_key[0] != p.volume_density_scale || c->lmaj_key[1] != p.volume_inv_maj ||
-         c->lmaj_key[2] != p.volume_maj || c->lmaj_key[3] != p.sample_range[0] || c->lmaj_key[4] != p.sample_range[1])) {
-      int rc = rebuild_local_majorants(c);
-      if (rc) return rc;
-    }
+    const bool dvr = p.render_mode == VX_MODE_DVR || p.render_mode == VX_MODE_DVR_PHONG;
+    int rc = VX_OK;
+    if (dvr && p.dvr_skip_empty && !p.debug_hits && !c->skip_table.current(p)) rc = rebuild_skip_mask(c);
+    if (!rc && proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits && !c->proj_table.current(p))
+      rc = rebuild_projection_bounds(c);
+    if (!rc && p.render_mode == VX_MODE_DEFAULT && !p.debug_hits && !c->lmaj_table.current(p)) rc = rebuild_local_majorants(c);
+    if (rc) return rc;
   }
   {
     // the layouts this launch samples, built on first use beside the one the upload built
@@ -1699,17 +1760,11 @@ static int prepare_render(VxContext* c, dim3& grid) {
       rc = ensure_brickf32(c);
     if (rc) return rc;
   }
-  if (shadow_on(c)) {   // the light grid, rebuilt when an input differs bitwise from the last build (a camera move does not)
-    float key[SHADOW_KEY];
-    shadow_key(c->params, key);
-    if (c->shadow_dirty || !c->shadow.t || memcmp(key, c->shadow_key, sizeof key) != 0) {
-      int rc = rebuild_light_grid(c);
-      if (rc) return rc;
-    }
+  if (shadow_on(c) && !c->shadow_table.current(c->params)) {   // after the layouts: the build samples them
+    int rc = rebuild_light_grid(c);
+    if (rc) return rc;
   }
-  uint32_t groups = (c->tm.tiles_per_shard + 7u) / 8u;
-  grid = dim3(groups * 128u);
-  return ensure_counters(c, (size_t)grid.x * 4u);  // one record per wave of the grid
+  return ensure_counters(c, (size_t)frame_blocks(c) * 4u);  // one record per wave of a frame's blocks
 }
 
 static int take_events(VxContext* c, EventPair& ev) {
@@ -1730,8 +1785,7 @@ int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_render_frame(m, frame_index, sample_weight); });
   VX_DEV(c);
-  dim3 grid;
-  int rc = prepare_render(c, grid);
+  int rc = prepare_render(c);
   if (rc) return rc;
   MultiOut mo{};
   mo.count = 1;
@@ -1742,14 +1796,14 @@ int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
   EventPair ev;
   if ((rc = take_events(c, ev))) return rc;
   VX_HIP(c, hipEventRecord(ev.a, c->stream));
-  rc = launch_planned(c, lp, mo, sample_weight, grid);
+  rc = launch_planned(c, lp, mo, sample_weight);
   VX_HIP(c, hipEventRecord(ev.b, c->stream));
   c->pending_events.push_back(ev);
   if (rc) return rc;
   if (lp.kernel == Kernel::GENERIC) c->order_builds_left = 0;   // render_generic runs its blocks in launch order
   else if (c->order_builds_left > 0) {
     c->order_builds_left--;
-    hipLaunchKernelGGL(build_order, dim3(1), dim3(1024), 0, c->stream, c->dc, c->order, grid.x);
+    hipLaunchKernelGGL(build_order, dim3(1), dim3(1024), 0, c->stream, c->dc, c->order, frame_blocks(c));
     VX_HIP(c, hipGetLastError());
   }
   c->note_launch(1);
@@ -1799,8 +1853,7 @@ int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const f
     ++done;
   }
   if (done == count) return VX_OK;
-  dim3 grid;
-  int rc = prepare_render(c, grid);
+  int rc = prepare_render(c);
   if (rc) return rc;
   if ((rc = ensure_pipes(c, (uint32_t)in_flight))) return rc;
   const uint32_t nq = (uint32_t)c->slab_quads;
@@ -1830,7 +1883,7 @@ int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const f
     EventPair ev;
     if ((rc = take_events(c, ev))) return rc;
     VX_HIP(c, hipEventRecord(ev.a, c->stream));
-    rc = launch_planned(c, lp, mo, 0.0f, grid);
+    rc = launch_planned(c, lp, mo, 0.0f);
     VX_HIP(c, hipEventRecord(ev.b, c->stream));   // the render kernel alone; the blend is timed apart
     c->pending_events.push_back(ev);
     if (rc) return rc;
@@ -1919,8 +1972,7 @@ int vx_probe_tile_costs(VxContext* c, uint32_t* costs, uint32_t n) {
   if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_probe_tile_costs: no volume uploaded");
   if (!c->has_params || !c->tf || !c->W) VX_FAIL(c, VX_ERR_INVALID, "vx_probe_tile_costs: params, transfer function and size first");
   if (n != c->tm.n_tiles) VX_FAIL(c, VX_ERR_INVALID, "vx_probe_tile_costs: the image has %u tiles, not %u", c->tm.n_tiles, n);
-  dim3 grid;
-  int rc = prepare_render(c, grid);   // skip mask, environment pointers
+  int rc = prepare_render(c);   // skip mask, environment pointers
   if (rc) return rc;
   uint32_t* d = nullptr;
   VX_HIP(c, hipMalloc(&d, (size_t)n * 4));
@@ -2205,23 +2257,23 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
   if (!c || !out3) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_probe_gather_spread(c->members[0], frame_index, out3));
   VX_DEV(c);
-  dim3 grid;
-  int rc = prepare_render(c, grid);
+  int rc = prepare_render(c);
   if (rc) return rc;
   MultiOut mo{};
   mo.count = 1;
   mo.out[0] = c->slab;   // never written by the probe build
   mo.frame[0] = frame_index;
-  if (plan_launch(c, mo).kernel != Kernel::DVR_CQ)
+  const LaunchPlan lp = plan_launch(c, mo, true);
+  if (lp.kernel != Kernel::DVR_CQ)
     VX_FAIL(c, VX_ERR_INVALID, "vx_probe_gather_spread: needs render_mode dvr on the cellquad layout");
-  const size_t waves = (size_t)grid.x * 4u;
+  const size_t waves = (size_t)frame_blocks(c) * 4u;
   DevCounters* d = nullptr;
   VX_HIP(c, hipMalloc(&d, waves * sizeof(DevCounters)));
   hipError_t e = hipMemsetAsync(d, 0, waves * sizeof(DevCounters), c->stream);
   mo.dc[0] = d;
-  if (e == hipSuccess) {
-    launch_dvr_cq_multi(c->params, c->dv, c->tf, c->tf_len, mo, 0.0f, c->tm, c->stream, nullptr, true);
-    e = hipGetLastError();
+  if (e == hipSuccess && (rc = launch_planned(c, lp, mo, 0.0f))) {
+    (void)hipFree(d);
+    return rc;
   }
   std::vector<DevCounters> h(waves);
   if (e == hipSuccess) e = hipMemcpyAsync(h.data(), d, waves * sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream);

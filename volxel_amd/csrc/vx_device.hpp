@@ -41,7 +41,7 @@ struct DevVolume {
   // {0, 0}: it serves the zero dword, so rows and chunks outside the volume decode to 0 (A4).
   const uint32_t* bu;
   const float2* bu_range;
-  uint32_t bu_active;           // this launch samples bricku8 (set by vx_api prepare_render)
+  uint32_t bu_active;           // unused: vx_api.hip plan_launch decides U8; kept so the offsets behind it stay
   // exact empty-space skipping (DVR): one bit per macro cell of 8 << skip_level voxels
   const uint32_t* skip_bits;    // nullptr: none
   uint32_t skip_level;

@@ -276,22 +276,5 @@ __global__ __launch_bounds__(256) void render_dvr_cq(const VxParams p, const Dev
   const uint32_t n_px = (uint32_t)__builtin_popcountll(__ballot(in_image));
   add_counts(dc, n_samples, n_rays, n_px, n_skipped, 0u, n_slots, blk, n_batches * (uint32_t)(2 * U), 0u, n_tf);
 }
-// 4 march steps per batch (U); probe: the measurement build (PROBE, vx_probe_gather_spread)
-inline void launch_dvr_cq_multi(const VxParams& p, const DevVolume& v, const float4* tf, uint32_t tf_len,
-                                const MultiOut& mo, float weight, const TileMap& tm, hipStream_t stream,
-                                const uint32_t* order, bool probe = false) {
-  uint32_t groups = (tm.tiles_per_shard + 7u) / 8u;
-  dim3 grid(groups * 128u * mo.count), block(256);
-  const bool skip = p.dvr_skip_empty && v.skip_bits;
-  size_t lds = (size_t)tf_len * sizeof(float4) + (skip ? (size_t)v.skip_words * 4u : 0u);
-#define VX_LAUNCH(SS, PR) \
-  hipLaunchKernelGGL((render_dvr_cq<4, SS, PR>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order)
-  if (probe) {
-    if (skip) VX_LAUNCH(true, true); else VX_LAUNCH(false, true);
-  } else {
-    if (skip) VX_LAUNCH(true, false); else VX_LAUNCH(false, false);
-  }
-#undef VX_LAUNCH
-}
 
 }  // namespace vx

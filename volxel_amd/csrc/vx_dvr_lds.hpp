@@ -165,38 +165,4 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W
 #include "vx_dvr_lds_march.inc"
 }
 
-// sg: the light grid of a shadowed DVR launch (nullptr: unshadowed)
-inline void launch_dvr_lds(const VxParams& p, const DevVolume& v, const float4* tf, uint32_t tf_len, const MultiOut& mo,
-                           float weight, const TileMap& tm, hipStream_t stream, const uint32_t* order,
-                           const ShadowGrid* sg = nullptr) {
-  const uint32_t groups = (tm.tiles_per_shard + 7u) / 8u;
-  const dim3 grid(groups * 128u * (mo.count ? mo.count : 1u)), block(256);
-  const bool skip = p.dvr_skip_empty && v.skip_bits;
-  const bool phong = p.render_mode == VX_MODE_DVR_PHONG;
-  const bool u8 = v.bu_active != 0u;
-  if (sg && !phong) {   // (vx_set_params refuses a stride with Phong)
-    const size_t lds = (size_t)tf_len * sizeof(float4) + (skip ? (((size_t)v.skip_words + 3u) & ~(size_t)3u) * 4u : 0u) +
-                       4u * (size_t)LdsTile<false>::FLOATS * sizeof(float);
-#define VX_LAUNCH_SH(SK, U) \
-  hipLaunchKernelGGL((render_dvr_lds_shadow<VX_LDS_S, SK, U>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order, *sg)
-    if (skip) { if (u8) VX_LAUNCH_SH(true, true); else VX_LAUNCH_SH(true, false); }
-    else      { if (u8) VX_LAUNCH_SH(false, true); else VX_LAUNCH_SH(false, false); }
-#undef VX_LAUNCH_SH
-    return;
-  }
-  const size_t tile_bytes = 4u * (size_t)(phong ? LdsTile<true>::FLOATS : LdsTile<false>::FLOATS) * sizeof(float);
-  const size_t lds = (size_t)tf_len * sizeof(float4) + (skip ? (((size_t)v.skip_words + 3u) & ~(size_t)3u) * 4u : 0u) + tile_bytes;
-#define VX_LAUNCH_LDS(PH, SK, U)                                                                                          \
-  hipLaunchKernelGGL((render_dvr_lds<(PH ? VX_LDS_S_PHONG : VX_LDS_S), PH, SK, U>), grid, block, lds, stream, p, v, tf, tf_len, \
-                     mo, weight, tm, order)
-  if (phong) {
-    if (skip) { if (u8) VX_LAUNCH_LDS(true, true, true); else VX_LAUNCH_LDS(true, true, false); }
-    else      { if (u8) VX_LAUNCH_LDS(true, false, true); else VX_LAUNCH_LDS(true, false, false); }
-  } else {
-    if (skip) { if (u8) VX_LAUNCH_LDS(false, true, true); else VX_LAUNCH_LDS(false, true, false); }
-    else      { if (u8) VX_LAUNCH_LDS(false, false, true); else VX_LAUNCH_LDS(false, false, false); }
-  }
-#undef VX_LAUNCH_LDS
-}
-
 }  // namespace vx

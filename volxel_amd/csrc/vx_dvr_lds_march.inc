@@ -529,7 +529,7 @@
         T = Tn;
         // early ray termination (vx_oracle.c dvr_pixel: contrib && tau >= ert): the ray has no further samples; its T
         // stays exp2(-tau log2 e), so that nothing later in the march touches its C, and becomes 0 after the march
-        // ert > 0 (the launcher sends an epsilon >= 1 to render_generic): only a contributing sample can carry tau over
+        // ert > 0 (plan_launch sends an epsilon >= 1 to render_generic): only a contributing sample can carry tau over
         // it, and the ray ends right there, so `tau >= ert` alone says "terminated" for every lane, now and later -- no
         // compare on alpha here, and nray follows once per window, after the march
         klim = tau >= ert ? 0.0f : klim;

@@ -162,7 +162,7 @@ struct MultiOut {
   uint32_t frame[MERGE_MAX];
   uint32_t count;
   // Round 4, behind the fields lane_frame_slot addresses (their offsets do not move): the running mean applied IN the render
-  // kernel.  fuse != 0 (vx_api.hip plan_launch's fuse rule: a launch of exactly 8, 16, 32 or 64 frames of the LDS-window DVR
+  // kernel.  fuse != 0 (the fuse rule, vx_api.hip folds: a launch of exactly 8, 16, 32 or 64 frames of the LDS-window DVR
   // kernel, of 32 frames of render_generic): a wave holds every frame of its 8, 4, 2 (or 1) pixels, so it folds their results in frame order into `accum` itself -- fragment.frag:158
   // with weight[k] for frame slot k, exactly what merge_results does -- and neither the per-frame result slabs nor the blend
   // kernel are touched.  fuse == 2: some weight of the launch is 0 (the previous value is then dropped: merge_results'
@@ -386,7 +386,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(generic_min
       const float4 r = f.template shade_pixel<MODE>(px, py, my_frame);
       L = v3(r.x, r.y, r.z);
     }
-    // wave-private scratch behind the transfer function (plan_launch adds it to the LDS size of a fused launch)
+    // wave-private scratch behind the transfer function (vx_api.hip lds_bytes adds it to the LDS size of a fused launch)
     float* const fold = reinterpret_cast<float*>(tf_lds + (tf_len <= TF_LDS_MAX ? tf_len : 0u)) + (threadIdx.x >> 6) * 320u;
     fold_frames(fold, threadIdx.x & 63u, L, active, si, mo.accum, fuse, 5u);
     flush_counts(dc, c, active ? 1u : 0u, blk);

@@ -27,25 +27,4 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W
 #include "vx_dvr_lds_march.inc"
 }
 
-// bounds: the table of range skipping, nullptr without it
-inline void launch_proj_lds(const VxParams& p, const DevVolume& v, const float4* tf, uint32_t tf_len, const MultiOut& mo,
-                            float weight, const TileMap& tm, hipStream_t stream, const uint32_t* order, const float* bounds) {
-  const uint32_t groups = (tm.tiles_per_shard + 7u) / 8u;
-  const dim3 grid(groups * 128u * (mo.count ? mo.count : 1u)), block(256);
-  const bool skip = bounds != nullptr;
-  const bool minip = p.render_mode == VX_MODE_MINIP;
-  const bool u8 = v.bu_active != 0u;
-  const size_t lds = (size_t)tf_len * sizeof(float4) + 4u * (size_t)LdsTile<false>::FLOATS * sizeof(float);
-#define VX_LAUNCH_PR(MI, SK, U) \
-  hipLaunchKernelGGL((render_proj_lds<VX_LDS_S, MI, SK, U>), grid, block, lds, stream, p, v, tf, tf_len, mo, weight, tm, order, bounds)
-  if (minip) {
-    if (skip) { if (u8) VX_LAUNCH_PR(true, true, true); else VX_LAUNCH_PR(true, true, false); }
-    else      { if (u8) VX_LAUNCH_PR(true, false, true); else VX_LAUNCH_PR(true, false, false); }
-  } else {
-    if (skip) { if (u8) VX_LAUNCH_PR(false, true, true); else VX_LAUNCH_PR(false, true, false); }
-    else      { if (u8) VX_LAUNCH_PR(false, false, true); else VX_LAUNCH_PR(false, false, false); }
-  }
-#undef VX_LAUNCH_PR
-}
-
 }  // namespace vx

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void build_light_grid(const VxParams p, const 
 
 // Shadowed DVR on the generic march (Frame::dvr<false, true>): where the LDS-window kernel does not run -- the REFERENCE and
 // CELLQUAD layouts, dvr_ert_tau <= 0, a TF longer than TF_LDS_MAX.  One pixel per lane as render_generic<VX_MODE_DVR>; DVR
-// launches of render_generic never fold the running mean (plan_launch), neither does this one.
+// launches of render_generic never fold the running mean (vx_api.hip folds), neither does this one.
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void render_generic_shadow(const VxParams p, const DevVolume v, const float4* __restrict__ tf_global,
                                                              uint32_t tf_len, const MultiOut mo, float weight, const TileMap tm,
