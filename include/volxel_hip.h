@@ -338,7 +338,8 @@ int vx_get_counters(VxContext* ctx, VxCounters* out);
 int vx_reset_counters(VxContext* ctx);
 
 /* library / device facts for logs (viewer.ts:225-242 device record).  group: member 0 (the display device).
- * The test and measurement hooks below (vx_debug_*, vx_probe_*) also run on member 0 of a group. */
+ * The test and measurement hooks below (vx_debug_*, vx_probe_*) and the slices (vx_slice, vx_slice_stats) also run on
+ * member 0 of a group. */
 int vx_device_info(VxContext* ctx, char* name_out, uint32_t name_cap, uint32_t* cu_count,
                    uint64_t* hbm_bytes);
 const char* vx_version(void);
@@ -382,6 +383,46 @@ int vx_shadow_stats(VxContext* ctx, uint64_t* builds, uint64_t* light_samples, d
  * ((k * dims[1]) + j) * dims[0] + i); out = NULL queries the dimensions only.  VX_ERR_INVALID before the first build.
  * Synchronises.  group: member 0. */
 int vx_debug_read_shadow_grid(VxContext* ctx, float* out, uint32_t dims_out[3]);
+
+/* ---- slices: multiplanar reformation and thick slabs (no reference counterpart; DESIGN.md section 2 "Slices").
+ * A slice is a W x H grid of pixels on a plane, each with N slab samples along dn.  Positions are in the cell frame of the
+ * march contract (q = index position - 1/2: the centre of voxel i is at q = i).  Per axis a,
+ *   q_a = fma(s, dn_a, fma(y, dv_a, fma(x, du_a, origin_a)))     pixel (x, y), sample s = 0 .. N-1 (exact fp32 integers),
+ * d_s = trilinear(q) * volume_inv_maj (A5 on any layout, taps outside the volume read 0, volume_density_scale and
+ * volume_inv_maj of the last vx_set_params; the clip box does not apply).  The reduction gives one value per pixel. */
+enum VxSliceReduce {
+  VX_SLICE_MEAN = 0, /* acc = d_0, acc = acc + d_s for s = 1 .. N-1 in order (fp32 adds), value = acc / N (IEEE)  */
+  VX_SLICE_MAX = 1,  /* fmaxf over the d_s: a thick-slab MIP                                                      */
+  VX_SLICE_MIN = 2   /* fminf over the d_s: a thick-slab MinIP                                                     */
+};
+/* the optional RGBA8 display of the values (alpha 255; fp32 operations, no contraction); a byte is
+ * (uint8_t)(c * 255 + 0.5) of c clamped to [0, 1] (gl_clamp) */
+enum VxSliceDisplay {
+  VX_SLICE_NONE = 0, /* no display output                                                                          */
+  VX_SLICE_GREY = 1, /* c = (value - window[0]) / (window[1] - window[0]) in r, g and b                            */
+  VX_SLICE_TF = 2    /* rgba = TF(value) by DVR's rule (NEAREST bin, 0 outside sample_range), shown (r*a, g*a, b*a) */
+};
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxSliceParams {
+  float origin[3], du[3], dv[3], dn[3]; /* cell frame, see above                                  */
+  uint32_t size[2];                      /* W, H: 1 .. 16384 each                                  */
+  uint32_t slab_samples;                 /* N: 1 .. 4096                                           */
+  int32_t reduce;                        /* enum VxSliceReduce                                     */
+  int32_t display;                       /* enum VxSliceDisplay                                    */
+  float window[2];                       /* VX_SLICE_GREY: the values shown black and white        */
+} VxSliceParams;
+/* One slice on the context's stream, behind every render already queued; synchronises.  values_out: W*H floats, row-major,
+ * row 0 = y = 0 (the accumulator's GL convention); rgba8_out: W*H*4 bytes, with a display other than VX_SLICE_NONE only.
+ * Either may be NULL; with both NULL only the kernel runs (timing).  The accumulator, the frame state and VxCounters are not
+ * touched.  The output buffers (W*H*8 bytes) stay with the context and grow with the largest slice.
+ * VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the field, before vx_set_params, for NULL sp, a size, N, reduce
+ * or display out of range, a non-finite vector component, a window with window[1] <= window[0] (or not finite) under
+ * VX_SLICE_GREY, VX_SLICE_TF without a transfer function, and rgba8_out with VX_SLICE_NONE.
+ * group: member 0 (the display device), like the probes. */
+int vx_slice(VxContext* ctx, const VxSliceParams* sp, float* values_out, uint8_t* rgba8_out);
+/* the last slice: its samples (W*H*N) and the HIP-event time of its kernel; both 0 before the first slice.  Any out pointer
+ * may be NULL.  group: member 0. */
+int vx_slice_stats(VxContext* ctx, uint64_t* samples, double* last_kernel_ms);
 
 /* test hook (no reference counterpart): the device's R8-unorm decode table, 256 floats */
 int vx_debug_unorm_table(VxContext* ctx, float* out256);

@@ -47,12 +47,18 @@ def struct_from_header(header: str, name: str):
 
 VxParams = struct_from_header("volxel_hip.h", "VxParams")
 VxCounters = struct_from_header("volxel_hip.h", "VxCounters")
+VxSliceParams = struct_from_header("volxel_hip.h", "VxSliceParams")
 
 MODE_DEFAULT, MODE_NO_DDA, MODE_RAYMARCH, MODE_DVR, MODE_DVR_PHONG, MODE_MIP, MODE_MINIP = range(7)
 LAYOUT_REFERENCE, LAYOUT_CELLQUAD, LAYOUT_BRICKF32, LAYOUT_AUTO = 0, 1, 2, 3
 RENDER_MODES = {"default": MODE_DEFAULT, "no_dda": MODE_NO_DDA, "raymarch": MODE_RAYMARCH,
                 "dvr": MODE_DVR, "dvr_phong": MODE_DVR_PHONG, "mip": MODE_MIP, "minip": MODE_MINIP}
 SHARD_TILE = 64
+SLICE_MEAN, SLICE_MAX, SLICE_MIN = range(3)            # enum VxSliceReduce
+SLICE_NONE, SLICE_GREY, SLICE_TF = range(3)            # enum VxSliceDisplay
+SLICE_REDUCE = {"mean": SLICE_MEAN, "max": SLICE_MAX, "min": SLICE_MIN}
+SLICE_DISPLAY = {None: SLICE_NONE, "grey": SLICE_GREY, "tf": SLICE_TF}
+SLICE_MAX_SIZE, SLICE_MAX_SAMPLES = 16384, 4096
 
 
 def declared_symbols(header: str):
@@ -130,6 +136,8 @@ def load_library():
         "vx_debug_build_projection_bounds": ([vp, P(u32), P(VxParams), vp, P(u32), P(u32)], i32),
         "vx_shadow_stats": ([vp, P(u64), P(u64), P(C.c_double)], i32),
         "vx_debug_read_shadow_grid": ([vp, vp, P(u32)], i32),
+        "vx_slice": ([vp, P(VxSliceParams), vp, vp], i32),
+        "vx_slice_stats": ([vp, P(u64), P(C.c_double)], i32),
         # preprocessor
         "vxb_build_from_u16": ([vp, P(u32), P(C.c_float), C.c_uint16, i32, P(vp)], i32),
         "vxb_read_dicoms_to_grid": ([P(vp), P(u64), u32, i32, P(vp)], i32),

@@ -18,6 +18,7 @@
 #include "vx_kernels.hpp"
 #include "vx_shadow.hpp"
 #include "vx_projection.hpp"
+#include "vx_slice.hpp"
 
 using namespace vx;
 
@@ -177,6 +178,13 @@ struct VxContext {
   // device group (vx_create_group): member i renders shard i of members.size(); empty for a plain context
   std::vector<VxContext*> members;
   hipEvent_t done = nullptr;   // a member's: recorded after its last render, waited on by the display stream
+  // slices (vx_slice): the output buffers, grown to the largest slice, and the facts of the last slice
+  float* slice_values = nullptr;
+  uchar4* slice_rgba = nullptr;
+  size_t slice_cap = 0;        // pixels of each buffer
+  hipEvent_t slice_ev[2] = {nullptr, nullptr};
+  uint64_t slice_samples = 0;
+  double slice_ms = 0.0;
 };
 
 static bool is_group(const VxContext* c) { return !c->members.empty(); }
@@ -883,6 +891,31 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
   return VX_OK;
 }
 
+// ---- slices (vx_slice): the kernel a slice runs, chosen apart from plan_launch (a slice is no render launch) ---------------
+// The layout a slice samples: what is resident at the time of the call -- brickf32, else cellquad, else the reference textures
+// (same bits on all three).  Not eff_layout: under AUTO it follows the render mode, and for `default` / `no_dda` it names
+// cellquad before the first render of such a mode has built it; under bricku8 the slice reads the reference textures.
+static int slice_layout(const VxContext* c) {
+  if (c->dv.bf) return VX_LAYOUT_BRICKF32;
+  if (c->dv.cq) return VX_LAYOUT_CELLQUAD;
+  return VX_LAYOUT_REFERENCE;
+}
+// launches slice_reduce<sp.reduce, the layout of slice_layout> for sp on the context's stream
+static void launch_slice(VxContext* c, const VxSliceParams& sp) {
+  const dim3 grid((sp.size[0] + 15u) / 16u, (sp.size[1] + 15u) / 16u);
+  const VxParams& p = c->params;
+  with_layout(slice_layout(c), [&](auto lay) {
+    constexpr int LAY = decltype(lay)::value;
+    auto go = [&](auto red) {
+      hipLaunchKernelGGL((slice_reduce<decltype(red)::value, LAY>), grid, dim3(256), 0, c->stream, sp, c->dv, p.volume_density_scale,
+                         p.volume_inv_maj, c->tf, c->tf_len, p.sample_range[0], p.sample_range[1], c->slice_values, c->slice_rgba);
+    };
+    if (sp.reduce == VX_SLICE_MAX) go(std::integral_constant<int, VX_SLICE_MAX>{});
+    else if (sp.reduce == VX_SLICE_MIN) go(std::integral_constant<int, VX_SLICE_MIN>{});
+    else go(std::integral_constant<int, VX_SLICE_MEAN>{});
+  });
+}
+
 // ---- device groups (vx_create_group): the entry points fan out to the members, read member 0, or gather --------
 // a member's failure, reported on the group handle with the member's index and device
 static int member_fail(VxContext* g, size_t i, int rc) {
@@ -1128,6 +1161,10 @@ void vx_destroy(VxContext* c) {
   if (c->pipe_dc_pool) (void)hipFree(c->pipe_dc_pool);
   if (c->slab_table) (void)hipFree(c->slab_table);
   if (c->done) (void)hipEventDestroy(c->done);
+  if (c->slice_values) (void)hipFree(c->slice_values);
+  if (c->slice_rgba) (void)hipFree(c->slice_rgba);
+  for (hipEvent_t e : c->slice_ev)
+    if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -2286,6 +2323,70 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
     out3[1] += w.rays;           // wave-wide distinct lines, summed over the q0 gathers
     out3[2] += w.pixels;         // look-ups of the 16 lane quads, summed over the q0 gathers
   }
+  return VX_OK;
+}
+
+int vx_slice(VxContext* c, const VxSliceParams* sp, float* values_out, uint8_t* rgba8_out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_slice(c->members[0], sp, values_out, rgba8_out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: sp is NULL");
+  for (int i = 0; i < 2; ++i)
+    if (sp->size[i] < 1u || sp->size[i] > 16384u)
+      VX_FAIL(c, VX_ERR_INVALID, "vx_slice: size[%d] = %u outside 1 .. 16384", i, sp->size[i]);
+  if (sp->slab_samples < 1u || sp->slab_samples > 4096u)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: slab_samples = %u outside 1 .. 4096", sp->slab_samples);
+  if (sp->reduce < VX_SLICE_MEAN || sp->reduce > VX_SLICE_MIN) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: unknown reduce %d", sp->reduce);
+  if (sp->display < VX_SLICE_NONE || sp->display > VX_SLICE_TF)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: unknown display %d", sp->display);
+  const struct { const char* name; const float* v; } vecs[4] = {{"origin", sp->origin}, {"du", sp->du}, {"dv", sp->dv}, {"dn", sp->dn}};
+  for (const auto& e : vecs)
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(e.v[i])) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: %s[%d] is not finite", e.name, i);
+  if (sp->display == VX_SLICE_GREY &&
+      !(std::isfinite(sp->window[0]) && std::isfinite(sp->window[1]) && sp->window[1] > sp->window[0]))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: window [%g, %g] with VX_SLICE_GREY: needs finite window[0] < window[1]",
+            (double)sp->window[0], (double)sp->window[1]);
+  if (sp->display == VX_SLICE_TF && !c->tf)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: display VX_SLICE_TF without a transfer function (vx_upload_transfer first)");
+  if (rgba8_out && sp->display == VX_SLICE_NONE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: rgba8_out with display VX_SLICE_NONE (no display output)");
+  const size_t px = (size_t)sp->size[0] * sp->size[1];
+  if (px > c->slice_cap) {   // (every earlier slice has completed: vx_slice synchronises)
+    if (c->slice_values) (void)hipFree(c->slice_values);
+    if (c->slice_rgba) (void)hipFree(c->slice_rgba);
+    c->slice_values = nullptr;
+    c->slice_rgba = nullptr;
+    c->slice_cap = 0;
+    VX_HIP(c, hipMalloc(&c->slice_values, px * sizeof(float)));
+    VX_HIP(c, hipMalloc(&c->slice_rgba, px * sizeof(uchar4)));
+    c->slice_cap = px;
+  }
+  for (hipEvent_t& e : c->slice_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  VX_HIP(c, hipEventRecord(c->slice_ev[0], c->stream));
+  launch_slice(c, *sp);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->slice_ev[1], c->stream));
+  if (values_out)
+    VX_HIP(c, hipMemcpyAsync(values_out, c->slice_values, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (rgba8_out) VX_HIP(c, hipMemcpyAsync(rgba8_out, c->slice_rgba, px * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  float ms = 0.0f;
+  VX_HIP(c, hipEventElapsedTime(&ms, c->slice_ev[0], c->slice_ev[1]));
+  c->slice_samples = (uint64_t)px * sp->slab_samples;
+  c->slice_ms = ms;
+  return VX_OK;
+}
+
+int vx_slice_stats(VxContext* c, uint64_t* samples, double* last_kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_slice_stats(c->members[0], samples, last_kernel_ms));
+  if (samples) *samples = c->slice_samples;
+  if (last_kernel_ms) *last_kernel_ms = c->slice_ms;
   return VX_OK;
 }
 

@@ -8,6 +8,11 @@ export type BrickGridMessage = {            // WasmWorkerMessageDicomReturn, com
   rangeMipmaps: { mipmap: Uint16Array; stride: [number, number, number] }[];
   indirection: Uint32Array; range: Uint16Array; atlas: Uint8Array; brickCounter: number;
 };
+/** a plane in the cell frame (q = index position - 1/2): sample s of pixel (x, y) at origin + x*du + y*dv + s*dn */
+export type SliceSpec = {
+  origin: [number, number, number]; du: [number, number, number]; dv: [number, number, number]; dn: [number, number, number];
+  size: [number, number]; slabSamples?: number;
+};
 export declare const VolxelRenderMode: { default: 0; no_dda: 1; raymarch: 2; dvr: 3; dvr_phong: 4; mip: 5; minip: 6 };
 export declare function generateTransferFunction(colors: ColorStop[], generatedSteps?: number): { data: Float32Array; length: number };
 export declare class Camera {
@@ -74,6 +79,15 @@ export declare class Volxel3DDicomRenderer {
   shadowStats(): { builds: number; lightSamples: number; lastBuildMs: number };
   /** the last light grid built (vx_debug_read_shadow_grid): transmittance toward the light per node, x fastest */
   readShadowGrid(): { dims: [number, number, number]; data: Float32Array };
+  /** index-space planes z = k, y = j, x = i through voxel centres, one pixel per voxel (patient orientation not modelled) */
+  axial(k: number): SliceSpec;
+  coronal(j: number): SliceSpec;
+  sagittal(i: number): SliceSpec;
+  /** a slice or thick slab on the GPU (include/volxel_hip.h vx_slice): values row-major, row 0 = y = 0; rgba8 with a display */
+  slice(spec: SliceSpec & { reduce?: "mean" | "max" | "min"; display?: "grey" | "tf" | null; window?: [number, number] | null }):
+    { values: Float32Array; rgba8: Uint8Array | null };
+  /** the last slice: W*H*N samples and its HIP-event kernel time */
+  sliceStats(): { samples: number; lastKernelMs: number };
   dispose(): void;
 }
 /** viewer.ts:1455-1462: keeps the worker factory, returns the element-name -> class table ("volxel-3d-viewer") */

@@ -16,11 +16,11 @@ const native = require('./volxel_napi.node');
 const RenderMode = Object.freeze({ default: 0, no_dda: 1, raymarch: 2, dvr: 3, dvr_phong: 4, mip: 5, minip: 6 });
 const LOW_RES_DURATION = 5; // viewer.ts:132
 
-// ---- VxParams field table, parsed from the C header (single source of truth) --------------
-function parseParamsLayout() {
+// ---- VxParams / VxSliceParams field tables, parsed from the C header (single source of truth) --------------
+function parseParamsLayout(name = 'VxParams', size = native.sizeofParams()) {
   const text = fs.readFileSync(path.join(__dirname, '..', '..', 'include', 'volxel_hip.h'), 'utf8')
     .replace(/\/\*[\s\S]*?\*\//g, '');
-  const body = /typedef\s+struct\s+VxParams\s*\{([\s\S]*?)\}\s*VxParams\s*;/.exec(text)[1];
+  const body = new RegExp(`typedef\\s+struct\\s+${name}\\s*\\{([\\s\\S]*?)\\}\\s*${name}\\s*;`).exec(text)[1];
   const fields = {};
   let off = 0;
   for (const decl of body.split(';')) {
@@ -33,15 +33,18 @@ function parseParamsLayout() {
       off += 4 * n;
     }
   }
-  if (off !== native.sizeofParams()) throw new Error('VxParams layout mismatch between header and library');
+  if (off !== size) throw new Error(`${name} layout mismatch between header and library`);
   return { fields, size: off };
 }
 const LAYOUT = parseParamsLayout();
+const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams());
+const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
+const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
 class ParamsBlock {
-  constructor() { this.buffer = new ArrayBuffer(LAYOUT.size); this.view = new DataView(this.buffer); }
+  constructor(layout = LAYOUT) { this.layout = layout; this.buffer = new ArrayBuffer(layout.size); this.view = new DataView(this.buffer); }
   set(name, value) {
-    const f = LAYOUT.fields[name];
+    const f = this.layout.fields[name];
     if (!f) throw new Error(`unknown uniform ${name}`);
     const vals = (typeof value === 'number') ? [value] : Array.from(value);
     if (vals.length !== f.count) throw new Error(`uniform ${name} expects ${f.count} values`);
@@ -541,6 +544,44 @@ class Volxel3DDicomRenderer {
   /** the last light grid built: node transmittances, x fastest */
   readShadowGrid() { return native.readShadowGrid(this.ctx); }
   resetCounters() { native.resetCounters(this.ctx); }
+
+  /** index-space planes through voxel centres, one pixel per voxel (Python: volxel_amd.mpr); patient orientation is not
+   *  modelled.  Each returns a slice spec for slice(). */
+  sliceExtent() {
+    if (!this.volume) throw new Error('Trying to slice without a volume.');
+    return this.volume.grid.indexExtent;
+  }
+  axial(k) { const e = this.sliceExtent(); return sliceSpec('k', k, e[2], [0, 0, k], [1, 0, 0], [0, 1, 0], [0, 0, 1], [e[0], e[1]]); }
+  coronal(j) { const e = this.sliceExtent(); return sliceSpec('j', j, e[1], [0, j, 0], [1, 0, 0], [0, 0, 1], [0, 1, 0], [e[0], e[2]]); }
+  sagittal(i) { const e = this.sliceExtent(); return sliceSpec('i', i, e[0], [i, 0, 0], [0, 1, 0], [0, 0, 1], [1, 0, 0], [e[1], e[2]]); }
+  /** vx_slice: { origin, du, dv, dn (cell frame), size: [W, H], slabSamples = 1, reduce = 'mean' | 'max' | 'min',
+   *  display = null | 'grey' | 'tf', window = [black, white] (grey only) } -> { values: Float32Array (W*H, row 0 = y = 0),
+   *  rgba8: Uint8Array (W*H*4) | null }.  Binds the current uniforms first. */
+  slice({ origin, du, dv, dn, size, slabSamples = 1, reduce = 'mean', display = null, window = null }) {
+    if (!(reduce in SliceReduce)) throw new Error(`slice: reduce must be 'mean', 'max' or 'min', not ${reduce}`);
+    if (display !== null && !(display in SliceDisplay)) throw new Error(`slice: display must be null, 'grey' or 'tf', not ${display}`);
+    if (display === 'grey' && !(window && window.length === 2 && Math.fround(window[1]) > Math.fround(window[0])))
+      throw new Error('slice: display grey needs window = [black, white] with black < white');
+    if (display !== 'grey' && window !== null) throw new Error('slice: window applies to display grey only');
+    const [W, H] = size;
+    if (!(W >= 1 && W <= 16384 && H >= 1 && H <= 16384)) throw new Error(`slice: size must be 1 .. 16384 per side, not ${W} x ${H}`);
+    const p = new ParamsBlock(SLICE_LAYOUT);
+    p.set('origin', origin); p.set('du', du); p.set('dv', dv); p.set('dn', dn);
+    p.set('size', [W, H]); p.set('slab_samples', slabSamples);
+    p.set('reduce', SliceReduce[reduce]); p.set('display', display === null ? 0 : SliceDisplay[display]);
+    p.set('window', display === 'grey' ? window : [0, 1]);
+    this.bindUniforms();
+    const values = new Float32Array(W * H), rgba8 = display === null ? null : new Uint8Array(W * H * 4);
+    native.slice(this.ctx, p.buffer, values, rgba8);
+    return { values, rgba8 };
+  }
+  /** the last slice: W*H*N samples and its kernel time (vx_slice_stats) */
+  sliceStats() { return native.sliceStats(this.ctx); }
+}
+
+function sliceSpec(name, i, n, origin, du, dv, dn, size) {
+  if (!Number.isInteger(i) || i < 0 || i >= n) throw new Error(`${name} must be a voxel index in [0, ${n}), not ${i}`);
+  return { origin, du, dv, dn, size, slabSamples: 1 };
 }
 
 module.exports = { Volxel3DDicomRenderer, Environment, VolxelRenderMode: RenderMode, generateTransferFunction, Camera, native,

@@ -496,6 +496,64 @@ static napi_value n_read_shadow_grid(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* optional typed array argument: undefined / null -> *data = NULL */
+static int typed_or_null(napi_env env, napi_value v, napi_typedarray_type want, void** data, size_t* len) {
+  napi_valuetype t;
+  if (napi_typeof(env, v, &t) != napi_ok) return 0;
+  *data = NULL;
+  *len = 0;
+  if (t == napi_undefined || t == napi_null) return 1;
+  return typed(env, v, want, data, len);
+}
+
+/* slice(ctx, ArrayBuffer holding one VxSliceParams, Float32Array | null values, Uint8Array | null rgba8) (vx_slice) */
+static napi_value n_slice(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* d;
+  size_t n;
+  NAPI_OK(napi_get_arraybuffer_info(env, a[1], &d, &n));
+  if (n != sizeof(VxSliceParams)) return throw_msg(env, "slice: buffer is not sizeof(VxSliceParams)");
+  VxSliceParams sp;
+  memcpy(&sp, d, sizeof sp);
+  void *vals, *rgba;
+  size_t nv, nr;
+  if (!typed_or_null(env, a[2], napi_float32_array, &vals, &nv)) return NULL;
+  if (!typed_or_null(env, a[3], napi_uint8_array, &rgba, &nr)) return NULL;
+  const size_t px = (size_t)sp.size[0] * sp.size[1];
+  if (vals && nv < px) return throw_msg(env, "slice: values shorter than size[0]*size[1] floats");
+  if (rgba && nr < px * 4) return throw_msg(env, "slice: rgba8 shorter than size[0]*size[1]*4 bytes");
+  if (vx_slice(c, &sp, (float*)vals, (uint8_t*)rgba) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+
+static napi_value n_sizeof_slice_params(napi_env env, napi_callback_info info) {
+  (void)info;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, (uint32_t)sizeof(VxSliceParams), &v));
+  return v;
+}
+
+/* sliceStats(ctx) -> { samples, lastKernelMs } (vx_slice_stats) */
+static napi_value n_slice_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint64_t samples = 0;
+  double ms = 0.0;
+  if (vx_slice_stats(c, &samples, &ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o, v;
+  NAPI_OK(napi_create_object(env, &o));
+  NAPI_OK(napi_create_double(env, (double)samples, &v));
+  NAPI_OK(napi_set_named_property(env, o, "samples", v));
+  NAPI_OK(napi_create_double(env, ms, &v));
+  NAPI_OK(napi_set_named_property(env, o, "lastKernelMs", v));
+  return o;
+}
+
 static napi_value n_reset_counters(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (!get_args(env, info, 1, a)) return NULL;
@@ -661,6 +719,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"readAccum", n_read_accum}, {"readDisplay", n_read_display},
       {"readDisplayScaled", n_read_display_scaled}, {"getCounters", n_get_counters},
       {"resetCounters", n_reset_counters}, {"shadowStats", n_shadow_stats}, {"readShadowGrid", n_read_shadow_grid},
+      {"slice", n_slice}, {"sliceStats", n_slice_stats}, {"sizeofSliceParams", n_sizeof_slice_params},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {

@@ -579,6 +579,48 @@ class Volxel3DRenderer:
         self._check(self._lib.vx_debug_read_shadow_grid(self._ctx, out.ctypes.data, dims))
         return out
 
+    def slice(self, sp, reduce: str = "mean", display: str | None = None, window=None):
+        """A slice or thick slab of the volume (vx_slice; planes from volxel_amd.mpr).  reduce: "mean", "max" or "min" over the
+        sp.slab_samples samples; display: None, "grey" (window = (value shown black, value shown white)) or "tf" (the transfer
+        function, premultiplied by its alpha).  Binds the current uniforms first (the densities use their density scale).
+        Returns the (H, W) float32 values, row 0 = y = 0, or (values, the (H, W, 4) uint8 display) when a display is asked."""
+        if not isinstance(sp, _abi.VxSliceParams):
+            raise TypeError("sp must be a VxSliceParams (volxel_amd.mpr builds them)")
+        if reduce not in _abi.SLICE_REDUCE:
+            raise ValueError(f"reduce must be one of {sorted(_abi.SLICE_REDUCE)}, not {reduce!r}")
+        if display not in _abi.SLICE_DISPLAY:
+            raise ValueError(f"display must be None, 'grey' or 'tf', not {display!r}")
+        q = _abi.VxSliceParams.from_buffer_copy(sp)
+        W, H, N = int(q.size[0]), int(q.size[1]), int(q.slab_samples)
+        if not (1 <= W <= _abi.SLICE_MAX_SIZE and 1 <= H <= _abi.SLICE_MAX_SIZE):
+            raise ValueError(f"slice size must be 1 .. {_abi.SLICE_MAX_SIZE} per side, not {W} x {H}")
+        if not 1 <= N <= _abi.SLICE_MAX_SAMPLES:
+            raise ValueError(f"slab_samples must be 1 .. {_abi.SLICE_MAX_SAMPLES}, not {N}")
+        for name in ("origin", "du", "dv", "dn"):
+            if not np.isfinite(np.asarray(getattr(q, name)[:], dtype=np.float32)).all():
+                raise ValueError(f"slice {name} must be finite")
+        if display == "grey":
+            w = np.asarray(window if window is not None else (), dtype=np.float64).reshape(-1)
+            if w.size != 2 or not np.isfinite(w.astype(np.float32)).all() or not np.float32(w[1]) > np.float32(w[0]):
+                raise ValueError(f"display 'grey' needs window = (black, white) with black < white, not {window!r}")
+            q.window[0], q.window[1] = float(w[0]), float(w[1])
+        elif window is not None:
+            raise ValueError("window applies to display 'grey' only")
+        q.reduce = _abi.SLICE_REDUCE[reduce]
+        q.display = _abi.SLICE_DISPLAY[display]
+        self.bind_uniforms()
+        values = np.empty((H, W), dtype=np.float32)
+        rgba = np.empty((H, W, 4), dtype=np.uint8) if display is not None else None
+        self._check(self._lib.vx_slice(self._ctx, C.byref(q), values.ctypes.data,
+                                       rgba.ctypes.data if rgba is not None else None))
+        return values if rgba is None else (values, rgba)
+
+    def slice_stats(self):
+        """(samples, kernel_ms) of the last slice: W * H * slab_samples and its HIP-event time"""
+        n, ms = C.c_uint64(), C.c_double()
+        self._check(self._lib.vx_slice_stats(self._ctx, C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
     def probe_gather_rate(self, lines: int, distinct: int | None = None):
         """clocks per 16-byte-per-lane gather instruction per CU (nominal clock) when the 64 lanes form `lines` groups of
         consecutive lanes, each inside one L1-resident line, using `distinct` (default: lines) different lines; and the
