@@ -28,52 +28,29 @@ LIGHT = np.array([-1.0, -1.0, -1.0]) / math.sqrt(3.0)
 
 
 def _scene(oracle, mode, **kw):
-    from tests.common import make_scene
-    vox = np.full((32, 32, 32), 2000, dtype=np.uint16)
-    vox[31, 31, 31] = 4000                       # max of the stack: the rest normalises to exactly 1/2
-    g = oracle.BrickGrid(vox, (1.0, 1.0, 1.0))
+    from tests.closed_form import homogeneous_grid, make_pin_scene
+    g = homogeneous_grid(oracle)                 # 32^3 of 1/2 (one brighter voxel in a far corner fixes the normalisation)
     tf = np.tile(np.array([*COLOUR, ALPHA], dtype=np.float32), (16, 1)).reshape(-1)
-    s, cam, vol, ds, p = make_scene(g, W, H, mode, cam_pos=tuple(EYE), look_at=tuple(LOOK),
-                                    clip_min=(CLIP_LO,) * 3, clip_max=(CLIP_HI,) * 3, show_environment=False,
-                                    use_env=False, light_dir=tuple(LIGHT), **kw)
+    s, cam, vol, ds, p = make_pin_scene(g, W, H, mode, EYE, LOOK, (CLIP_LO,) * 3, (CLIP_HI,) * 3, LIGHT, **kw)
     return g, tf, 16, p
 
 
 def _rays(sub=1):
-    """world-space camera rays through the pixel grid (closed form); sub x sub positions per pixel covering the
-    support of the reference's jitter (+-1 pixel, triangular weights, fragment.frag:146)"""
-    aspect, th = W / H, math.tan(math.pi / 6.0)                      # fovy = pi / 3 (scene.ts:55)
-    z = (EYE - LOOK) / np.linalg.norm(EYE - LOOK)
-    x = np.cross([0.0, 1.0, 0.0], z); x /= np.linalg.norm(x)
-    y = np.cross(z, x)
-    offs = np.array([0.0]) if sub == 1 else (np.arange(sub) + 0.5) / sub * 2.0 - 1.0     # in pixels
-    wts = np.array([1.0]) if sub == 1 else (1.0 - np.abs(offs))
-    wts = wts / wts.sum()
-    py, px = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    dirs, weights = [], []
-    for oy, wy in zip(offs, wts):
-        for ox, wx in zip(offs, wts):
-            nx = ((px + 0.5 + ox) / W) * 2.0 - 1.0
-            ny = ((py + 0.5 + oy) / H) * 2.0 - 1.0
-            d = x[None, None, :] * (nx * aspect * th)[..., None] + y[None, None, :] * (ny * th)[..., None] - z[None, None, :]
-            dirs.append(d / np.linalg.norm(d, axis=-1, keepdims=True))
-            weights.append(wx * wy)
-    return dirs, weights
+    """world-space camera rays through the pixel grid (closed form, tests/closed_form.py); sub x sub positions per pixel
+    covering the support of the reference's jitter"""
+    from tests.closed_form import camera_rays
+    return camera_rays(EYE, LOOK, W, H, sub)
 
 
 def _box():
     """the clipped box in world space: index -> world is (i - 32) / 64 per axis (padded extent 64, spacing 1)"""
-    lo = (np.array([CLIP_LO] * 3) * 64.0 - 32.0) / 64.0
-    hi = (np.array([CLIP_HI] * 3) * 64.0 - 32.0) / 64.0
-    return lo, hi
+    from tests.closed_form import world_box
+    return world_box((64, 64, 64), (1.0, 1.0, 1.0), (CLIP_LO,) * 3, (CLIP_HI,) * 3)
 
 
 def _slab(o, d, lo, hi):
-    with np.errstate(divide="ignore", invalid="ignore"):
-        t0, t1 = (lo - o) / d, (hi - o) / d
-    near = np.maximum(0.0, np.minimum(t0, t1).max(axis=-1))
-    far = np.maximum(t0, t1).min(axis=-1)
-    return near, far
+    from tests.closed_form import slab
+    return slab(o, d, lo, hi)
 
 
 SIGMA = 64.0 * ALPHA            # extinction per world unit: u_volume_maj (= density scale 64) * alpha (viewer.ts:1322)
