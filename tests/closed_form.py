@@ -10,7 +10,9 @@ FOVY = math.pi / 3.0                    # scene.ts:55
 
 
 def homogeneous_grid(oracle, n=32, spacing=(1.0, 1.0, 1.0)):
-    """an n^3 stack of constant value with one brighter voxel in the far corner: every other voxel normalises to exactly 1/2"""
+    """an n^3 stack of constant value with one brighter voxel in the far corner: every other voxel normalises to exactly 1/2
+    and decodes to it, except in the brick of the brighter voxel: its u8 codes span [0, 1] (the brick's dilated window reaches the
+    zero padding), and 1/2 decodes to 128/255 there"""
     vox = np.full((n, n, n), 2000, dtype=np.uint16)
     vox[n - 1, n - 1, n - 1] = 4000
     return oracle.BrickGrid(vox, tuple(spacing))
@@ -149,3 +151,66 @@ def neighbour_steps(dec, lo=None, hi=None):
     lo, hi = np.clip(lo, 0, np.array(pad.shape[::-1])), np.clip(hi, 0, np.array(pad.shape[::-1]))
     blk = pad[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
     return np.array([np.abs(np.diff(blk, axis=a)).max() if blk.shape[a] > 1 else 0.0 for a in (2, 1, 0)])
+
+
+def ortho_rays(eye, look, width, height, half_height, near=0.1):
+    """world-space rays of the orthographic camera (scene.ortho, near plane 0.1): each pixel centre's point on the near plane,
+    all running along the camera's -z.  Returns (origins (H, W, 3), dirs (H, W, 3))"""
+    x, y, z = camera_basis(eye, look)
+    aspect = width / height
+    py, px = np.meshgrid(np.arange(height), np.arange(width), indexing="ij")
+    nx = ((px + 0.5) / width) * 2.0 - 1.0
+    ny = ((py + 0.5) / height) * 2.0 - 1.0
+    o = (np.asarray(eye, float) + x * (nx * aspect * half_height)[..., None] + y * (ny * half_height)[..., None]
+         - z * near)
+    return o, np.broadcast_to(-z, o.shape).copy()
+
+
+def march_samples(o, d, lo, hi, ipw, step, max_steps, start=0.5):
+    """the DVR march contract in float64: dt = step / |d * ipw| world units, t0 = near + start dt,
+    n = min(ceil((far - t0) / dt), max_steps) samples (none unless the quotient is positive) at t0 + k dt.  Returns
+    (dt, quotient (far - t0) / dt, n, valid (..., N), world positions (..., N, 3))"""
+    o, d = np.broadcast_arrays(np.asarray(o, float), np.asarray(d, float))
+    near, far = slab(o, d, lo, hi)
+    dt = step / np.linalg.norm(d * np.asarray(ipw, float), axis=-1)
+    t0 = near + start * dt
+    x = (far - t0) / dt
+    n = np.where(x > 0, np.minimum(np.ceil(np.where(x > 0, x, 0.0)), max_steps), 0).astype(np.int64)
+    k = np.arange(max(int(n.max()), 1))
+    valid = k < n[..., None]
+    t = t0[..., None] + k * dt[..., None]
+    return dt, x, n, valid, o[..., None, :] + t[..., None] * d[..., None, :]
+
+
+def central_differences(dec, q):
+    """(T(q), D) at cell-frame positions q (..., 3): T the float64 trilinear of dec and D[..., i] = T(c + e_i) - T(c - e_i),
+    the trilinear of the cells one voxel either side along axis i with the sample's own fractions"""
+    q = np.asarray(q, float)
+    T = trilinear(dec, q[..., 0], q[..., 1], q[..., 2])
+    D = []
+    for a in range(3):
+        e = np.zeros(3)
+        e[a] = 1.0
+        D.append(trilinear(dec, *np.moveaxis(q + e, -1, 0)) - trilinear(dec, *np.moveaxis(q - e, -1, 0)))
+    return T, np.stack(D, axis=-1)
+
+
+def blinn_phong(colour, n, light, h, ka, kd, ks, shininess):
+    """Blinn-Phong of a TF colour (..., 3) with unit normals n (..., 3): colour (ka + kd max(0, n.l)) + ks max(0, n.h)^s,
+    l = -light (the direction toward the light), h the half vector; spec is white, 0^0 = 1"""
+    ndl = np.maximum(0.0, (n * -np.asarray(light, float)).sum(axis=-1))
+    ndh = np.maximum(0.0, (n * h).sum(axis=-1))
+    spec = ks * (np.ones_like(ndh) if shininess == 0 else ndh ** shininess)
+    return colour * (ka + kd * ndl)[..., None] + spec[..., None]
+
+
+def half_vector(light, d):
+    """Blinn's h = normalize(l + v), l = -light toward the light, v = -d toward the eye"""
+    h = -np.asarray(light, float) - np.asarray(d, float)
+    return h / np.linalg.norm(h, axis=-1, keepdims=True)
+
+
+def directional_environment(d, light, strength=1.0):
+    """the background of the directional light without an environment map: strength (clamp(max(0, d.l)^300) 4 + 0.01)"""
+    c = np.maximum(0.0, (np.asarray(d, float) * -np.asarray(light, float)).sum(axis=-1))
+    return strength * (np.clip(c ** 300, 0.0, 1.0) * 4.0 + 0.01)

@@ -131,13 +131,16 @@ def test_oracle_single_scatter_expectation(oracle, mode):
 
 @pytest.mark.gpu
 def test_hip_dvr_is_beer_lambert(oracle):
+    """every layout (4: the opt-in u8 bricks) against Beer-Lambert.  (dvr_phong is not dvr here: the brick of the brighter
+    corner voxel decodes its other voxels to 128/255, inside the gradient taps of the far corner of the clip box; the flat-field
+    Phong == DVR pin is tests/test_phong_pins.py, whose clip box keeps the taps clear of that brick)"""
     from volxel_amd import Volxel3DRenderer
     import ctypes as C
     g, tf, L, p = _scene(oracle, "dvr", dvr_step_voxels=0.125)
     want, _ = expected_dvr()
     dt = 0.125 / 64.0
     tol = (0.9 * F_P * LE) * COLOUR.max() * (SIGMA * dt * 0.5 + 2e-4) + 1e-6
-    for layout in (0, 1, 2):
+    for layout in (0, 1, 2, 4):
         r = Volxel3DRenderer(W, H, layout=layout)
         r.setup_from_grid(g)
         r.change_transfer_func(tf, L)

@@ -727,11 +727,7 @@ EDGE_CASES = {
 }
 
 
-@pytest.mark.parametrize("case", sorted(EDGE_CASES))
-def test_edge_cases_match_oracle(oracle, case):
-    """ragged image sizes, degenerate clip boxes / ranges / step sizes / LUT lengths, camera inside the
-    volume, on a ragged (40x24x11 -> 64^3 padded) anisotropic volume: DVR == oracle with equal sample
-    counts for all three layouts, one stochastic mode agrees"""
+def _edge_case_scene(oracle, case, mode):
     from tests.common import make_scene, benchmark_tf, BENCH_CAM
     (w, h), kw, tf_len = EDGE_CASES[case]
     rng = np.random.default_rng(17)
@@ -748,7 +744,18 @@ def test_edge_cases_match_oracle(oracle, case):
     for k, v in BENCH_CAM.items():
         kw.setdefault(k, v)
     kw.setdefault("sample_range", (0.05, 1.0))
-    s, cam, vol, ds, p = make_scene(g, w, h, "dvr", **kw)
+    s, cam, vol, ds, p = make_scene(g, w, h, mode, **kw)
+    return g, tf, L, kw, p
+
+
+@pytest.mark.parametrize("case", sorted(EDGE_CASES))
+def test_edge_cases_match_oracle(oracle, case):
+    """ragged image sizes, degenerate clip boxes / ranges / step sizes / LUT lengths, camera inside the
+    volume, on a ragged (40x24x11 -> 64^3 padded) anisotropic volume: DVR == oracle with equal sample
+    counts for all three layouts, one stochastic mode agrees"""
+    from tests.common import make_scene
+    (w, h), _, _ = EDGE_CASES[case]
+    g, tf, L, kw, p = _edge_case_scene(oracle, case, "dvr")
     want, oc = oracle.render(p, g, tf, L)
     for layout in (0, 1, 2, 4):
         r = _renderer(g, tf, L, p, layout)
@@ -765,6 +772,27 @@ def test_edge_cases_match_oracle(oracle, case):
     diff = np.abs(img - want).max(axis=2)
     assert (diff <= 1e-4).mean() >= 0.999, (case, diff.max())
     assert r.counters().rays == oc.rays
+
+
+@pytest.mark.parametrize("case", sorted(EDGE_CASES))
+def test_edge_cases_phong_match_oracle(oracle, case):
+    """the edge cases of test_edge_cases_match_oracle in dvr_phong, on every layout (the LDS-window Phong kernel stages a
+    12 x 10 x 10 window and reads +-1 voxel around every shaded sample; the generic kernel serves the reference and cellquad
+    layouts, a TF past the LDS-resident LUT and ERT thresholds <= 0): the goldens' Phong tolerance, 1e-5 (the Blinn terms on
+    the hardware's 1-ulp rsq / log2 / exp2 against libm), and every counter exact"""
+    (w, h), _, _ = EDGE_CASES[case]
+    g, tf, L, kw, p = _edge_case_scene(oracle, case, "dvr_phong")
+    want, oc = oracle.render(p, g, tf, L)
+    for layout in (0, 1, 2, 4):
+        r = _renderer(g, tf, L, p, layout)
+        r.reset_counters()
+        img = _render_with_params(r, p)
+        c = r.counters()
+        r.close()
+        assert img.shape == (h, w, 4)
+        assert np.abs(img - want).max() <= 1e-5, (case, layout, float(np.abs(img - want).max()))
+        assert (c.samples, c.rays, c.pixels, c.tf_samples, c.grad_samples) == \
+            (oc.samples, oc.rays, w * h, oc.tf_samples, oc.grad_samples), (case, layout)
 
 
 def test_upload_from_native_grid_handle(oracle):
