@@ -338,8 +338,8 @@ int vx_get_counters(VxContext* ctx, VxCounters* out);
 int vx_reset_counters(VxContext* ctx);
 
 /* library / device facts for logs (viewer.ts:225-242 device record).  group: member 0 (the display device).
- * The test and measurement hooks below (vx_debug_*, vx_probe_*) and the slices (vx_slice, vx_slice_stats) also run on
- * member 0 of a group. */
+ * The test and measurement hooks below (vx_debug_*, vx_probe_*), the slices (vx_slice, vx_slice_stats) and the isosurfaces
+ * (vx_isosurface, vx_iso_stats) also run on member 0 of a group. */
 int vx_device_info(VxContext* ctx, char* name_out, uint32_t name_cap, uint32_t* cu_count,
                    uint64_t* hbm_bytes);
 const char* vx_version(void);
@@ -423,6 +423,46 @@ int vx_slice(VxContext* ctx, const VxSliceParams* sp, float* values_out, uint8_t
 /* the last slice: its samples (W*H*N) and the HIP-event time of its kernel; both 0 before the first slice.  Any out pointer
  * may be NULL.  group: member 0. */
 int vx_slice_stats(VxContext* ctx, uint64_t* samples, double* last_kernel_ms);
+
+/* ---- isosurfaces: the first hit of a density threshold and per-pixel picking (no reference counterpart; DESIGN.md section 2
+ * "Isosurfaces").  Rays and samples are DVR's, from the last vx_set_params (camera, ortho flag, clip box,
+ * density_transform_inv, dvr_step_voxels, dvr_max_steps, volume_density_scale, volume_inv_maj), always with the pixel-centre
+ * ray and start offset 1/2: dvr_jitter, the shard fields, render_mode and debug_hits have no effect.  Sample k of a ray's n sits
+ * at q_k = fma(k, dq, q0) (the march contract) and has d_k = trilinear(q_k) * volume_inv_maj.
+ *   hit:     the first k < n with d_k >= iso.  k = 0 is a cap (the ray enters the clip box inside the surface): s* = 0.  Otherwise
+ *            `refine` bisection steps on the fp32 sample parameter: lo = k - 1, hi = k; mid = 0.5f * (lo + hi), d at
+ *            fma(mid, dq, q0); d >= iso ? hi = mid : lo = mid; s* = hi.  n = 0, or no d_k >= iso: a miss.
+ *   hit_out: (w_x, w_y, w_z, t), t = fma(s*, dt, t0) the world ray parameter (>= 0) and w = fma(t, d, o) per axis;
+ *            a miss is (0, 0, 0, -1).
+ *   rgba_out: Blinn-Phong on color with alpha 1, n = -g/|g| from Phong's central difference at q(s*) in its own cell frame
+ *            scaled by the diagonal of density_transform_inv (Frame::dvr<PHONG>); a cap or |g|^2 <= 1e-12 takes n = -ray
+ *            direction.  c = color * fma(kd, max(0, n.l), ka) + ks * max(0, n.h)^shininess, l = -light_dir, h as Phong's.
+ *            A miss is (0, 0, 0, 0).
+ * Hit flags, k, s*, t, w and the counters are exact on every layout, with skipping on or off; the normal and the colour use the
+ * hardware rsq / log2 / exp2 as Phong does (tolerance 1e-5).  skip = 1: a sample whose macro cell has an upper density bound
+ * (the intensity projections' table) below iso cannot be a hit; it is passed over, counted in `skipped`, not in `samples`. */
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxIsoParams {
+  float iso;               /* threshold on d = trilinear(q) * volume_inv_maj, the value DVR hands to the TF  */
+  float color[3];          /* surface albedo                                                                 */
+  float ka, kd, ks, shininess;
+  uint32_t refine;         /* bisection steps, 0 .. 16                                                       */
+  int32_t skip;            /* 0 / 1: range skipping                                                          */
+  uint32_t window[4];      /* x0, y0, x1, y1 of the render size, x0 <= x < x1; all zero = the whole image    */
+} VxIsoParams;
+/* One isosurface image of the window on the context's stream, behind every render already queued; synchronises.  rgba_out and
+ * hit_out: 4 floats per window pixel, row-major, row 0 = y0; either may be NULL.  The accumulator, the frame state, VxCounters,
+ * the light grid and VxParams are not touched; the output buffers (8 floats per window pixel) stay with the context and grow
+ * with the largest window.  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the field, before vx_set_params, for NULL
+ * ip, a non-finite iso, color or Phong term, shininess < 0, refine > 16, skip not 0 / 1, an empty window or one outside the
+ * render size, and params set for another mode that fail DVR's march checks (dvr_step_voxels > 0, dvr_max_steps in [0, 2^24]).
+ * group: member 0 (the display device), like the slices. */
+int vx_isosurface(VxContext* ctx, const VxIsoParams* ip, float* rgba_out, float* hit_out);
+/* the last isosurface: rays that hit the clip box, hits, march samples evaluated, bisection samples (refine x hits that are
+ * not caps), samples passed over by range skipping, and the HIP-event time of its kernel; all 0 before the first call.  Per ray
+ * samples + skipped = k + 1 for a hit, n for a miss.  Any out pointer may be NULL.  group: member 0. */
+int vx_iso_stats(VxContext* ctx, uint64_t* rays, uint64_t* hits, uint64_t* samples, uint64_t* refine_samples,
+                 uint64_t* skipped, double* last_kernel_ms);
 
 /* test hook (no reference counterpart): the device's R8-unorm decode table, 256 floats */
 int vx_debug_unorm_table(VxContext* ctx, float* out256);

@@ -48,6 +48,7 @@ def struct_from_header(header: str, name: str):
 VxParams = struct_from_header("volxel_hip.h", "VxParams")
 VxCounters = struct_from_header("volxel_hip.h", "VxCounters")
 VxSliceParams = struct_from_header("volxel_hip.h", "VxSliceParams")
+VxIsoParams = struct_from_header("volxel_hip.h", "VxIsoParams")
 
 MODE_DEFAULT, MODE_NO_DDA, MODE_RAYMARCH, MODE_DVR, MODE_DVR_PHONG, MODE_MIP, MODE_MINIP = range(7)
 LAYOUT_REFERENCE, LAYOUT_CELLQUAD, LAYOUT_BRICKF32, LAYOUT_AUTO = 0, 1, 2, 3
@@ -59,6 +60,7 @@ SLICE_NONE, SLICE_GREY, SLICE_TF = range(3)            # enum VxSliceDisplay
 SLICE_REDUCE = {"mean": SLICE_MEAN, "max": SLICE_MAX, "min": SLICE_MIN}
 SLICE_DISPLAY = {None: SLICE_NONE, "grey": SLICE_GREY, "tf": SLICE_TF}
 SLICE_MAX_SIZE, SLICE_MAX_SAMPLES = 16384, 4096
+ISO_MAX_REFINE = 16
 
 
 def declared_symbols(header: str):
@@ -138,6 +140,8 @@ def load_library():
         "vx_debug_read_shadow_grid": ([vp, vp, P(u32)], i32),
         "vx_slice": ([vp, P(VxSliceParams), vp, vp], i32),
         "vx_slice_stats": ([vp, P(u64), P(C.c_double)], i32),
+        "vx_isosurface": ([vp, P(VxIsoParams), vp, vp], i32),
+        "vx_iso_stats": ([vp, P(u64), P(u64), P(u64), P(u64), P(u64), P(C.c_double)], i32),
         # preprocessor
         "vxb_build_from_u16": ([vp, P(u32), P(C.c_float), C.c_uint16, i32, P(vp)], i32),
         "vxb_read_dicoms_to_grid": ([P(vp), P(u64), u32, i32, P(vp)], i32),

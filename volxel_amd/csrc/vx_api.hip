@@ -19,6 +19,7 @@
 #include "vx_shadow.hpp"
 #include "vx_projection.hpp"
 #include "vx_slice.hpp"
+#include "vx_iso.hpp"
 
 using namespace vx;
 
@@ -55,6 +56,7 @@ std::array<uint32_t, (sizeof(T) + ...) / 4> key_of(const T&... v) {
 }
 auto skip_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.sample_range); }
 auto proj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.render_mode); }
+auto iso_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj); }
 auto lmaj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.volume_maj, p.sample_range); }
 auto shadow_key(const VxParams& p) {
   return key_of(p.light_dir, p.density_transform_inv, p.volume_aabb_min, p.volume_aabb_max, p.volume_maj, p.volume_inv_maj,
@@ -185,6 +187,18 @@ struct VxContext {
   hipEvent_t slice_ev[2] = {nullptr, nullptr};
   uint64_t slice_samples = 0;
   double slice_ms = 0.0;
+  // isosurfaces (vx_isosurface): the output buffers, grown to the largest window; the upper density bounds of range skipping
+  // (its own copy of the projections' table, so that MIP's bookkeeping is never disturbed); the counts of the last call
+  float4* iso_rgba = nullptr;
+  float4* iso_hit = nullptr;
+  size_t iso_cap = 0;          // pixels of each buffer
+  float* iso_bound_dev = nullptr;
+  IsoBound iso_bound{};
+  DerivedTable<iso_key> iso_table;
+  unsigned long long* iso_count_dev = nullptr;   // ISO_NCOUNTS
+  hipEvent_t iso_ev[2] = {nullptr, nullptr};
+  uint64_t iso_counts[ISO_NCOUNTS] = {};
+  double iso_ms = 0.0;
 };
 
 static bool is_group(const VxContext* c) { return !c->members.empty(); }
@@ -220,7 +234,7 @@ static void free_volume(VxContext* c) {
   c->bu_alloc = c->bur_alloc = nullptr;
   c->dv = DevVolume{};
   c->has_volume = false;
-  c->skip_table.stale = c->proj_table.stale = c->lmaj_table.stale = c->shadow_table.stale = true;
+  c->skip_table.stale = c->proj_table.stale = c->lmaj_table.stale = c->shadow_table.stale = c->iso_table.stale = true;
   if (c->lmaj_dev) (void)hipFree(c->lmaj_dev);
   c->lmaj_dev = nullptr;
   if (c->shadow_dev) (void)hipFree(c->shadow_dev);
@@ -916,6 +930,47 @@ static void launch_slice(VxContext* c, const VxSliceParams& sp) {
   });
 }
 
+// ---- isosurfaces (vx_isosurface): the upper density bounds of range skipping and the launch --------------------------------
+// The projections' bound table (compute_projection_bounds, its widening argument included), upper bounds only, kept in a buffer
+// of its own: building it never marks, frees or replaces the table MIP / MinIP launches read (proj_table / proj_dev).
+static int rebuild_iso_bounds(VxContext* c) {
+  const VxParams& p = c->params;
+  c->iso_table.stale = true;   // until this build is complete
+  std::vector<float> lohi;
+  int level = 1;
+  uint32_t md[3];
+  compute_projection_bounds(p, c->range_host.data(), c->dv.bc, c->dv.extent, lohi, level, md);
+  const size_t n = lohi.size() / 2;
+  std::vector<float> hi(n);
+  for (size_t i = 0; i < n; ++i) hi[i] = lohi[2 * i + 1];
+  if (c->iso_bound_dev) (void)hipFree(c->iso_bound_dev);
+  c->iso_bound_dev = nullptr;
+  VX_HIP(c, hipMalloc(&c->iso_bound_dev, n * sizeof(float)));
+  VX_HIP(c, hipMemcpyAsync(c->iso_bound_dev, hi.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  IsoBound& b = c->iso_bound;
+  b.hi = c->iso_bound_dev;
+  b.sh = 3u + (uint32_t)level;
+  b.md0 = md[0];
+  b.md1 = md[1];
+  for (int a = 0; a < 3; ++a) b.cmax[a] = c->dv.extent[a] + 7u;
+  c->iso_table.built(p);
+  return VX_OK;
+}
+// launches iso_first_hit<the layout of slice_layout, ip.skip> over the window (x0, y0, ww, wh) on the context's stream
+static void launch_iso(VxContext* c, const VxIsoParams& ip, uint32_t ww, uint32_t wh) {
+  const dim3 grid((ww + 15u) / 16u, (wh + 15u) / 16u);
+  with_layout(slice_layout(c), [&](auto lay) {
+    constexpr int LAY = decltype(lay)::value;
+    if (ip.skip)
+      hipLaunchKernelGGL((iso_first_hit<LAY, true>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, c->iso_bound, c->iso_rgba,
+                         c->iso_hit, c->iso_count_dev);
+    else
+      hipLaunchKernelGGL((iso_first_hit<LAY, false>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, IsoBound{}, c->iso_rgba,
+                         c->iso_hit, c->iso_count_dev);
+  });
+}
+
 // ---- device groups (vx_create_group): the entry points fan out to the members, read member 0, or gather --------
 // a member's failure, reported on the group handle with the member's index and device
 static int member_fail(VxContext* g, size_t i, int rc) {
@@ -1164,6 +1219,12 @@ void vx_destroy(VxContext* c) {
   if (c->slice_values) (void)hipFree(c->slice_values);
   if (c->slice_rgba) (void)hipFree(c->slice_rgba);
   for (hipEvent_t e : c->slice_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->iso_rgba) (void)hipFree(c->iso_rgba);
+  if (c->iso_hit) (void)hipFree(c->iso_hit);
+  if (c->iso_bound_dev) (void)hipFree(c->iso_bound_dev);
+  if (c->iso_count_dev) (void)hipFree(c->iso_count_dev);
+  for (hipEvent_t e : c->iso_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1448,7 +1509,7 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
     c->dv.extent[i] = index_extent[i];
   }
   c->range_host.assign((const uint32_t*)range, (const uint32_t*)range + nb);
-  c->skip_table.stale = c->proj_table.stale = true;
+  c->skip_table.stale = c->proj_table.stale = c->iso_table.stale = true;
   c->order_builds_left = 2;
   uint32_t n_layers = 0;
   if ((rc = alloc_layout(c, n_layers))) { free_volume(c); return rc; }
@@ -2387,6 +2448,82 @@ int vx_slice_stats(VxContext* c, uint64_t* samples, double* last_kernel_ms) {
   if (is_group(c)) return on_member0(c, vx_slice_stats(c->members[0], samples, last_kernel_ms));
   if (samples) *samples = c->slice_samples;
   if (last_kernel_ms) *last_kernel_ms = c->slice_ms;
+  return VX_OK;
+}
+
+int vx_isosurface(VxContext* c, const VxIsoParams* ip, float* rgba_out, float* hit_out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_isosurface(c->members[0], ip, rgba_out, hit_out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_isosurface: no volume uploaded");
+  if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: vx_set_params first (the camera, clip box and march come from it)");
+  if (!ip) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: ip is NULL");
+  // the march of any render mode's params: the checks vx_set_params makes for the marching modes
+  if (!(c->params.dvr_step_voxels > 0.0f)) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: params.dvr_step_voxels must be > 0");
+  if (c->params.dvr_max_steps < 0 || c->params.dvr_max_steps > (1 << 24))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: params.dvr_max_steps %d outside [0, 2^24]", c->params.dvr_max_steps);
+  const struct { const char* name; float v; } terms[8] = {{"iso", ip->iso}, {"color[0]", ip->color[0]}, {"color[1]", ip->color[1]},
+                                                          {"color[2]", ip->color[2]}, {"ka", ip->ka}, {"kd", ip->kd},
+                                                          {"ks", ip->ks}, {"shininess", ip->shininess}};
+  for (const auto& e : terms)
+    if (!std::isfinite(e.v)) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: %s is not finite", e.name);
+  if (ip->shininess < 0.0f) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: shininess = %g < 0", (double)ip->shininess);
+  if (ip->refine > 16u) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: refine = %u outside 0 .. 16", ip->refine);
+  if (ip->skip != 0 && ip->skip != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: skip = %d is not 0 or 1", ip->skip);
+  const uint32_t W = (uint32_t)c->params.res[0], H = (uint32_t)c->params.res[1];
+  VxIsoParams q = *ip;
+  if (!q.window[0] && !q.window[1] && !q.window[2] && !q.window[3]) {
+    q.window[2] = W;
+    q.window[3] = H;
+  }
+  if (!(q.window[0] < q.window[2] && q.window[1] < q.window[3] && q.window[2] <= W && q.window[3] <= H))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: window (%u, %u, %u, %u) is empty or outside the render size %u x %u", q.window[0],
+            q.window[1], q.window[2], q.window[3], W, H);
+  const uint32_t ww = q.window[2] - q.window[0], wh = q.window[3] - q.window[1];
+  const size_t px = (size_t)ww * wh;
+  if (px > c->iso_cap) {   // (every earlier call has completed: vx_isosurface synchronises)
+    if (c->iso_rgba) (void)hipFree(c->iso_rgba);
+    if (c->iso_hit) (void)hipFree(c->iso_hit);
+    c->iso_rgba = c->iso_hit = nullptr;
+    c->iso_cap = 0;
+    VX_HIP(c, hipMalloc(&c->iso_rgba, px * sizeof(float4)));
+    VX_HIP(c, hipMalloc(&c->iso_hit, px * sizeof(float4)));
+    c->iso_cap = px;
+  }
+  if (q.skip && !c->iso_table.current(c->params)) {
+    const int rc = rebuild_iso_bounds(c);
+    if (rc) return rc;
+  }
+  if (!c->iso_count_dev) VX_HIP(c, hipMalloc(&c->iso_count_dev, ISO_NCOUNTS * sizeof(unsigned long long)));
+  for (hipEvent_t& e : c->iso_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  VX_HIP(c, hipMemsetAsync(c->iso_count_dev, 0, ISO_NCOUNTS * sizeof(unsigned long long), c->stream));
+  VX_HIP(c, hipEventRecord(c->iso_ev[0], c->stream));
+  launch_iso(c, q, ww, wh);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->iso_ev[1], c->stream));
+  uint64_t counts[ISO_NCOUNTS];
+  VX_HIP(c, hipMemcpyAsync(counts, c->iso_count_dev, sizeof counts, hipMemcpyDeviceToHost, c->stream));
+  if (rgba_out) VX_HIP(c, hipMemcpyAsync(rgba_out, c->iso_rgba, px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  if (hit_out) VX_HIP(c, hipMemcpyAsync(hit_out, c->iso_hit, px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  float ms = 0.0f;
+  VX_HIP(c, hipEventElapsedTime(&ms, c->iso_ev[0], c->iso_ev[1]));
+  memcpy(c->iso_counts, counts, sizeof counts);
+  c->iso_ms = ms;
+  return VX_OK;
+}
+
+int vx_iso_stats(VxContext* c, uint64_t* rays, uint64_t* hits, uint64_t* samples, uint64_t* refine_samples, uint64_t* skipped,
+                 double* last_kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_iso_stats(c->members[0], rays, hits, samples, refine_samples, skipped, last_kernel_ms));
+  if (rays) *rays = c->iso_counts[ISO_RAYS];
+  if (hits) *hits = c->iso_counts[ISO_HITS];
+  if (samples) *samples = c->iso_counts[ISO_SAMPLES];
+  if (refine_samples) *refine_samples = c->iso_counts[ISO_REFINE];
+  if (skipped) *skipped = c->iso_counts[ISO_SKIPPED];
+  if (last_kernel_ms) *last_kernel_ms = c->iso_ms;
   return VX_OK;
 }
 

@@ -88,6 +88,15 @@ export declare class Volxel3DDicomRenderer {
     { values: Float32Array; rgba8: Uint8Array | null };
   /** the last slice: W*H*N samples and its HIP-event kernel time */
   sliceStats(): { samples: number; lastKernelMs: number };
+  /** the shaded first-hit isosurface of density iso on the GPU (include/volxel_hip.h vx_isosurface): 4 floats per window pixel,
+   *  row 0 = y0; hit = (world x, y, z, t), (0, 0, 0, -1) on a miss.  window = [x0, y0, x1, y1] of the render size (GL rows) */
+  isosurface(iso: number, opts?: { color?: [number, number, number]; phong?: [number, number, number, number]; refine?: number;
+    skip?: boolean; window?: [number, number, number, number] | null }):
+    { rgba: Float32Array; hit: Float32Array; width: number; height: number };
+  /** the world point under pixel (x, y) (GL rows) on the isosurface iso, or null when the ray misses it */
+  pick(x: number, y: number, iso: number, opts?: { refine?: number }): [number, number, number] | null;
+  /** the last isosurface: rays, hits, march samples, bisection samples, samples passed over and its HIP-event kernel time */
+  isoStats(): { rays: number; hits: number; samples: number; refineSamples: number; skipped: number; lastKernelMs: number };
   dispose(): void;
 }
 /** viewer.ts:1455-1462: keeps the worker factory, returns the element-name -> class table ("volxel-3d-viewer") */

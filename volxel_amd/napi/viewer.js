@@ -38,6 +38,7 @@ function parseParamsLayout(name = 'VxParams', size = native.sizeofParams()) {
 }
 const LAYOUT = parseParamsLayout();
 const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams());
+const ISO_LAYOUT = parseParamsLayout('VxIsoParams', native.sizeofIsoParams());
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
 const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
@@ -577,6 +578,40 @@ class Volxel3DDicomRenderer {
   }
   /** the last slice: W*H*N samples and its kernel time (vx_slice_stats) */
   sliceStats() { return native.sliceStats(this.ctx); }
+
+  /** vx_isosurface: the shaded first hit of density iso.  opts: { color = [1, 1, 1], phong = settings.phong
+   *  ([ka, kd, ks, shininess]), refine = 8, skip = true, window = null ([x0, y0, x1, y1] of the render size, GL rows) }
+   *  -> { rgba, hit: Float32Array (4 floats per window pixel, row 0 = y0), width, height }; hit = (world x, y, z, t),
+   *  (0, 0, 0, -1) on a miss.  Binds the current uniforms first. */
+  isosurface(iso, { color = [1, 1, 1], phong = null, refine = 8, skip = true, window = null } = {}) {
+    const fin = (v, n) => Array.isArray(v) && v.length === n && v.every((x) => Number.isFinite(Math.fround(x)));
+    if (!Number.isFinite(Math.fround(iso))) throw new Error(`isosurface: iso must be finite, not ${iso}`);
+    if (!fin(color, 3)) throw new Error('isosurface: color must be three finite numbers');
+    const ph = phong === null ? this.settings.phong : phong;
+    if (!fin(ph, 4) || ph[3] < 0) throw new Error('isosurface: phong must be [ka, kd, ks, shininess], finite, shininess >= 0');
+    if (!Number.isInteger(refine) || refine < 0 || refine > 16) throw new Error(`isosurface: refine must be an integer 0 .. 16, not ${refine}`);
+    if (typeof skip !== 'boolean') throw new Error('isosurface: skip must be true or false');
+    this.bindUniforms();
+    const W = this.width, H = this.height;
+    const [x0, y0, x1, y1] = window === null ? [0, 0, W, H] : window;
+    if (![x0, y0, x1, y1].every(Number.isInteger) || !(x0 >= 0 && x0 < x1 && x1 <= W && y0 >= 0 && y0 < y1 && y1 <= H))
+      throw new Error(`isosurface: window ${window} is empty or outside the render size ${W} x ${H}`);
+    const p = new ParamsBlock(ISO_LAYOUT);
+    p.set('iso', iso); p.set('color', color);
+    p.set('ka', ph[0]); p.set('kd', ph[1]); p.set('ks', ph[2]); p.set('shininess', ph[3]);
+    p.set('refine', refine); p.set('skip', skip ? 1 : 0); p.set('window', [x0, y0, x1, y1]);
+    const n = (x1 - x0) * (y1 - y0);
+    const rgba = new Float32Array(4 * n), hit = new Float32Array(4 * n);
+    native.isosurface(this.ctx, p.buffer, rgba, hit);
+    return { rgba, hit, width: x1 - x0, height: y1 - y0 };
+  }
+  /** the world point [x, y, z] where the ray of pixel (x, y) (GL rows) first reaches density iso, or null on a miss */
+  pick(x, y, iso, { refine = 16 } = {}) {
+    const { hit } = this.isosurface(iso, { refine, window: [x, y, x + 1, y + 1] });
+    return hit[3] < 0 ? null : [hit[0], hit[1], hit[2]];
+  }
+  /** the last isosurface: rays, hits, samples, refineSamples, skipped and its kernel time (vx_iso_stats) */
+  isoStats() { return native.isoStats(this.ctx); }
 }
 
 function sliceSpec(name, i, n, origin, du, dv, dn, size) {

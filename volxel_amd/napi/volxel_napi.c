@@ -554,6 +554,60 @@ static napi_value n_slice_stats(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* isosurface(ctx, ArrayBuffer holding one VxIsoParams, Float32Array | null rgba, Float32Array | null hit) (vx_isosurface); the
+ * arrays hold 4 floats per pixel of the window (ip.window; all zero: the whole render size) */
+static napi_value n_isosurface(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* d;
+  size_t n;
+  NAPI_OK(napi_get_arraybuffer_info(env, a[1], &d, &n));
+  if (n != sizeof(VxIsoParams)) return throw_msg(env, "isosurface: buffer is not sizeof(VxIsoParams)");
+  VxIsoParams ip;
+  memcpy(&ip, d, sizeof ip);
+  void *rgba, *hit;
+  size_t nr, nh;
+  if (!typed_or_null(env, a[2], napi_float32_array, &rgba, &nr)) return NULL;
+  if (!typed_or_null(env, a[3], napi_float32_array, &hit, &nh)) return NULL;
+  if (ip.window[2] <= ip.window[0] || ip.window[3] <= ip.window[1])
+    return throw_msg(env, "isosurface: the host passes an explicit window (x0 < x1, y0 < y1)");
+  const size_t px = (size_t)(ip.window[2] - ip.window[0]) * (ip.window[3] - ip.window[1]);
+  if (rgba && nr < px * 4) return throw_msg(env, "isosurface: rgba shorter than 4 floats per window pixel");
+  if (hit && nh < px * 4) return throw_msg(env, "isosurface: hit shorter than 4 floats per window pixel");
+  if (vx_isosurface(c, &ip, (float*)rgba, (float*)hit) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+
+static napi_value n_sizeof_iso_params(napi_env env, napi_callback_info info) {
+  (void)info;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, (uint32_t)sizeof(VxIsoParams), &v));
+  return v;
+}
+
+/* isoStats(ctx) -> { rays, hits, samples, refineSamples, skipped, lastKernelMs } (vx_iso_stats) */
+static napi_value n_iso_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint64_t v6[5] = {0, 0, 0, 0, 0};
+  double ms = 0.0;
+  if (vx_iso_stats(c, &v6[0], &v6[1], &v6[2], &v6[3], &v6[4], &ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  static const char* names[5] = {"rays", "hits", "samples", "refineSamples", "skipped"};
+  napi_value o, v;
+  NAPI_OK(napi_create_object(env, &o));
+  for (int i = 0; i < 5; ++i) {
+    NAPI_OK(napi_create_double(env, (double)v6[i], &v));
+    NAPI_OK(napi_set_named_property(env, o, names[i], v));
+  }
+  NAPI_OK(napi_create_double(env, ms, &v));
+  NAPI_OK(napi_set_named_property(env, o, "lastKernelMs", v));
+  return o;
+}
+
 static napi_value n_reset_counters(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (!get_args(env, info, 1, a)) return NULL;
@@ -720,6 +774,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"readDisplayScaled", n_read_display_scaled}, {"getCounters", n_get_counters},
       {"resetCounters", n_reset_counters}, {"shadowStats", n_shadow_stats}, {"readShadowGrid", n_read_shadow_grid},
       {"slice", n_slice}, {"sliceStats", n_slice_stats}, {"sizeofSliceParams", n_sizeof_slice_params},
+      {"isosurface", n_isosurface}, {"isoStats", n_iso_stats}, {"sizeofIsoParams", n_sizeof_iso_params},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {

@@ -621,6 +621,65 @@ class Volxel3DRenderer:
         self._check(self._lib.vx_slice_stats(self._ctx, C.byref(n), C.byref(ms)))
         return n.value, ms.value
 
+    def isosurface(self, iso: float, color=(1.0, 1.0, 1.0), phong=None, refine: int = 8, skip: bool = True, window=None):
+        """The shaded first-hit isosurface d = iso of the current view (vx_isosurface, DESIGN.md section 2 "Isosurfaces"): DVR's
+        rays and samples, `refine` bisection steps, Blinn-Phong on `color` with phong = (ka, kd, ks, shininess) (default: the
+        settings' phong).  skip: range skipping (same bits).  window = (x0, y0, x1, y1) of the render size (x0 <= x < x1, GL rows:
+        y = 0 is the bottom row) or None for the whole image.  Binds the current uniforms first.  Returns (rgba, hit), both
+        (h, w, 4) float32 over the window, row 0 = y0: rgba alpha 1 on a hit and all 0 on a miss; hit = (world x, y, z, t) or
+        (0, 0, 0, -1) on a miss."""
+        q = _abi.VxIsoParams()
+        iso32 = np.float32(iso)
+        if not np.isfinite(iso32):
+            raise ValueError(f"iso must be finite, not {iso!r}")
+        col = np.asarray(color, dtype=np.float64).reshape(-1)
+        if col.size != 3 or not np.isfinite(col.astype(np.float32)).all():
+            raise ValueError(f"color must be three finite values, not {color!r}")
+        ph = np.asarray(self.settings.phong if phong is None else phong, dtype=np.float64).reshape(-1)
+        if ph.size != 4 or not np.isfinite(ph.astype(np.float32)).all():
+            raise ValueError(f"phong must be four finite values (ka, kd, ks, shininess), not {phong!r}")
+        if ph[3] < 0:
+            raise ValueError(f"shininess must be >= 0, not {ph[3]}")
+        if isinstance(refine, bool) or int(refine) != refine or not 0 <= int(refine) <= _abi.ISO_MAX_REFINE:
+            raise ValueError(f"refine must be an integer 0 .. {_abi.ISO_MAX_REFINE}, not {refine!r}")
+        if skip not in (True, False, 0, 1):
+            raise ValueError(f"skip must be True or False, not {skip!r}")
+        W, H = int(self.width), int(self.height)
+        if window is None:
+            x0, y0, x1, y1 = 0, 0, W, H
+        else:
+            w = tuple(window)
+            if len(w) != 4 or any(isinstance(a, bool) or int(a) != a for a in w):
+                raise ValueError(f"window must be four integers (x0, y0, x1, y1), not {window!r}")
+            x0, y0, x1, y1 = (int(a) for a in w)
+            if not (0 <= x0 < x1 <= W and 0 <= y0 < y1 <= H):
+                raise ValueError(f"window {window!r} is empty or outside the render size {W} x {H}")
+        q.iso = float(iso32)
+        q.color[0], q.color[1], q.color[2] = (float(a) for a in col)
+        q.ka, q.kd, q.ks, q.shininess = (float(a) for a in ph)
+        q.refine = int(refine)
+        q.skip = 1 if skip else 0
+        q.window[0], q.window[1], q.window[2], q.window[3] = x0, y0, x1, y1
+        self.bind_uniforms()
+        rgba = np.empty((y1 - y0, x1 - x0, 4), dtype=np.float32)
+        hit = np.empty((y1 - y0, x1 - x0, 4), dtype=np.float32)
+        self._check(self._lib.vx_isosurface(self._ctx, C.byref(q), rgba.ctypes.data, hit.ctypes.data))
+        return rgba, hit
+
+    def pick(self, x: int, y: int, iso: float, refine: int = 16):
+        """the world point (x, y, z) where the ray of pixel (x, y) (GL rows: y = 0 is the bottom row) first reaches density iso,
+        or None when it misses: a one-pixel isosurface window"""
+        _, hit = self.isosurface(iso, refine=refine, window=(x, y, x + 1, y + 1))
+        h = hit[0, 0]
+        return None if h[3] < 0 else tuple(float(a) for a in h[:3])
+
+    def iso_stats(self):
+        """(rays, hits, samples, refine_samples, skipped, kernel_ms) of the last isosurface"""
+        v = [C.c_uint64() for _ in range(5)]
+        ms = C.c_double()
+        self._check(self._lib.vx_iso_stats(self._ctx, *[C.byref(a) for a in v], C.byref(ms)))
+        return tuple(a.value for a in v) + (ms.value,)
+
     def probe_gather_rate(self, lines: int, distinct: int | None = None):
         """clocks per 16-byte-per-lane gather instruction per CU (nominal clock) when the 64 lanes form `lines` groups of
         consecutive lanes, each inside one L1-resident line, using `distinct` (default: lines) different lines; and the
