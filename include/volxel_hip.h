@@ -338,8 +338,8 @@ int vx_get_counters(VxContext* ctx, VxCounters* out);
 int vx_reset_counters(VxContext* ctx);
 
 /* library / device facts for logs (viewer.ts:225-242 device record).  group: member 0 (the display device).
- * The test and measurement hooks below (vx_debug_*, vx_probe_*), the slices (vx_slice, vx_slice_stats) and the isosurfaces
- * (vx_isosurface, vx_iso_stats) also run on member 0 of a group. */
+ * The test and measurement hooks below (vx_debug_*, vx_probe_*), the slices (vx_slice, vx_slice_stats) the isosurfaces
+ * (vx_isosurface, vx_iso_stats) and the segments (vx_segment and its siblings) also run on member 0 of a group. */
 int vx_device_info(VxContext* ctx, char* name_out, uint32_t name_cap, uint32_t* cu_count,
                    uint64_t* hbm_bytes);
 const char* vx_version(void);
@@ -463,6 +463,54 @@ int vx_isosurface(VxContext* ctx, const VxIsoParams* ip, float* rgba_out, float*
  * samples + skipped = k + 1 for a hit, n for a miss.  Any out pointer may be NULL.  group: member 0. */
 int vx_iso_stats(VxContext* ctx, uint64_t* rays, uint64_t* hits, uint64_t* samples, uint64_t* refine_samples,
                  uint64_t* skipped, double* last_kernel_ms);
+
+/* ---- segmentation: seeded region growing (no reference counterpart; DESIGN.md section 2 "Segmentation").  Voxel i = (x, y, z)
+ * of index_extent has density d(i) = (volume_density_scale * v(i)) * volume_inv_maj (two fp32 products, the last
+ * vx_set_params), bit for bit the trilinear density at q = i.  P(i) = lo <= d(i) <= hi and box_lo <= i <= box_hi per axis (the
+ * clip box does not apply).  The segment is the connected component of P holding the seed, 6- (faces) or 26-connected (faces,
+ * edges, corners); empty when P(seed) is false.  It is unique: the mask does not depend on layout, scheduling or launch shape. */
+/* box_hi[a] = VX_SEGMENT_BOX_END: the box reaches the far face of index_extent on axis a (box_lo 0 and box_hi all END: the whole
+ * volume).  Every other value is an inclusive voxel index. */
+#define VX_SEGMENT_BOX_END 0xffffffffu
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxSegmentParams {
+  uint32_t seed[3];        /* voxel index, inside index_extent                                                    */
+  float lo, hi;            /* finite, lo <= hi, both bounds inclusive                                             */
+  int32_t connectivity;    /* 6 or 26                                                                              */
+  uint32_t box_lo[3];      /* inclusive voxel box inside index_extent, box_lo <= box_hi                           */
+  uint32_t box_hi[3];      /* or VX_SEGMENT_BOX_END per axis: to the far face                                      */
+  uint32_t max_rounds;     /* cap on flood rounds; 0 = the number of voxels (capped at 2^32 - 2), which bounds any component */
+} VxSegmentParams;
+/* count, bbox (inclusive; all 0 for an empty segment), min / max of d (0 when empty) and the float64 sum of d over the segment:
+ * exact and identical from run to run (the sum adds each brick in a fixed voxel order, then the bricks in a fixed tree).
+ * rounds (flood launches with a non-empty worklist) and brick_visits may vary from run to run.  converged = 0: max_rounds
+ * ended the flood first and the mask is a connected subset of the segment. */
+typedef struct VxSegmentResult {
+  uint64_t count;
+  uint32_t bbox_lo[3], bbox_hi[3];
+  float d_min, d_max;
+  double d_sum;
+  uint32_t rounds, converged;
+  uint64_t brick_visits;
+} VxSegmentResult;
+/* Grows the segment of sp on the context's stream behind every queued render and synchronises; it replaces the context's one
+ * segment.  out may be NULL.  The accumulator, the frame state, VxCounters, the light grid, the bound tables and VxParams are not
+ * touched.  Reads the layout resident at the call (all layouts give the same bits).  Its buffers (2 x 64 B, 8 B and 4 x 4 B per
+ * brick) are allocated on first use and freed with the volume.  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the
+ * field, before vx_set_params, for NULL sp, a seed outside index_extent, a non-finite lo / hi or lo > hi, connectivity not 6 or
+ * 26, and a box that is empty or outside the volume.  group: member 0, like the slices and the isosurfaces. */
+int vx_segment(VxContext* ctx, const VxSegmentParams* sp, VxSegmentResult* out);
+/* the current segment as one bit per voxel of (z, y, x) in C order, LSB first (np.packbits(mask.ravel(), bitorder="little")):
+ * nbytes must be X * Y * Z / 8 of index_extent.  VX_ERR_INVALID with no current segment (none yet, or a volume uploaded since) */
+int vx_segment_read_mask(VxContext* ctx, uint8_t* bits, uint64_t nbytes);
+/* the segment on a slice: out[y * W + x] = 1 when for any slab sample s the nearest voxel floor(q + 0.5f) per axis (q as in
+ * vx_slice: the fma chain and its +-2^24 clamp) is in the volume and in the segment, else 0.  reduce, display and window are
+ * ignored; vx_slice's checks on size, slab_samples and finite vectors apply.  VX_ERR_INVALID with no current segment. */
+int vx_slice_segment_mask(VxContext* ctx, const VxSliceParams* sp, uint8_t* out);
+/* the last segment: flood rounds, brick visits and the HIP-event times of its predicate pass, its flood (from the first round
+ * to the last, host read-backs of the worklist length included) and its statistics, kernel_ms[0 .. 2]; all 0 before the first
+ * call.  Any pointer may be NULL.  group: member 0. */
+int vx_segment_stats(VxContext* ctx, uint32_t* rounds, uint64_t* brick_visits, double* kernel_ms);
 
 /* test hook (no reference counterpart): the device's R8-unorm decode table, 256 floats */
 int vx_debug_unorm_table(VxContext* ctx, float* out256);

@@ -1,0 +1,557 @@
+"""Seeded region growing on the GPU (vx_segment, DESIGN.md section 2 "Segmentation"): every layout and both connectivities against
+the NumPy / SciPy restatement (tests/segment_ref.py) -- mask bit for bit, count, bbox, min and max exact, the float64 sum within
+1e-9 of math.fsum and identical over two runs -- on value noise, the CT phantom, a volume whose sides are no multiple of 8, a
+one-voxel serpentine of many rounds and a volume 130 bricks long; the round cap, the slice overlay, pick -> voxel_index ->
+segment on config 2's bone, rendering left alone, staleness after an upload, device groups, the refusals and the JS host."""
+import ctypes as C
+import json
+import math
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import segment_ref as SG
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAPI = os.path.join(ROOT, "volxel_amd", "napi")
+F32 = np.float32
+LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1, "auto": 3}
+F32_MAX = float(np.finfo(np.float32).max)
+
+
+def _grid(vox, sp):
+    from volxel_amd import read_u16_stack_to_grid
+    return read_u16_stack_to_grid(vox, sp)
+
+
+def _serpentine():
+    """a one-voxel-wide path: rows along x at every other y, joined at alternating ends, in every other z layer, the layers
+    joined at the end of their last row; no two parts of it closer than 2 voxels except along the path, so it is one path under
+    6 and 26 alike, and it crosses brick faces hundreds of times"""
+    X, Y, Z = 48, 40, 16
+    v = np.zeros((Z, Y, X), dtype=np.uint16)
+    x = 0
+    rows, layers = list(range(0, Y, 2)), list(range(0, Z, 2))
+    for li, z in enumerate(layers):
+        order = rows if li % 2 == 0 else rows[::-1]
+        for ri, y in enumerate(order):
+            xe = X - 1 if x == 0 else 0
+            v[z, y, min(x, xe):max(x, xe) + 1] = 3000
+            x = xe
+            if ri + 1 < len(order):
+                v[z, (y + order[ri + 1]) // 2, x] = 3000
+        if li + 1 < len(layers):
+            v[z + 1, order[-1], x] = 3000
+    return v, (1.0, 1.0, 1.0)
+
+
+def _tube():
+    """1040 x 16 x 24: a noisy tube along x through 130 bricks, with noise below the threshold around it"""
+    X, Y, Z = 1040, 16, 24
+    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
+    r2 = (y - 7.5 - 3 * np.sin(x / 40.0)) ** 2 + (z - 11.5 - 4 * np.cos(x / 55.0)) ** 2
+    rng = np.random.default_rng(5)
+    v = np.where(r2 < 16, 2500, 600) + rng.integers(0, 300, size=r2.shape)
+    return v.astype(np.uint16), (0.5, 0.5, 0.8)
+
+
+def _odd():
+    """a 37 x 29 x 45 stack: the builder pads it to 40 x 32 x 48 (index_extent is always 8 x the brick grid, so no brick is
+    partial), and the padding is part of the volume the segment runs over"""
+    from volxel_amd import synth
+    v, _ = synth.value_noise(48, seed=3, zero_quantile=0.3)
+    return np.ascontiguousarray(v[:45, :29, :37]), (1.0, 1.2, 0.9)
+
+
+@pytest.fixture(scope="module")
+def volumes():
+    from tests.common import small_noise
+    from volxel_amd import synth
+    return {"noise": _grid(*small_noise(64)), "phantom": _grid(*synth.ct_phantom(64)), "odd": _grid(*_odd()),
+            "serpentine": _grid(*_serpentine()), "tube": _grid(*_tube())}
+
+
+def _renderer(g, layout=None, devices=None, w=64, h=48):
+    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
+    r = Volxel3DRenderer(w, h, device=None if devices else 0, layout=layout, devices=devices)
+    r.setup_from_grid(g)
+    r.restore_settings(BENCHMARK_SETTINGS)
+    r.settings.render_mode = "dvr"
+    r.settings.dvr_jitter = False
+    return r
+
+
+_D = {}
+
+
+def _densities(name, g, p):
+    key = (name, float(p.volume_density_scale), float(p.volume_inv_maj))
+    if key not in _D:
+        _D[key] = SG.densities(g, p.volume_density_scale, p.volume_inv_maj)
+    return _D[key]
+
+
+# (volume, seed rule, lo, hi, box): lo / hi as quantiles of d ("q0.6") or values; seed: the voxel of the largest d in the
+# predicate, or a fixed voxel
+CASES = {
+    "noise_q60": ("noise", "max", "q0.6", None, None),     # small_noise is half zeros: q0.5 would be lo = 0, the whole volume
+    "noise_q70": ("noise", "max", "q0.7", None, None),
+    "noise_q90": ("noise", "max", "q0.9", None, None),
+    "noise_band": ("noise", "max", "q0.6", "q0.95", ((3, 0, 5), (60, 50, 63))),
+    "phantom_bone": ("phantom", "max", 0.75, None, None),
+    "phantom_air": ("phantom", (0, 0, 0), 0.0, 0.05, None),
+    "odd": ("odd", "max", "q0.55", None, None),
+    "serpentine": ("serpentine", (0, 0, 0), "half", None, None),
+    "tube": ("tube", (0, 8, 12), "half", None, None),
+}
+
+
+def _resolve(d, seed, lo, hi, box):
+    def val(v):
+        if v is None:
+            return F32_MAX
+        if isinstance(v, str) and v.startswith("q"):
+            return float(np.quantile(d, float(v[1:])))
+        if v == "half":
+            return float(d.max()) / 2
+        return float(v)
+    lo_v, hi_v = val(lo), val(hi)
+    p = SG.predicate(d, lo_v, hi_v, box)
+    if seed == "max":
+        dd = np.where(p, d, -np.inf)
+        z, y, x = np.unravel_index(int(np.argmax(dd)), d.shape)
+        seed = (int(x), int(y), int(z))
+    return seed, lo_v, hi_v, p
+
+
+def _check_against_ref(r, name, g, case, conn):
+    vol, seed, lo, hi, box = CASES[case]
+    p = r.bind_uniforms()
+    d = _densities(vol, g, p)
+    seed, lo_v, hi_v, pred = _resolve(d, seed, lo, hi, box)
+    want = SG.component(pred, seed, conn)
+    st = SG.stats(want, d)
+    s1 = r.segment(seed, lo_v, hi_v, connectivity=conn, box=box)
+    m1 = r.segment_mask()
+    s2 = r.segment(seed, lo_v, hi_v, connectivity=conn, box=box)
+    m2 = r.segment_mask()
+    assert s1.converged and s2.converged
+    assert np.array_equal(m1, want), (case, conn, int(m1.sum()), int(want.sum()))
+    assert np.array_equal(m2, want)
+    assert s1.count == st["count"] and s1.bbox_lo == st["bbox_lo"] and s1.bbox_hi == st["bbox_hi"]
+    assert F32(s1.d_min) == F32(st["d_min"]) and F32(s1.d_max) == F32(st["d_max"])
+    assert s1.d_sum == s2.d_sum                                   # bit-identical from run to run
+    assert abs(s1.d_sum - st["d_sum"]) <= 1e-9 * abs(st["d_sum"])
+    return s1, want, d, seed
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(CASES))
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+@pytest.mark.parametrize("conn", [6, 26])
+def test_segment_matches_the_restatement(volumes, case, layout, conn):
+    g = volumes[CASES[case][0]]
+    r = _renderer(g, layout=LAYOUTS[layout])
+    try:
+        s, want, _, _ = _check_against_ref(r, CASES[case][0], g, case, conn)
+    finally:
+        r.close()
+    assert s.count > 0
+    if case == "serpentine":
+        assert s.count > 1000 and s.rounds > 100, (s.count, s.rounds)
+    if case == "tube":
+        assert s.bbox_lo[0] == 0 and s.bbox_hi[0] == 1039
+
+
+# one-voxel chains whose only links are diagonal (no two voxels share a face), 40 long in a 40^3 volume (5 bricks a side): each
+# step of a chain changes two or three coordinates at once, and 39 = 8 * 5 - 1 makes the reversed coordinate cross a brick
+# boundary at the same step as the others.  So every brick-to-brick step is across a brick edge (two coordinates) or a brick
+# corner (three), never a face: only the 12 edge and 8 corner directions of the 26-flood can follow them.  The seed is the
+# middle voxel, so the flood runs both ways and each chain uses both opposite directions of its edge / corner.
+CHAINS = {
+    "corner+++": lambda k: (k, k, k), "corner+-+": lambda k: (k, 39 - k, k), "corner-++": lambda k: (39 - k, k, k),
+    "corner++-": lambda k: (k, k, 39 - k),
+    "edge_xy++": lambda k: (k, k, 20), "edge_xy+-": lambda k: (k, 39 - k, 20),
+    "edge_xz++": lambda k: (k, 20, k), "edge_xz+-": lambda k: (k, 20, 39 - k),
+    "edge_yz++": lambda k: (20, k, k), "edge_yz+-": lambda k: (20, k, 39 - k),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("chain", sorted(CHAINS))
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_diagonal_chains_cross_brick_edges_and_corners(chain, layout):
+    v = np.zeros((40, 40, 40), dtype=np.uint16)
+    pts = [CHAINS[chain](k) for k in range(40)]
+    for x, y, z in pts:
+        v[z, y, x] = 3000
+    g = _grid(v, (1.0, 1.0, 1.0))
+    r = _renderer(g, layout=LAYOUTS[layout])
+    try:
+        p = r.bind_uniforms()
+        d = SG.densities(g, p.volume_density_scale, p.volume_inv_maj)
+        lo = float(d.max()) / 2
+        seed = pts[20]
+        s26 = r.segment(seed, lo, connectivity=26)
+        m26 = r.segment_mask()
+        s6 = r.segment(seed, lo, connectivity=6)
+        m6 = r.segment_mask()
+    finally:
+        r.close()
+    pred = SG.predicate(d, lo, F32_MAX)
+    assert int(pred.sum()) == 40
+    assert s26.converged and s26.count == 40 and np.array_equal(m26, pred)
+    assert np.array_equal(m26, SG.component(pred, seed, 26))
+    st = SG.stats(pred, d)
+    assert (s26.bbox_lo, s26.bbox_hi, F32(s26.d_min), F32(s26.d_max)) == (st["bbox_lo"], st["bbox_hi"], F32(st["d_min"]),
+                                                                           F32(st["d_max"]))
+    assert s26.rounds >= 3                                   # the chain spans 5 bricks on each moving axis
+    assert s6.converged and s6.count == 1 and m6.sum() == 1 and m6[seed[2], seed[1], seed[0]]
+
+
+@pytest.mark.gpu
+def test_box_edges_and_the_one_voxel_box(volumes):
+    """box = ((0, 0, 0), (0, 0, 0)) is the voxel at the origin, not the whole volume; VX_SEGMENT_BOX_END reaches the far face"""
+    from volxel_amd import _abi
+    g = volumes["noise"]
+    r = _renderer(g)
+    try:
+        one = r.segment((0, 0, 0), 0.0, box=((0, 0, 0), (0, 0, 0)))
+        m = r.segment_mask()
+        assert one.count == 1 and m.sum() == 1 and m[0, 0, 0]
+        lib, ctx = r._lib, r._ctx
+        q = _abi.VxSegmentParams()
+        q.lo, q.hi, q.connectivity = 0.0, F32_MAX, 6
+        q.box_lo[:] = (0, 2, 0)
+        q.box_hi[:] = (0xFFFFFFFF, 0xFFFFFFFF, 9)
+        q.seed[:] = (5, 5, 5)
+        res = _abi.VxSegmentResult()
+        r.bind_uniforms()
+        assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 0
+        assert res.count == 64 * 62 * 10 and tuple(res.bbox_lo) == (0, 2, 0) and tuple(res.bbox_hi) == (63, 63, 9)
+    finally:
+        r.close()
+
+
+@pytest.mark.gpu
+def test_density_is_trilinear_at_voxel_centres(volumes):
+    """the slice at an axial plane with one sample through voxel centres shows d(i) bit for bit"""
+    from volxel_amd import mpr
+    g = volumes["noise"]
+    r = _renderer(g)
+    try:
+        vals = r.slice(mpr.axial(r, 17))
+        d = _densities("noise", g, r._params)
+    finally:
+        r.close()
+    assert np.array_equal(vals.view(np.uint32), d[17].view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_round_cap_gives_a_connected_subset(volumes):
+    g = volumes["serpentine"]
+    r = _renderer(g)
+    try:
+        p = r.bind_uniforms()
+        d = _densities("serpentine", g, p)
+        lo = float(d.max()) / 2
+        full = r.segment((0, 0, 0), lo)
+        fm = r.segment_mask()
+        part = r.segment((0, 0, 0), lo, max_rounds=5)
+        pm = r.segment_mask()
+    finally:
+        r.close()
+    assert full.converged and not part.converged
+    assert 0 < part.count < full.count and part.rounds <= 5
+    assert not (pm & ~fm).any()
+    assert np.array_equal(SG.component(pm, (0, 0, 0), 6), pm)   # connected
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("conn", [6, 26])
+def test_slice_overlay_matches_the_restatement(volumes, conn):
+    from volxel_amd import mpr
+    g = volumes["phantom"]
+    r = _renderer(g)
+    try:
+        s, want, _, _ = _check_against_ref(r, "phantom", g, "phantom_bone", conn)
+        sps = [mpr.axial(r, 30), mpr.coronal(r, 40), mpr.sagittal(r, 20),
+               mpr.oblique(r, (0.02, 0.01, 0.0), (0.3, 0.5, 0.8), (0, 1, 0), 0.006, (90, 70)),
+               mpr.oblique(r, (0.0, 0.05, 0.0), (0.0, 0.0, 1.0), (0, 1, 0), 0.008, (80, 80), thickness=0.2, samples=9)]
+        for sp in sps:
+            got = r.slice_mask(sp)
+            ref = SG.overlay(sp, want)
+            assert np.array_equal(got, ref)
+        assert any(SG.overlay(sp, want).any() for sp in sps)
+    finally:
+        r.close()
+
+
+@pytest.mark.gpu
+def test_pick_voxel_index_segment_on_config2_bone():
+    """config 2 (the 256^3 CT phantom, spacing (0.7, 0.7, 1.0)): pick a point of the spine, take its nearest voxel as the seed"""
+    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer, synth
+    g = _grid(*synth.ct_phantom(256))
+    r = Volxel3DRenderer(480, 270, device=0)
+    try:
+        r.setup_from_grid(g)
+        r.restore_settings(BENCHMARK_SETTINGS)
+        r.settings.volume_clip_min, r.settings.volume_clip_max = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
+        r.settings.dvr_step_voxels = 0.5
+        iso = 0.75
+        _, hit = r.isosurface(iso, refine=8)
+        ys, xs = np.nonzero(hit[..., 3] >= 0)
+        assert len(xs) > 100
+        seed = None
+        for k in np.argsort((xs - np.median(xs)) ** 2 + (ys - np.median(ys)) ** 2):
+            w = hit[ys[k], xs[k], :3]
+            vi = r.voxel_index(w)
+            if vi is None:
+                continue
+            p = r._params
+            d = SG.densities(g, p.volume_density_scale, p.volume_inv_maj)
+            if d[vi[2], vi[1], vi[0]] >= F32(iso):
+                seed = vi
+                break
+        assert seed is not None
+        s = r.segment(seed, iso)
+        m = r.segment_mask()
+    finally:
+        r.close()
+    want = SG.component(SG.predicate(d, iso, F32_MAX), seed, 6)
+    assert np.array_equal(m, want)
+    assert s.count > 1000
+    assert math.isclose(s.volume_grid, s.count * 0.7 * 0.7 * 1.0, rel_tol=1e-6)
+    assert s.volume_world > 0 and s.mean == s.d_sum / s.count
+
+
+@pytest.mark.gpu
+def test_rendering_is_left_alone(volumes):
+    g = volumes["noise"]
+    r = _renderer(g)
+    try:
+        r.bind_uniforms()
+        r.reset_counters()
+        r.restart_rendering()
+        r.render(frames=1, in_flight=1)
+        a = r.read_accum().copy()
+        c1 = r.counters()
+        c1 = {f: getattr(c1, f) for f, _ in c1._fields_ if not f.endswith("_ms")}
+        r.segment((10, 10, 10), 0.2, connectivity=26)
+        r.segment_mask()
+        from volxel_amd import mpr
+        r.slice_mask(mpr.axial(r, 10))
+        r.reset_counters()
+        r.restart_rendering()
+        r.render(frames=1, in_flight=1)
+        b = r.read_accum().copy()
+        c2 = r.counters()
+        c2 = {f: getattr(c2, f) for f, _ in c2._fields_ if not f.endswith("_ms")}
+    finally:
+        r.close()
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    assert c1 == c2
+
+
+@pytest.mark.gpu
+def test_upload_makes_the_segment_stale(volumes):
+    from volxel_amd import VolxelError, mpr
+    g = volumes["noise"]
+    r = _renderer(g)
+    try:
+        s = r.segment((5, 5, 5), 0.0, connectivity=6)
+        assert s.count == 64 ** 3                       # lo = 0 admits every voxel (densities are >= 0)
+        assert r.segment_mask().all()
+        r.setup_from_grid(volumes["phantom"])
+        with pytest.raises(VolxelError, match="no current segment"):
+            r.segment_mask()
+        with pytest.raises(VolxelError, match="no current segment"):
+            r.slice_mask(mpr.axial(r, 3))
+    finally:
+        r.close()
+
+
+@pytest.mark.gpu
+def test_device_group_gives_member0_bits(volumes):
+    g = volumes["noise"]
+    r1 = _renderer(g)
+    try:
+        p = r1.bind_uniforms()
+        d = _densities("noise", g, p)
+        seed, lo, hi, _ = _resolve(d, "max", "q0.7", None, None)
+        a = r1.segment(seed, lo, connectivity=26)
+        ma = r1.segment_mask()
+    finally:
+        r1.close()
+    r2 = _renderer(g, devices=[0, 0])
+    try:
+        b = r2.segment(seed, lo, connectivity=26)
+        mb = r2.segment_mask()
+        st = r2.segment_stats()
+    finally:
+        r2.close()
+    assert np.array_equal(ma, mb)
+    assert (a.count, a.bbox_lo, a.bbox_hi, a.d_min, a.d_max, a.d_sum) == (b.count, b.bbox_lo, b.bbox_hi, b.d_min, b.d_max, b.d_sum)
+    assert st[0] == b.rounds and st[1] == b.brick_visits and all(t >= 0 for t in st[2:])
+
+
+def _upload(lib, ctx, g):
+    u3 = lambda t: (C.c_uint32 * 3)(*[int(x) for x in t])
+    ind = np.ascontiguousarray(g.indirection, dtype=np.uint32)
+    rng = np.ascontiguousarray(g.range, dtype=np.uint16)
+    atl = np.ascontiguousarray(g.atlas, dtype=np.uint8)
+    mips = [np.ascontiguousarray(m, dtype=np.uint16) for m, _ in g.range_mipmaps]
+    mp = (C.c_void_p * 3)(*[m.ctypes.data for m in mips])
+    ms = (C.c_uint32 * 9)(*[int(x) for _, s in g.range_mipmaps for x in s])
+    return lib.vx_upload_volume(ctx, ind.ctypes.data, u3(g.indirection_size), rng.ctypes.data, u3(g.range_size),
+                                atl.ctypes.data, u3(g.atlas_size), 3, mp, C.cast(ms, C.c_void_p), u3(g.index_extent))
+
+
+@pytest.mark.gpu
+def test_refusals(volumes):
+    from volxel_amd import _abi, mpr
+    g = volumes["noise"]
+    lib = _abi.load_library()
+    q = _abi.VxSegmentParams()
+    q.seed[0], q.seed[1], q.seed[2] = 3, 4, 5
+    q.lo, q.hi, q.connectivity = 0.1, 1.0, 6
+    res = _abi.VxSegmentResult()
+    nbytes = 64 ** 3 // 8
+    bits = np.zeros(nbytes, dtype=np.uint8)
+    ctx = C.c_void_p()
+    assert lib.vx_create(0, C.byref(ctx)) == 0
+    try:
+        assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 3                    # VX_ERR_NO_VOLUME
+        assert lib.vx_segment_stats(ctx, None, None, None) == 0
+        assert _upload(lib, ctx, g) == 0
+        assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 1 and b"vx_set_params" in lib.vx_last_error(ctx)
+        assert lib.vx_segment_read_mask(ctx, bits.ctypes.data, nbytes) == 1 and b"no current segment" in lib.vx_last_error(ctx)
+        r = _renderer(g)
+        try:
+            p = r.bind_uniforms()
+            sp = mpr.axial(r, 3)
+        finally:
+            r.close()
+        ov = np.zeros(64 * 64, dtype=np.uint8)
+        assert lib.vx_resize(ctx, 64, 48) == 0 and lib.vx_set_params(ctx, C.byref(p)) == 0
+        assert lib.vx_slice_segment_mask(ctx, C.byref(sp), ov.ctypes.data) == 1 and b"no current segment" in lib.vx_last_error(ctx)
+        assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 0
+        assert lib.vx_segment(ctx, C.byref(q), None) == 0
+        assert lib.vx_segment(ctx, None, C.byref(res)) == 1 and b"sp" in lib.vx_last_error(ctx)
+
+        def refused(field, value, word):
+            b = _abi.VxSegmentParams.from_buffer_copy(q)
+            if isinstance(field, tuple):
+                getattr(b, field[0])[field[1]] = value
+            else:
+                setattr(b, field, value)
+            assert lib.vx_segment(ctx, C.byref(b), C.byref(res)) == 1, (field, value)
+            assert word in lib.vx_last_error(ctx), (field, lib.vx_last_error(ctx))
+
+        refused(("seed", 0), 64, b"seed[0]")
+        refused(("seed", 2), 1000, b"seed[2]")
+        for name in ("lo", "hi"):
+            refused(name, float("nan"), name.encode())
+            refused(name, float("inf"), name.encode())
+        refused("lo", 2.0, b"lo")
+        for cn in (0, 4, 8, 18, 27, -6):
+            refused("connectivity", cn, b"connectivity")
+        for lo3, hi3 in (((5, 0, 0), (4, 63, 63)), ((0, 0, 0), (64, 10, 10)), ((0, 0, 9), (10, 10, 8)), ((0, 0, 0), (0, 0, 64))):
+            b = _abi.VxSegmentParams.from_buffer_copy(q)
+            b.box_lo[:] = lo3
+            b.box_hi[:] = hi3
+            assert lib.vx_segment(ctx, C.byref(b), C.byref(res)) == 1 and b"box" in lib.vx_last_error(ctx), (lo3, hi3)
+        # a refused call leaves no current segment behind it only when it got past the checks: the last good one stands
+        assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 0
+        assert lib.vx_segment_read_mask(ctx, bits.ctypes.data, nbytes - 1) == 1 and b"nbytes" in lib.vx_last_error(ctx)
+        assert lib.vx_segment_read_mask(ctx, bits.ctypes.data, nbytes + 8) == 1 and b"nbytes" in lib.vx_last_error(ctx)
+        assert lib.vx_segment_read_mask(ctx, bits.ctypes.data, nbytes) == 0
+        assert lib.vx_slice_segment_mask(ctx, C.byref(sp), ov.ctypes.data) == 0
+        assert lib.vx_slice_segment_mask(ctx, None, ov.ctypes.data) == 1 and b"sp" in lib.vx_last_error(ctx)
+        for field, value, word in ((("size", 0), 0, b"size[0]"), (("size", 1), 16385, b"size[1]"), ("slab_samples", 0, b"slab_samples"),
+                                   ("slab_samples", 4097, b"slab_samples"), (("origin", 1), float("nan"), b"origin[1]"),
+                                   (("dn", 2), float("inf"), b"dn[2]")):
+            b = _abi.VxSliceParams.from_buffer_copy(sp)
+            if isinstance(field, tuple):
+                getattr(b, field[0])[field[1]] = value
+            else:
+                setattr(b, field, value)
+            assert lib.vx_slice_segment_mask(ctx, C.byref(b), ov.ctypes.data) == 1 and word in lib.vx_last_error(ctx), field
+        # an empty segment (P(seed) false) is no error
+        b = _abi.VxSegmentParams.from_buffer_copy(q)
+        b.lo, b.hi = 5.0, 6.0
+        assert lib.vx_segment(ctx, C.byref(b), C.byref(res)) == 0
+        assert res.count == 0 and res.converged == 1 and tuple(res.bbox_lo) == (0, 0, 0)
+        assert lib.vx_segment_read_mask(ctx, bits.ctypes.data, nbytes) == 0 and not bits.any()
+    finally:
+        lib.vx_destroy(ctx)
+
+
+@pytest.mark.gpu
+@pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
+def test_js_host_segment_has_the_python_bits(volumes, tmp_path):
+    subprocess.check_call(["make", "-C", NAPI, "-s"])
+    from volxel_amd import BENCHMARK_SETTINGS, mpr
+    g = volumes["noise"]
+    r = _renderer(g)
+    try:
+        p = r.bind_uniforms()
+        d = _densities("noise", g, p)
+        seed, lo, _, _ = _resolve(d, "max", "q0.6", None, None)
+        s = r.segment(seed, lo, connectivity=26, box=((2, 3, 4), (60, 61, 62)))
+        m = r.segment_mask()
+        sl = r.slice_mask(mpr.axial(r, seed[2]))
+        w = [tuple(float(a) for a in pt) for pt in np.random.default_rng(9).uniform(-0.6, 0.6, size=(24, 3))]
+        vi = [r.voxel_index(pt) for pt in w]
+    finally:
+        r.close()
+    (tmp_path / "grid.json").write_text(json.dumps({
+        "indirectionSize": list(map(int, g.indirection_size)), "rangeSize": list(map(int, g.range_size)),
+        "atlasSize": list(map(int, g.atlas_size)), "indexExtent": list(map(int, g.index_extent)),
+        "minMaj": list(map(float, g.min_maj)), "transform": list(map(float, g.transform)),
+        "mips": [list(map(int, sz)) for _, sz in g.range_mipmaps]}))
+    np.asarray(g.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
+    np.asarray(g.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
+    np.asarray(g.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
+    for i, (mm, _) in enumerate(g.range_mipmaps):
+        np.asarray(mm, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
+    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
+    (tmp_path / "args.json").write_text(json.dumps({"seed": list(seed), "lo": lo, "w": list(w)}))
+    script = r"""
+const fs = require('fs'), path = require('path');
+const [napi, dir] = process.argv.slice(2);
+const v = require(napi);
+const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
+const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
+const a = JSON.parse(fs.readFileSync(path.join(dir, 'args.json')));
+const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
+  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
+  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
+  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
+const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
+r.setupFromGrid(grid);
+r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
+r.settings.renderMode = 'dvr';
+const s = r.segment(a.seed, a.lo, { connectivity: 26, box: [[2, 3, 4], [60, 61, 62]] });
+const m = r.segmentMask();
+const sl = r.sliceMask(r.axial(a.seed[2]));
+const st = r.segmentStats();
+fs.writeFileSync(path.join(dir, 'mask.bin'), Buffer.from(m.buffer, m.byteOffset, m.byteLength));
+fs.writeFileSync(path.join(dir, 'slice.bin'), Buffer.from(sl.mask.buffer, sl.mask.byteOffset, sl.mask.byteLength));
+console.log(JSON.stringify({ s, st, vi: a.w.map((p) => r.voxelIndex(p)), size: [sl.width, sl.height] }));
+r.dispose();
+"""
+    (tmp_path / "s.js").write_text(script)
+    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    assert np.array_equal(np.fromfile(tmp_path / "mask.bin", dtype=np.uint8), SG.packed(m))
+    assert out["size"] == [64, 64]
+    assert np.array_equal(np.fromfile(tmp_path / "slice.bin", dtype=np.uint8).reshape(64, 64), sl.astype(np.uint8))
+    js = out["s"]
+    assert js["count"] == s.count and tuple(js["bboxLo"]) == s.bbox_lo and tuple(js["bboxHi"]) == s.bbox_hi
+    assert F32(js["dMin"]) == F32(s.d_min) and F32(js["dMax"]) == F32(s.d_max) and js["dSum"] == s.d_sum
+    assert js["converged"] is True and out["st"]["rounds"] == js["rounds"]
+    assert [None if v is None else tuple(v) for v in out["vi"]] == vi
+    assert any(v is None for v in vi) and any(v is not None for v in vi)

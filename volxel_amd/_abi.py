@@ -49,6 +49,8 @@ VxParams = struct_from_header("volxel_hip.h", "VxParams")
 VxCounters = struct_from_header("volxel_hip.h", "VxCounters")
 VxSliceParams = struct_from_header("volxel_hip.h", "VxSliceParams")
 VxIsoParams = struct_from_header("volxel_hip.h", "VxIsoParams")
+VxSegmentParams = struct_from_header("volxel_hip.h", "VxSegmentParams")
+VxSegmentResult = struct_from_header("volxel_hip.h", "VxSegmentResult")
 
 MODE_DEFAULT, MODE_NO_DDA, MODE_RAYMARCH, MODE_DVR, MODE_DVR_PHONG, MODE_MIP, MODE_MINIP = range(7)
 LAYOUT_REFERENCE, LAYOUT_CELLQUAD, LAYOUT_BRICKF32, LAYOUT_AUTO = 0, 1, 2, 3
@@ -142,6 +144,10 @@ def load_library():
         "vx_slice_stats": ([vp, P(u64), P(C.c_double)], i32),
         "vx_isosurface": ([vp, P(VxIsoParams), vp, vp], i32),
         "vx_iso_stats": ([vp, P(u64), P(u64), P(u64), P(u64), P(u64), P(C.c_double)], i32),
+        "vx_segment": ([vp, P(VxSegmentParams), P(VxSegmentResult)], i32),
+        "vx_segment_read_mask": ([vp, vp, u64], i32),
+        "vx_slice_segment_mask": ([vp, P(VxSliceParams), vp], i32),
+        "vx_segment_stats": ([vp, P(u32), P(u64), P(C.c_double)], i32),
         # preprocessor
         "vxb_build_from_u16": ([vp, P(u32), P(C.c_float), C.c_uint16, i32, P(vp)], i32),
         "vxb_read_dicoms_to_grid": ([P(vp), P(u64), u32, i32, P(vp)], i32),

@@ -20,6 +20,7 @@
 #include "vx_projection.hpp"
 #include "vx_slice.hpp"
 #include "vx_iso.hpp"
+#include "vx_segment.hpp"
 
 using namespace vx;
 
@@ -38,6 +39,7 @@ struct Switches {
   bool dvr_fuse = true;            // VX_DVR_FUSE=0: no kernel folds the running mean; merge_results blends every multi-frame launch
   bool ray_shortcuts = true;       // VX_RAY_SHORTCUTS=0: the per-ray divisions themselves (DevVolume::ray_flags = 0)
   std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
+  uint32_t seg_check_max = 64;     // VX_SEG_CHECK_MAX (1 .. 4096): the largest batch of flood rounds between read-backs (vx_segment)
 };
 
 // ---- the tables a launch derives from the params and the uploads ---------------------------------------------------------
@@ -199,6 +201,18 @@ struct VxContext {
   hipEvent_t iso_ev[2] = {nullptr, nullptr};
   uint64_t iso_counts[ISO_NCOUNTS] = {};
   double iso_ms = 0.0;
+  // segmentation (vx_segment): one allocation for the masks, flags, stamps, worklists, partial sums and statistics of the
+  // volume's brick grid (freed with the volume); the packed read-back and the overlay buffers grow on demand; the last result
+  void* seg_alloc = nullptr;
+  SegDev seg{};
+  bool seg_valid = false;     // a segment of the resident volume is current
+  uint8_t* seg_bytes = nullptr;
+  size_t seg_bytes_cap = 0;
+  uint8_t* seg_ov = nullptr;
+  size_t seg_ov_cap = 0;
+  hipEvent_t seg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  VxSegmentResult seg_res{};
+  double seg_ms[3] = {0.0, 0.0, 0.0};
 };
 
 static bool is_group(const VxContext* c) { return !c->members.empty(); }
@@ -241,6 +255,13 @@ static void free_volume(VxContext* c) {
   c->shadow_dev = nullptr;
   c->shadow_cap = 0;
   c->shadow = ShadowGrid{};
+  if (c->seg_alloc) (void)hipFree(c->seg_alloc);
+  c->seg_alloc = nullptr;
+  c->seg = SegDev{};
+  c->seg_valid = false;
+  if (c->seg_bytes) (void)hipFree(c->seg_bytes);
+  c->seg_bytes = nullptr;
+  c->seg_bytes_cap = 0;
 }
 
 static void drain_events(VxContext* c) {
@@ -1114,6 +1135,7 @@ int vx_create(int device_id, VxContext** out) {
   if (const char* v = getenv("VX_DVR_FUSE")) sw.dvr_fuse = atoi(v) != 0;
   if (const char* v = getenv("VX_RAY_SHORTCUTS"); v && atoi(v) == 0) sw.ray_shortcuts = false;
   if (const char* v = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) sw.cellquad_max_bytes = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VX_SEG_CHECK_MAX")) sw.seg_check_max = (uint32_t)std::min(std::max(atoi(v), 1), 4096);
   *out = c;
   return VX_OK;
 }
@@ -1225,6 +1247,9 @@ void vx_destroy(VxContext* c) {
   if (c->iso_bound_dev) (void)hipFree(c->iso_bound_dev);
   if (c->iso_count_dev) (void)hipFree(c->iso_count_dev);
   for (hipEvent_t e : c->iso_ev)
+    if (e) (void)hipEventDestroy(e);
+  if (c->seg_ov) (void)hipFree(c->seg_ov);
+  for (hipEvent_t e : c->seg_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2524,6 +2549,240 @@ int vx_iso_stats(VxContext* c, uint64_t* rays, uint64_t* hits, uint64_t* samples
   if (refine_samples) *refine_samples = c->iso_counts[ISO_REFINE];
   if (skipped) *skipped = c->iso_counts[ISO_SKIPPED];
   if (last_kernel_ms) *last_kernel_ms = c->iso_ms;
+  return VX_OK;
+}
+
+// ---- segmentation (vx_segment): seg_predicate, the flood rounds, seg_stats / seg_sum (vx_segment.hpp) ----------------------
+// rounds between host read-backs of the next worklist's length: 1, 2, 4, ... up to Switches::seg_check_max (64; NOTEBOOK
+// "Segmentation" compares caps).  A queued round that finds its worklist empty exits at once (one launch boundary, a few
+// microseconds); a read-back is a host round trip.
+
+// the device buffers of the brick grid, carved from one allocation (sizes in DESIGN.md / INTEGRATION.md's memory bill)
+static int ensure_segment(VxContext* c) {
+  if (c->seg_alloc) return VX_OK;
+  const uint32_t nb = c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2];
+  const size_t bytes = (size_t)nb * (64u + 64u + 8u + 4u * 4u) + 16u + sizeof(SegStats);
+  VX_HIP(c, hipMalloc(&c->seg_alloc, bytes));
+  char* p = static_cast<char*>(c->seg_alloc);
+  SegDev& s = c->seg;
+  s.pred = reinterpret_cast<uint64_t*>(p);
+  p += (size_t)nb * 64u;
+  s.seg = reinterpret_cast<uint64_t*>(p);
+  p += (size_t)nb * 64u;
+  s.partial = reinterpret_cast<double*>(p);
+  p += (size_t)nb * 8u;
+  s.st = reinterpret_cast<SegStats*>(p);
+  p += sizeof(SegStats);
+  s.any = reinterpret_cast<uint32_t*>(p);
+  p += (size_t)nb * 4u;
+  s.stamp = reinterpret_cast<uint32_t*>(p);
+  p += (size_t)nb * 4u;
+  s.list[0] = reinterpret_cast<uint32_t*>(p);
+  p += (size_t)nb * 4u;
+  s.list[1] = reinterpret_cast<uint32_t*>(p);
+  p += (size_t)nb * 4u;
+  s.cnt = reinterpret_cast<uint32_t*>(p);
+  for (int a = 0; a < 3; ++a) s.bc[a] = c->dv.bc[a];
+  s.nb = nb;
+  return VX_OK;
+}
+
+static void launch_seg_predicate(VxContext* c, const SegPredParams& pp) {
+  const VxParams& p = c->params;
+  const uint32_t blocks = std::min<uint32_t>((c->seg.nb + 3u) / 4u, 4096u);
+  with_layout(slice_layout(c), [&](auto lay) {
+    constexpr int LAY = decltype(lay)::value;
+    hipLaunchKernelGGL((seg_predicate<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
+                       pp, c->seg);
+  });
+}
+static void launch_seg_flood(VxContext* c, int conn, const SegSeed& seed, uint32_t round) {
+  const uint32_t blocks = std::min<uint32_t>((c->seg.nb + 255u) / 256u, 1024u);
+  if (conn == 26)
+    hipLaunchKernelGGL((seg_flood<26>), dim3(blocks), dim3(256), 0, c->stream, c->seg, seed, round);
+  else
+    hipLaunchKernelGGL((seg_flood<6>), dim3(blocks), dim3(256), 0, c->stream, c->seg, seed, round);
+}
+static void launch_seg_stats(VxContext* c) {
+  const VxParams& p = c->params;
+  const uint32_t blocks = std::min<uint32_t>((c->seg.nb + 3u) / 4u, 4096u);
+  with_layout(slice_layout(c), [&](auto lay) {
+    constexpr int LAY = decltype(lay)::value;
+    hipLaunchKernelGGL((seg_stats<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
+                       c->seg);
+  });
+  hipLaunchKernelGGL(seg_sum, dim3(1), dim3(1024), 0, c->stream, c->seg);
+}
+static float seg_key_float(uint32_t k) {
+  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  memcpy(&f, &u, sizeof f);
+  return f;
+}
+
+int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment(c->members[0], sp, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: sp is NULL");
+  const uint32_t* E = c->dv.extent;
+  for (int a = 0; a < 3; ++a)
+    if (sp->seed[a] >= E[a])
+      VX_FAIL(c, VX_ERR_INVALID, "vx_segment: seed[%d] = %u outside the index extent %u", a, sp->seed[a], E[a]);
+  if (!std::isfinite(sp->lo)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: lo is not finite");
+  if (!std::isfinite(sp->hi)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: hi is not finite");
+  if (sp->lo > sp->hi) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: lo = %g > hi = %g", (double)sp->lo, (double)sp->hi);
+  if (sp->connectivity != 6 && sp->connectivity != 26)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment: connectivity = %d is not 6 or 26", sp->connectivity);
+  SegPredParams pp{sp->lo, sp->hi, {sp->box_lo[0], sp->box_lo[1], sp->box_lo[2]}, {sp->box_hi[0], sp->box_hi[1], sp->box_hi[2]}};
+  for (int a = 0; a < 3; ++a) {
+    if (pp.box_hi[a] == VX_SEGMENT_BOX_END) pp.box_hi[a] = E[a] - 1u;
+    if (pp.box_lo[a] > pp.box_hi[a] || pp.box_hi[a] >= E[a])
+      VX_FAIL(c, VX_ERR_INVALID, "vx_segment: box axis %d [%u, %u] is empty or outside the index extent %u", a, sp->box_lo[a],
+              sp->box_hi[a], E[a]);
+  }
+  c->seg_valid = false;
+  {
+    const int rc = ensure_segment(c);
+    if (rc) return rc;
+  }
+  for (hipEvent_t& e : c->seg_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  const SegDev& s = c->seg;
+  const uint32_t bc0 = c->dv.bc[0], bc1 = c->dv.bc[1];
+  const uint32_t sx = sp->seed[0], sy = sp->seed[1], sz = sp->seed[2];
+  const SegSeed seed{((sz >> 3) * bc1 + (sy >> 3)) * bc0 + (sx >> 3), sz & 7u, 1ull << (((sy & 7u) << 3) | (sx & 7u))};
+  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
+  const uint64_t cap = sp->max_rounds ? (uint64_t)sp->max_rounds : std::min<uint64_t>(nvox, 0xfffffffeull);
+  VX_HIP(c, hipMemsetAsync(s.seg, 0, (size_t)s.nb * 64u, c->stream));
+  VX_HIP(c, hipMemsetAsync(s.stamp, 0, (size_t)s.nb * 4u, c->stream));
+  VX_HIP(c, hipEventRecord(c->seg_ev[0], c->stream));
+  launch_seg_predicate(c, pp);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->seg_ev[1], c->stream));
+  hipLaunchKernelGGL(seg_seed, dim3(1), dim3(64), 0, c->stream, s, seed);
+  VX_HIP(c, hipGetLastError());
+  // the rounds: queued in batches of 1, 2, 4, ... SEG_CHECK_MAX, the next worklist's length read back after each batch
+  uint64_t launched = 0;
+  uint32_t batch = 1, next = 1;
+  bool converged = false;
+  while (true) {
+    const uint64_t k = std::min<uint64_t>(batch, cap - launched);
+    for (uint64_t i = 0; i < k; ++i) launch_seg_flood(c, sp->connectivity, seed, (uint32_t)(launched + i));
+    VX_HIP(c, hipGetLastError());
+    launched += k;
+    VX_HIP(c, hipMemcpyAsync(&next, s.cnt + launched % 3u, sizeof next, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (next == 0u) {
+      converged = true;
+      break;
+    }
+    if (launched >= cap) break;
+    batch = std::min(batch * 2u, c->sw.seg_check_max);
+  }
+  VX_HIP(c, hipEventRecord(c->seg_ev[2], c->stream));
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->seg_ev[3], c->stream));
+  SegStats st;
+  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.0f;
+    VX_HIP(c, hipEventElapsedTime(&ms, c->seg_ev[i], c->seg_ev[i + 1]));
+    c->seg_ms[i] = ms;
+  }
+  VxSegmentResult r{};
+  r.count = st.count;
+  if (st.count) {
+    for (int a = 0; a < 3; ++a) {
+      r.bbox_lo[a] = st.lo[a];
+      r.bbox_hi[a] = st.hi[a];
+    }
+    r.d_min = seg_key_float(st.dmin);
+    r.d_max = seg_key_float(st.dmax);
+    r.d_sum = st.sum;
+  }
+  r.rounds = st.rounds;
+  r.converged = converged ? 1u : 0u;
+  r.brick_visits = st.visits;
+  c->seg_res = r;
+  c->seg_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_segment_read_mask(VxContext* c, uint8_t* bits, uint64_t nbytes) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_read_mask(c->members[0], bits, nbytes));
+  VX_DEV(c);
+  if (!c->seg_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: no current segment (vx_segment first; an upload drops it)");
+  if (!bits) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: bits is NULL");
+  const uint32_t* E = c->dv.extent;
+  const size_t want = (size_t)E[0] * E[1] * E[2] / 8u;
+  if (nbytes != want)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: nbytes = %llu, the mask of %u x %u x %u voxels is %zu bytes",
+            (unsigned long long)nbytes, E[0], E[1], E[2], want);
+  if (want > c->seg_bytes_cap) {
+    if (c->seg_bytes) (void)hipFree(c->seg_bytes);
+    c->seg_bytes = nullptr;
+    c->seg_bytes_cap = 0;
+    VX_HIP(c, hipMalloc(&c->seg_bytes, want));
+    c->seg_bytes_cap = want;
+  }
+  const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 8192u);
+  hipLaunchKernelGGL(seg_pack, dim3(blocks), dim3(256), 0, c->stream, c->seg, E[0], E[1], want, c->seg_bytes);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipMemcpyAsync(bits, c->seg_bytes, want, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_slice_segment_mask(VxContext* c, const VxSliceParams* sp, uint8_t* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_slice_segment_mask(c->members[0], sp, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice_segment_mask: no volume uploaded");
+  if (!c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: no current segment (vx_segment first; an upload drops it)");
+  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: sp is NULL");
+  if (!out) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: out is NULL");
+  for (int i = 0; i < 2; ++i)
+    if (sp->size[i] < 1u || sp->size[i] > 16384u)
+      VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: size[%d] = %u outside 1 .. 16384", i, sp->size[i]);
+  if (sp->slab_samples < 1u || sp->slab_samples > 4096u)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: slab_samples = %u outside 1 .. 4096", sp->slab_samples);
+  const struct { const char* name; const float* v; } vecs[4] = {{"origin", sp->origin}, {"du", sp->du}, {"dv", sp->dv}, {"dn", sp->dn}};
+  for (const auto& e : vecs)
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(e.v[i])) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: %s[%d] is not finite", e.name, i);
+  const size_t px = (size_t)sp->size[0] * sp->size[1];
+  if (px > c->seg_ov_cap) {   // (every earlier call has completed: each one synchronises)
+    if (c->seg_ov) (void)hipFree(c->seg_ov);
+    c->seg_ov = nullptr;
+    c->seg_ov_cap = 0;
+    VX_HIP(c, hipMalloc(&c->seg_ov, px));
+    c->seg_ov_cap = px;
+  }
+  const dim3 grid((sp->size[0] + 15u) / 16u, (sp->size[1] + 15u) / 16u);
+  hipLaunchKernelGGL(seg_slice_mask, grid, dim3(256), 0, c->stream, *sp, c->seg, c->dv.extent[0], c->dv.extent[1], c->dv.extent[2],
+                     c->seg_ov);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipMemcpyAsync(out, c->seg_ov, px, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_segment_stats(VxContext* c, uint32_t* rounds, uint64_t* brick_visits, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_stats(c->members[0], rounds, brick_visits, kernel_ms));
+  if (rounds) *rounds = c->seg_res.rounds;
+  if (brick_visits) *brick_visits = c->seg_res.brick_visits;
+  if (kernel_ms)
+    for (int i = 0; i < 3; ++i) kernel_ms[i] = c->seg_ms[i];
   return VX_OK;
 }
 

@@ -104,3 +104,26 @@ def oblique(renderer, center, normal, up, pixel_size: float, size, thickness: fl
     m3 = m[:3, :3]
     q0 = m3 @ o + m[:3, 3] - 0.5
     return _params(q0, m3 @ (pixel_size * u), m3 @ (pixel_size * v), m3 @ (spacing * n), (W, H), samples)
+
+
+def overlay(rgba8, mask, color=(1.0, 0.0, 0.0), alpha: float = 0.5):
+    """A segment overlay for display (pure NumPy): where `mask` (H, W) is True, each colour channel c of the (H, W, 3 or 4) uint8
+    image becomes round((1 - alpha) * c + alpha * 255 * color); elsewhere, and in the alpha channel, the image is unchanged.
+    color: three values in [0, 1]; alpha in [0, 1].  Returns a new array.  Renderer.slice_mask gives the mask of a slice."""
+    img = np.asarray(rgba8)
+    m = np.asarray(mask, dtype=bool)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
+        raise ValueError(f"rgba8 must be an (H, W, 3 or 4) uint8 image, not {img.dtype} {img.shape}")
+    if m.shape != img.shape[:2]:
+        raise ValueError(f"mask must be {img.shape[:2]}, not {m.shape}")
+    col = np.asarray(color, dtype=np.float64).reshape(-1)
+    if col.size != 3 or not np.isfinite(col).all() or (col < 0).any() or (col > 1).any():
+        raise ValueError(f"color must be three values in [0, 1], not {color!r}")
+    a = float(alpha)
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], not {alpha!r}")
+    out = img.copy()
+    rgb = out[..., :3].astype(np.float64)
+    blend = np.floor((1.0 - a) * rgb + a * 255.0 * col + 0.5)
+    out[..., :3] = np.where(m[..., None], np.clip(blend, 0, 255), rgb).astype(np.uint8)
+    return out

@@ -97,6 +97,20 @@ export declare class Volxel3DDicomRenderer {
   pick(x: number, y: number, iso: number, opts?: { refine?: number }): [number, number, number] | null;
   /** the last isosurface: rays, hits, march samples, bisection samples, samples passed over and its HIP-event kernel time */
   isoStats(): { rays: number; hits: number; samples: number; refineSamples: number; skipped: number; lastKernelMs: number };
+  /** the connected component of lo <= d <= hi holding voxel seed on the GPU (include/volxel_hip.h vx_segment) */
+  segment(seed: [number, number, number], lo: number, opts?: { hi?: number; connectivity?: 6 | 26;
+    box?: [[number, number, number], [number, number, number]] | null; maxRounds?: number }):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** the current segment: one bit per voxel of (z, y, x) in C order, LSB first */
+  segmentMask(): Uint8Array;
+  /** the current segment on a slice spec: 0 / 1 per pixel, row 0 = y = 0 */
+  sliceMask(spec: { origin: number[]; du: number[]; dv: number[]; dn: number[]; size: [number, number]; slabSamples?: number }):
+    { mask: Uint8Array; width: number; height: number };
+  /** the voxel nearest a world point, or null outside the volume */
+  voxelIndex(w: [number, number, number]): [number, number, number] | null;
+  /** the last segment: flood rounds, brick visits and the times of its predicate pass, flood and statistics */
+  segmentStats(): { rounds: number; brickVisits: number; predicateMs: number; floodMs: number; statsMs: number };
   dispose(): void;
 }
 /** viewer.ts:1455-1462: keeps the worker factory, returns the element-name -> class table ("volxel-3d-viewer") */

@@ -39,6 +39,7 @@ function parseParamsLayout(name = 'VxParams', size = native.sizeofParams()) {
 const LAYOUT = parseParamsLayout();
 const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams());
 const ISO_LAYOUT = parseParamsLayout('VxIsoParams', native.sizeofIsoParams());
+const SEGMENT_LAYOUT = parseParamsLayout('VxSegmentParams', native.sizeofSegmentParams());
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
 const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
@@ -423,6 +424,10 @@ class Volxel3DDicomRenderer {
     this.restartRendering();
   }
 
+  densityTransform() { return M.mul(this.volume.transform, this.volume.grid.transform); } // volume.ts:14-16
+  /** the index-from-world matrix bindUniforms sends as density_transform_inv (doubles; the uniform holds them as float32) */
+  densityTransformInv() { return M.invert(this.densityTransform()); }
+
   bindUniforms() { // viewer.ts:1295-1357 + scene.ts:53-56
     if (!this.volume) throw new Error('Trying to bind uniforms without a volume.');
     const p = new ParamsBlock(), s = this.settings;
@@ -430,7 +435,7 @@ class Volxel3DDicomRenderer {
     p.set('camera_view', view); p.set('camera_proj', proj);
     p.set('camera_view_inv', M.invert(M.f32(view))); p.set('camera_proj_inv', M.invert(M.f32(proj)));
     p.set('camera_ortho', this.camera.orthoHalfHeight !== null ? 1 : 0);
-    const combined = M.mul(this.volume.transform, this.volume.grid.transform); // volume.ts:14-16
+    const combined = this.densityTransform();
     const e = this.volume.grid.indexExtent;
     const lo = M.apply(combined, [0, 0, 0, 1]), hi = M.apply(combined, [e[0], e[1], e[2], 1]);
     p.set('volume_aabb_min', [0, 1, 2].map(i => lo[i] + (hi[i] - lo[i]) * s.volumeClipMin[i]));
@@ -438,7 +443,7 @@ class Volxel3DDicomRenderer {
     const [mn, maj] = this.volume.grid.minMaj, k = this.densityScale * s.densityMultiplier;
     p.set('volume_min', mn * k); p.set('volume_maj', maj * k); p.set('volume_inv_maj', 1 / (maj * k));
     p.set('volume_albedo', [0.9, 0.9, 0.9]); p.set('volume_phase_g', 0); p.set('volume_density_scale', k);
-    p.set('density_transform', combined); p.set('density_transform_inv', M.invert(combined));
+    p.set('density_transform', combined); p.set('density_transform_inv', this.densityTransformInv());
     p.set('sample_range', s.sampleRange);
     p.set('light_dir', s.lightDir); p.set('env_strength', this.envStrength);
     p.set('show_environment', s.showEnvironment ? 1 : 0); p.set('use_env', s.useEnv && this.environment ? 1 : 0); p.set('bounces', s.bounces);
@@ -612,6 +617,65 @@ class Volxel3DDicomRenderer {
   }
   /** the last isosurface: rays, hits, samples, refineSamples, skipped and its kernel time (vx_iso_stats) */
   isoStats() { return native.isoStats(this.ctx); }
+
+  /** vx_segment: the connected component of lo <= d <= hi holding the voxel seed = [x, y, z] (DESIGN.md section 2
+   *  "Segmentation").  opts: { hi = Infinity (the largest float32), connectivity = 6 | 26, box = null ([[x0, y0, z0],
+   *  [x1, y1, z1]], inclusive; null: the whole volume), maxRounds = 0 (no practical cap) } -> { count, bboxLo, bboxHi, dMin,
+   *  dMax, dSum, mean, rounds, converged, brickVisits }.  Binds the current uniforms first. */
+  segment(seed, lo, { hi = Infinity, connectivity = 6, box = null, maxRounds = 0 } = {}) {
+    const e = this.sliceExtent();
+    const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
+    if (!ints(seed) || !seed.every((x, a) => x >= 0 && x < e[a])) throw new Error(`segment: seed ${seed} is outside the index extent ${e}`);
+    const F32_MAX = 3.4028234663852886e38;
+    const l32 = Math.fround(lo), h32 = hi === Infinity ? F32_MAX : Math.fround(hi);
+    if (!Number.isFinite(l32) || !Number.isFinite(h32)) throw new Error('segment: lo and hi must be finite (hi may be Infinity)');
+    if (l32 > h32) throw new Error(`segment: lo = ${lo} > hi = ${hi}`);
+    if (connectivity !== 6 && connectivity !== 26) throw new Error(`segment: connectivity must be 6 or 26, not ${connectivity}`);
+    const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
+    if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
+      throw new Error(`segment: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+    if (!Number.isInteger(maxRounds) || maxRounds < 0 || maxRounds > 4294967295) throw new Error(`segment: maxRounds must be an integer >= 0`);
+    const p = new ParamsBlock(SEGMENT_LAYOUT);
+    p.set('seed', seed); p.set('lo', l32); p.set('hi', h32); p.set('connectivity', connectivity);
+    p.set('box_lo', blo); p.set('box_hi', bhi); p.set('max_rounds', maxRounds);
+    this.bindUniforms();
+    const r = native.segment(this.ctx, p.buffer);
+    r.mean = r.count ? r.dSum / r.count : NaN;
+    return r;
+  }
+  /** the current segment, one bit per voxel of (z, y, x) in C order, LSB first: a Uint8Array of X*Y*Z/8 bytes */
+  segmentMask() {
+    const e = this.sliceExtent();
+    const bits = new Uint8Array(e[0] * e[1] * e[2] / 8);
+    native.segmentMask(this.ctx, bits);
+    return bits;
+  }
+  /** the current segment on a slice spec (axial / coronal / sagittal or { origin, du, dv, dn, size, slabSamples }):
+   *  { mask: Uint8Array (W*H, 0 / 1, row 0 = y = 0), width, height } */
+  sliceMask({ origin, du, dv, dn, size, slabSamples = 1 }) {
+    const [W, H] = size;
+    if (!(W >= 1 && W <= 16384 && H >= 1 && H <= 16384)) throw new Error(`sliceMask: size must be 1 .. 16384 per side, not ${W} x ${H}`);
+    const p = new ParamsBlock(SLICE_LAYOUT);
+    p.set('origin', origin); p.set('du', du); p.set('dv', dv); p.set('dn', dn);
+    p.set('size', [W, H]); p.set('slab_samples', slabSamples); p.set('reduce', 0); p.set('display', 0); p.set('window', [0, 1]);
+    const mask = new Uint8Array(W * H);
+    native.sliceMask(this.ctx, p.buffer, mask);
+    return { mask, width: W, height: H };
+  }
+  /** the voxel [x, y, z] nearest a world point, or null outside the volume: q = density_transform_inv * w - 1/2 in doubles,
+   *  with the float32 matrix the uniforms carry (densityTransformInv, as bindUniforms sends it), each row summed x, y, z,
+   *  translation in that order, then floor(q + 1/2) per axis -- what Renderer.voxel_index does in Python */
+  voxelIndex(w) {
+    if (!this.volume) throw new Error('voxelIndex: no volume');
+    if (!(Array.isArray(w) && w.length === 3 && w.every(Number.isFinite))) throw new Error('voxelIndex: w must be three finite numbers');
+    const e = this.volume.grid.indexExtent;
+    const m = this.densityTransformInv().map(Math.fround);
+    const q = [0, 1, 2].map(r => m[r] * w[0] + m[4 + r] * w[1] + m[8 + r] * w[2] + m[12 + r] - 0.5);
+    const i = q.map(a => Math.floor(a + 0.5));
+    return i.every((x, a) => x >= 0 && x < e[a]) ? i : null;
+  }
+  /** the last segment: rounds, brickVisits and the times of its predicate pass, flood and statistics (vx_segment_stats) */
+  segmentStats() { return native.segmentStats(this.ctx); }
 }
 
 function sliceSpec(name, i, n, origin, du, dv, dn, size) {

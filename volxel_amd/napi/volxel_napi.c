@@ -608,6 +608,104 @@ static napi_value n_iso_stats(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* segment(ctx, ArrayBuffer holding one VxSegmentParams) -> { count, bboxLo, bboxHi, dMin, dMax, dSum, rounds, converged,
+ * brickVisits } (vx_segment) */
+static napi_value set_num(napi_env env, napi_value o, const char* name, double x) {
+  napi_value v;
+  if (napi_create_double(env, x, &v) != napi_ok || napi_set_named_property(env, o, name, v) != napi_ok) return NULL;
+  return o;
+}
+static napi_value set_u3(napi_env env, napi_value o, const char* name, const uint32_t* x) {
+  napi_value arr, v;
+  if (napi_create_array_with_length(env, 3, &arr) != napi_ok) return NULL;
+  for (uint32_t i = 0; i < 3; ++i)
+    if (napi_create_uint32(env, x[i], &v) != napi_ok || napi_set_element(env, arr, i, v) != napi_ok) return NULL;
+  if (napi_set_named_property(env, o, name, arr) != napi_ok) return NULL;
+  return o;
+}
+static napi_value n_segment(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* d;
+  size_t n;
+  NAPI_OK(napi_get_arraybuffer_info(env, a[1], &d, &n));
+  if (n != sizeof(VxSegmentParams)) return throw_msg(env, "segment: buffer is not sizeof(VxSegmentParams)");
+  VxSegmentParams sp;
+  memcpy(&sp, d, sizeof sp);
+  VxSegmentResult r;
+  if (vx_segment(c, &sp, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o, b;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "count", (double)r.count) || !set_u3(env, o, "bboxLo", r.bbox_lo) || !set_u3(env, o, "bboxHi", r.bbox_hi) ||
+      !set_num(env, o, "dMin", r.d_min) || !set_num(env, o, "dMax", r.d_max) || !set_num(env, o, "dSum", r.d_sum) ||
+      !set_num(env, o, "rounds", r.rounds) || !set_num(env, o, "brickVisits", (double)r.brick_visits))
+    return throw_msg(env, "segment: could not build the result");
+  NAPI_OK(napi_get_boolean(env, r.converged != 0, &b));
+  NAPI_OK(napi_set_named_property(env, o, "converged", b));
+  return o;
+}
+
+static napi_value n_sizeof_segment_params(napi_env env, napi_callback_info info) {
+  (void)info;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, (uint32_t)sizeof(VxSegmentParams), &v));
+  return v;
+}
+
+/* segmentMask(ctx, Uint8Array of X*Y*Z/8 bytes) (vx_segment_read_mask) */
+static napi_value n_segment_mask(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* bits;
+  size_t nb;
+  if (!typed_or_null(env, a[1], napi_uint8_array, &bits, &nb)) return NULL;
+  if (!bits) return throw_msg(env, "segmentMask: bits must be a Uint8Array");
+  if (vx_segment_read_mask(c, (uint8_t*)bits, (uint64_t)nb) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+
+/* sliceMask(ctx, ArrayBuffer holding one VxSliceParams, Uint8Array of size[0]*size[1] bytes) (vx_slice_segment_mask) */
+static napi_value n_slice_mask(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* d;
+  size_t n;
+  NAPI_OK(napi_get_arraybuffer_info(env, a[1], &d, &n));
+  if (n != sizeof(VxSliceParams)) return throw_msg(env, "sliceMask: buffer is not sizeof(VxSliceParams)");
+  VxSliceParams sp;
+  memcpy(&sp, d, sizeof sp);
+  void* out;
+  size_t no;
+  if (!typed_or_null(env, a[2], napi_uint8_array, &out, &no)) return NULL;
+  if (!out || no < (size_t)sp.size[0] * sp.size[1]) return throw_msg(env, "sliceMask: out shorter than size[0]*size[1] bytes");
+  if (vx_slice_segment_mask(c, &sp, (uint8_t*)out) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+
+/* segmentStats(ctx) -> { rounds, brickVisits, predicateMs, floodMs, statsMs } (vx_segment_stats) */
+static napi_value n_segment_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t rounds = 0;
+  uint64_t visits = 0;
+  double ms[3] = {0.0, 0.0, 0.0};
+  if (vx_segment_stats(c, &rounds, &visits, ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "rounds", rounds) || !set_num(env, o, "brickVisits", (double)visits) || !set_num(env, o, "predicateMs", ms[0]) ||
+      !set_num(env, o, "floodMs", ms[1]) || !set_num(env, o, "statsMs", ms[2]))
+    return throw_msg(env, "segmentStats: could not build the result");
+  return o;
+}
+
 static napi_value n_reset_counters(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (!get_args(env, info, 1, a)) return NULL;
@@ -775,6 +873,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"resetCounters", n_reset_counters}, {"shadowStats", n_shadow_stats}, {"readShadowGrid", n_read_shadow_grid},
       {"slice", n_slice}, {"sliceStats", n_slice_stats}, {"sizeofSliceParams", n_sizeof_slice_params},
       {"isosurface", n_isosurface}, {"isoStats", n_iso_stats}, {"sizeofIsoParams", n_sizeof_iso_params},
+      {"segment", n_segment}, {"sizeofSegmentParams", n_sizeof_segment_params}, {"segmentMask", n_segment_mask},
+      {"sliceMask", n_slice_mask}, {"segmentStats", n_segment_stats},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {

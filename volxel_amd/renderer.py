@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -122,6 +123,27 @@ def register_volxel_components(worker_factory=None):
     _worker_factory = worker_factory
     COMPONENTS["volxel-3d-viewer"] = Volxel3DRenderer
     return COMPONENTS
+
+
+@dataclass(frozen=True)
+class Segment:
+    """What Volxel3DRenderer.segment returns (VxSegmentResult): the voxel count, the inclusive bbox (x, y, z), min / max / sum
+    (float64) / mean of the density over the segment (0, 0, 0 and nan when empty), the flood's rounds and brick visits (which may
+    vary from run to run), whether it converged, and its volume: volume_grid = count * |det(grid.transform[:3, :3])| in the
+    grid's own units (the voxel spacing: mm^3 for DICOM), volume_world = count * |det(density_transform[:3, :3])| in the
+    scene's, where the volume is normalised to a unit box."""
+    count: int
+    bbox_lo: tuple
+    bbox_hi: tuple
+    d_min: float
+    d_max: float
+    d_sum: float
+    mean: float
+    rounds: int
+    converged: bool
+    brick_visits: int
+    volume_grid: float
+    volume_world: float
 
 
 class Volxel3DRenderer:
@@ -679,6 +701,118 @@ class Volxel3DRenderer:
         ms = C.c_double()
         self._check(self._lib.vx_iso_stats(self._ctx, *[C.byref(a) for a in v], C.byref(ms)))
         return tuple(a.value for a in v) + (ms.value,)
+
+    def segment(self, seed, lo: float, hi: float = math.inf, connectivity: int = 6, box=None, max_rounds: int = 0):
+        """Seeded region growing (vx_segment, DESIGN.md section 2 "Segmentation"): the connected component of
+        lo <= d(i) <= hi (both inclusive; d(i) = (volume_density_scale * v(i)) * volume_inv_maj, the isosurfaces' density at
+        q = i) inside `box` that holds the voxel `seed` = (x, y, z).  connectivity: 6 (faces) or 26 (faces, edges, corners).
+        box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices, or None for the whole volume.  hi = inf stands for the
+        largest float32.  max_rounds: a cap on the flood's rounds (0: no practical cap); a capped flood returns
+        converged = False and a connected part of the segment.  Binds the current uniforms first.  Returns a `Segment`; the
+        mask stays on the device (segment_mask, slice_mask) until the next segment or upload."""
+        if self.volume is None:
+            raise VolxelError("segment: no volume (setup_from_grid first)")
+        ext = [int(e) for e in self.volume.grid.index_extent]
+        q = _abi.VxSegmentParams()
+        sd = tuple(seed)
+        if len(sd) != 3 or any(isinstance(a, bool) or int(a) != a for a in sd):
+            raise ValueError(f"seed must be three integer voxel indices (x, y, z), not {seed!r}")
+        if not all(0 <= int(a) < e for a, e in zip(sd, ext)):
+            raise ValueError(f"seed {seed!r} is outside the index extent {tuple(ext)}")
+        lo32 = np.float32(lo)
+        hi32 = np.float32(np.finfo(np.float32).max) if hi == math.inf else np.float32(hi)
+        if not (np.isfinite(lo32) and np.isfinite(hi32)):
+            raise ValueError(f"lo and hi must be finite (hi may be inf), not {lo!r}, {hi!r}")
+        if lo32 > hi32:
+            raise ValueError(f"lo = {lo!r} > hi = {hi!r}")
+        if connectivity not in (6, 26) or isinstance(connectivity, bool):
+            raise ValueError(f"connectivity must be 6 or 26, not {connectivity!r}")
+        if box is None:
+            blo, bhi = (0, 0, 0), tuple(e - 1 for e in ext)
+        else:
+            try:
+                blo, bhi = (tuple(v) for v in box)
+            except (TypeError, ValueError):
+                raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)), not {box!r}") from None
+            if len(blo) != 3 or len(bhi) != 3 or any(isinstance(a, bool) or int(a) != a for a in blo + bhi):
+                raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)) of integers, not {box!r}")
+            blo, bhi = tuple(int(a) for a in blo), tuple(int(a) for a in bhi)
+            if not all(0 <= a <= b < e for a, b, e in zip(blo, bhi, ext)):
+                raise ValueError(f"box {box!r} is empty or outside the index extent {tuple(ext)}")
+        if isinstance(max_rounds, bool) or int(max_rounds) != max_rounds or not 0 <= int(max_rounds) < 2 ** 32:
+            raise ValueError(f"max_rounds must be an integer 0 .. 2^32 - 1, not {max_rounds!r}")
+        q.seed[0], q.seed[1], q.seed[2] = (int(a) for a in sd)
+        q.lo, q.hi = float(lo32), float(hi32)
+        q.connectivity = int(connectivity)
+        q.box_lo[0], q.box_lo[1], q.box_lo[2] = blo
+        q.box_hi[0], q.box_hi[1], q.box_hi[2] = bhi
+        q.max_rounds = int(max_rounds)
+        p = self.bind_uniforms()
+        res = _abi.VxSegmentResult()
+        self._check(self._lib.vx_segment(self._ctx, C.byref(q), C.byref(res)))
+        g3 = np.asarray(self.volume.grid.transform, dtype=np.float64)[:3, :3]
+        d3 = np.asarray(p.density_transform[:], dtype=np.float32).astype(np.float64).reshape(4, 4).T[:3, :3]
+        n = int(res.count)
+        return Segment(count=n, bbox_lo=tuple(res.bbox_lo[:]), bbox_hi=tuple(res.bbox_hi[:]), d_min=float(res.d_min),
+                       d_max=float(res.d_max), d_sum=float(res.d_sum), mean=float(res.d_sum) / n if n else math.nan,
+                       rounds=int(res.rounds), converged=bool(res.converged), brick_visits=int(res.brick_visits),
+                       volume_grid=n * abs(float(np.linalg.det(g3))), volume_world=n * abs(float(np.linalg.det(d3))))
+
+    def segment_mask(self) -> np.ndarray:
+        """the current segment as a (Z, Y, X) bool array over the index extent (vx_segment_read_mask)"""
+        if self.volume is None:
+            raise VolxelError("segment_mask: no volume")
+        X, Y, Z = (int(e) for e in self.volume.grid.index_extent)
+        bits = np.empty(X * Y * Z // 8, dtype=np.uint8)
+        self._check(self._lib.vx_segment_read_mask(self._ctx, bits.ctypes.data, bits.size))
+        return np.unpackbits(bits, bitorder="little").astype(bool).reshape(Z, Y, X)
+
+    def slice_mask(self, sp) -> np.ndarray:
+        """the current segment on the slice or slab sp (volxel_amd.mpr; reduce, display and window are ignored): an (H, W)
+        bool array, True where the nearest voxel of any slab sample is in the segment (vx_slice_segment_mask)"""
+        if not isinstance(sp, _abi.VxSliceParams):
+            raise TypeError("sp must be a VxSliceParams (volxel_amd.mpr builds them)")
+        W, H, N = int(sp.size[0]), int(sp.size[1]), int(sp.slab_samples)
+        if not (1 <= W <= _abi.SLICE_MAX_SIZE and 1 <= H <= _abi.SLICE_MAX_SIZE):
+            raise ValueError(f"slice size must be 1 .. {_abi.SLICE_MAX_SIZE} per side, not {W} x {H}")
+        if not 1 <= N <= _abi.SLICE_MAX_SAMPLES:
+            raise ValueError(f"slab_samples must be 1 .. {_abi.SLICE_MAX_SAMPLES}, not {N}")
+        for name in ("origin", "du", "dv", "dn"):
+            if not np.isfinite(np.asarray(getattr(sp, name)[:], dtype=np.float32)).all():
+                raise ValueError(f"slice {name} must be finite")
+        out = np.empty((H, W), dtype=np.uint8)
+        self._check(self._lib.vx_slice_segment_mask(self._ctx, C.byref(sp), out.ctypes.data))
+        return out.astype(bool)
+
+    def segment_stats(self):
+        """(rounds, brick_visits, predicate_ms, flood_ms, stats_ms) of the last segment; flood_ms runs from the first round to
+        the last, the host's read-backs of the worklist length included"""
+        n, v = C.c_uint32(), C.c_uint64()
+        ms = (C.c_double * 3)()
+        self._check(self._lib.vx_segment_stats(self._ctx, C.byref(n), C.byref(v), ms))
+        return (n.value, v.value) + tuple(ms)
+
+    def voxel_index(self, world_point):
+        """the voxel (x, y, z) nearest a world point, or None outside the volume: q = density_transform_inv * w - 1/2 in float64
+        (the current params, as mpr.oblique maps planes), then floor(q + 1/2) per axis.  A point from pick() lies on the
+        interpolated surface, so its nearest voxel can fall just below the threshold: seed a segment with it where the
+        structure is thicker than a voxel, or lower lo a little."""
+        if self.volume is None:
+            raise VolxelError("voxel_index: no volume")
+        w = np.asarray(world_point, dtype=np.float64).reshape(-1)
+        if w.size != 3 or not np.isfinite(w).all():
+            raise ValueError(f"world_point must be three finite numbers, not {world_point!r}")
+        # the float32 matrix the uniforms carry now (compute_params, as bind_uniforms sends it), not a copy from an earlier bind
+        p = compute_params(self.settings, self.camera, self.volume, self.density_scale, self.width, self.height,
+                           self.env_strength, self.shard_rank, self.shard_count, has_environment=self.environment is not None)
+        m = [float(v) for v in np.asarray(p.density_transform_inv[:], dtype=np.float32)]   # column major
+        # q = m * w - 1/2 in float64, each row summed x, y, z, translation in that order (the JS host's voxelIndex sums alike)
+        qv = [m[r] * w[0] + m[4 + r] * w[1] + m[8 + r] * w[2] + m[12 + r] - 0.5 for r in range(3)]
+        i = [math.floor(a + 0.5) for a in qv]
+        ext = [int(e) for e in self.volume.grid.index_extent]
+        if not all(0 <= a < e for a, e in zip(i, ext)):
+            return None
+        return tuple(int(a) for a in i)
 
     def probe_gather_rate(self, lines: int, distinct: int | None = None):
         """clocks per 16-byte-per-lane gather instruction per CU (nominal clock) when the 64 lanes form `lines` groups of
