@@ -512,6 +512,27 @@ int vx_slice_segment_mask(VxContext* ctx, const VxSliceParams* sp, uint8_t* out)
  * call.  Any pointer may be NULL.  group: member 0. */
 int vx_segment_stats(VxContext* ctx, uint32_t* rounds, uint64_t* brick_visits, double* kernel_ms);
 
+/* ---- segment views (DESIGN.md section 2 "Segment views"): show only, or hide, the current segment.  With a view other than
+ * OFF the covered calls -- vx_render_frame / vx_render_frames in VX_MODE_DVR, _DVR_PHONG, _MIP and _MINIP, and vx_isosurface
+ * (hence picking) -- sample the masked volume: every decoded voxel v(i) reads +0.0f where it is hidden (ONLY: i is not in the
+ * segment; HIDE: i is in it) and exactly what it reads today elsewhere.  The image is, bit for bit, that of a volume whose hidden
+ * voxels decode to 0.  Masked launches run without range skipping (dvr_skip_empty and VxIsoParams::skip are ignored; the
+ * isosurface reports skipped = 0).  vx_slice, vx_slice_segment_mask and vx_segment keep reading the unmasked data.  With the view
+ * on, a covered call returns VX_ERR_INVALID, naming the reason, for a path-traced render mode, debug_hits, dvr_shadow_stride != 0,
+ * a launch without an LDS-window kernel (a REFERENCE or CELLQUAD layout for DVR and the projections, dvr_ert_tau <= 0, a TF
+ * longer than the LDS holds, VX_DVR_KERNEL=generic) and no current segment.  An upload drops the segment and resets the view to
+ * OFF; a new vx_segment replaces the mask the next covered call reads. */
+typedef enum VxSegmentView {
+  VX_SEGVIEW_OFF = 0,   /* default: the unmasked volume                       */
+  VX_SEGVIEW_ONLY = 1,  /* the segment alone: voxels outside it read 0         */
+  VX_SEGVIEW_HIDE = 2   /* everything but the segment: its voxels read 0       */
+} VxSegmentView;
+/* VX_ERR_INVALID for a value outside VxSegmentView, a device group (the segment lives on member 0 only), and ONLY / HIDE with no
+ * current segment.  Host state only: nothing is launched; the accumulator is the caller's to restart. */
+int vx_set_segment_view(VxContext* ctx, int view);
+/* the current view (VX_SEGVIEW_OFF after an upload); VX_ERR_INVALID for NULL view */
+int vx_get_segment_view(VxContext* ctx, int* view);
+
 /* test hook (no reference counterpart): the device's R8-unorm decode table, 256 floats */
 int vx_debug_unorm_table(VxContext* ctx, float* out256);
 /* test hook: the host-built empty-space bitmask (pure CPU; bits_out may be NULL to query level/dims) */

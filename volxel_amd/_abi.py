@@ -148,6 +148,8 @@ def load_library():
         "vx_segment_read_mask": ([vp, vp, u64], i32),
         "vx_slice_segment_mask": ([vp, P(VxSliceParams), vp], i32),
         "vx_segment_stats": ([vp, P(u32), P(u64), P(C.c_double)], i32),
+        "vx_set_segment_view": ([vp, i32], i32),
+        "vx_get_segment_view": ([vp, P(i32)], i32),
         # preprocessor
         "vxb_build_from_u16": ([vp, P(u32), P(C.c_float), C.c_uint16, i32, P(vp)], i32),
         "vxb_read_dicoms_to_grid": ([P(vp), P(u64), u32, i32, P(vp)], i32),

@@ -206,6 +206,7 @@ struct VxContext {
   void* seg_alloc = nullptr;
   SegDev seg{};
   bool seg_valid = false;     // a segment of the resident volume is current
+  int seg_view = VX_SEGVIEW_OFF;   // vx_set_segment_view; OFF again after an upload (free_volume)
   uint8_t* seg_bytes = nullptr;
   size_t seg_bytes_cap = 0;
   uint8_t* seg_ov = nullptr;
@@ -259,6 +260,7 @@ static void free_volume(VxContext* c) {
   c->seg_alloc = nullptr;
   c->seg = SegDev{};
   c->seg_valid = false;
+  c->seg_view = VX_SEGVIEW_OFF;
   if (c->seg_bytes) (void)hipFree(c->seg_bytes);
   c->seg_bytes = nullptr;
   c->seg_bytes_cap = 0;
@@ -762,6 +764,9 @@ struct LaunchPlan {
   dim3 grid, block{256};
   size_t lds = 0;                     // dynamic LDS bytes
   bool fuse = false;                  // the kernel folds the running mean of the launch itself (MultiOut::fuse)
+  bool segv = false;                  // DVR_LDS, PROJ_LDS: the segment view's kernel (render_dvr_lds_seg, render_proj_lds_seg)
+  const uint32_t* segm = nullptr;     // its segment mask (SegDev::seg as dwords)
+  uint32_t seg_inv = 0u;              // 0: ONLY, ~0u: HIDE
 };
 
 static bool tuned_possible(const VxContext* c) {
@@ -791,6 +796,7 @@ static bool is_tuned(const VxContext* c) {
 // kernels at 8, 16, 32 or 64 frames (a wave holds every frame of its 8, 4, 2 or 1 pixels), render_generic for `default`,
 // `no_dda` or `raymarch` at exactly 32 frames (2 pixels x 32 frames per wave).  Every other multi-frame launch writes
 // per-frame result slabs that merge_results blends in frame order.
+static bool lds_window_kernel(Kernel k) { return k == Kernel::DVR_LDS || k == Kernel::PROJ_LDS; }
 static bool folds(Kernel kernel, int mode, uint32_t n) {
   switch (kernel) {
     case Kernel::DVR_LDS:
@@ -832,11 +838,19 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo, bool probe
   } else {
     lp.skip = p.dvr_skip_empty && c->dv.skip_bits;
   }
+  // the segment view (check_segment_view has refused every launch it does not cover): the masked instance, without skipping
+  if (c->seg_view != VX_SEGVIEW_OFF && lds_window_kernel(lp.kernel)) {
+    lp.segv = true;
+    lp.segm = reinterpret_cast<const uint32_t*>(c->seg.seg);
+    lp.seg_inv = c->seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u;
+    lp.skip = false;
+    lp.bounds = nullptr;
+  }
   lp.u8 = lp.layout == VX_LAYOUT_BRICKU8 && c->dv.bu;
   lp.probe = probe;
   lp.order = probe ? nullptr : c->order;
   // a frame's blocks per frame slot (the LDS-window kernels take a count of 0 as 1)
-  const bool lds_window = lp.kernel == Kernel::DVR_LDS || lp.kernel == Kernel::PROJ_LDS;
+  const bool lds_window = lds_window_kernel(lp.kernel);
   lp.grid = dim3(frame_blocks(c) * (lds_window && mo.count == 0u ? 1u : mo.count));
   lp.fuse = c->sw.dvr_fuse && folds(lp.kernel, lp.mode, mo.count);
   lp.lds = lds_bytes(c, lp);
@@ -876,6 +890,16 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
   const hipStream_t s = c->stream;
   switch (lp.kernel) {
     case Kernel::DVR_LDS:
+      if (lp.segv) {
+        with_bool(lp.u8, [&](auto u8) {
+          with_bool(lp.phong, [&](auto ph) {
+            constexpr bool PH = decltype(ph)::value;
+            hipLaunchKernelGGL((render_dvr_lds_seg<(PH ? VX_LDS_S_PHONG : VX_LDS_S), PH, decltype(u8)::value>), lp.grid, lp.block,
+                               lp.lds, s, p, v, tf, n, mo, weight, tm, lp.order, lp.segm, lp.seg_inv);
+          });
+        });
+        break;
+      }
       with_bool(lp.skip, [&](auto sk) {
         with_bool(lp.u8, [&](auto u8) {
           constexpr bool SK = decltype(sk)::value, U8 = decltype(u8)::value;
@@ -893,6 +917,15 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
       });
       break;
     case Kernel::PROJ_LDS:
+      if (lp.segv) {
+        with_bool(lp.minip, [&](auto mi) {
+          with_bool(lp.u8, [&](auto u8) {
+            hipLaunchKernelGGL((render_proj_lds_seg<VX_LDS_S, decltype(mi)::value, decltype(u8)::value>), lp.grid, lp.block, lp.lds, s,
+                               p, v, tf, n, mo, weight, tm, lp.order, lp.segm, lp.seg_inv);
+          });
+        });
+        break;
+      }
       with_bool(lp.minip, [&](auto mi) {
         with_bool(lp.skip, [&](auto sk) {
           with_bool(lp.u8, [&](auto u8) {
@@ -979,11 +1012,15 @@ static int rebuild_iso_bounds(VxContext* c) {
   return VX_OK;
 }
 // launches iso_first_hit<the layout of slice_layout, ip.skip> over the window (x0, y0, ww, wh) on the context's stream
+// (the segment view: iso_first_hit_seg<the layout of slice_layout>, never skipping)
 static void launch_iso(VxContext* c, const VxIsoParams& ip, uint32_t ww, uint32_t wh) {
   const dim3 grid((ww + 15u) / 16u, (wh + 15u) / 16u);
   with_layout(slice_layout(c), [&](auto lay) {
     constexpr int LAY = decltype(lay)::value;
-    if (ip.skip)
+    if (c->seg_view != VX_SEGVIEW_OFF)
+      hipLaunchKernelGGL((iso_first_hit_seg<LAY>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, c->iso_rgba, c->iso_hit,
+                         c->iso_count_dev, reinterpret_cast<const uint32_t*>(c->seg.seg), c->seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u);
+    else if (ip.skip)
       hipLaunchKernelGGL((iso_first_hit<LAY, true>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, c->iso_bound, c->iso_rgba,
                          c->iso_hit, c->iso_count_dev);
     else
@@ -1792,6 +1829,28 @@ int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
   return alloc_framebuffers(c);
 }
 
+// The segment view's refusals, in one place: a covered call (`iso`: vx_isosurface; else a render launch, after its layouts are
+// resident) with the view on fails here, before anything is launched, unless a masked instance serves it.
+static int check_segment_view(VxContext* c, const char* fn, bool iso) {
+  if (c->seg_view == VX_SEGVIEW_OFF) return VX_OK;
+  const char* view = c->seg_view == VX_SEGVIEW_ONLY ? "only" : "hide";
+  if (is_group(c)) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for a device group (the segment lives on member 0)", fn, view);
+  if (!c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s without a current segment (vx_segment first; an upload drops it)", fn, view);
+  if (iso) return VX_OK;
+  const VxParams& p = c->params;
+  if (p.render_mode <= VX_MODE_RAYMARCH)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for the path-traced render mode %d (default, no_dda, raymarch)", fn, view,
+            p.render_mode);
+  if (p.debug_hits) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not with debug_hits", fn, view);
+  if (p.dvr_shadow_stride != 0)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for shadowed DVR (dvr_shadow_stride = %d)", fn, view, p.dvr_shadow_stride);
+  if (!use_lds_kernel(c))
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: this launch has no LDS-window kernel (layout %d, dvr_ert_tau <= 0, a TF of "
+            "more than %u entries or VX_DVR_KERNEL=generic)", fn, view, eff_layout(c), (unsigned)TF_LDS_MAX);
+  return VX_OK;
+}
+
 static int prepare_render(VxContext* c) {
   if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
   if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
@@ -1883,6 +1942,7 @@ static int prepare_render(VxContext* c) {
       rc = ensure_brickf32(c);
     if (rc) return rc;
   }
+  if (int rc = check_segment_view(c, "vx_render_frame", false)) return rc;
   if (shadow_on(c) && !c->shadow_table.current(c->params)) {   // after the layouts: the build samples them
     int rc = rebuild_light_grid(c);
     if (rc) return rc;
@@ -2515,6 +2575,8 @@ int vx_isosurface(VxContext* c, const VxIsoParams* ip, float* rgba_out, float* h
     VX_HIP(c, hipMalloc(&c->iso_hit, px * sizeof(float4)));
     c->iso_cap = px;
   }
+  if (int rc = check_segment_view(c, "vx_isosurface", true)) return rc;
+  if (c->seg_view != VX_SEGVIEW_OFF) q.skip = 0;   // masked: no range skipping
   if (q.skip && !c->iso_table.current(c->params)) {
     const int rc = rebuild_iso_bounds(c);
     if (rc) return rc;
@@ -2569,6 +2631,8 @@ static int ensure_segment(VxContext* c) {
   p += (size_t)nb * 64u;
   s.seg = reinterpret_cast<uint64_t*>(p);
   p += (size_t)nb * 64u;
+  // (the masked LDS-window staging reads the dword right behind the mask for the zero chunk behind the last brick -- the first
+  // of `partial`, inside this allocation -- and drops its bits: vx_dvr_lds_march.inc)
   s.partial = reinterpret_cast<double*>(p);
   p += (size_t)nb * 8u;
   s.st = reinterpret_cast<SegStats*>(p);
@@ -2773,6 +2837,24 @@ int vx_slice_segment_mask(VxContext* c, const VxSliceParams* sp, uint8_t* out) {
   VX_HIP(c, hipGetLastError());
   VX_HIP(c, hipMemcpyAsync(out, c->seg_ov, px, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_set_segment_view(VxContext* c, int view) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_set_segment_view", "the segment lives on member 0 only");
+  if (view < VX_SEGVIEW_OFF || view > VX_SEGVIEW_HIDE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: view = %d is not VX_SEGVIEW_OFF, _ONLY or _HIDE", view);
+  if (view != VX_SEGVIEW_OFF && !c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: %s without a current segment (vx_segment first; an upload drops it)",
+            view == VX_SEGVIEW_ONLY ? "only" : "hide");
+  c->seg_view = view;
+  return VX_OK;
+}
+
+int vx_get_segment_view(VxContext* c, int* view) {
+  if (!c || !view) return VX_ERR_INVALID;
+  *view = c->seg_view;
   return VX_OK;
 }
 

@@ -148,6 +148,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PHONG ? (SK
   constexpr int PROJ = 0;
   const ShadowGrid sg{};
   const float* const pbound = nullptr;
+  constexpr bool SEGV = false;
+  [[maybe_unused]] const uint32_t* const segm = nullptr;
+  [[maybe_unused]] const uint32_t seg_inv = 0u;
+#include "vx_dvr_lds_march.inc"
+}
+// The segment view (VX_SEGVIEW_ONLY / _HIDE, DESIGN.md section 2 "Segment views"): the same march on the masked volume -- the
+// staging zeroes a voxel whose bit of the segment mask `segm` (brick-major, 8 x u64 per brick, as vx_segment.hpp) XOR `seg_inv`
+// (0: ONLY, ~0u: HIDE) is 0.  No range skipping: the skip bits are built from the unmasked bricks' ranges.  A kernel of its own,
+// as the shadowed form: the kernels above stay the code they were.
+template <int S, bool PHONG, bool U8>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PHONG ? VX_W_LDS_PHONG : VX_W_LDS, 8))) void render_dvr_lds_seg(
+    const VxParams p, const DevVolume v, const float4* __restrict__ tf_global, uint32_t tf_len, const MultiOut mo, float weight,
+    const TileMap tm, const uint32_t* __restrict__ order, const uint32_t* __restrict__ segm, const uint32_t seg_inv) {
+  constexpr bool SKIP = false;
+  constexpr bool SHADOW = false;
+  constexpr int PROJ = 0;
+  const ShadowGrid sg{};
+  const float* const pbound = nullptr;
+  constexpr bool SEGV = true;
 #include "vx_dvr_lds_march.inc"
 }
 // Shadowed DVR (VxParams::dvr_shadow_stride): the same march, and a contributing sample adds w = dT * T_L,
@@ -162,6 +181,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W
   constexpr bool SHADOW = true;
   constexpr int PROJ = 0;
   const float* const pbound = nullptr;
+  constexpr bool SEGV = false;
+  [[maybe_unused]] const uint32_t* const segm = nullptr;
+  [[maybe_unused]] const uint32_t seg_inv = 0u;
 #include "vx_dvr_lds_march.inc"
 }
 

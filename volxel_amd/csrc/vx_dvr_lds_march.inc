@@ -7,6 +7,9 @@
 // In scope at the point of inclusion: the template parameters S, PHONG, SKIP, U8, `constexpr bool SHADOW` and `constexpr int
 // PROJ` (0: DVR / Phong; 1: MIP, 2: MinIP), the kernel arguments p, v, tf_global, tf_len, mo, weight, tm, order, `sg` (the light
 // grid; unused unless SHADOW) and `pbound` (the density bounds of range skipping per macro cell; unused unless PROJ and SKIP).
+// `constexpr bool SEGV`, `segm` and `seg_inv`: the segment view (render_dvr_lds_seg, render_proj_lds_seg; SKIP is false there) --
+// the staging zeroes every voxel whose segment bit XOR seg_inv is 0, so the march, the gradient taps and the fold see the masked
+// volume with no other change.  SEGV is false in the other kernels, where segm and seg_inv are unused.
 // PROJ: the march evaluates the same samples, keeps their largest (smallest) density instead of compositing, has no early ray
 // termination, and SKIP means range skipping: a lane flies over a macro cell whose bound cannot change its m.
   using TL = LdsTile<PHONG>;
@@ -252,6 +255,11 @@
       // selected away, whatever their index came to.)
       const uint32_t rowbase = (mad24(mad24((uint32_t)gz >> 3, bcy, (uint32_t)gy >> 3) & 0xffffffu, bcx, 0u) << 7) +
                                ((((uint32_t)gz & 7u) << 4) | (((uint32_t)gy & 7u) << 1));
+      // SEGV: the chunk's four segment bits.  A 16-byte unit `at` (brick * 128 + z * 16 + y * 2 + x / 4) is nibble `at` of
+      // the brick-major mask (8 x u64 per brick, word z, bit y * 8 + x): dword at >> 3, bits (at & 7) * 4 .. + 3, x = 0 .. 3 of
+      // the chunk.  The zero chunk behind the last brick reads the dword behind the mask (vx_api.hip ensure_segment keeps one
+      // there); its value is +0 whatever the bits say.
+      [[maybe_unused]] uint32_t sbits[NC];
       if (U8) {
         // codes and brick ranges of the row's chunks first (all loads in flight), then the decode; the unit behind the
         // last brick is a zero dword under the range {0, 0}: fma(0, 0, 0) = +0, as A4 asks for outside the volume
@@ -264,6 +272,7 @@
           const float2 rr = bur[at >> 7];
           code[c] = cw;
           rg[c] = rr;
+          if (SEGV) sbits[c] = (segm[at >> 3] >> ((at & 7u) << 2)) ^ seg_inv;
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -276,10 +285,22 @@
           const uint32_t at = (rin && xin[c]) ? rowbase + xoff[c] : zero_chunk;
           const float4 val = bf4[at];
           vals[ps][c] = val;
+          if (SEGV) sbits[c] = (segm[at >> 3] >> ((at & 7u) << 2)) ^ seg_inv;
+        }
+      }
+      if (SEGV) {   // a hidden voxel reads +0 (decode first, then mask: the masked volume's value)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          float4& val = vals[ps][c];
+          val.x = (sbits[c] & 1u) ? val.x : 0.0f;
+          val.y = (sbits[c] & 2u) ? val.y : 0.0f;
+          val.z = (sbits[c] & 4u) ? val.z : 0.0f;
+          val.w = (sbits[c] & 8u) ? val.w : 0.0f;
         }
       }
     }
-    n_loads += (U8 ? 2u : 1u) * (uint32_t)NC * (uint32_t)TL::PASSES;   // U8: a dword of codes and a brick range per chunk
+    // U8: a dword of codes and a brick range per chunk; SEGV: and a dword of segment bits
+    n_loads += ((U8 ? 2u : 1u) + (SEGV ? 1u : 0u)) * (uint32_t)NC * (uint32_t)TL::PASSES;
   };
   // stage, part 2: the rows into the wave's tile
   auto write_tile = [&](float4 (&vals)[TL::PASSES][NC]) {

@@ -24,116 +24,53 @@ struct IsoBound {
   uint32_t cmax[3];               // extent + 7 per axis
 };
 
+// The segment view (DESIGN.md section 2 "Segment views"): the decoded voxel (x, y, z) of the masked volume -- +0 where its bit of
+// the brick-major segment mask (8 x u64 per brick, word z, bit y * 8 + x; read as 16 dwords, dword z * 2 + y / 4, bit
+// (y & 3) * 8 + x) XOR `inv` (0: ONLY, ~0u: HIDE) is 0.  A voxel outside the volume reads 0 anyway; its mask index is clamped.
+template <int LAYOUT>
+VXD float seg_voxel(const DevVolume& v, const uint32_t* __restrict__ segm, uint32_t inv, int x, int y, int z) {
+  const float d = lookup_density_nearest<LAYOUT>(v, x, y, z);
+  const bool in = (uint32_t)x < v.extent[0] && (uint32_t)y < v.extent[1] && (uint32_t)z < v.extent[2];
+  const uint32_t ux = in ? (uint32_t)x : 0u, uy = in ? (uint32_t)y : 0u, uz = in ? (uint32_t)z : 0u;
+  const uint32_t b = ((uz >> 3) * v.bc[1] + (uy >> 3)) * v.bc[0] + (ux >> 3);
+  const uint32_t w = segm[(size_t)b * 16u + ((uz & 7u) << 1) + ((uy & 7u) >> 2)];
+  return ((w >> (((uy & 3u) << 3) | (ux & 7u))) ^ inv) & 1u ? d : 0.0f;
+}
+// the eight taps of cell (ix, iy, iz), mixed as trilinear_cell mixes them; SEGV: each tap through seg_voxel
+template <int LAYOUT, bool SEGV>
+VXD float iso_cell(const DevVolume& v, const uint32_t* __restrict__ segm, uint32_t inv, float density_scale, int ix, int iy, int iz,
+                   float fx, float fy, float fz) {
+  if (!SEGV) return trilinear_cell<LAYOUT>(v, density_scale, ix, iy, iz, fx, fy, fz);
+  const float v000 = seg_voxel<LAYOUT>(v, segm, inv, ix, iy, iz), v100 = seg_voxel<LAYOUT>(v, segm, inv, ix + 1, iy, iz);
+  const float v010 = seg_voxel<LAYOUT>(v, segm, inv, ix, iy + 1, iz), v110 = seg_voxel<LAYOUT>(v, segm, inv, ix + 1, iy + 1, iz);
+  const float v001 = seg_voxel<LAYOUT>(v, segm, inv, ix, iy, iz + 1), v101 = seg_voxel<LAYOUT>(v, segm, inv, ix + 1, iy, iz + 1);
+  const float v011 = seg_voxel<LAYOUT>(v, segm, inv, ix, iy + 1, iz + 1);
+  const float v111 = seg_voxel<LAYOUT>(v, segm, inv, ix + 1, iy + 1, iz + 1);
+  const float lx0 = gl_mix(v000, v100, fx), lx1 = gl_mix(v010, v110, fx);
+  const float hx0 = gl_mix(v001, v101, fx), hx1 = gl_mix(v011, v111, fx);
+  return density_scale * gl_mix(gl_mix(lx0, lx1, fy), gl_mix(hx0, hx1, fy), fz);
+}
+
 template <int LAYOUT, bool SKIP>
 __global__ __launch_bounds__(256) void iso_first_hit(const VxParams p, const DevVolume v, const VxIsoParams ip, const IsoBound ib,
                                                      float4* __restrict__ rgba_out, float4* __restrict__ hit_out,
                                                      unsigned long long* __restrict__ counts) {
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const uint32_t x = ip.window[0] + blockIdx.x * 16u + (wave & 1u) * 8u + (lane & 7u);
-  const uint32_t y = ip.window[1] + blockIdx.y * 16u + (wave >> 1) * 8u + (lane >> 3);
-  const bool in_window = x < ip.window[2] && y < ip.window[3];   // no lane returns early: the counts are whole-wave sums
-
-  // DVR's ray (dvr_setup without jitter; the per-launch ray terms evaluated here: the same bits)
-  const float tex_x = tex_coord((int)x, p.res[0], nullptr, 0), tex_y = tex_coord((int)y, p.res[1], nullptr, 1);
-  const Ray ray = setup_world_ray(p, tex_x, tex_y, 0.5f, 0.5f);
-  float near = 0.0f, far = 0.0f;
-  const bool box = in_window && ray_box_intersection(ray, p.volume_aabb_min, p.volume_aabb_max, near, far);
-  V3 ipos, idir;
-  to_index(p, ray, ipos, idir);
-  const float dt = p.dvr_step_voxels / sqrtf(dot3(idir, idir));
-  const float t0 = fma_(0.5f, dt, near);
-  const float xq = (far - t0) / dt;
-  const float nf = (box && xq > 0.0f) ? fminf(ceilf(xq), (float)p.dvr_max_steps) : 0.0f;
-  const V3 dq = v3(dt * idir.x, dt * idir.y, dt * idir.z);
-  const V3 q0 = v3(fma_(t0, idir.x, ipos.x) - 0.5f, fma_(t0, idir.y, ipos.y) - 0.5f, fma_(t0, idir.z, ipos.z) - 0.5f);
-
-  const float scale = p.volume_density_scale, inv_maj = p.volume_inv_maj, iso = ip.iso;
-  auto density = [&](float s) {
-    const float qx = fma_(s, dq.x, q0.x), qy = fma_(s, dq.y, q0.y), qz = fma_(s, dq.z, q0.z);
-    const float flx = floorf(qx), fly = floorf(qy), flz = floorf(qz);
-    return trilinear_cell<LAYOUT>(v, scale, f2i(flx), f2i(fly), f2i(flz), qx - flx, qy - fly, qz - flz) * inv_maj;
-  };
-
-  // the march: the first k < n with d_k >= iso
-  float kf = 0.0f;
-  uint32_t n_samples = 0, n_skipped = 0;
-  bool found = false;
-#pragma unroll 1
-  for (; kf < nf; kf += 1.0f) {
-    if (SKIP) {
-      const float qx = fma_(kf, dq.x, q0.x), qy = fma_(kf, dq.y, q0.y), qz = fma_(kf, dq.z, q0.z);
-      uint32_t cx = (uint32_t)(f2i(floorf(qx)) + 1), cy = (uint32_t)(f2i(floorf(qy)) + 1), cz = (uint32_t)(f2i(floorf(qz)) + 1);
-      cx = cx < ib.cmax[0] ? cx : ib.cmax[0];
-      cy = cy < ib.cmax[1] ? cy : ib.cmax[1];
-      cz = cz < ib.cmax[2] ? cz : ib.cmax[2];
-      if (ib.hi[((cz >> ib.sh) * ib.md1 + (cy >> ib.sh)) * ib.md0 + (cx >> ib.sh)] < iso) {
-        n_skipped += 1u;
-        continue;
-      }
-    }
-    n_samples += 1u;
-    if (density(kf) >= iso) {
-      found = true;
-      break;
-    }
-  }
-  const bool cap = found && kf == 0.0f;
-
-  // bisection on the sample parameter between the last sample below the threshold and the first at or above it
-  float s = kf;
-  if (found && !cap) {
-    float lo = kf - 1.0f, hi = kf;
-#pragma unroll 1
-    for (uint32_t i = 0; i < ip.refine; ++i) {
-      const float mid = 0.5f * (lo + hi);
-      if (density(mid) >= iso) hi = mid;
-      else lo = mid;
-    }
-    s = hi;
-  }
-
-  if (in_window) {
-    const size_t o = (size_t)(y - ip.window[1]) * (ip.window[2] - ip.window[0]) + (x - ip.window[0]);
-    float4 h = make_float4(0.0f, 0.0f, 0.0f, -1.0f), c = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (found) {
-      const float t = fma_(s, dt, t0);
-      h = make_float4(fma_(t, ray.d.x, ray.o.x), fma_(t, ray.d.y, ray.o.y), fma_(t, ray.d.z, ray.o.z), t);
-      // Phong's gradient (Frame::dvr<PHONG>): central differences one voxel either side in the cell frame of q(s*)
-      V3 g = v3(0.0f, 0.0f, 0.0f);
-      if (!cap) {
-        const float qx = fma_(s, dq.x, q0.x), qy = fma_(s, dq.y, q0.y), qz = fma_(s, dq.z, q0.z);
-        const float flx = floorf(qx), fly = floorf(qy), flz = floorf(qz);
-        const float fx = qx - flx, fy = qy - fly, fz = qz - flz;
-        const int cx = f2i(flx), cy = f2i(fly), cz = f2i(flz);
-        const float gx = trilinear_cell<LAYOUT>(v, scale, cx + 1, cy, cz, fx, fy, fz) - trilinear_cell<LAYOUT>(v, scale, cx - 1, cy, cz, fx, fy, fz);
-        const float gy = trilinear_cell<LAYOUT>(v, scale, cx, cy + 1, cz, fx, fy, fz) - trilinear_cell<LAYOUT>(v, scale, cx, cy - 1, cz, fx, fy, fz);
-        const float gz = trilinear_cell<LAYOUT>(v, scale, cx, cy, cz + 1, fx, fy, fz) - trilinear_cell<LAYOUT>(v, scale, cx, cy, cz - 1, fx, fy, fz);
-        g = v3(gx * p.density_transform_inv[0], gy * p.density_transform_inv[5], gz * p.density_transform_inv[10]);
-      }
-      const float g2 = dot3(g, g);
-      const V3 n = (!cap && g2 > 1e-12f) ? scale3(g, -rsq_fast(g2)) : v3(-ray.d.x, -ray.d.y, -ray.d.z);
-      const V3 nl = v3(-p.light_dir[0], -p.light_dir[1], -p.light_dir[2]);
-      const V3 hv = normalize3(sub3(nl, ray.d));
-      const float diff = fma_(ip.kd, gl_max(0.0f, dot3(n, nl)), ip.ka);
-      const float spec = ip.ks * pow_fast(gl_max(0.0f, dot3(n, hv)), ip.shininess);
-      c = make_float4(fma_(ip.color[0], diff, spec), fma_(ip.color[1], diff, spec), fma_(ip.color[2], diff, spec), 1.0f);
-    }
-    if (rgba_out) rgba_out[o] = c;
-    if (hit_out) hit_out[o] = h;
-  }
-
-  const uint32_t n_rays = (uint32_t)__builtin_popcountll(__ballot(box));
-  const uint32_t n_hits = (uint32_t)__builtin_popcountll(__ballot(found));
-  const uint32_t n_refined = (uint32_t)__builtin_popcountll(__ballot(found && !cap));
-  n_samples = wave_sum(n_samples);
-  n_skipped = wave_sum(n_skipped);
-  if (lane == 0u) {
-    if (n_rays) atomicAdd(&counts[ISO_RAYS], (unsigned long long)n_rays);
-    if (n_hits) atomicAdd(&counts[ISO_HITS], (unsigned long long)n_hits);
-    if (n_samples) atomicAdd(&counts[ISO_SAMPLES], (unsigned long long)n_samples);
-    if (n_refined) atomicAdd(&counts[ISO_REFINE], (unsigned long long)n_refined * ip.refine);
-    if (n_skipped) atomicAdd(&counts[ISO_SKIPPED], (unsigned long long)n_skipped);
-  }
+  constexpr bool SEGV = false;
+  [[maybe_unused]] const uint32_t* const segm = nullptr;
+  [[maybe_unused]] const uint32_t seg_inv = 0u;
+#include "vx_iso_march.inc"
+}
+// the segment view: the first hit on the masked volume (iso_cell<LAYOUT, true>), without range skipping -- the bound table is
+// built from the unmasked bricks' ranges; ISO_SKIPPED stays 0
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void iso_first_hit_seg(const VxParams p, const DevVolume v, const VxIsoParams ip,
+                                                         float4* __restrict__ rgba_out, float4* __restrict__ hit_out,
+                                                         unsigned long long* __restrict__ counts, const uint32_t* __restrict__ segm,
+                                                         const uint32_t seg_inv) {
+  constexpr bool SKIP = false;
+  constexpr bool SEGV = true;
+  const IsoBound ib{};
+#include "vx_iso_march.inc"
 }
 
 }  // namespace vx

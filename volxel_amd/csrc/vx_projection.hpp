@@ -24,6 +24,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SKIP ? VX_W
   constexpr bool SHADOW = false;
   constexpr int PROJ = MINIP ? 2 : 1;
   const ShadowGrid sg{};
+  constexpr bool SEGV = false;
+  [[maybe_unused]] const uint32_t* const segm = nullptr;
+  [[maybe_unused]] const uint32_t seg_inv = 0u;
+#include "vx_dvr_lds_march.inc"
+}
+// the segment view (render_dvr_lds_seg, vx_dvr_lds.hpp): the projection of the masked volume, without range skipping (the bound
+// table is built from the unmasked bricks).  MinIP sees the hidden voxels' zeros.
+template <int S, bool MINIP, bool U8>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(VX_W_LDS, 8))) void render_proj_lds_seg(
+    const VxParams p, const DevVolume v, const float4* __restrict__ tf_global, uint32_t tf_len, const MultiOut mo, float weight,
+    const TileMap tm, const uint32_t* __restrict__ order, const uint32_t* __restrict__ segm, const uint32_t seg_inv) {
+  constexpr bool SKIP = false;
+  constexpr bool PHONG = false;
+  constexpr bool SHADOW = false;
+  constexpr int PROJ = MINIP ? 2 : 1;
+  const ShadowGrid sg{};
+  const float* const pbound = nullptr;
+  constexpr bool SEGV = true;
 #include "vx_dvr_lds_march.inc"
 }
 

@@ -104,6 +104,9 @@ export declare class Volxel3DDicomRenderer {
       mean: number; rounds: number; converged: boolean; brickVisits: number };
   /** the current segment: one bit per voxel of (z, y, x) in C order, LSB first */
   segmentMask(): Uint8Array;
+  /** show only, or hide, the current segment in DVR, Phong, MIP / MinIP and the isosurfaces (vx_set_segment_view); 'off' after
+   *  a new volume; setting it restarts accumulation */
+  segmentView: 'off' | 'only' | 'hide';
   /** the current segment on a slice spec: 0 / 1 per pixel, row 0 = y = 0 */
   sliceMask(spec: { origin: number[]; du: number[]; dv: number[]; dn: number[]; size: [number, number]; slabSamples?: number }):
     { mask: Uint8Array; width: number; height: number };

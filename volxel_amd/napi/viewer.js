@@ -40,6 +40,7 @@ const LAYOUT = parseParamsLayout();
 const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams());
 const ISO_LAYOUT = parseParamsLayout('VxIsoParams', native.sizeofIsoParams());
 const SEGMENT_LAYOUT = parseParamsLayout('VxSegmentParams', native.sizeofSegmentParams());
+const SEGMENT_VIEWS = ['off', 'only', 'hide'];   // VX_SEGVIEW_OFF, _ONLY, _HIDE
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
 const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
@@ -641,7 +642,18 @@ class Volxel3DDicomRenderer {
     this.bindUniforms();
     const r = native.segment(this.ctx, p.buffer);
     r.mean = r.count ? r.dSum / r.count : NaN;
+    if (this.segmentView !== 'off') this.restartRendering();   // the masked views show the new segment
     return r;
+  }
+  /** 'off' (the default, and again after a new volume), 'only' (the current segment alone) or 'hide' (everything but it):
+   *  DVR, Phong, MIP / MinIP and the isosurfaces (hence pick) sample a volume whose hidden voxels read 0 (vx_set_segment_view,
+   *  DESIGN.md section 2 "Segment views"); slices and segment() keep the unmasked data.  Setting it restarts accumulation. */
+  get segmentView() { return SEGMENT_VIEWS[native.getSegmentView(this.ctx)]; }
+  set segmentView(view) {
+    const i = SEGMENT_VIEWS.indexOf(view);
+    if (i < 0) throw new Error(`segmentView must be one of ${SEGMENT_VIEWS.join(', ')}, not ${view}`);
+    native.setSegmentView(this.ctx, i);
+    this.restartRendering();
   }
   /** the current segment, one bit per voxel of (z, y, x) in C order, LSB first: a Uint8Array of X*Y*Z/8 bytes */
   segmentMask() {

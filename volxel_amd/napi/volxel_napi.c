@@ -706,6 +706,29 @@ static napi_value n_segment_stats(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* setSegmentView(ctx, 0 | 1 | 2) (vx_set_segment_view); getSegmentView(ctx) -> 0 | 1 | 2 (vx_get_segment_view) */
+static napi_value n_set_segment_view(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  int32_t view = 0;
+  if (napi_get_value_int32(env, a[1], &view) != napi_ok) return throw_msg(env, "setSegmentView: view must be a number");
+  if (vx_set_segment_view(c, view) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+static napi_value n_get_segment_view(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  int view = 0;
+  if (vx_get_segment_view(c, &view) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value v;
+  NAPI_OK(napi_create_int32(env, view, &v));
+  return v;
+}
+
 static napi_value n_reset_counters(napi_env env, napi_callback_info info) {
   napi_value a[1];
   if (!get_args(env, info, 1, a)) return NULL;
@@ -874,7 +897,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"slice", n_slice}, {"sliceStats", n_slice_stats}, {"sizeofSliceParams", n_sizeof_slice_params},
       {"isosurface", n_isosurface}, {"isoStats", n_iso_stats}, {"sizeofIsoParams", n_sizeof_iso_params},
       {"segment", n_segment}, {"sizeofSegmentParams", n_sizeof_segment_params}, {"segmentMask", n_segment_mask},
-      {"sliceMask", n_slice_mask}, {"segmentStats", n_segment_stats},
+      {"sliceMask", n_slice_mask}, {"segmentStats", n_segment_stats}, {"setSegmentView", n_set_segment_view},
+      {"getSegmentView", n_get_segment_view},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {

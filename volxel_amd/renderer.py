@@ -750,6 +750,8 @@ class Volxel3DRenderer:
         p = self.bind_uniforms()
         res = _abi.VxSegmentResult()
         self._check(self._lib.vx_segment(self._ctx, C.byref(q), C.byref(res)))
+        if self.segment_view != "off":   # the masked views show the new segment: the picture changed
+            self.restart_rendering()
         g3 = np.asarray(self.volume.grid.transform, dtype=np.float64)[:3, :3]
         d3 = np.asarray(p.density_transform[:], dtype=np.float32).astype(np.float64).reshape(4, 4).T[:3, :3]
         n = int(res.count)
@@ -757,6 +759,24 @@ class Volxel3DRenderer:
                        d_max=float(res.d_max), d_sum=float(res.d_sum), mean=float(res.d_sum) / n if n else math.nan,
                        rounds=int(res.rounds), converged=bool(res.converged), brick_visits=int(res.brick_visits),
                        volume_grid=n * abs(float(np.linalg.det(g3))), volume_world=n * abs(float(np.linalg.det(d3))))
+
+    SEGMENT_VIEWS = ("off", "only", "hide")   # VX_SEGVIEW_OFF, _ONLY, _HIDE
+
+    @property
+    def segment_view(self) -> str:
+        """"off" (the default, and again after setup_from_grid), "only" (the current segment alone) or "hide" (everything but
+        it): DVR, Phong, MIP / MinIP renders and the isosurfaces (hence pick) sample a volume whose hidden voxels read 0
+        (vx_set_segment_view, DESIGN.md section 2 "Segment views"); slices and segment() keep the unmasked data"""
+        v = C.c_int32()
+        self._check(self._lib.vx_get_segment_view(self._ctx, C.byref(v)))
+        return self.SEGMENT_VIEWS[v.value]
+
+    @segment_view.setter
+    def segment_view(self, view: str):
+        if view not in self.SEGMENT_VIEWS:
+            raise VolxelError(f"segment_view must be one of {self.SEGMENT_VIEWS}, not {view!r}")
+        self._check(self._lib.vx_set_segment_view(self._ctx, self.SEGMENT_VIEWS.index(view)))
+        self.restart_rendering()
 
     def segment_mask(self) -> np.ndarray:
         """the current segment as a (Z, Y, X) bool array over the index extent (vx_segment_read_mask)"""
