@@ -512,6 +512,54 @@ int vx_slice_segment_mask(VxContext* ctx, const VxSliceParams* sp, uint8_t* out)
  * call.  Any pointer may be NULL.  group: member 0. */
 int vx_segment_stats(VxContext* ctx, uint32_t* rounds, uint64_t* brick_visits, double* kernel_ms);
 
+/* ---- segment edits (DESIGN.md section 2 "Segment edits"): morphology on the current segment M, a set of voxels of index_extent
+ * (padding voxels included).  N_c(i) is voxel i with its 6 face neighbours or its 26 face, edge and corner neighbours.
+ *   DILATE      D(M) = { i in the volume : N_c(i) meets M }; voxels outside the volume count as NOT set.  steps applies D n times.
+ *               band = 1: D_P(M) = M | (D(M) & P) per step, P the predicate words of the last vx_segment on this volume
+ *               ("grow, but only into voxels that pass the threshold"); voxels of M outside P stay.
+ *   ERODE       E(M) = ~D(~M), the complement taken inside the volume: voxels outside the volume count as SET, so a structure
+ *               cut by the edge of the scan does not erode from outside and the whole volume erodes to itself.
+ *   OPEN        D^n(E^n(M));  CLOSE  E^n(D^n(M)), each half with its own border rule: closing is extensive, opening
+ *               anti-extensive, both idempotent, also at the faces of the volume.
+ *   FILL_HOLES  M | H, H the c-connected components of ~M (inside the volume) that hold no voxel on any of the six faces of
+ *               index_extent; connectivity is that of the BACKGROUND.  steps must be 0 or 1 and is ignored.
+ * Every result is a unique set: it does not depend on layout, launch shape or scheduling.  An empty M is legal. */
+typedef enum VxSegmentEditOp {
+  VX_SEGEDIT_DILATE = 0,
+  VX_SEGEDIT_ERODE = 1,
+  VX_SEGEDIT_OPEN = 2,
+  VX_SEGEDIT_CLOSE = 3,
+  VX_SEGEDIT_FILL_HOLES = 4
+} VxSegmentEditOp;
+#define VX_SEGEDIT_MAX_STEPS 1024u
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxSegmentEditParams {
+  int32_t op;              /* VxSegmentEditOp                                                                      */
+  int32_t connectivity;    /* 6 or 26                                                                              */
+  uint32_t steps;          /* 1 .. VX_SEGEDIT_MAX_STEPS; 0 or 1 for FILL_HOLES                                      */
+  int32_t band;            /* 0, or 1 with DILATE: only into the predicate of the last vx_segment                  */
+} VxSegmentEditParams;
+/* Edits the current segment in place, on the context's stream behind every queued render, and synchronises.  out (may be NULL)
+ * holds the statistics of the new mask: count, bbox, min / max and the float64 sum as vx_segment computes them (the scale and
+ * inv_maj of the last vx_set_params), all 0 when empty; rounds and brick_visits are those of FILL_HOLES' background flood and 0
+ * for the other ops; converged = 1.  The accumulator, the frame state, VxCounters, the light grid, the bound tables, VxParams,
+ * the segment view and what vx_segment_stats reports are not touched; with a view on, the next covered call reads the edited
+ * mask.  Two scratch masks (64 B per brick each: 1 bit per voxel) and 4 B per brick are allocated by the first edit and freed
+ * with the volume.  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the field, before vx_set_params, for NULL params,
+ * an op outside the enum, connectivity not 6 or 26, steps out of range, band not 0 or 1, band = 1 with another op or with no
+ * vx_segment on this volume, and with no current segment.  A refused call changes nothing.  group: member 0. */
+int vx_segment_edit(VxContext* ctx, const VxSegmentEditParams* params, VxSegmentResult* out);
+/* The inverse of vx_segment_read_mask: installs bits (one bit per voxel of (z, y, x) in C order, LSB first, nbytes = X * Y * Z / 8)
+ * as the current segment, creating one where there was none, and computes its statistics into out (may be NULL; rounds and
+ * brick_visits 0, converged 1).  The predicate words of the last vx_segment and the segment view stay.  Stream, group and
+ * untouched state as vx_segment_edit.  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID before vx_set_params, for NULL bits
+ * and a wrong nbytes. */
+int vx_segment_write_mask(VxContext* ctx, const uint8_t* bits, uint64_t nbytes, VxSegmentResult* out);
+/* the last vx_segment_edit or vx_segment_write_mask: kernels launched by the edit itself, and the HIP-event times of the edit
+ * (FILL_HOLES: host read-backs of the worklist length included) and of the statistics, kernel_ms[0 .. 1]; all 0 before the
+ * first call.  Any pointer may be NULL.  group: member 0. */
+int vx_segment_edit_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
+
 /* ---- segment views (DESIGN.md section 2 "Segment views"): show only, or hide, the current segment.  With a view other than
  * OFF the covered calls -- vx_render_frame / vx_render_frames in VX_MODE_DVR, _DVR_PHONG, _MIP and _MINIP, and vx_isosurface
  * (hence picking) -- sample the masked volume: every decoded voxel v(i) reads +0.0f where it is hidden (ONLY: i is not in the

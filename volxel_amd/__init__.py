@@ -14,5 +14,5 @@ from .preprocessor import read_u16_stack_to_grid, read_dicoms_to_grid, BrickGrid
 from .environment import Environment  # noqa: F401,E402
 from .containers import ZipReadError, read_zip_slices, decode_environment  # noqa: F401,E402
 from .mpr import axial, coronal, sagittal, oblique, overlay  # noqa: F401,E402
-from ._abi import VxSliceParams, VxIsoParams, VxSegmentParams, VxSegmentResult  # noqa: F401,E402
+from ._abi import VxSliceParams, VxIsoParams, VxSegmentParams, VxSegmentResult, VxSegmentEditParams  # noqa: F401,E402
 from .renderer import Segment  # noqa: F401,E402

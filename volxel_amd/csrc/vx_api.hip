@@ -21,6 +21,7 @@
 #include "vx_slice.hpp"
 #include "vx_iso.hpp"
 #include "vx_segment.hpp"
+#include "vx_segedit.hpp"
 
 using namespace vx;
 
@@ -214,6 +215,15 @@ struct VxContext {
   hipEvent_t seg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
   VxSegmentResult seg_res{};
   double seg_ms[3] = {0.0, 0.0, 0.0};
+  // segment edits (vx_segment_edit, vx_segment_write_mask): two scratch masks and the fill's flags, allocated by the first edit
+  // and freed with the volume; seg_pred_valid: SegDev::pred holds the predicate of a vx_segment on the resident volume
+  void* sed_alloc = nullptr;
+  uint64_t* sed_mask[2] = {nullptr, nullptr};
+  uint32_t* sed_any = nullptr;
+  bool seg_pred_valid = false;
+  hipEvent_t sed_ev[3] = {nullptr, nullptr, nullptr};
+  uint32_t sed_launches = 0;
+  double sed_ms[2] = {0.0, 0.0};
 };
 
 static bool is_group(const VxContext* c) { return !c->members.empty(); }
@@ -260,7 +270,12 @@ static void free_volume(VxContext* c) {
   c->seg_alloc = nullptr;
   c->seg = SegDev{};
   c->seg_valid = false;
+  c->seg_pred_valid = false;
   c->seg_view = VX_SEGVIEW_OFF;
+  if (c->sed_alloc) (void)hipFree(c->sed_alloc);
+  c->sed_alloc = nullptr;
+  c->sed_mask[0] = c->sed_mask[1] = nullptr;
+  c->sed_any = nullptr;
   if (c->seg_bytes) (void)hipFree(c->seg_bytes);
   c->seg_bytes = nullptr;
   c->seg_bytes_cap = 0;
@@ -1287,6 +1302,8 @@ void vx_destroy(VxContext* c) {
     if (e) (void)hipEventDestroy(e);
   if (c->seg_ov) (void)hipFree(c->seg_ov);
   for (hipEvent_t e : c->seg_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->sed_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2660,12 +2677,37 @@ static void launch_seg_predicate(VxContext* c, const SegPredParams& pp) {
                        pp, c->seg);
   });
 }
-static void launch_seg_flood(VxContext* c, int conn, const SegSeed& seed, uint32_t round) {
-  const uint32_t blocks = std::min<uint32_t>((c->seg.nb + 255u) / 256u, 1024u);
+static void launch_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint32_t round) {
+  const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 1024u);
   if (conn == 26)
-    hipLaunchKernelGGL((seg_flood<26>), dim3(blocks), dim3(256), 0, c->stream, c->seg, seed, round);
+    hipLaunchKernelGGL((seg_flood<26>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
   else
-    hipLaunchKernelGGL((seg_flood<6>), dim3(blocks), dim3(256), 0, c->stream, c->seg, seed, round);
+    hipLaunchKernelGGL((seg_flood<6>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
+}
+// the rounds of a flood on the view s (vx_segment: the segment; vx_segment_edit: the background of fill holes), from a round-0
+// worklist that is already on the device: queued in batches of 1, 2, 4, ... SEG_CHECK_MAX, the next worklist's length read back
+// after each batch.  Ends synchronised; *launched counts the flood launches.
+static int run_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint64_t cap, bool* converged,
+                         uint64_t* launched_out) {
+  uint64_t launched = 0;
+  uint32_t batch = 1, next = 1;
+  *converged = false;
+  while (true) {
+    const uint64_t k = std::min<uint64_t>(batch, cap - launched);
+    for (uint64_t i = 0; i < k; ++i) launch_seg_flood(c, s, conn, seed, (uint32_t)(launched + i));
+    VX_HIP(c, hipGetLastError());
+    launched += k;
+    VX_HIP(c, hipMemcpyAsync(&next, s.cnt + launched % 3u, sizeof next, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (next == 0u) {
+      *converged = true;
+      break;
+    }
+    if (launched >= cap) break;
+    batch = std::min(batch * 2u, c->sw.seg_check_max);
+  }
+  if (launched_out) *launched_out = launched;
+  return VX_OK;
 }
 static void launch_seg_stats(VxContext* c) {
   const VxParams& p = c->params;
@@ -2709,6 +2751,7 @@ int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
               sp->box_hi[a], E[a]);
   }
   c->seg_valid = false;
+  c->seg_pred_valid = false;
   {
     const int rc = ensure_segment(c);
     if (rc) return rc;
@@ -2729,24 +2772,8 @@ int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
   VX_HIP(c, hipEventRecord(c->seg_ev[1], c->stream));
   hipLaunchKernelGGL(seg_seed, dim3(1), dim3(64), 0, c->stream, s, seed);
   VX_HIP(c, hipGetLastError());
-  // the rounds: queued in batches of 1, 2, 4, ... SEG_CHECK_MAX, the next worklist's length read back after each batch
-  uint64_t launched = 0;
-  uint32_t batch = 1, next = 1;
   bool converged = false;
-  while (true) {
-    const uint64_t k = std::min<uint64_t>(batch, cap - launched);
-    for (uint64_t i = 0; i < k; ++i) launch_seg_flood(c, sp->connectivity, seed, (uint32_t)(launched + i));
-    VX_HIP(c, hipGetLastError());
-    launched += k;
-    VX_HIP(c, hipMemcpyAsync(&next, s.cnt + launched % 3u, sizeof next, hipMemcpyDeviceToHost, c->stream));
-    VX_HIP(c, hipStreamSynchronize(c->stream));
-    if (next == 0u) {
-      converged = true;
-      break;
-    }
-    if (launched >= cap) break;
-    batch = std::min(batch * 2u, c->sw.seg_check_max);
-  }
+  if (int rc = run_seg_flood(c, s, sp->connectivity, seed, cap, &converged, nullptr)) return rc;
   VX_HIP(c, hipEventRecord(c->seg_ev[2], c->stream));
   launch_seg_stats(c);
   VX_HIP(c, hipGetLastError());
@@ -2775,6 +2802,7 @@ int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
   r.brick_visits = st.visits;
   c->seg_res = r;
   c->seg_valid = true;
+  c->seg_pred_valid = true;
   if (out) *out = r;
   return VX_OK;
 }
@@ -2865,6 +2893,194 @@ int vx_segment_stats(VxContext* c, uint32_t* rounds, uint64_t* brick_visits, dou
   if (brick_visits) *brick_visits = c->seg_res.brick_visits;
   if (kernel_ms)
     for (int i = 0; i < 3; ++i) kernel_ms[i] = c->seg_ms[i];
+  return VX_OK;
+}
+
+// ---- segment edits (vx_segment_edit, vx_segment_write_mask; kernels in vx_segedit.hpp) ---------------------------------------
+// the scratch of the edits: two masks of nb * 8 words (1 bit per voxel each) and the fill's nb "any background" flags
+static int ensure_segedit(VxContext* c) {
+  for (hipEvent_t& e : c->sed_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  if (c->sed_alloc) return VX_OK;
+  const size_t nb = c->seg.nb;
+  VX_HIP(c, hipMalloc(&c->sed_alloc, nb * (64u + 64u + 4u)));
+  char* p = static_cast<char*>(c->sed_alloc);
+  c->sed_mask[0] = reinterpret_cast<uint64_t*>(p);
+  c->sed_mask[1] = reinterpret_cast<uint64_t*>(p + nb * 64u);
+  c->sed_any = reinterpret_cast<uint32_t*>(p + nb * 128u);
+  return VX_OK;
+}
+
+// the statistics of the mask in SegDev::seg, behind the edit on the stream: events, seg_stats / seg_sum, the read-back.  The
+// flood's rounds and visits are kept when `fill`.  Ends synchronised.
+static int finish_segedit(VxContext* c, bool fill, VxSegmentResult* out) {
+  const SegDev& s = c->seg;
+  VX_HIP(c, hipEventRecord(c->sed_ev[1], c->stream));
+  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 0u);
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->sed_ev[2], c->stream));
+  SegStats st;
+  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 2; ++i) {
+    float ms = 0.0f;
+    VX_HIP(c, hipEventElapsedTime(&ms, c->sed_ev[i], c->sed_ev[i + 1]));
+    c->sed_ms[i] = ms;
+  }
+  VxSegmentResult r{};
+  r.count = st.count;
+  if (st.count) {
+    for (int a = 0; a < 3; ++a) {
+      r.bbox_lo[a] = st.lo[a];
+      r.bbox_hi[a] = st.hi[a];
+    }
+    r.d_min = seg_key_float(st.dmin);
+    r.d_max = seg_key_float(st.dmax);
+    r.d_sum = st.sum;
+  }
+  r.rounds = fill ? st.rounds : 0u;
+  r.converged = 1u;
+  r.brick_visits = fill ? st.visits : 0u;
+  c->seg_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+// `steps` steps of one kind from the mask at *cur.  A step never writes the mask it reads: the chain alternates between the two
+// scratch masks, and the last step of the edit (`last`) writes SegDev::seg itself unless it would read it, so the masked render
+// kernels, seg_pack and the overlay keep the one pointer they read at launch time.
+static void launch_sed_steps(VxContext* c, int conn, bool invert, bool band, uint32_t steps, bool last, uint64_t** cur) {
+  const SegDev& s = c->seg;
+  const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
+  const uint64_t inv = invert ? ~0ull : 0ull;
+  for (uint32_t i = 0; i < steps; ++i) {
+    uint64_t* src = *cur;
+    uint64_t* dst = (last && i + 1u == steps && src != s.seg) ? s.seg : (src == c->sed_mask[0] ? c->sed_mask[1] : c->sed_mask[0]);
+    auto go = [&](auto conn_c, auto band_c) {
+      hipLaunchKernelGGL((sed_step<decltype(conn_c)::value, decltype(band_c)::value>), dim3(blocks), dim3(256), 0, c->stream, src,
+                         dst, s.pred, inv, s.bc[0], s.bc[1], s.bc[2]);
+    };
+    if (conn == 26) {
+      if (band) go(std::integral_constant<int, 26>{}, std::true_type{});
+      else go(std::integral_constant<int, 26>{}, std::false_type{});
+    } else {
+      if (band) go(std::integral_constant<int, 6>{}, std::true_type{});
+      else go(std::integral_constant<int, 6>{}, std::false_type{});
+    }
+    *cur = dst;
+    ++c->sed_launches;
+  }
+}
+
+int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_edit(c->members[0], ep, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_edit: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!ep) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: params is NULL");
+  if (ep->op < VX_SEGEDIT_DILATE || ep->op > VX_SEGEDIT_FILL_HOLES)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: op = %d is not a VxSegmentEditOp (0 .. 4)", ep->op);
+  if (ep->connectivity != 6 && ep->connectivity != 26)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: connectivity = %d is not 6 or 26", ep->connectivity);
+  const bool fill = ep->op == VX_SEGEDIT_FILL_HOLES;
+  if (fill ? ep->steps > 1u : (ep->steps < 1u || ep->steps > VX_SEGEDIT_MAX_STEPS))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: steps = %u outside %s", ep->steps, fill ? "0 .. 1 (fill holes)" : "1 .. 1024");
+  if (ep->band != 0 && ep->band != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = %d is not 0 or 1", ep->band);
+  if (ep->band && ep->op != VX_SEGEDIT_DILATE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 is for VX_SEGEDIT_DILATE only (op = %d)", ep->op);
+  if (!c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: no current segment (vx_segment or vx_segment_write_mask first; an upload drops it)");
+  if (ep->band && !c->seg_pred_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
+  if (int rc = ensure_segedit(c)) return rc;
+  const SegDev& s = c->seg;
+  const int conn = ep->connectivity;
+  const uint32_t n = ep->steps;
+  c->sed_launches = 0;
+  VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
+  uint64_t* cur = s.seg;
+  switch (ep->op) {
+    case VX_SEGEDIT_DILATE: launch_sed_steps(c, conn, false, ep->band != 0, n, true, &cur); break;
+    case VX_SEGEDIT_ERODE: launch_sed_steps(c, conn, true, false, n, true, &cur); break;
+    case VX_SEGEDIT_OPEN:
+      launch_sed_steps(c, conn, true, false, n, false, &cur);
+      launch_sed_steps(c, conn, false, false, n, true, &cur);
+      break;
+    case VX_SEGEDIT_CLOSE:
+      launch_sed_steps(c, conn, false, false, n, false, &cur);
+      launch_sed_steps(c, conn, true, false, n, true, &cur);
+      break;
+    default: {
+      // the background flood on a second view: predicate ~M and the reached set in the scratch masks, the bookkeeping shared
+      // with vx_segment (its predicate WORDS stay: band dilation after a fill is legal)
+      SegDev f = s;
+      f.pred = c->sed_mask[0];
+      f.seg = c->sed_mask[1];
+      f.any = c->sed_any;
+      const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
+      hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 1u);
+      hipLaunchKernelGGL(sed_fill_seed, dim3(blocks), dim3(256), 0, c->stream, s.seg, f);
+      VX_HIP(c, hipGetLastError());
+      bool converged = false;
+      uint64_t launched = 0;
+      const uint64_t nvox = (uint64_t)c->dv.extent[0] * c->dv.extent[1] * c->dv.extent[2];
+      if (int rc = run_seg_flood(c, f, conn, SegSeed{0u, 0u, 0ull}, std::min<uint64_t>(nvox, 0xfffffffeull), &converged, &launched))
+        return rc;
+      const size_t words = (size_t)s.nb * 8u;
+      hipLaunchKernelGGL(sed_fill_finish, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream,
+                         f.seg, s.seg, words);
+      c->sed_launches = (uint32_t)std::min<uint64_t>(launched + 3u, 0xffffffffull);
+      cur = s.seg;
+    }
+  }
+  VX_HIP(c, hipGetLastError());
+  // a single step read SegDev::seg and so wrote a scratch mask: copy it home on the stream
+  if (cur != s.seg) VX_HIP(c, hipMemcpyAsync(s.seg, cur, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
+  return finish_segedit(c, fill, out);
+}
+
+int vx_segment_write_mask(VxContext* c, const uint8_t* bits, uint64_t nbytes, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_write_mask(c->members[0], bits, nbytes, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_write_mask: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_write_mask: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!bits) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_write_mask: bits is NULL");
+  const uint32_t* E = c->dv.extent;
+  const size_t want = (size_t)E[0] * E[1] * E[2] / 8u;
+  if (nbytes != want)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_write_mask: nbytes = %llu, the mask of %u x %u x %u voxels is %zu bytes",
+            (unsigned long long)nbytes, E[0], E[1], E[2], want);
+  if (int rc = ensure_segment(c)) return rc;
+  if (int rc = ensure_segedit(c)) return rc;
+  if (want > c->seg_bytes_cap) {   // (every earlier call has completed: each one synchronises)
+    if (c->seg_bytes) (void)hipFree(c->seg_bytes);
+    c->seg_bytes = nullptr;
+    c->seg_bytes_cap = 0;
+    VX_HIP(c, hipMalloc(&c->seg_bytes, want));
+    c->seg_bytes_cap = want;
+  }
+  const SegDev& s = c->seg;
+  VX_HIP(c, hipMemcpyAsync(c->seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
+  VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
+  const size_t words = (size_t)s.nb * 8u;
+  hipLaunchKernelGGL(sed_unpack, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream, s, E[1],
+                     c->seg_bytes);
+  VX_HIP(c, hipGetLastError());
+  c->sed_launches = 1;
+  return finish_segedit(c, false, out);
+}
+
+int vx_segment_edit_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_edit_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->sed_launches;
+  if (kernel_ms)
+    for (int i = 0; i < 2; ++i) kernel_ms[i] = c->sed_ms[i];
   return VX_OK;
 }
 

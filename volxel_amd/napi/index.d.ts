@@ -104,6 +104,16 @@ export declare class Volxel3DDicomRenderer {
       mean: number; rounds: number; converged: boolean; brickVisits: number };
   /** the current segment: one bit per voxel of (z, y, x) in C order, LSB first */
   segmentMask(): Uint8Array;
+  /** dilate, erode, open, close or fill the holes of the current segment on the GPU (include/volxel_hip.h vx_segment_edit) */
+  segmentEdit(op: 'dilate' | 'erode' | 'open' | 'close' | 'fill_holes', opts?: { steps?: number; connectivity?: 6 | 26; band?: boolean }):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** install a packed mask (the layout of segmentMask()) as the current segment (vx_segment_write_mask) */
+  setSegmentMask(bits: Uint8Array):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** the last segmentEdit or setSegmentMask: kernels launched, the times of the edit and of its statistics */
+  segmentEditStats(): { launches: number; editMs: number; statsMs: number };
   /** show only, or hide, the current segment in DVR, Phong, MIP / MinIP and the isosurfaces (vx_set_segment_view); 'off' after
    *  a new volume; setting it restarts accumulation */
   segmentView: 'off' | 'only' | 'hide';

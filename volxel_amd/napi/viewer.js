@@ -41,6 +41,7 @@ const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams
 const ISO_LAYOUT = parseParamsLayout('VxIsoParams', native.sizeofIsoParams());
 const SEGMENT_LAYOUT = parseParamsLayout('VxSegmentParams', native.sizeofSegmentParams());
 const SEGMENT_VIEWS = ['off', 'only', 'hide'];   // VX_SEGVIEW_OFF, _ONLY, _HIDE
+const SEGMENT_EDIT_OPS = ['dilate', 'erode', 'open', 'close', 'fill_holes'];   // VxSegmentEditOp, in order
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
 const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
@@ -640,11 +641,40 @@ class Volxel3DDicomRenderer {
     p.set('seed', seed); p.set('lo', l32); p.set('hi', h32); p.set('connectivity', connectivity);
     p.set('box_lo', blo); p.set('box_hi', bhi); p.set('max_rounds', maxRounds);
     this.bindUniforms();
-    const r = native.segment(this.ctx, p.buffer);
+    return this._segmentResult(native.segment(this.ctx, p.buffer));
+  }
+  /** vx_segment_edit (DESIGN.md section 2 "Segment edits"): op 'dilate' | 'erode' | 'open' | 'close' | 'fill_holes' on the
+   *  current segment; opts: { steps = 1 (1 .. 1024; ignored by fill_holes), connectivity = 6 | 26, band = false (dilate only:
+   *  grow only into voxels that pass the predicate of the last segment()) } -> what segment() returns, for the edited mask
+   *  (rounds and brickVisits: the fill's background flood).  Binds the current uniforms first. */
+  segmentEdit(op, { steps = 1, connectivity = 6, band = false } = {}) {
+    const i = SEGMENT_EDIT_OPS.indexOf(op);
+    if (i < 0) throw new Error(`segmentEdit: op must be one of ${SEGMENT_EDIT_OPS.join(', ')}, not ${op}`);
+    if (connectivity !== 6 && connectivity !== 26) throw new Error(`segmentEdit: connectivity must be 6 or 26, not ${connectivity}`);
+    const fill = op === 'fill_holes';
+    if (!Number.isInteger(steps) || steps < (fill ? 0 : 1) || steps > (fill ? 1 : 1024))
+      throw new Error(`segmentEdit: steps must be an integer ${fill ? '0 .. 1' : '1 .. 1024'} for ${op}, not ${steps}`);
+    if (typeof band !== 'boolean') throw new Error(`segmentEdit: band must be a boolean, not ${band}`);
+    if (band && op !== 'dilate') throw new Error(`segmentEdit: band is for dilate only, not ${op}`);
+    this.bindUniforms();
+    return this._segmentResult(native.segmentEdit(this.ctx, i, connectivity, steps, band ? 1 : 0));
+  }
+  /** vx_segment_write_mask, the inverse of segmentMask(): installs a Uint8Array of X*Y*Z/8 bytes (one bit per voxel of
+   *  (z, y, x) in C order, LSB first) as the current segment -> what segment() returns, for that mask */
+  setSegmentMask(bits) {
+    const e = this.sliceExtent();
+    if (!(bits instanceof Uint8Array) || bits.length !== e[0] * e[1] * e[2] / 8)
+      throw new Error(`setSegmentMask: bits must be a Uint8Array of ${e[0] * e[1] * e[2] / 8} bytes`);
+    this.bindUniforms();
+    return this._segmentResult(native.setSegmentMask(this.ctx, bits));
+  }
+  _segmentResult(r) {
     r.mean = r.count ? r.dSum / r.count : NaN;
-    if (this.segmentView !== 'off') this.restartRendering();   // the masked views show the new segment
+    if (this.segmentView !== 'off') this.restartRendering();   // the masked views show the new mask
     return r;
   }
+  /** the last segmentEdit or setSegmentMask: kernels launched and the times of the edit and of the statistics */
+  segmentEditStats() { return native.segmentEditStats(this.ctx); }
   /** 'off' (the default, and again after a new volume), 'only' (the current segment alone) or 'hide' (everything but it):
    *  DVR, Phong, MIP / MinIP and the isosurfaces (hence pick) sample a volume whose hidden voxels read 0 (vx_set_segment_view,
    *  DESIGN.md section 2 "Segment views"); slices and segment() keep the unmasked data.  Setting it restarts accumulation. */

@@ -623,6 +623,17 @@ static napi_value set_u3(napi_env env, napi_value o, const char* name, const uin
   if (napi_set_named_property(env, o, name, arr) != napi_ok) return NULL;
   return o;
 }
+static napi_value segment_result(napi_env env, const VxSegmentResult* r) {
+  napi_value o, b;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "count", (double)r->count) || !set_u3(env, o, "bboxLo", r->bbox_lo) || !set_u3(env, o, "bboxHi", r->bbox_hi) ||
+      !set_num(env, o, "dMin", r->d_min) || !set_num(env, o, "dMax", r->d_max) || !set_num(env, o, "dSum", r->d_sum) ||
+      !set_num(env, o, "rounds", r->rounds) || !set_num(env, o, "brickVisits", (double)r->brick_visits))
+    return throw_msg(env, "segment: could not build the result");
+  NAPI_OK(napi_get_boolean(env, r->converged != 0, &b));
+  NAPI_OK(napi_set_named_property(env, o, "converged", b));
+  return o;
+}
 static napi_value n_segment(napi_env env, napi_callback_info info) {
   napi_value a[2];
   if (!get_args(env, info, 2, a)) return NULL;
@@ -636,14 +647,54 @@ static napi_value n_segment(napi_env env, napi_callback_info info) {
   memcpy(&sp, d, sizeof sp);
   VxSegmentResult r;
   if (vx_segment(c, &sp, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
-  napi_value o, b;
+  return segment_result(env, &r);
+}
+
+/* segmentEdit(ctx, op 0 .. 4, connectivity, steps, band 0 | 1) -> what segment returns, for the edited mask (vx_segment_edit) */
+static napi_value n_segment_edit(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!get_args(env, info, 5, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  int32_t op, conn, band;
+  uint32_t steps;
+  if (napi_get_value_int32(env, a[1], &op) != napi_ok || napi_get_value_int32(env, a[2], &conn) != napi_ok ||
+      napi_get_value_uint32(env, a[3], &steps) != napi_ok || napi_get_value_int32(env, a[4], &band) != napi_ok)
+    return throw_msg(env, "segmentEdit: op, connectivity, steps and band must be numbers");
+  VxSegmentEditParams ep = {op, conn, steps, band};
+  VxSegmentResult r;
+  if (vx_segment_edit(c, &ep, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return segment_result(env, &r);
+}
+
+/* setSegmentMask(ctx, Uint8Array of X*Y*Z/8 bytes) -> what segment returns, for the installed mask (vx_segment_write_mask) */
+static napi_value n_set_segment_mask(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* bits;
+  size_t nb;
+  if (!typed_or_null(env, a[1], napi_uint8_array, &bits, &nb)) return NULL;
+  if (!bits) return throw_msg(env, "setSegmentMask: bits must be a Uint8Array");
+  VxSegmentResult r;
+  if (vx_segment_write_mask(c, (const uint8_t*)bits, (uint64_t)nb, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return segment_result(env, &r);
+}
+
+/* segmentEditStats(ctx) -> { launches, editMs, statsMs } (vx_segment_edit_stats) */
+static napi_value n_segment_edit_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t launches = 0;
+  double ms[2] = {0.0, 0.0};
+  if (vx_segment_edit_stats(c, &launches, ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o;
   NAPI_OK(napi_create_object(env, &o));
-  if (!set_num(env, o, "count", (double)r.count) || !set_u3(env, o, "bboxLo", r.bbox_lo) || !set_u3(env, o, "bboxHi", r.bbox_hi) ||
-      !set_num(env, o, "dMin", r.d_min) || !set_num(env, o, "dMax", r.d_max) || !set_num(env, o, "dSum", r.d_sum) ||
-      !set_num(env, o, "rounds", r.rounds) || !set_num(env, o, "brickVisits", (double)r.brick_visits))
-    return throw_msg(env, "segment: could not build the result");
-  NAPI_OK(napi_get_boolean(env, r.converged != 0, &b));
-  NAPI_OK(napi_set_named_property(env, o, "converged", b));
+  if (!set_num(env, o, "launches", launches) || !set_num(env, o, "editMs", ms[0]) || !set_num(env, o, "statsMs", ms[1]))
+    return throw_msg(env, "segmentEditStats: could not build the result");
   return o;
 }
 
@@ -898,7 +949,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"isosurface", n_isosurface}, {"isoStats", n_iso_stats}, {"sizeofIsoParams", n_sizeof_iso_params},
       {"segment", n_segment}, {"sizeofSegmentParams", n_sizeof_segment_params}, {"segmentMask", n_segment_mask},
       {"sliceMask", n_slice_mask}, {"segmentStats", n_segment_stats}, {"setSegmentView", n_set_segment_view},
-      {"getSegmentView", n_get_segment_view},
+      {"getSegmentView", n_get_segment_view}, {"segmentEdit", n_segment_edit}, {"setSegmentMask", n_set_segment_mask},
+      {"segmentEditStats", n_segment_edit_stats},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {

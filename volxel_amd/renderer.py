@@ -750,7 +750,12 @@ class Volxel3DRenderer:
         p = self.bind_uniforms()
         res = _abi.VxSegmentResult()
         self._check(self._lib.vx_segment(self._ctx, C.byref(q), C.byref(res)))
-        if self.segment_view != "off":   # the masked views show the new segment: the picture changed
+        return self._segment_result(res, p)
+
+    def _segment_result(self, res, p) -> Segment:
+        """the `Segment` of a VxSegmentResult under the uniforms p just bound (segment, segment_edit, set_segment_mask); the
+        masked views show the new mask, so accumulation restarts when one is on"""
+        if self.segment_view != "off":
             self.restart_rendering()
         g3 = np.asarray(self.volume.grid.transform, dtype=np.float64)[:3, :3]
         d3 = np.asarray(p.density_transform[:], dtype=np.float32).astype(np.float64).reshape(4, 4).T[:3, :3]
@@ -759,6 +764,62 @@ class Volxel3DRenderer:
                        d_max=float(res.d_max), d_sum=float(res.d_sum), mean=float(res.d_sum) / n if n else math.nan,
                        rounds=int(res.rounds), converged=bool(res.converged), brick_visits=int(res.brick_visits),
                        volume_grid=n * abs(float(np.linalg.det(g3))), volume_world=n * abs(float(np.linalg.det(d3))))
+
+    SEGMENT_EDIT_OPS = ("dilate", "erode", "open", "close", "fill_holes")   # VxSegmentEditOp, in order
+
+    def segment_edit(self, op: str, steps: int = 1, connectivity: int = 6, band: bool = False) -> Segment:
+        """Edits the current segment on the GPU (vx_segment_edit, DESIGN.md section 2 "Segment edits"): "dilate" / "erode" by
+        `steps` voxels of the 6- or 26-neighbourhood (outside the volume counts as not set for dilate and as set for erode),
+        "open" (erode then dilate), "close" (dilate then erode), or "fill_holes" (the background components, under
+        `connectivity`, that touch no face of the volume; steps is ignored).  band=True (dilate only) grows only into voxels
+        that pass the predicate of the last segment().  Binds the current uniforms first; returns the `Segment` of the edited
+        mask (rounds and brick_visits: the fill's background flood)."""
+        if self.volume is None:
+            raise VolxelError("segment_edit: no volume (setup_from_grid first)")
+        if op not in self.SEGMENT_EDIT_OPS:
+            raise ValueError(f"op must be one of {self.SEGMENT_EDIT_OPS}, not {op!r}")
+        if connectivity not in (6, 26) or isinstance(connectivity, bool):
+            raise ValueError(f"connectivity must be 6 or 26, not {connectivity!r}")
+        fill = op == "fill_holes"
+        lo = 0 if fill else 1
+        hi = 1 if fill else _abi.SEGEDIT_MAX_STEPS
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or not lo <= int(steps) <= hi:
+            raise ValueError(f"steps must be an integer {lo} .. {hi} for {op}, not {steps!r}")
+        if not isinstance(band, (bool, np.bool_)):
+            raise ValueError(f"band must be a bool, not {band!r}")
+        if band and op != "dilate":
+            raise ValueError(f"band is for dilate only, not {op}")
+        q = _abi.VxSegmentEditParams()
+        q.op, q.connectivity, q.steps, q.band = _abi.SEGEDIT_OPS[op], int(connectivity), int(steps), int(bool(band))
+        p = self.bind_uniforms()
+        res = _abi.VxSegmentResult()
+        self._check(self._lib.vx_segment_edit(self._ctx, C.byref(q), C.byref(res)))
+        return self._segment_result(res, p)
+
+    def set_segment_mask(self, mask) -> Segment:
+        """Installs a (Z, Y, X) bool array over the index extent as the current segment (vx_segment_write_mask, the inverse of
+        segment_mask): a saved segmentation, a host-side combination of masks, or an undo.  The predicate of the last
+        segment() and the segment view stay.  Binds the current uniforms first; returns the mask's `Segment`."""
+        if self.volume is None:
+            raise VolxelError("set_segment_mask: no volume (setup_from_grid first)")
+        X, Y, Z = (int(e) for e in self.volume.grid.index_extent)
+        m = np.asarray(mask)
+        if m.dtype != np.bool_:
+            raise ValueError(f"mask must be a bool array, not {m.dtype}")
+        if m.shape != (Z, Y, X):
+            raise ValueError(f"mask shape must be (Z, Y, X) = {(Z, Y, X)} of the index extent, not {m.shape}")
+        bits = np.packbits(np.ascontiguousarray(m).ravel(), bitorder="little")
+        p = self.bind_uniforms()
+        res = _abi.VxSegmentResult()
+        self._check(self._lib.vx_segment_write_mask(self._ctx, bits.ctypes.data, bits.size, C.byref(res)))
+        return self._segment_result(res, p)
+
+    def segment_edit_stats(self):
+        """(launches, edit_ms, stats_ms) of the last segment_edit or set_segment_mask (vx_segment_edit_stats)"""
+        n = C.c_uint32()
+        ms = (C.c_double * 2)()
+        self._check(self._lib.vx_segment_edit_stats(self._ctx, C.byref(n), ms))
+        return (n.value,) + tuple(ms)
 
     SEGMENT_VIEWS = ("off", "only", "hide")   # VX_SEGVIEW_OFF, _ONLY, _HIDE
 
