@@ -581,6 +581,54 @@ int vx_set_segment_view(VxContext* ctx, int view);
 /* the current view (VX_SEGVIEW_OFF after an upload); VX_ERR_INVALID for NULL view */
 int vx_get_segment_view(VxContext* ctx, int* view);
 
+/* ---- meshes (no reference counterpart; DESIGN.md section 2 "Meshes"): the surface of an isosurface or of the current segment
+ * as an indexed triangle mesh, by naive surface nets -- one vertex per grid cell the surface passes through, one quad (two
+ * triangles) per grid edge it crosses.
+ *   DENSITY  f(i) = d(i) of vx_segment (the last vx_set_params), inside(i) = f(i) >= iso, the comparison vx_isosurface makes
+ *   SEGMENT  inside(i) = the bit of the current segment, f = inside ? 1 : 0, iso = 0.5: every crossing at the middle of its edge
+ * Every voxel outside [box_lo, box_hi] (VxSegmentParams' meaning, VX_SEGMENT_BOX_END included) or outside index_extent is outside
+ * with f = 0, so a mesh is closed where a structure meets the box or a face of the volume.  The renderer's clip box does not apply.
+ * Cell c (c_a in [-1, extent_a - 1]) has the corners c + {0, 1}^3; one with a crossing edge owns the vertex c + (the fp32 mean of
+ * its crossings), in voxel-centre coordinates (voxel i at i; a host adds 1/2 for index space).  Vertex and triangle order are a
+ * function of the input only: two calls, and every layout, give the same bytes.  Triangles wind so that the normal points from
+ * inside to outside: the signed volume of a mesh is positive. */
+typedef enum VxMeshSource {
+  VX_MESH_DENSITY = 0,
+  VX_MESH_SEGMENT = 1
+} VxMeshSource;
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxMeshParams {
+  int32_t source;          /* VxMeshSource                                                                         */
+  float iso;               /* DENSITY: finite, > 0; SEGMENT: ignored                                               */
+  uint32_t box_lo[3];      /* inclusive voxel box inside index_extent, box_lo <= box_hi                           */
+  uint32_t box_hi[3];      /* or VX_SEGMENT_BOX_END per axis: to the far face                                      */
+  uint32_t max_vertices;   /* 0 = 2^32 - 2                                                                         */
+  uint32_t max_triangles;  /* 0 = 2^32 - 2                                                                         */
+} VxMeshParams;
+/* blocks: the cell blocks of the volume (8^3 cells each, one more than bricks per axis); active_blocks: those with an active
+ * cell.  bbox: the inclusive cell box of the active cells, all 0 when the mesh is empty; a component is an int32_t in two's
+ * complement (cells start at -1: 0xffffffff). */
+typedef struct VxMeshResult {
+  uint64_t vertices, triangles, active_blocks, blocks;
+  uint32_t bbox_lo[3], bbox_hi[3];
+} VxMeshResult;
+/* Builds the context's one mesh on the device, on the context's stream behind every queued render, and synchronises.  out may
+ * be NULL.  An empty mesh is no error.  The accumulator, the frame state, VxCounters, the light grid, the bound tables, VxParams,
+ * the current segment and the segment view are not touched.  Reads the layout resident at the call (all layouts give the same
+ * bits).  Its buffers (64 B per brick, 64 B + 2 x 8 B per cell block) are allocated on first use, the outputs (24 B per vertex,
+ * 12 B per triangle) grow to the largest mesh, and all are freed with the volume; an upload drops the mesh.  VX_ERR_NO_VOLUME
+ * before an upload; VX_ERR_INVALID, naming the field, before vx_set_params, for NULL params, an unknown source, iso not finite
+ * or <= 0 (DENSITY), a box that is empty or outside the volume, SEGMENT with no current segment, and a mesh of more than
+ * max_vertices / max_triangles (the message carries both counts; no mesh is kept, the previous one is dropped too).  Any other
+ * refused call changes nothing.  group: member 0. */
+int vx_mesh_extract(VxContext* ctx, const VxMeshParams* params, VxMeshResult* out);
+/* the current mesh: 3 floats and 3 cell components per vertex, 3 vertex indices per triangle.  Any pointer may be NULL.
+ * VX_ERR_INVALID with no current mesh. */
+int vx_mesh_read(VxContext* ctx, float* verts_xyz, int32_t* cells_xyz, uint32_t* tris);
+/* the last vx_mesh_extract: kernels launched (the same for every mesh) and the HIP-event times of the inside words, of the
+ * active cells with their scan, and of the emission, kernel_ms[0 .. 2]; all 0 before the first call.  group: member 0. */
+int vx_mesh_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
+
 /* test hook (no reference counterpart): the device's R8-unorm decode table, 256 floats */
 int vx_debug_unorm_table(VxContext* ctx, float* out256);
 /* test hook: the host-built empty-space bitmask (pure CPU; bits_out may be NULL to query level/dims) */

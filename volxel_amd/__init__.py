@@ -15,4 +15,6 @@ from .environment import Environment  # noqa: F401,E402
 from .containers import ZipReadError, read_zip_slices, decode_environment  # noqa: F401,E402
 from .mpr import axial, coronal, sagittal, oblique, overlay  # noqa: F401,E402
 from ._abi import VxSliceParams, VxIsoParams, VxSegmentParams, VxSegmentResult, VxSegmentEditParams  # noqa: F401,E402
+from ._abi import VxMeshParams, VxMeshResult  # noqa: F401,E402
+from .mesh import Mesh  # noqa: F401,E402
 from .renderer import Segment  # noqa: F401,E402

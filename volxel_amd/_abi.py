@@ -52,6 +52,8 @@ VxIsoParams = struct_from_header("volxel_hip.h", "VxIsoParams")
 VxSegmentParams = struct_from_header("volxel_hip.h", "VxSegmentParams")
 VxSegmentResult = struct_from_header("volxel_hip.h", "VxSegmentResult")
 VxSegmentEditParams = struct_from_header("volxel_hip.h", "VxSegmentEditParams")
+VxMeshParams = struct_from_header("volxel_hip.h", "VxMeshParams")
+VxMeshResult = struct_from_header("volxel_hip.h", "VxMeshResult")
 
 MODE_DEFAULT, MODE_NO_DDA, MODE_RAYMARCH, MODE_DVR, MODE_DVR_PHONG, MODE_MIP, MODE_MINIP = range(7)
 LAYOUT_REFERENCE, LAYOUT_CELLQUAD, LAYOUT_BRICKF32, LAYOUT_AUTO = 0, 1, 2, 3
@@ -66,6 +68,7 @@ SLICE_MAX_SIZE, SLICE_MAX_SAMPLES = 16384, 4096
 ISO_MAX_REFINE = 16
 SEGEDIT_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3, "fill_holes": 4}   # enum VxSegmentEditOp
 SEGEDIT_MAX_STEPS = 1024
+MESH_DENSITY, MESH_SEGMENT = range(2)                  # enum VxMeshSource
 
 
 def declared_symbols(header: str):
@@ -156,6 +159,9 @@ def load_library():
         "vx_segment_edit": ([vp, P(VxSegmentEditParams), P(VxSegmentResult)], i32),
         "vx_segment_write_mask": ([vp, vp, u64, P(VxSegmentResult)], i32),
         "vx_segment_edit_stats": ([vp, P(u32), P(C.c_double)], i32),
+        "vx_mesh_extract": ([vp, P(VxMeshParams), P(VxMeshResult)], i32),
+        "vx_mesh_read": ([vp, vp, vp, vp], i32),
+        "vx_mesh_stats": ([vp, P(u32), P(C.c_double)], i32),
         # preprocessor
         "vxb_build_from_u16": ([vp, P(u32), P(C.c_float), C.c_uint16, i32, P(vp)], i32),
         "vxb_read_dicoms_to_grid": ([P(vp), P(u64), u32, i32, P(vp)], i32),

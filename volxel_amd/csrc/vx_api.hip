@@ -22,6 +22,7 @@
 #include "vx_iso.hpp"
 #include "vx_segment.hpp"
 #include "vx_segedit.hpp"
+#include "vx_mesh.hpp"
 
 using namespace vx;
 
@@ -224,6 +225,20 @@ struct VxContext {
   hipEvent_t sed_ev[3] = {nullptr, nullptr, nullptr};
   uint32_t sed_launches = 0;
   double sed_ms[2] = {0.0, 0.0};
+  // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans (freed with the
+  // volume); the vertex / cell and the triangle buffers grow to the largest mesh (freed with the volume too)
+  void* mesh_alloc = nullptr;
+  MeshDev mesh{};
+  bool mesh_valid = false;    // a mesh of the resident volume is current
+  float* mesh_verts = nullptr;
+  int32_t* mesh_cells = nullptr;
+  size_t mesh_vcap = 0;       // vertices
+  uint32_t* mesh_tris = nullptr;
+  size_t mesh_tcap = 0;       // triangles
+  uint64_t mesh_nv = 0, mesh_nt = 0;
+  hipEvent_t mesh_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint32_t mesh_launches = 0;
+  double mesh_ms[3] = {0.0, 0.0, 0.0};
 };
 
 static bool is_group(const VxContext* c) { return !c->members.empty(); }
@@ -279,6 +294,18 @@ static void free_volume(VxContext* c) {
   if (c->seg_bytes) (void)hipFree(c->seg_bytes);
   c->seg_bytes = nullptr;
   c->seg_bytes_cap = 0;
+  if (c->mesh_alloc) (void)hipFree(c->mesh_alloc);
+  c->mesh_alloc = nullptr;
+  c->mesh = MeshDev{};
+  c->mesh_valid = false;
+  if (c->mesh_verts) (void)hipFree(c->mesh_verts);
+  if (c->mesh_cells) (void)hipFree(c->mesh_cells);
+  if (c->mesh_tris) (void)hipFree(c->mesh_tris);
+  c->mesh_verts = nullptr;
+  c->mesh_cells = nullptr;
+  c->mesh_tris = nullptr;
+  c->mesh_vcap = c->mesh_tcap = 0;
+  c->mesh_nv = c->mesh_nt = 0;
 }
 
 static void drain_events(VxContext* c) {
@@ -1304,6 +1331,8 @@ void vx_destroy(VxContext* c) {
   for (hipEvent_t e : c->seg_ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->sed_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->mesh_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -3081,6 +3110,180 @@ int vx_segment_edit_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (launches) *launches = c->sed_launches;
   if (kernel_ms)
     for (int i = 0; i < 2; ++i) kernel_ms[i] = c->sed_ms[i];
+  return VX_OK;
+}
+
+// ---- meshes (vx_mesh_extract, vx_mesh_read; kernels in vx_mesh.hpp) -----------------------------------------------------------
+// Five launches whatever the mesh: the inside words, the active cells with their counts, the two launches that finish the
+// exclusive scan, the emission.  The totals are read back once, between the scan and the emission, to size the outputs.
+static int ensure_mesh(VxContext* c) {
+  if (c->mesh_alloc) return VX_OK;
+  MeshDev& m = c->mesh;
+  for (int a = 0; a < 3; ++a) {
+    m.bc[a] = c->dv.bc[a];
+    m.cb[a] = c->dv.bc[a] + 1u;
+  }
+  const size_t nb = (size_t)m.bc[0] * m.bc[1] * m.bc[2], ncb = (size_t)m.cb[0] * m.cb[1] * m.cb[2];
+  if (ncb > 0xffffff00ull) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: %zu cell blocks are beyond the 32-bit block index", ncb);
+  const size_t np = (ncb + 255u) / 256u;
+  const size_t bytes = nb * 64u + ncb * (64u + 8u + 8u) + np * 16u + sizeof(MeshStats);
+  VX_HIP(c, hipMalloc(&c->mesh_alloc, bytes));
+  char* p = static_cast<char*>(c->mesh_alloc);
+  m.inside = reinterpret_cast<uint64_t*>(p);
+  p += nb * 64u;
+  m.act = reinterpret_cast<uint64_t*>(p);
+  p += ncb * 64u;
+  m.vq = reinterpret_cast<uint2*>(p);
+  p += ncb * 8u;
+  m.off = reinterpret_cast<uint2*>(p);
+  p += ncb * 8u;
+  m.part = reinterpret_cast<uint2*>(p);
+  p += np * 8u;
+  m.poff = reinterpret_cast<uint2*>(p);
+  p += np * 8u;
+  m.st = reinterpret_cast<MeshStats*>(p);
+  m.nb = (uint32_t)nb;
+  m.ncb = (uint32_t)ncb;
+  m.np = (uint32_t)np;
+  return VX_OK;
+}
+
+int vx_mesh_extract(VxContext* c, const VxMeshParams* mp, VxMeshResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_mesh_extract(c->members[0], mp, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_mesh_extract: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!mp) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: params is NULL");
+  if (mp->source != VX_MESH_DENSITY && mp->source != VX_MESH_SEGMENT)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: source = %d is not VX_MESH_DENSITY or VX_MESH_SEGMENT", mp->source);
+  const bool segment = mp->source == VX_MESH_SEGMENT;
+  if (!segment && !(std::isfinite(mp->iso) && mp->iso > 0.0f))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: iso = %g is not finite and > 0", (double)mp->iso);
+  const uint32_t* E = c->dv.extent;
+  MeshBox box{{mp->box_lo[0], mp->box_lo[1], mp->box_lo[2]}, {mp->box_hi[0], mp->box_hi[1], mp->box_hi[2]}};
+  for (int a = 0; a < 3; ++a) {
+    if (box.hi[a] == VX_SEGMENT_BOX_END) box.hi[a] = E[a] - 1u;
+    if (box.lo[a] > box.hi[a] || box.hi[a] >= E[a])
+      VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: box axis %d [%u, %u] is empty or outside the index extent %u", a, mp->box_lo[a],
+              mp->box_hi[a], E[a]);
+  }
+  if (segment && !c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: source = VX_MESH_SEGMENT with no current segment (vx_segment or vx_segment_write_mask "
+            "first; an upload drops it)");
+  if (int rc = ensure_mesh(c)) return rc;
+  for (hipEvent_t& e : c->mesh_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  c->mesh_valid = false;
+  c->mesh_nv = c->mesh_nt = 0;
+  const MeshDev& m = c->mesh;
+  const VxParams& p = c->params;
+  const float iso = segment ? 0.5f : mp->iso;
+  VX_HIP(c, hipEventRecord(c->mesh_ev[0], c->stream));
+  if (segment) {
+    const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)m.nb * 8u + 255u) / 256u, 8192u);
+    hipLaunchKernelGGL(mesh_inside_segment, dim3(blocks), dim3(256), 0, c->stream, c->seg.seg, box, m);
+  } else {
+    const uint32_t blocks = std::min<uint32_t>((m.nb + 3u) / 4u, 4096u);
+    with_layout(slice_layout(c), [&](auto lay) {
+      constexpr int LAY = decltype(lay)::value;
+      hipLaunchKernelGGL((mesh_inside_density<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale,
+                         p.volume_inv_maj, iso, box, m);
+    });
+  }
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->mesh_ev[1], c->stream));
+  hipLaunchKernelGGL(mesh_active, dim3(m.np), dim3(256), 0, c->stream, m);
+  hipLaunchKernelGGL(mesh_scan_partials, dim3(1), dim3(1024), 0, c->stream, m);
+  hipLaunchKernelGGL(mesh_offsets, dim3(m.np), dim3(256), 0, c->stream, m);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->mesh_ev[2], c->stream));
+  MeshStats st;
+  VX_HIP(c, hipMemcpyAsync(&st, m.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  const uint64_t nv = st.verts, nt = 2u * (uint64_t)st.quads;
+  const uint64_t maxv = mp->max_vertices ? mp->max_vertices : 0xfffffffeull, maxt = mp->max_triangles ? mp->max_triangles : 0xfffffffeull;
+  if (nv > maxv || nt > maxt)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: the mesh has %llu vertices and %llu triangles, more than max_vertices = %llu or "
+            "max_triangles = %llu", (unsigned long long)nv, (unsigned long long)nt, (unsigned long long)maxv, (unsigned long long)maxt);
+  if (nv > c->mesh_vcap) {   // (every earlier call has completed: each one synchronises)
+    if (c->mesh_verts) (void)hipFree(c->mesh_verts);
+    if (c->mesh_cells) (void)hipFree(c->mesh_cells);
+    c->mesh_verts = nullptr;
+    c->mesh_cells = nullptr;
+    c->mesh_vcap = 0;
+    VX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->mesh_verts), (size_t)nv * 12u));
+    VX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->mesh_cells), (size_t)nv * 12u));
+    c->mesh_vcap = (size_t)nv;
+  }
+  if (nt > c->mesh_tcap) {
+    if (c->mesh_tris) (void)hipFree(c->mesh_tris);
+    c->mesh_tris = nullptr;
+    c->mesh_tcap = 0;
+    VX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->mesh_tris), (size_t)nt * 12u));
+    c->mesh_tcap = (size_t)nt;
+  }
+  {
+    const uint32_t blocks = std::min<uint32_t>((m.ncb + 3u) / 4u, 4096u);
+    if (segment)   // no voxel is read: one instance serves every layout
+      hipLaunchKernelGGL((mesh_emit<LAYOUT_REF, true>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
+                         iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->mesh_verts, c->mesh_cells, c->mesh_tris);
+    else
+      with_layout(slice_layout(c), [&](auto lay) {
+        constexpr int LAY = decltype(lay)::value;
+        hipLaunchKernelGGL((mesh_emit<LAY, false>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
+                           iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->mesh_verts, c->mesh_cells, c->mesh_tris);
+      });
+  }
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipEventRecord(c->mesh_ev[3], c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  for (int i = 0; i < 3; ++i) {
+    float ms = 0.0f;
+    VX_HIP(c, hipEventElapsedTime(&ms, c->mesh_ev[i], c->mesh_ev[i + 1]));
+    c->mesh_ms[i] = ms;
+  }
+  c->mesh_launches = 5u;
+  c->mesh_nv = nv;
+  c->mesh_nt = nt;
+  c->mesh_valid = true;
+  if (out) {
+    VxMeshResult r{};
+    r.vertices = nv;
+    r.triangles = nt;
+    r.active_blocks = st.active_blocks;
+    r.blocks = m.ncb;
+    if (nv)
+      for (int a = 0; a < 3; ++a) {
+        r.bbox_lo[a] = st.lo[a] - 1u;   // the statistics hold cell + 1; cell -1 wraps to its two's complement
+        r.bbox_hi[a] = st.hi[a] - 1u;
+      }
+    *out = r;
+  }
+  return VX_OK;
+}
+
+int vx_mesh_read(VxContext* c, float* verts_xyz, int32_t* cells_xyz, uint32_t* tris) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_mesh_read(c->members[0], verts_xyz, cells_xyz, tris));
+  VX_DEV(c);
+  if (!c->mesh_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_read: no current mesh (vx_mesh_extract first; an upload drops it)");
+  if (verts_xyz && c->mesh_nv)
+    VX_HIP(c, hipMemcpyAsync(verts_xyz, c->mesh_verts, (size_t)c->mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
+  if (cells_xyz && c->mesh_nv)
+    VX_HIP(c, hipMemcpyAsync(cells_xyz, c->mesh_cells, (size_t)c->mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
+  if (tris && c->mesh_nt) VX_HIP(c, hipMemcpyAsync(tris, c->mesh_tris, (size_t)c->mesh_nt * 12u, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_mesh_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_mesh_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->mesh_launches;
+  if (kernel_ms)
+    for (int i = 0; i < 3; ++i) kernel_ms[i] = c->mesh_ms[i];
   return VX_OK;
 }
 

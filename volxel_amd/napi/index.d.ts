@@ -114,6 +114,15 @@ export declare class Volxel3DDicomRenderer {
       mean: number; rounds: number; converged: boolean; brickVisits: number };
   /** the last segmentEdit or setSegmentMask: kernels launched, the times of the edit and of its statistics */
   segmentEditStats(): { launches: number; editMs: number; statsMs: number };
+  /** the surface of the isosurface d = iso, or of the current segment, as a closed indexed triangle mesh built on the GPU
+   *  (include/volxel_hip.h vx_mesh_extract): 3 numbers per vertex, 3 cell components per vertex, 3 indices per triangle */
+  extractMesh(opts: { iso?: number; segment?: boolean; box?: [[number, number, number], [number, number, number]] | null;
+    space?: 'voxel' | 'grid' | 'world'; maxVertices?: number; maxTriangles?: number }):
+    { vertices: Float64Array; cells: Int32Array; triangles: Uint32Array };
+  /** the last extractMesh: kernels launched and the times of the inside words, the active cells with their scan, the emission */
+  meshStats(): { launches: number; insideMs: number; activeMs: number; emitMs: number };
+  /** binary STL (80-byte header, u32 count, 50 bytes per triangle) of a mesh from extractMesh */
+  meshToStl(mesh: { vertices: Float64Array; triangles: Uint32Array }): Buffer;
   /** show only, or hide, the current segment in DVR, Phong, MIP / MinIP and the isosurfaces (vx_set_segment_view); 'off' after
    *  a new volume; setting it restarts accumulation */
   segmentView: 'off' | 'only' | 'hide';

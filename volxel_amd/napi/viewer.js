@@ -40,6 +40,8 @@ const LAYOUT = parseParamsLayout();
 const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams());
 const ISO_LAYOUT = parseParamsLayout('VxIsoParams', native.sizeofIsoParams());
 const SEGMENT_LAYOUT = parseParamsLayout('VxSegmentParams', native.sizeofSegmentParams());
+const MESH_LAYOUT = parseParamsLayout('VxMeshParams', native.sizeofMeshParams());
+const MESH_SPACES = ['voxel', 'grid', 'world'];
 const SEGMENT_VIEWS = ['off', 'only', 'hide'];   // VX_SEGVIEW_OFF, _ONLY, _HIDE
 const SEGMENT_EDIT_OPS = ['dilate', 'erode', 'open', 'close', 'fill_holes'];   // VxSegmentEditOp, in order
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
@@ -675,6 +677,68 @@ class Volxel3DDicomRenderer {
   }
   /** the last segmentEdit or setSegmentMask: kernels launched and the times of the edit and of the statistics */
   segmentEditStats() { return native.segmentEditStats(this.ctx); }
+  /** vx_mesh_extract (DESIGN.md section 2 "Meshes"): the surface of the isosurface d = iso, or ({ segment: true }) of the current
+   *  segment, as a closed indexed triangle mesh built on the GPU (naive surface nets).  opts: { iso | segment, box = null
+   *  ([[x0, y0, z0], [x1, y1, z1]], inclusive; voxels outside count as outside: the mesh is capped there), space = 'world'
+   *  ('voxel': voxel i at i; 'grid': grid.transform * (q + 1/2); 'world': the space of pick()), maxVertices = 0, maxTriangles
+   *  = 0 (0: 2^32 - 2) } -> { vertices: Float64Array (3 per vertex), cells: Int32Array (3 per vertex), triangles: Uint32Array
+   *  (3 per triangle, normals pointing out) }.  Binds the current uniforms first. */
+  extractMesh({ iso = null, segment = false, box = null, space = 'world', maxVertices = 0, maxTriangles = 0 } = {}) {
+    if (typeof segment !== 'boolean') throw new Error(`extractMesh: segment must be a boolean, not ${segment}`);
+    if ((iso === null) === !segment) throw new Error('extractMesh takes exactly one of iso and segment: true');
+    if (!MESH_SPACES.includes(space)) throw new Error(`extractMesh: space must be one of ${MESH_SPACES.join(', ')}, not ${space}`);
+    for (const [k, v] of [['maxVertices', maxVertices], ['maxTriangles', maxTriangles]])
+      if (!Number.isInteger(v) || v < 0 || v > 4294967295) throw new Error(`extractMesh: ${k} must be an integer 0 .. 2^32 - 1, not ${v}`);
+    const i32 = segment ? 0 : Math.fround(iso);
+    if (!segment && !(Number.isFinite(i32) && i32 > 0)) throw new Error(`extractMesh: iso must be finite and > 0, not ${iso}`);
+    const e = this.sliceExtent();
+    const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
+    const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
+    if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
+      throw new Error(`extractMesh: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+    const p = new ParamsBlock(MESH_LAYOUT);
+    p.set('source', segment ? 1 : 0); p.set('iso', i32); p.set('box_lo', blo); p.set('box_hi', bhi);
+    p.set('max_vertices', maxVertices); p.set('max_triangles', maxTriangles);
+    this.bindUniforms();
+    const res = native.meshExtract(this.ctx, p.buffer);
+    const v32 = new Float32Array(3 * res.vertices), cells = new Int32Array(3 * res.vertices);
+    let triangles = new Uint32Array(3 * res.triangles);
+    native.meshRead(this.ctx, v32, cells, triangles);
+    const vertices = Float64Array.from(v32);
+    if (space !== 'voxel') {
+      // m * (q + 1/2, 1) in doubles; voxel i occupies [i, i + 1] in index space
+      const m = Array.from(space === 'grid' ? this.volume.grid.transform : this.densityTransform());
+      for (let k = 0; k < vertices.length; k += 3) {
+        const x = vertices[k] + 0.5, y = vertices[k + 1] + 0.5, z = vertices[k + 2] + 0.5;
+        for (let r = 0; r < 3; ++r) vertices[k + r] = m[r] * x + m[4 + r] * y + m[8 + r] * z + m[12 + r];
+      }
+      const det = m[0] * (m[5] * m[10] - m[9] * m[6]) - m[4] * (m[1] * m[10] - m[9] * m[2]) + m[8] * (m[1] * m[6] - m[5] * m[2]);
+      if (det < 0) for (let k = 0; k < triangles.length; k += 3) { const t = triangles[k + 1]; triangles[k + 1] = triangles[k + 2]; triangles[k + 2] = t; }
+    }
+    return { vertices, cells, triangles };
+  }
+  /** the last extractMesh: kernels launched (the same for every mesh) and the times of its three stages (vx_mesh_stats) */
+  meshStats() { return native.meshStats(this.ctx); }
+  /** binary STL of a mesh from extractMesh: an 80-byte header, the u32 triangle count, 50 bytes per triangle (the unit facet
+   *  normal of the float32 corners, (0, 0, 0) for a degenerate one) -- the bytes of Mesh.write_stl in Python */
+  meshToStl({ vertices, triangles }) {
+    const n = triangles.length / 3;
+    const out = Buffer.alloc(84 + 50 * n);
+    out.fill(' ', 0, 80);
+    out.write('volxel_amd binary STL', 0, 'ascii');
+    out.writeUInt32LE(n, 80);
+    const c = [[0, 0, 0], [0, 0, 0], [0, 0, 0]];
+    for (let t = 0; t < n; ++t) {
+      for (let k = 0; k < 3; ++k) for (let a = 0; a < 3; ++a) c[k][a] = Math.fround(vertices[3 * triangles[3 * t + k] + a]);
+      const u = [c[1][0] - c[0][0], c[1][1] - c[0][1], c[1][2] - c[0][2]], w = [c[2][0] - c[0][0], c[2][1] - c[0][1], c[2][2] - c[0][2]];
+      let nx = u[1] * w[2] - u[2] * w[1], ny = u[2] * w[0] - u[0] * w[2], nz = u[0] * w[1] - u[1] * w[0];
+      const len = Math.sqrt(nx * nx + ny * ny + nz * nz);
+      if (len > 0) { nx /= len; ny /= len; nz /= len; } else { nx = ny = nz = 0; }
+      let o = 84 + 50 * t;
+      for (const f of [nx, ny, nz, ...c[0], ...c[1], ...c[2]]) { out.writeFloatLE(f, o); o += 4; }
+    }
+    return out;
+  }
   /** 'off' (the default, and again after a new volume), 'only' (the current segment alone) or 'hide' (everything but it):
    *  DVR, Phong, MIP / MinIP and the isosurfaces (hence pick) sample a volume whose hidden voxels read 0 (vx_set_segment_view,
    *  DESIGN.md section 2 "Segment views"); slices and segment() keep the unmasked data.  Setting it restarts accumulation. */

@@ -698,6 +698,79 @@ static napi_value n_segment_edit_stats(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* meshExtract(ctx, ArrayBuffer holding one VxMeshParams) -> { vertices, triangles, activeBlocks, blocks, bboxLo, bboxHi }
+ * (vx_mesh_extract; the bbox components are cells, -1 included) */
+static napi_value n_mesh_extract(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* d;
+  size_t n;
+  NAPI_OK(napi_get_arraybuffer_info(env, a[1], &d, &n));
+  if (n != sizeof(VxMeshParams)) return throw_msg(env, "extractMesh: buffer is not sizeof(VxMeshParams)");
+  VxMeshParams mp;
+  memcpy(&mp, d, sizeof mp);
+  VxMeshResult r;
+  if (vx_mesh_extract(c, &mp, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o, lo, hi, v;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "vertices", (double)r.vertices) || !set_num(env, o, "triangles", (double)r.triangles) ||
+      !set_num(env, o, "activeBlocks", (double)r.active_blocks) || !set_num(env, o, "blocks", (double)r.blocks))
+    return throw_msg(env, "extractMesh: could not build the result");
+  NAPI_OK(napi_create_array_with_length(env, 3, &lo));
+  NAPI_OK(napi_create_array_with_length(env, 3, &hi));
+  for (uint32_t i = 0; i < 3; ++i) {
+    NAPI_OK(napi_create_int32(env, (int32_t)r.bbox_lo[i], &v));
+    NAPI_OK(napi_set_element(env, lo, i, v));
+    NAPI_OK(napi_create_int32(env, (int32_t)r.bbox_hi[i], &v));
+    NAPI_OK(napi_set_element(env, hi, i, v));
+  }
+  NAPI_OK(napi_set_named_property(env, o, "bboxLo", lo));
+  NAPI_OK(napi_set_named_property(env, o, "bboxHi", hi));
+  return o;
+}
+
+static napi_value n_sizeof_mesh_params(napi_env env, napi_callback_info info) {
+  (void)info;
+  napi_value v;
+  NAPI_OK(napi_create_uint32(env, (uint32_t)sizeof(VxMeshParams), &v));
+  return v;
+}
+
+/* meshRead(ctx, Float32Array of 3 * vertices, Int32Array of 3 * vertices, Uint32Array of 3 * triangles) (vx_mesh_read); the
+ * lengths are those meshExtract returned -- viewer.js allocates them from its result */
+static napi_value n_mesh_read(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void *v, *ce, *t;
+  size_t nv, nc, nt;
+  if (!typed_or_null(env, a[1], napi_float32_array, &v, &nv) || !typed_or_null(env, a[2], napi_int32_array, &ce, &nc) ||
+      !typed_or_null(env, a[3], napi_uint32_array, &t, &nt))
+    return NULL;
+  if (vx_mesh_read(c, (float*)v, (int32_t*)ce, (uint32_t*)t) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+
+/* meshStats(ctx) -> { launches, insideMs, activeMs, emitMs } (vx_mesh_stats) */
+static napi_value n_mesh_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t launches = 0;
+  double ms[3] = {0.0, 0.0, 0.0};
+  if (vx_mesh_stats(c, &launches, ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "launches", launches) || !set_num(env, o, "insideMs", ms[0]) || !set_num(env, o, "activeMs", ms[1]) ||
+      !set_num(env, o, "emitMs", ms[2]))
+    return throw_msg(env, "meshStats: could not build the result");
+  return o;
+}
+
 static napi_value n_sizeof_segment_params(napi_env env, napi_callback_info info) {
   (void)info;
   napi_value v;
@@ -951,6 +1024,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"sliceMask", n_slice_mask}, {"segmentStats", n_segment_stats}, {"setSegmentView", n_set_segment_view},
       {"getSegmentView", n_get_segment_view}, {"segmentEdit", n_segment_edit}, {"setSegmentMask", n_set_segment_mask},
       {"segmentEditStats", n_segment_edit_stats},
+      {"meshExtract", n_mesh_extract}, {"sizeofMeshParams", n_sizeof_mesh_params}, {"meshRead", n_mesh_read},
+      {"meshStats", n_mesh_stats},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},
       {"readDicomsToGrid", n_read_dicoms_to_grid}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; ++i) {

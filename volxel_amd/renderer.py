@@ -27,6 +27,7 @@ from .scene import Camera, Grid, Volume, flat, from_flat
 from .environment import Environment
 from .settings import ViewerSettings, verify_settings
 from .transfer import default_transfer_function, generate_transfer_function
+from .mesh import Mesh, check_extract_args
 
 LOW_RESOLUTION_DURATION = 5  # viewer.ts:132
 
@@ -819,6 +820,61 @@ class Volxel3DRenderer:
         n = C.c_uint32()
         ms = (C.c_double * 2)()
         self._check(self._lib.vx_segment_edit_stats(self._ctx, C.byref(n), ms))
+        return (n.value,) + tuple(ms)
+
+    def extract_mesh(self, iso=None, *, segment: bool = False, box=None, space: str = "world", max_vertices: int = 0,
+                     max_triangles: int = 0) -> Mesh:
+        """The surface of the isosurface d = iso, or (segment=True) of the current segment, as a closed, indexed triangle mesh
+        (vx_mesh_extract, DESIGN.md section 2 "Meshes": naive surface nets on the GPU).  Exactly one of iso / segment=True.
+        box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices, or None for the whole volume; voxels outside it (and
+        outside the volume) count as outside, so the mesh is capped there.  space: "voxel" (voxel i at i, the device's
+        coordinates), "grid" (grid.transform * (q + 1/2, 1): mm for DICOM, the space of Segment.volume_grid) or "world" (the
+        space of pick()).  max_vertices / max_triangles: refuse a larger mesh (0: 2^32 - 2).  Binds the current uniforms."""
+        iso32 = check_extract_args(iso, segment, space, max_vertices, max_triangles)
+        if self.volume is None:
+            raise VolxelError("extract_mesh: no volume (setup_from_grid first)")
+        ext = [int(e) for e in self.volume.grid.index_extent]
+        if box is None:
+            blo, bhi = (0, 0, 0), tuple(e - 1 for e in ext)
+        else:
+            try:
+                blo, bhi = (tuple(v) for v in box)
+            except (TypeError, ValueError):
+                raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)), not {box!r}") from None
+            if len(blo) != 3 or len(bhi) != 3 or any(isinstance(a, bool) or int(a) != a for a in blo + bhi):
+                raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)) of integers, not {box!r}")
+            blo, bhi = tuple(int(a) for a in blo), tuple(int(a) for a in bhi)
+            if not all(0 <= a <= b < e for a, b, e in zip(blo, bhi, ext)):
+                raise ValueError(f"box {box!r} is empty or outside the index extent {tuple(ext)}")
+        q = _abi.VxMeshParams()
+        q.source = _abi.MESH_SEGMENT if segment else _abi.MESH_DENSITY
+        q.iso = 0.0 if segment else float(iso32)
+        q.box_lo[0], q.box_lo[1], q.box_lo[2] = blo
+        q.box_hi[0], q.box_hi[1], q.box_hi[2] = bhi
+        q.max_vertices, q.max_triangles = int(max_vertices), int(max_triangles)
+        self.bind_uniforms()
+        res = _abi.VxMeshResult()
+        self._check(self._lib.vx_mesh_extract(self._ctx, C.byref(q), C.byref(res)))
+        self.last_mesh_result = res
+        nv, nt = int(res.vertices), int(res.triangles)
+        verts = np.empty((nv, 3), dtype=np.float32)
+        cells = np.empty((nv, 3), dtype=np.int32)
+        tris = np.empty((nt, 3), dtype=np.uint32)
+        self._check(self._lib.vx_mesh_read(self._ctx, verts.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p),
+                                           tris.ctypes.data_as(C.c_void_p)))
+        mesh = Mesh(verts.astype(np.float64), cells, tris, "voxel")
+        if space == "voxel":
+            return mesh
+        half = np.eye(4)
+        half[:3, 3] = 0.5   # voxel i occupies [i, i + 1] in index space
+        m = np.asarray(self.volume.grid.transform if space == "grid" else self.volume.combined_transform(), dtype=np.float64)
+        return mesh.transformed(m @ half, space)
+
+    def mesh_stats(self):
+        """(launches, inside_ms, active_and_scan_ms, emit_ms) of the last extract_mesh (vx_mesh_stats)"""
+        n = C.c_uint32()
+        ms = (C.c_double * 3)()
+        self._check(self._lib.vx_mesh_stats(self._ctx, C.byref(n), ms))
         return (n.value,) + tuple(ms)
 
     SEGMENT_VIEWS = ("off", "only", "hide")   # VX_SEGVIEW_OFF, _ONLY, _HIDE
