@@ -560,6 +560,68 @@ int vx_segment_write_mask(VxContext* ctx, const uint8_t* bits, uint64_t nbytes, 
  * first call.  Any pointer may be NULL.  group: member 0. */
 int vx_segment_edit_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
 
+/* ---- islands (DESIGN.md section 2 "Islands"): the c-connected components (c = 6 or 26) of the current segment M inside the
+ * volume.  Island I has count(I) voxels, anchor(I) = its first voxel in C order over (z, y, x) and an inclusive bbox.  The
+ * canonical order is by count descending, ties by the C-order index of the anchor ascending; island k (0-based) of that order
+ * has label k + 1, the background label 0.  All of it is a function of M and c alone: not of layout, launch shape or run. */
+/* The whole band as the current segment, without a seed: M = { i : P(i) } (lo, hi and the box as for vx_segment; seed,
+ * connectivity and max_rounds are ignored).  The band also becomes the predicate of band dilation, as vx_segment leaves it.
+ * out (may be NULL): the statistics as vx_segment computes them, rounds = brick_visits = 0, converged = 1; vx_segment_stats keeps
+ * reporting the last vx_segment.  Stream, group, untouched state and refusals (other than the seed's and the connectivity's) as
+ * vx_segment.  No new kernel: seg_predicate and seg_stats behind an entry point of their own. */
+int vx_segment_threshold(VxContext* ctx, const VxSegmentParams* sp, VxSegmentResult* out);
+typedef enum VxIslandsOp {
+  VX_ISLANDS_LABEL = 0,         /* changes nothing: labels M and fills the table                                    */
+  VX_ISLANDS_KEEP_LARGEST = 1,  /* keeps islands 0 .. keep - 1 of the canonical order (keep >= islands: all)        */
+  VX_ISLANDS_REMOVE_SMALL = 2,  /* keeps the islands with count >= min_voxels (none left is legal)                  */
+  VX_ISLANDS_KEEP_AT = 3        /* keeps the island that holds voxel seed; the empty set when seed is not in M      */
+} VxIslandsOp;
+/* every member is 4 or 8 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxIslandsParams {
+  int32_t op;              /* VxIslandsOp                                                                          */
+  int32_t connectivity;    /* 6 or 26                                                                              */
+  uint64_t keep;           /* KEEP_LARGEST: >= 1; ignored by the other ops                                         */
+  uint64_t min_voxels;     /* REMOVE_SMALL: >= 1; ignored by the other ops                                         */
+  uint32_t seed[3];        /* KEEP_AT: a voxel inside index_extent; ignored by the other ops                       */
+  uint32_t reserved;       /* 0                                                                                    */
+} VxIslandsParams;
+/* islands: the islands of M BEFORE the op; kept: after it; largest: the count of island 0 before the op (0 for an empty M);
+ * seg: the statistics of the mask AFTER the op, as vx_segment_edit reports them (rounds = brick_visits = 0, converged = 1) */
+typedef struct VxIslandsResult {
+  uint64_t islands, kept, largest;
+  VxSegmentResult seg;
+} VxIslandsResult;
+/* one row of the table: x, y, z order in anchor and bbox */
+typedef struct VxIsland {
+  uint64_t count;
+  uint32_t anchor[3];
+  uint32_t bbox_lo[3], bbox_hi[3];
+  uint32_t label;          /* its place in the canonical order + 1 */
+} VxIsland;
+/* Labels the current segment and applies op, on the context's stream behind every queued render, and synchronises.  After a
+ * modifying op the table and the labels describe the NEW mask (a filter of the old table: the kept islands keep their order).
+ * The number of kernel launches is a function of the op alone, never of the mask: a union-find over the brick words, not a flood
+ * (vx_islands.hpp).  Labels are 4 B per voxel, with 8 B per brick, allocated by the first call and freed with the volume; the table
+ * (40 + 4 B per island) grows to the largest count met.  The accumulator, the frame state, VxCounters, the light grid, the bound
+ * tables, the mesh, VxParams, the segment view and what vx_segment_stats reports are not touched; with a view on, the next covered
+ * call reads the new mask.  An empty M is legal (0 islands).  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the
+ * field and changing nothing, before vx_set_params, for NULL params, no current segment, an op outside the enum, connectivity not
+ * 6 or 26, keep = 0 (KEEP_LARGEST), min_voxels = 0 (REMOVE_SMALL), a KEEP_AT seed outside index_extent and a volume of 2^31
+ * voxels or more.  out may be NULL.  group: member 0. */
+int vx_segment_islands(VxContext* ctx, const VxIslandsParams* params, VxIslandsResult* out);
+/* rows first .. first + n - 1 of the table in canonical order.  VX_ERR_INVALID with no current table (none yet; an upload,
+ * vx_segment, vx_segment_threshold, vx_segment_edit and vx_segment_write_mask drop it), for first + n beyond the number of
+ * islands and for NULL out with n > 0. */
+int vx_islands_read(VxContext* ctx, uint64_t first, uint64_t n, VxIsland* out);
+/* the dense label volume, (Z, Y, X) in C order: nvoxels must be X * Y * Z of index_extent.  VX_ERR_INVALID with no current table,
+ * for NULL labels and a wrong nvoxels.  Its device buffer (4 B per voxel) is allocated by the first read. */
+int vx_islands_read_labels(VxContext* ctx, uint32_t* labels, uint64_t nvoxels);
+/* the last vx_segment_islands: kernels launched, and kernel_ms[0 .. 6] = the HIP-event times of the in-brick labelling, the
+ * merge across bricks, the flattening with the scan of the root counts, the table, the HOST's ranking of the rows (wall clock:
+ * the read-back of the rows, the sort and the upload of the labels), the apply pass (0 for LABEL) and the statistics; all 0 before
+ * the first call.  Any pointer may be NULL.  group: member 0. */
+int vx_islands_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
+
 /* ---- segment views (DESIGN.md section 2 "Segment views"): show only, or hide, the current segment.  With a view other than
  * OFF the covered calls -- vx_render_frame / vx_render_frames in VX_MODE_DVR, _DVR_PHONG, _MIP and _MINIP, and vx_isosurface
  * (hence picking) -- sample the masked volume: every decoded voxel v(i) reads +0.0f where it is hidden (ONLY: i is not in the

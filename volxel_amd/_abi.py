@@ -42,7 +42,9 @@ def struct_from_header(header: str, name: str):
                 fields.append((am.group(1), ctype * int(am.group(2))))
             else:
                 fields.append((item, ctype))
-    return type(name, (C.Structure,), {"_fields_": fields})
+    cls = type(name, (C.Structure,), {"_fields_": fields})
+    _CTYPES[name] = cls   # a later struct may hold this one by value (VxIslandsResult::seg)
+    return cls
 
 
 VxParams = struct_from_header("volxel_hip.h", "VxParams")
@@ -52,6 +54,9 @@ VxIsoParams = struct_from_header("volxel_hip.h", "VxIsoParams")
 VxSegmentParams = struct_from_header("volxel_hip.h", "VxSegmentParams")
 VxSegmentResult = struct_from_header("volxel_hip.h", "VxSegmentResult")
 VxSegmentEditParams = struct_from_header("volxel_hip.h", "VxSegmentEditParams")
+VxIslandsParams = struct_from_header("volxel_hip.h", "VxIslandsParams")
+VxIslandsResult = struct_from_header("volxel_hip.h", "VxIslandsResult")
+VxIsland = struct_from_header("volxel_hip.h", "VxIsland")
 VxMeshParams = struct_from_header("volxel_hip.h", "VxMeshParams")
 VxMeshResult = struct_from_header("volxel_hip.h", "VxMeshResult")
 
@@ -68,6 +73,7 @@ SLICE_MAX_SIZE, SLICE_MAX_SAMPLES = 16384, 4096
 ISO_MAX_REFINE = 16
 SEGEDIT_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3, "fill_holes": 4}   # enum VxSegmentEditOp
 SEGEDIT_MAX_STEPS = 1024
+ISLANDS_OPS = {"label": 0, "keep_largest": 1, "remove_small": 2, "keep_at": 3}   # enum VxIslandsOp
 MESH_DENSITY, MESH_SEGMENT = range(2)                  # enum VxMeshSource
 
 
@@ -159,6 +165,11 @@ def load_library():
         "vx_segment_edit": ([vp, P(VxSegmentEditParams), P(VxSegmentResult)], i32),
         "vx_segment_write_mask": ([vp, vp, u64, P(VxSegmentResult)], i32),
         "vx_segment_edit_stats": ([vp, P(u32), P(C.c_double)], i32),
+        "vx_segment_threshold": ([vp, P(VxSegmentParams), P(VxSegmentResult)], i32),
+        "vx_segment_islands": ([vp, P(VxIslandsParams), P(VxIslandsResult)], i32),
+        "vx_islands_read": ([vp, u64, u64, P(VxIsland)], i32),
+        "vx_islands_read_labels": ([vp, vp, u64], i32),
+        "vx_islands_stats": ([vp, P(u32), P(C.c_double)], i32),
         "vx_mesh_extract": ([vp, P(VxMeshParams), P(VxMeshResult)], i32),
         "vx_mesh_read": ([vp, vp, vp, vp], i32),
         "vx_mesh_stats": ([vp, P(u32), P(C.c_double)], i32),

@@ -22,6 +22,7 @@
 #include "vx_iso.hpp"
 #include "vx_segment.hpp"
 #include "vx_segedit.hpp"
+#include "vx_islands.hpp"
 #include "vx_mesh.hpp"
 
 using namespace vx;
@@ -225,6 +226,19 @@ struct VxContext {
   hipEvent_t sed_ev[3] = {nullptr, nullptr, nullptr};
   uint32_t sed_launches = 0;
   double sed_ms[2] = {0.0, 0.0};
+  // islands (vx_segment_islands): the labels (one u32 per voxel, brick-major), the root counts and their scan in one allocation
+  // made by the first call and freed with the volume; the rows and their labels grow to the largest table; the ranked table
+  // lives on the host; the dense label volume is allocated by the first vx_islands_read_labels
+  void* isl_alloc = nullptr;
+  void* isl_rows_alloc = nullptr;
+  IslDev isl{};
+  bool isl_valid = false;     // the table and the labels describe the current segment
+  std::vector<VxIsland> isl_table;
+  uint32_t* isl_dense = nullptr;
+  size_t isl_dense_cap = 0;
+  hipEvent_t isl_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint32_t isl_launches = 0;
+  double isl_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans (freed with the
   // volume); the vertex / cell and the triangle buffers grow to the largest mesh (freed with the volume too)
   void* mesh_alloc = nullptr;
@@ -294,6 +308,15 @@ static void free_volume(VxContext* c) {
   if (c->seg_bytes) (void)hipFree(c->seg_bytes);
   c->seg_bytes = nullptr;
   c->seg_bytes_cap = 0;
+  if (c->isl_alloc) (void)hipFree(c->isl_alloc);
+  if (c->isl_rows_alloc) (void)hipFree(c->isl_rows_alloc);
+  if (c->isl_dense) (void)hipFree(c->isl_dense);
+  c->isl_alloc = c->isl_rows_alloc = nullptr;
+  c->isl_dense = nullptr;
+  c->isl_dense_cap = 0;
+  c->isl = IslDev{};
+  c->isl_valid = false;
+  c->isl_table.clear();
   if (c->mesh_alloc) (void)hipFree(c->mesh_alloc);
   c->mesh_alloc = nullptr;
   c->mesh = MeshDev{};
@@ -1333,6 +1356,8 @@ void vx_destroy(VxContext* c) {
   for (hipEvent_t e : c->sed_ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->mesh_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->isl_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2781,6 +2806,7 @@ int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
   }
   c->seg_valid = false;
   c->seg_pred_valid = false;
+  c->isl_valid = false;
   {
     const int rc = ensure_segment(c);
     if (rc) return rc;
@@ -3025,6 +3051,7 @@ int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult
   if (ep->band && !c->seg_pred_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
   if (int rc = ensure_segedit(c)) return rc;
+  c->isl_valid = false;
   const SegDev& s = c->seg;
   const int conn = ep->connectivity;
   const uint32_t n = ep->steps;
@@ -3093,6 +3120,7 @@ int vx_segment_write_mask(VxContext* c, const uint8_t* bits, uint64_t nbytes, Vx
     VX_HIP(c, hipMalloc(&c->seg_bytes, want));
     c->seg_bytes_cap = want;
   }
+  c->isl_valid = false;
   const SegDev& s = c->seg;
   VX_HIP(c, hipMemcpyAsync(c->seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
   VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
@@ -3110,6 +3138,284 @@ int vx_segment_edit_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (launches) *launches = c->sed_launches;
   if (kernel_ms)
     for (int i = 0; i < 2; ++i) kernel_ms[i] = c->sed_ms[i];
+  return VX_OK;
+}
+
+// ---- islands (vx_segment_threshold, vx_segment_islands, vx_islands_read*; kernels in vx_islands.hpp) ---------------------------
+int vx_segment_threshold(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_threshold(c->members[0], sp, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_threshold: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: sp is NULL");
+  const uint32_t* E = c->dv.extent;
+  if (!std::isfinite(sp->lo)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: lo is not finite");
+  if (!std::isfinite(sp->hi)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: hi is not finite");
+  if (sp->lo > sp->hi) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: lo = %g > hi = %g", (double)sp->lo, (double)sp->hi);
+  SegPredParams pp{sp->lo, sp->hi, {sp->box_lo[0], sp->box_lo[1], sp->box_lo[2]}, {sp->box_hi[0], sp->box_hi[1], sp->box_hi[2]}};
+  for (int a = 0; a < 3; ++a) {
+    if (pp.box_hi[a] == VX_SEGMENT_BOX_END) pp.box_hi[a] = E[a] - 1u;
+    if (pp.box_lo[a] > pp.box_hi[a] || pp.box_hi[a] >= E[a])
+      VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: box axis %d [%u, %u] is empty or outside the index extent %u", a,
+              sp->box_lo[a], sp->box_hi[a], E[a]);
+  }
+  if (int rc = ensure_segment(c)) return rc;
+  if (int rc = ensure_segedit(c)) return rc;   // (its events time the call, as for vx_segment_write_mask)
+  c->seg_valid = false;
+  c->seg_pred_valid = false;
+  c->isl_valid = false;
+  const SegDev& s = c->seg;
+  VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
+  launch_seg_predicate(c, pp);
+  VX_HIP(c, hipGetLastError());
+  // the mask = the predicate words.  SegDev::seg keeps its address: the masked render kernels read it at launch time
+  VX_HIP(c, hipMemcpyAsync(s.seg, s.pred, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
+  c->sed_launches = 1;
+  const int rc = finish_segedit(c, false, out);
+  if (rc == VX_OK) c->seg_pred_valid = true;
+  return rc;
+}
+
+static int ensure_islands(VxContext* c) {
+  for (hipEvent_t& e : c->isl_ev)
+    if (!e) VX_HIP(c, hipEventCreate(&e));
+  if (c->isl_alloc) return VX_OK;
+  const size_t nb = c->seg.nb;
+  VX_HIP(c, hipMalloc(&c->isl_alloc, nb * (512u * 4u + 4u + 4u) + sizeof(IslHdr)));
+  char* p = static_cast<char*>(c->isl_alloc);
+  IslDev& d = c->isl;
+  d.lab = reinterpret_cast<uint32_t*>(p);
+  p += nb * 2048u;
+  d.nroots = reinterpret_cast<uint32_t*>(p);
+  p += nb * 4u;
+  d.off = reinterpret_cast<uint32_t*>(p);
+  p += nb * 4u;
+  d.hdr = reinterpret_cast<IslHdr*>(p);
+  return VX_OK;
+}
+
+// room for n rows and their labels (every earlier call has completed: each one synchronises)
+static int ensure_island_rows(VxContext* c, uint32_t n) {
+  IslDev& d = c->isl;
+  n = std::max(n, 1u);
+  if (n <= d.cap) return VX_OK;
+  if (c->isl_rows_alloc) (void)hipFree(c->isl_rows_alloc);
+  c->isl_rows_alloc = nullptr;
+  d.rows = nullptr;
+  d.newlab = nullptr;
+  d.cap = 0;
+  const size_t cap = std::max<size_t>(n, 1024u);
+  VX_HIP(c, hipMalloc(&c->isl_rows_alloc, cap * (sizeof(IslRow) + 4u)));
+  d.rows = static_cast<IslRow*>(c->isl_rows_alloc);
+  d.newlab = reinterpret_cast<uint32_t*>(static_cast<char*>(c->isl_rows_alloc) + cap * sizeof(IslRow));
+  d.cap = (uint32_t)cap;
+  return VX_OK;
+}
+
+int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_islands(c->members[0], ip, out));
+  VX_DEV(c);
+  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_islands: no volume uploaded");
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
+  if (!ip) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: params is NULL");
+  if (ip->op < VX_ISLANDS_LABEL || ip->op > VX_ISLANDS_KEEP_AT)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: op = %d is not a VxIslandsOp (0 .. 3)", ip->op);
+  if (ip->connectivity != 6 && ip->connectivity != 26)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: connectivity = %d is not 6 or 26", ip->connectivity);
+  if (ip->op == VX_ISLANDS_KEEP_LARGEST && ip->keep == 0)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: keep = 0 (KEEP_LARGEST keeps at least one island)");
+  if (ip->op == VX_ISLANDS_REMOVE_SMALL && ip->min_voxels == 0)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: min_voxels = 0 (REMOVE_SMALL needs a size of at least 1)");
+  const uint32_t* E = c->dv.extent;
+  if (ip->op == VX_ISLANDS_KEEP_AT)
+    for (int a = 0; a < 3; ++a)
+      if (ip->seed[a] >= E[a])
+        VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: seed[%d] = %u outside the index extent %u", a, ip->seed[a], E[a]);
+  if (!c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: no current segment (vx_segment, vx_segment_threshold or vx_segment_write_mask "
+                               "first; an upload drops it)");
+  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
+  if (nvox >= 0x80000000ull)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: %llu voxels are beyond the 31-bit voxel index of the labels",
+            (unsigned long long)nvox);
+  if (int rc = ensure_islands(c)) return rc;
+  if (int rc = ensure_island_rows(c, 1u)) return rc;
+  c->isl_valid = false;
+  const SegDev& s = c->seg;
+  const bool c26 = ip->connectivity == 26;
+  const bool modify = ip->op != VX_ISLANDS_LABEL;
+  const dim3 grid(std::min<uint32_t>((s.nb + 3u) / 4u, 16384u)), block(256);
+  uint32_t launches = 0;
+  VX_HIP(c, hipMemsetAsync(c->isl.hdr, 0, sizeof(IslHdr), c->stream));
+  VX_HIP(c, hipEventRecord(c->isl_ev[0], c->stream));
+  if (c26) hipLaunchKernelGGL(isl_local<26>, grid, block, 0, c->stream, s, c->isl);
+  else hipLaunchKernelGGL(isl_local<6>, grid, block, 0, c->stream, s, c->isl);
+  VX_HIP(c, hipEventRecord(c->isl_ev[1], c->stream));
+  if (c26) hipLaunchKernelGGL(isl_merge<26>, grid, block, 0, c->stream, s, c->isl);
+  else hipLaunchKernelGGL(isl_merge<6>, grid, block, 0, c->stream, s, c->isl);
+  VX_HIP(c, hipEventRecord(c->isl_ev[2], c->stream));
+  hipLaunchKernelGGL(isl_flatten, grid, block, 0, c->stream, s, c->isl);
+  hipLaunchKernelGGL(isl_scan, dim3(1), dim3(1024), 0, c->stream, s, c->isl);
+  VX_HIP(c, hipGetLastError());
+  launches += 4;
+  VX_HIP(c, hipEventRecord(c->isl_ev[3], c->stream));
+  // the one read-back that sizes the table: the number of islands
+  IslHdr hdr{};
+  VX_HIP(c, hipMemcpyAsync(&hdr, c->isl.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  const uint32_t R = hdr.roots;
+  if (int rc = ensure_island_rows(c, R)) return rc;
+  const IslDev& d = c->isl;
+  SegSeed seed{0u, 0u, 1ull};
+  if (ip->op == VX_ISLANDS_KEEP_AT) {
+    const uint32_t sx = ip->seed[0], sy = ip->seed[1], sz = ip->seed[2];
+    seed = SegSeed{((sz >> 3) * s.bc[1] + (sy >> 3)) * s.bc[0] + (sx >> 3), sz & 7u, 1ull << (((sy & 7u) << 3) | (sx & 7u))};
+  }
+  hipLaunchKernelGGL(isl_rootid, grid, block, 0, c->stream, s, d);
+  hipLaunchKernelGGL(isl_table, grid, block, 0, c->stream, s, d);
+  hipLaunchKernelGGL(isl_seed_row, dim3(1), dim3(64), 0, c->stream, s, d, seed);
+  VX_HIP(c, hipGetLastError());
+  launches += 3;
+  VX_HIP(c, hipEventRecord(c->isl_ev[4], c->stream));
+  VX_HIP(c, hipEventSynchronize(c->isl_ev[4]));
+  // the host's share: the rows come back once, are ranked by (count descending, anchor ascending), and every row's label
+  // (0: dropped by the op) goes back up.  O(islands), not O(voxels).
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<IslRow> rows(R);
+  VX_HIP(c, hipMemcpyAsync(&hdr, d.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+  if (R) VX_HIP(c, hipMemcpyAsync(rows.data(), d.rows, (size_t)R * sizeof(IslRow), hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<uint32_t> order(R);
+  for (uint32_t i = 0; i < R; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    return rows[a].count != rows[b].count ? rows[a].count > rows[b].count : rows[a].anchor < rows[b].anchor;
+  });
+  std::vector<uint32_t> newlab(std::max(R, 1u), 0u);
+  std::vector<VxIsland> table;
+  table.reserve(R);
+  for (uint32_t k = 0; k < R; ++k) {
+    const uint32_t i = order[k];
+    const IslRow& r = rows[i];
+    bool keep = true;
+    switch (ip->op) {
+      case VX_ISLANDS_KEEP_LARGEST: keep = (uint64_t)k < ip->keep; break;
+      case VX_ISLANDS_REMOVE_SMALL: keep = r.count >= ip->min_voxels; break;
+      case VX_ISLANDS_KEEP_AT: keep = i == hdr.seed_row; break;
+      default: break;
+    }
+    if (!keep) continue;
+    VxIsland v{};
+    v.count = r.count;
+    v.anchor[0] = r.anchor % E[0];
+    v.anchor[1] = (r.anchor / E[0]) % E[1];
+    v.anchor[2] = r.anchor / (E[0] * E[1]);
+    for (int a = 0; a < 3; ++a) {
+      v.bbox_lo[a] = r.lo[a];
+      v.bbox_hi[a] = r.hi[a];
+    }
+    table.push_back(v);
+    table.back().label = (uint32_t)table.size();
+    newlab[i] = (uint32_t)table.size();
+  }
+  VX_HIP(c, hipMemcpyAsync(d.newlab, newlab.data(), newlab.size() * 4u, hipMemcpyHostToDevice, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));   // (newlab is pageable host memory of this frame)
+  const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  VX_HIP(c, hipEventRecord(c->isl_ev[5], c->stream));
+  if (modify) {
+    hipLaunchKernelGGL(isl_apply, grid, block, 0, c->stream, s, d);
+    ++launches;
+  }
+  VX_HIP(c, hipEventRecord(c->isl_ev[6], c->stream));
+  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 0u);
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  launches += 3;
+  VX_HIP(c, hipEventRecord(c->isl_ev[7], c->stream));
+  SegStats st;
+  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  static const int slot[7] = {0, 1, 2, 3, -1, 5, 6};   // kernel_ms[k] = ev[slot] .. ev[slot + 1]; 4 is the host's
+  for (int k = 0; k < 7; ++k) {
+    float ms = 0.0f;
+    if (slot[k] >= 0) VX_HIP(c, hipEventElapsedTime(&ms, c->isl_ev[slot[k]], c->isl_ev[slot[k] + 1]));
+    c->isl_ms[k] = slot[k] >= 0 ? (double)ms : host_ms;
+  }
+  if (!modify) c->isl_ms[5] = 0.0;   // (two events back to back still measure a few microseconds)
+  c->isl_launches = launches;
+  VxIslandsResult r{};
+  r.islands = R;
+  r.kept = table.size();
+  r.largest = R ? rows[order[0]].count : 0u;
+  r.seg.count = st.count;
+  if (st.count) {
+    for (int a = 0; a < 3; ++a) {
+      r.seg.bbox_lo[a] = st.lo[a];
+      r.seg.bbox_hi[a] = st.hi[a];
+    }
+    r.seg.d_min = seg_key_float(st.dmin);
+    r.seg.d_max = seg_key_float(st.dmax);
+    r.seg.d_sum = st.sum;
+  }
+  r.seg.converged = 1u;
+  c->isl_table.swap(table);
+  c->isl_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_islands_read(VxContext* c, uint64_t first, uint64_t n, VxIsland* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_islands_read(c->members[0], first, n, out));
+  if (!c->isl_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: no current table (vx_segment_islands first; an upload and every call that "
+                               "changes the segment drop it)");
+  const uint64_t have = c->isl_table.size();
+  if (first > have || n > have - first)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: rows %llu .. %llu are beyond the %llu islands of the table",
+            (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)have);
+  if (n && !out) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: out is NULL");
+  if (n) memcpy(out, c->isl_table.data() + first, (size_t)n * sizeof(VxIsland));
+  return VX_OK;
+}
+
+int vx_islands_read_labels(VxContext* c, uint32_t* labels, uint64_t nvoxels) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_islands_read_labels(c->members[0], labels, nvoxels));
+  VX_DEV(c);
+  if (!c->isl_valid || !c->seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: no current table (vx_segment_islands first; an upload and every call "
+                               "that changes the segment drop it)");
+  if (!labels) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: labels is NULL");
+  const uint32_t* E = c->dv.extent;
+  const size_t want = (size_t)E[0] * E[1] * E[2];
+  if (nvoxels != want)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: nvoxels = %llu, the volume has %u x %u x %u = %zu voxels",
+            (unsigned long long)nvoxels, E[0], E[1], E[2], want);
+  if (want > c->isl_dense_cap) {   // (every earlier call has completed: each one synchronises)
+    if (c->isl_dense) (void)hipFree(c->isl_dense);
+    c->isl_dense = nullptr;
+    c->isl_dense_cap = 0;
+    VX_HIP(c, hipMalloc(&c->isl_dense, want * 4u));
+    c->isl_dense_cap = want;
+  }
+  const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 16384u);
+  hipLaunchKernelGGL(isl_labels_out, dim3(blocks), dim3(256), 0, c->stream, c->seg, c->isl, E[0], E[1], want, c->isl_dense);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipMemcpyAsync(labels, c->isl_dense, want * 4u, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_islands_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_islands_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->isl_launches;
+  if (kernel_ms)
+    for (int i = 0; i < 7; ++i) kernel_ms[i] = c->isl_ms[i];
   return VX_OK;
 }
 

@@ -114,6 +114,28 @@ export declare class Volxel3DDicomRenderer {
       mean: number; rounds: number; converged: boolean; brickVisits: number };
   /** the last segmentEdit or setSegmentMask: kernels launched, the times of the edit and of its statistics */
   segmentEditStats(): { launches: number; editMs: number; statsMs: number };
+  /** the whole band lo <= d <= hi as the current segment, without a seed (include/volxel_hip.h vx_segment_threshold) */
+  threshold(lo: number, opts?: { hi?: number; box?: [[number, number, number], [number, number, number]] | null }):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** the islands (connected components) of the current segment, largest first (include/volxel_hip.h vx_segment_islands) */
+  islands(opts?: { connectivity?: 6 | 26 }): { count: number; largest: number; sizes: Float64Array;
+    table: { label: number; count: number; anchor: [number, number, number]; bboxLo: [number, number, number];
+             bboxHi: [number, number, number] }[];
+    segment: { count: number; dSum: number; mean: number }; labels(): Uint32Array };
+  /** the dense label volume over (z, y, x) of the current island table: 0 outside the segment, k + 1 on island k */
+  islandLabels(): Uint32Array;
+  /** keep the n largest islands / drop the islands below minVoxels / keep the island under a voxel: the statistics of the new
+   *  mask as segment() returns them, with the islands before the op, those kept and the size of the largest */
+  keepLargestIslands(n?: number, opts?: { connectivity?: 6 | 26 }): { count: number; islands: number; kept: number; largest: number;
+    dSum: number; mean: number; bboxLo: [number, number, number]; bboxHi: [number, number, number] };
+  removeSmallIslands(minVoxels: number, opts?: { connectivity?: 6 | 26 }): { count: number; islands: number; kept: number;
+    largest: number; dSum: number; mean: number; bboxLo: [number, number, number]; bboxHi: [number, number, number] };
+  keepIslandAt(voxel: [number, number, number], opts?: { connectivity?: 6 | 26 }): { count: number; islands: number; kept: number;
+    largest: number; dSum: number; mean: number; bboxLo: [number, number, number]; bboxHi: [number, number, number] };
+  /** the last islands call: kernels launched and the times of its passes (hostRankMs: the host's ranking of the table) */
+  islandsStats(): { launches: number; localMs: number; mergeMs: number; flattenMs: number; tableMs: number; hostRankMs: number;
+    applyMs: number; statsMs: number };
   /** the surface of the isosurface d = iso, or of the current segment, as a closed indexed triangle mesh built on the GPU
    *  (include/volxel_hip.h vx_mesh_extract): 3 numbers per vertex, 3 cell components per vertex, 3 indices per triangle */
   extractMesh(opts: { iso?: number; segment?: boolean; box?: [[number, number, number], [number, number, number]] | null;

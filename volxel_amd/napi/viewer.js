@@ -677,6 +677,70 @@ class Volxel3DDicomRenderer {
   }
   /** the last segmentEdit or setSegmentMask: kernels launched and the times of the edit and of the statistics */
   segmentEditStats() { return native.segmentEditStats(this.ctx); }
+  /** vx_segment_threshold: the whole band lo <= d <= hi (inside box) as the current segment, without a seed; opts: { hi =
+   *  Infinity, box = null } -> what segment() returns (rounds = brickVisits = 0).  Binds the current uniforms first. */
+  threshold(lo, { hi = Infinity, box = null } = {}) {
+    const e = this.sliceExtent();
+    const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
+    const F32_MAX = 3.4028234663852886e38;
+    const l32 = Math.fround(lo), h32 = hi === Infinity ? F32_MAX : Math.fround(hi);
+    if (!Number.isFinite(l32) || !Number.isFinite(h32)) throw new Error('threshold: lo and hi must be finite (hi may be Infinity)');
+    if (l32 > h32) throw new Error(`threshold: lo = ${lo} > hi = ${hi}`);
+    const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
+    if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
+      throw new Error(`threshold: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+    const p = new ParamsBlock(SEGMENT_LAYOUT);
+    p.set('seed', [0, 0, 0]); p.set('lo', l32); p.set('hi', h32); p.set('connectivity', 6);
+    p.set('box_lo', blo); p.set('box_hi', bhi); p.set('max_rounds', 0);
+    this.bindUniforms();
+    return this._segmentResult(native.segmentThreshold(this.ctx, p.buffer));
+  }
+  _islandsCall(name, op, connectivity, keep = 0, minVoxels = 0, seed = [0, 0, 0]) {
+    if (connectivity !== 6 && connectivity !== 26) throw new Error(`${name}: connectivity must be 6 or 26, not ${connectivity}`);
+    this.bindUniforms();
+    const r = native.segmentIslands(this.ctx, op, connectivity, keep, minVoxels, seed[0], seed[1], seed[2]);
+    this._islandRows = r.kept;
+    r.seg.mean = r.seg.count ? r.seg.dSum / r.seg.count : NaN;
+    if (op !== 0 && this.segmentView !== 'off') this.restartRendering();   // the masked views show the new mask
+    return r;
+  }
+  /** vx_segment_islands, LABEL (DESIGN.md section 2 "Islands"): the 6- / 26-connected components of the current segment, by
+   *  voxel count descending, ties by the first voxel in C order -> { count, largest, sizes: Float64Array, table: [{ label, count,
+   *  anchor, bboxLo, bboxHi }], segment, labels(): Uint32Array over (z, y, x) }.  The segment is not changed. */
+  islands({ connectivity = 6 } = {}) {
+    const r = this._islandsCall('islands', 0, connectivity);
+    const table = native.islandsRead(this.ctx, 0, r.kept);
+    return { count: r.islands, largest: r.largest, sizes: Float64Array.from(table, t => t.count), table, segment: r.seg,
+             labels: () => this.islandLabels() };
+  }
+  /** the dense label volume of the current island table (vx_islands_read_labels) */
+  islandLabels() {
+    const e = this.sliceExtent();
+    const out = new Uint32Array(e[0] * e[1] * e[2]);
+    native.islandsReadLabels(this.ctx, out);
+    return out;
+  }
+  _islandSegment(r) { return Object.assign(r.seg, { islands: r.islands, kept: r.kept, largest: r.largest }); }
+  /** keeps the n largest islands of the current segment -> what segment() returns for the new mask, with islands (before),
+   *  kept (after) and largest */
+  keepLargestIslands(n = 1, { connectivity = 6 } = {}) {
+    if (!Number.isInteger(n) || n < 1) throw new Error(`keepLargestIslands: n must be an integer >= 1, not ${n}`);
+    return this._islandSegment(this._islandsCall('keepLargestIslands', 1, connectivity, n));
+  }
+  /** removes the islands of fewer than minVoxels voxels from the current segment */
+  removeSmallIslands(minVoxels, { connectivity = 6 } = {}) {
+    if (!Number.isInteger(minVoxels) || minVoxels < 1) throw new Error(`removeSmallIslands: minVoxels must be an integer >= 1, not ${minVoxels}`);
+    return this._islandSegment(this._islandsCall('removeSmallIslands', 2, connectivity, 0, minVoxels));
+  }
+  /** keeps the island of the current segment that holds voxel = [x, y, z] (the empty set when the voxel is not in it) */
+  keepIslandAt(voxel, { connectivity = 6 } = {}) {
+    const e = this.sliceExtent();
+    if (!Array.isArray(voxel) || voxel.length !== 3 || !voxel.every((x, a) => Number.isInteger(x) && x >= 0 && x < e[a]))
+      throw new Error(`keepIslandAt: voxel ${voxel} is outside the index extent ${e}`);
+    return this._islandSegment(this._islandsCall('keepIslandAt', 3, connectivity, 0, 0, voxel));
+  }
+  /** the last islands call: kernels launched and the times of its passes; hostRankMs is the host's ranking of the rows */
+  islandsStats() { return native.islandsStats(this.ctx); }
   /** vx_mesh_extract (DESIGN.md section 2 "Meshes"): the surface of the isosurface d = iso, or ({ segment: true }) of the current
    *  segment, as a closed indexed triangle mesh built on the GPU (naive surface nets).  opts: { iso | segment, box = null
    *  ([[x0, y0, z0], [x1, y1, z1]], inclusive; voxels outside count as outside: the mesh is capped there), space = 'world'

@@ -698,6 +698,118 @@ static napi_value n_segment_edit_stats(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* segmentThreshold(ctx, ArrayBuffer holding one VxSegmentParams) -> what segment returns, for the whole band (vx_segment_threshold) */
+static napi_value n_segment_threshold(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* d;
+  size_t n;
+  NAPI_OK(napi_get_arraybuffer_info(env, a[1], &d, &n));
+  if (n != sizeof(VxSegmentParams)) return throw_msg(env, "threshold: buffer is not sizeof(VxSegmentParams)");
+  VxSegmentParams sp;
+  memcpy(&sp, d, sizeof sp);
+  VxSegmentResult r;
+  if (vx_segment_threshold(c, &sp, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return segment_result(env, &r);
+}
+
+/* segmentIslands(ctx, op 0 .. 3, connectivity, keep, minVoxels, sx, sy, sz) -> { islands, kept, largest, seg: what segment
+ * returns, for the mask after the op } (vx_segment_islands; counts up to 2^53 as doubles) */
+static napi_value n_segment_islands(napi_env env, napi_callback_info info) {
+  napi_value a[8];
+  if (!get_args(env, info, 8, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  int32_t op, conn;
+  double keep, minv;
+  uint32_t sd[3];
+  if (napi_get_value_int32(env, a[1], &op) != napi_ok || napi_get_value_int32(env, a[2], &conn) != napi_ok ||
+      napi_get_value_double(env, a[3], &keep) != napi_ok || napi_get_value_double(env, a[4], &minv) != napi_ok ||
+      napi_get_value_uint32(env, a[5], &sd[0]) != napi_ok || napi_get_value_uint32(env, a[6], &sd[1]) != napi_ok ||
+      napi_get_value_uint32(env, a[7], &sd[2]) != napi_ok || !(keep >= 0.0) || !(minv >= 0.0))
+    return throw_msg(env, "segmentIslands: op, connectivity, keep, minVoxels and the seed must be numbers >= 0");
+  VxIslandsParams ip = {op, conn, (uint64_t)keep, (uint64_t)minv, {sd[0], sd[1], sd[2]}, 0u};
+  VxIslandsResult r;
+  if (vx_segment_islands(c, &ip, &r) != VX_OK) return throw_msg(env, vx_last_error(c));
+  napi_value o, seg = segment_result(env, &r.seg);
+  if (!seg) return NULL;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "islands", (double)r.islands) || !set_num(env, o, "kept", (double)r.kept) ||
+      !set_num(env, o, "largest", (double)r.largest) || napi_set_named_property(env, o, "seg", seg) != napi_ok)
+    return throw_msg(env, "segmentIslands: could not build the result");
+  return o;
+}
+
+/* islandsRead(ctx, first, n) -> [{ label, count, anchor, bboxLo, bboxHi }] (vx_islands_read) */
+static napi_value n_islands_read(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  double first, n;
+  if (napi_get_value_double(env, a[1], &first) != napi_ok || napi_get_value_double(env, a[2], &n) != napi_ok || !(first >= 0.0) ||
+      !(n >= 0.0) || n > 268435456.0)
+    return throw_msg(env, "islandsRead: first and n must be numbers >= 0 (n <= 2^28)");
+  const size_t cnt = (size_t)n;
+  VxIsland* rows = (VxIsland*)malloc((cnt ? cnt : 1) * sizeof(VxIsland));
+  if (!rows) return throw_msg(env, "islandsRead: out of memory");
+  if (vx_islands_read(c, (uint64_t)first, (uint64_t)cnt, rows) != VX_OK) {
+    free(rows);
+    return throw_msg(env, vx_last_error(c));
+  }
+  napi_value arr;
+  if (napi_create_array_with_length(env, cnt, &arr) != napi_ok) {
+    free(rows);
+    return throw_msg(env, "islandsRead: could not build the result");
+  }
+  for (size_t i = 0; i < cnt; ++i) {
+    napi_value o;
+    if (napi_create_object(env, &o) != napi_ok || !set_num(env, o, "label", rows[i].label) ||
+        !set_num(env, o, "count", (double)rows[i].count) || !set_u3(env, o, "anchor", rows[i].anchor) ||
+        !set_u3(env, o, "bboxLo", rows[i].bbox_lo) || !set_u3(env, o, "bboxHi", rows[i].bbox_hi) ||
+        napi_set_element(env, arr, (uint32_t)i, o) != napi_ok) {
+      free(rows);
+      return throw_msg(env, "islandsRead: could not build the result");
+    }
+  }
+  free(rows);
+  return arr;
+}
+
+/* islandsReadLabels(ctx, Uint32Array of X*Y*Z labels) (vx_islands_read_labels) */
+static napi_value n_islands_read_labels(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  void* out;
+  size_t n;
+  if (!typed_or_null(env, a[1], napi_uint32_array, &out, &n)) return NULL;
+  if (!out) return throw_msg(env, "islandsReadLabels: labels must be a Uint32Array");
+  if (vx_islands_read_labels(c, (uint32_t*)out, (uint64_t)n) != VX_OK) return throw_msg(env, vx_last_error(c));
+  return NULL;
+}
+
+/* islandsStats(ctx) -> { launches, localMs, mergeMs, flattenMs, tableMs, hostRankMs, applyMs, statsMs } (vx_islands_stats) */
+static napi_value n_islands_stats(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  VxContext* c = get_ctx(env, a[0]);
+  if (!c) return NULL;
+  uint32_t launches = 0;
+  double ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (vx_islands_stats(c, &launches, ms) != VX_OK) return throw_msg(env, vx_last_error(c));
+  static const char* names[7] = {"localMs", "mergeMs", "flattenMs", "tableMs", "hostRankMs", "applyMs", "statsMs"};
+  napi_value o;
+  NAPI_OK(napi_create_object(env, &o));
+  if (!set_num(env, o, "launches", launches)) return throw_msg(env, "islandsStats: could not build the result");
+  for (int i = 0; i < 7; ++i)
+    if (!set_num(env, o, names[i], ms[i])) return throw_msg(env, "islandsStats: could not build the result");
+  return o;
+}
+
 /* meshExtract(ctx, ArrayBuffer holding one VxMeshParams) -> { vertices, triangles, activeBlocks, blocks, bboxLo, bboxHi }
  * (vx_mesh_extract; the bbox components are cells, -1 included) */
 static napi_value n_mesh_extract(napi_env env, napi_callback_info info) {
@@ -1024,6 +1136,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"sliceMask", n_slice_mask}, {"segmentStats", n_segment_stats}, {"setSegmentView", n_set_segment_view},
       {"getSegmentView", n_get_segment_view}, {"segmentEdit", n_segment_edit}, {"setSegmentMask", n_set_segment_mask},
       {"segmentEditStats", n_segment_edit_stats},
+      {"segmentThreshold", n_segment_threshold}, {"segmentIslands", n_segment_islands}, {"islandsRead", n_islands_read},
+      {"islandsReadLabels", n_islands_read_labels}, {"islandsStats", n_islands_stats},
       {"meshExtract", n_mesh_extract}, {"sizeofMeshParams", n_sizeof_mesh_params}, {"meshRead", n_mesh_read},
       {"meshStats", n_mesh_stats},
       {"version", n_version}, {"buildBrickGrid", n_build_brick_grid},

@@ -147,6 +147,39 @@ class Segment:
     volume_world: float
 
 
+@dataclass(frozen=True)
+class IslandSegment(Segment):
+    """The `Segment` of the mask after keep_largest_islands / remove_small_islands / keep_island_at, with the op's own
+    figures (VxIslandsResult): `islands` of the mask before the op, `kept` after it, `largest` = the voxel count of the
+    largest island before the op (0 for an empty mask)."""
+    islands: int = 0
+    kept: int = 0
+    largest: int = 0
+
+
+class Islands:
+    """What Volxel3DRenderer.islands returns: the islands of the current segment in canonical order (count descending, ties by
+    the C-order index of the anchor ascending; island k has label k + 1).  count: how many; sizes: their voxel counts (uint64);
+    table: one dict per island (label, count, anchor, bbox_lo, bbox_hi, each (x, y, z)); largest; segment: the `Segment` of the
+    labelled mask; labels(): the dense (Z, Y, X) uint32 label volume, read from the device when asked (refused once the
+    segment has changed)."""
+
+    def __init__(self, renderer, res, rows, segment):
+        self._renderer = renderer
+        self.count = int(res.islands)
+        self.largest = int(res.largest)
+        self.segment = segment
+        self.sizes = np.array([r.count for r in rows], dtype=np.uint64)
+        self.table = [dict(label=int(r.label), count=int(r.count), anchor=tuple(r.anchor[:]), bbox_lo=tuple(r.bbox_lo[:]),
+                           bbox_hi=tuple(r.bbox_hi[:])) for r in rows]
+
+    def labels(self) -> np.ndarray:
+        return self._renderer.island_labels()
+
+    def __len__(self):
+        return self.count
+
+
 class Volxel3DRenderer:
     """Headless counterpart of the `<volxel-3d-viewer>` element's render core."""
 
@@ -753,10 +786,10 @@ class Volxel3DRenderer:
         self._check(self._lib.vx_segment(self._ctx, C.byref(q), C.byref(res)))
         return self._segment_result(res, p)
 
-    def _segment_result(self, res, p) -> Segment:
+    def _segment_result(self, res, p, restart: bool = True) -> Segment:
         """the `Segment` of a VxSegmentResult under the uniforms p just bound (segment, segment_edit, set_segment_mask); the
         masked views show the new mask, so accumulation restarts when one is on"""
-        if self.segment_view != "off":
+        if restart and self.segment_view != "off":
             self.restart_rendering()
         g3 = np.asarray(self.volume.grid.transform, dtype=np.float64)[:3, :3]
         d3 = np.asarray(p.density_transform[:], dtype=np.float32).astype(np.float64).reshape(4, 4).T[:3, :3]
@@ -820,6 +853,119 @@ class Volxel3DRenderer:
         n = C.c_uint32()
         ms = (C.c_double * 2)()
         self._check(self._lib.vx_segment_edit_stats(self._ctx, C.byref(n), ms))
+        return (n.value,) + tuple(ms)
+
+    def threshold(self, lo: float, hi: float = math.inf, box=None) -> Segment:
+        """The whole band as the current segment, without a seed (vx_segment_threshold): every voxel with lo <= d(i) <= hi
+        inside `box`; arguments as for segment().  It also becomes the predicate of band dilation.  Returns its `Segment`
+        (rounds = brick_visits = 0)."""
+        if self.volume is None:
+            raise VolxelError("threshold: no volume (setup_from_grid first)")
+        ext = [int(e) for e in self.volume.grid.index_extent]
+        lo32 = np.float32(lo)
+        hi32 = np.float32(np.finfo(np.float32).max) if hi == math.inf else np.float32(hi)
+        if not (np.isfinite(lo32) and np.isfinite(hi32)):
+            raise ValueError(f"lo and hi must be finite (hi may be inf), not {lo!r}, {hi!r}")
+        if lo32 > hi32:
+            raise ValueError(f"lo = {lo!r} > hi = {hi!r}")
+        if box is None:
+            blo, bhi = (0, 0, 0), tuple(e - 1 for e in ext)
+        else:
+            try:
+                blo, bhi = (tuple(v) for v in box)
+            except (TypeError, ValueError):
+                raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)), not {box!r}") from None
+            if len(blo) != 3 or len(bhi) != 3 or any(isinstance(a, bool) or int(a) != a for a in blo + bhi):
+                raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)) of integers, not {box!r}")
+            blo, bhi = tuple(int(a) for a in blo), tuple(int(a) for a in bhi)
+            if not all(0 <= a <= b < e for a, b, e in zip(blo, bhi, ext)):
+                raise ValueError(f"box {box!r} is empty or outside the index extent {tuple(ext)}")
+        q = _abi.VxSegmentParams()
+        q.lo, q.hi = float(lo32), float(hi32)
+        q.connectivity = 6
+        q.box_lo[0], q.box_lo[1], q.box_lo[2] = blo
+        q.box_hi[0], q.box_hi[1], q.box_hi[2] = bhi
+        p = self.bind_uniforms()
+        res = _abi.VxSegmentResult()
+        self._check(self._lib.vx_segment_threshold(self._ctx, C.byref(q), C.byref(res)))
+        return self._segment_result(res, p)
+
+    def _islands_call(self, name, op, connectivity, keep=0, min_voxels=0, seed=(0, 0, 0)):
+        if self.volume is None:
+            raise VolxelError(f"{name}: no volume (setup_from_grid first)")
+        if connectivity not in (6, 26) or isinstance(connectivity, bool):
+            raise ValueError(f"connectivity must be 6 or 26, not {connectivity!r}")
+        q = _abi.VxIslandsParams()
+        q.op, q.connectivity, q.keep, q.min_voxels = _abi.ISLANDS_OPS[op], int(connectivity), int(keep), int(min_voxels)
+        q.seed[0], q.seed[1], q.seed[2] = (int(a) for a in seed)
+        p = self.bind_uniforms()
+        res = _abi.VxIslandsResult()
+        self._check(self._lib.vx_segment_islands(self._ctx, C.byref(q), C.byref(res)))
+        self._island_rows = int(res.kept)
+        # (labelling leaves the mask as it was: a masked view does not restart)
+        return res, self._segment_result(res.seg, p, restart=op != "label")
+
+    def _island_segment(self, res, seg) -> IslandSegment:
+        return IslandSegment(**{f: getattr(seg, f) for f in Segment.__dataclass_fields__}, islands=int(res.islands),
+                             kept=int(res.kept), largest=int(res.largest))
+
+    def islands(self, connectivity: int = 6) -> Islands:
+        """Labels the islands of the current segment on the GPU (vx_segment_islands, DESIGN.md section 2 "Islands"): its 6- or
+        26-connected components, ordered by voxel count descending, ties by the first voxel in C order.  The segment is not
+        changed.  Returns an `Islands` (count, sizes, table, labels())."""
+        res, seg = self._islands_call("islands", "label", connectivity)
+        return Islands(self, res, self.island_table(), seg)
+
+    def island_table(self, first: int = 0, n: int | None = None):
+        """rows first .. first + n - 1 (default: all the rest) of the current island table as VxIsland structs (vx_islands_read)"""
+        if n is None:
+            n = max(getattr(self, "_island_rows", 0) - int(first), 0)
+        rows = (_abi.VxIsland * max(int(n), 1))()
+        self._check(self._lib.vx_islands_read(self._ctx, int(first), int(n), rows))
+        return list(rows[:int(n)])
+
+    def island_labels(self) -> np.ndarray:
+        """the dense (Z, Y, X) uint32 label volume of the current island table: 0 outside the segment, k + 1 for island k
+        (vx_islands_read_labels)"""
+        if self.volume is None:
+            raise VolxelError("island_labels: no volume")
+        X, Y, Z = (int(e) for e in self.volume.grid.index_extent)
+        out = np.empty((Z, Y, X), dtype=np.uint32)
+        self._check(self._lib.vx_islands_read_labels(self._ctx, out.ctypes.data, out.size))
+        return out
+
+    def keep_largest_islands(self, n: int = 1, connectivity: int = 6) -> IslandSegment:
+        """Keeps the n largest islands of the current segment (canonical order; n >= the number of islands keeps all).  Returns
+        the `Segment` of the new mask with .islands (before), .kept (after) and .largest."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) < 2 ** 64:
+            raise ValueError(f"n must be an integer >= 1, not {n!r}")
+        return self._island_segment(*self._islands_call("keep_largest_islands", "keep_largest", connectivity, keep=n))
+
+    def remove_small_islands(self, min_voxels: int, connectivity: int = 6) -> IslandSegment:
+        """Removes the islands of fewer than min_voxels voxels from the current segment (none left is legal)."""
+        if isinstance(min_voxels, bool) or not isinstance(min_voxels, (int, np.integer)) or not 1 <= int(min_voxels) < 2 ** 64:
+            raise ValueError(f"min_voxels must be an integer >= 1, not {min_voxels!r}")
+        return self._island_segment(*self._islands_call("remove_small_islands", "remove_small", connectivity,
+                                                        min_voxels=min_voxels))
+
+    def keep_island_at(self, voxel, connectivity: int = 6) -> IslandSegment:
+        """Keeps the island of the current segment that holds `voxel` = (x, y, z); the empty set when the voxel is not in it."""
+        if self.volume is None:
+            raise VolxelError("keep_island_at: no volume (setup_from_grid first)")
+        ext = [int(e) for e in self.volume.grid.index_extent]
+        sd = tuple(voxel)
+        if len(sd) != 3 or any(isinstance(a, bool) or int(a) != a for a in sd):
+            raise ValueError(f"voxel must be three integer voxel indices (x, y, z), not {voxel!r}")
+        if not all(0 <= int(a) < e for a, e in zip(sd, ext)):
+            raise ValueError(f"voxel {voxel!r} is outside the index extent {tuple(ext)}")
+        return self._island_segment(*self._islands_call("keep_island_at", "keep_at", connectivity, seed=sd))
+
+    def islands_stats(self):
+        """(launches, local_ms, merge_ms, flatten_ms, table_ms, host_rank_ms, apply_ms, stats_ms) of the last islands call
+        (vx_islands_stats); host_rank_ms is the host's wall clock for reading back, ranking and re-uploading the rows"""
+        n = C.c_uint32()
+        ms = (C.c_double * 7)()
+        self._check(self._lib.vx_islands_stats(self._ctx, C.byref(n), ms))
         return (n.value,) + tuple(ms)
 
     def extract_mesh(self, iso=None, *, segment: bool = False, box=None, space: str = "world", max_vertices: int = 0,
