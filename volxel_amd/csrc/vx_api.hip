@@ -24,6 +24,7 @@
 #include "vx_segedit.hpp"
 #include "vx_islands.hpp"
 #include "vx_mesh.hpp"
+#include "vx_host.hpp"
 
 using namespace vx;
 
@@ -81,51 +82,77 @@ struct DerivedTable {
 
 }  // namespace
 
-struct VxContext {
-  int device = 0;
+struct VxContext : VxCore {   // (device, the stream the launches go to, the last error: vx_host.hpp)
   hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  std::string err;
   hipDeviceProp_t prop;
 
-  // volume
-  bool has_volume = false;
-  DevVolume dv{};
-  std::vector<void*> vol_allocs;
-  void* cq_alloc = nullptr;
-  void* bf_alloc = nullptr;
-  void* bu_alloc = nullptr;    // bricku8 codes (+ one zero unit)
-  void* bur_alloc = nullptr;   // bricku8 per-brick {min, max - min} (+ the {0, 0} entry of the zero unit)
+  // Everything that describes the resident volume: vx_upload_volume drops it as a whole (free_volume), so a buffer or a flag
+  // that must not outlive the volume belongs here and needs no line anywhere else.
+  struct Volume {
+    bool has_volume = false;
+    DevVolume dv{};
+    DevBuf<void> cq_alloc, bf_alloc;
+    DevBuf<void> bu_alloc;     // bricku8 codes (+ one zero unit)
+    DevBuf<void> bur_alloc;    // bricku8 per-brick {min, max - min} (+ the {0, 0} entry of the zero unit)
+    // the derived tables (their device arrays below, outside: rebuilt before the next launch that reads them)
+    DerivedTable<skip_key> skip_table;
+    DerivedTable<proj_key> proj_table;
+    DerivedTable<lmaj_key> lmaj_table;
+    DerivedTable<shadow_key> shadow_table;
+    DerivedTable<iso_key> iso_table;
+    DevBuf<float> lmaj_dev;    // default mode: local-majorant table (DevVolume::lmaj)
+    // shadowed DVR: the light grid (vx_shadow.hpp)
+    DevBuf<float> shadow_dev;
+    ShadowGrid shadow{};       // what the last build made (t == nullptr: none since the last upload)
+    // segmentation (vx_segment): one allocation for the masks, flags, stamps, worklists, partial sums and statistics of the
+    // brick grid (ensure_segment); the packed mask of vx_segment_read_mask / vx_segment_write_mask grows on demand
+    DevBuf<void> seg_alloc;
+    SegDev seg{};
+    bool seg_valid = false;        // a segment of the resident volume is current
+    bool seg_pred_valid = false;   // SegDev::pred holds the predicate of a vx_segment / vx_segment_threshold on this volume
+    int seg_view = VX_SEGVIEW_OFF;   // vx_set_segment_view; OFF again after an upload
+    DevBuf<uint8_t> seg_bytes;
+    // segment edits: two scratch masks and the fill's flags, allocated by the first vx_segment_edit (ensure_segedit)
+    DevBuf<void> sed_alloc;
+    uint64_t* sed_mask[2] = {nullptr, nullptr};
+    uint32_t* sed_any = nullptr;
+    // islands (vx_segment_islands): the labels (one u32 per voxel, brick-major), the root counts and their scan in one
+    // allocation made by the first call; the rows and their labels grow to the largest table; the ranked table lives on the
+    // host; the dense label volume is allocated by the first vx_islands_read_labels
+    DevBuf<void> isl_alloc, isl_rows_alloc;
+    IslDev isl{};
+    bool isl_valid = false;    // the table and the labels describe the current segment
+    std::vector<VxIsland> isl_table;
+    DevBuf<uint32_t> isl_dense;
+    // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans
+    // (ensure_mesh); the vertex / cell buffers (3 values per vertex, grown together) and the triangles grow to the largest mesh
+    DevBuf<void> mesh_alloc;
+    MeshDev mesh{};
+    bool mesh_valid = false;   // a mesh of the resident volume is current
+    DevBuf<float> mesh_verts;
+    DevBuf<int32_t> mesh_cells;
+    DevBuf<uint32_t> mesh_tris;
+    uint64_t mesh_nv = 0, mesh_nt = 0;
+  } vol;
+  std::vector<void*> vol_allocs;     // the uploaded arrays DevVolume points to (free_volume)
   int layout = VX_LAYOUT_AUTO;       // what the host asked for (vx_set_layout); eff_layout() is what a launch samples
   bool auto_no_cq = false;           // AUTO: no cellquad layout (index range or memory budget): `default` / `no_dda` take primary_layout
   bool auto_no_bf = false;           // AUTO: too large for brickf32 as well (everything uses REFERENCE)
 
+  // ---- what survives an upload ----
   // transfer function
-  float4* tf = nullptr;
+  DevBuf<float4> tf;
   uint32_t tf_len = 0;
   std::vector<float> tf_host;
 
-  // exact empty-space skipping (DVR): macro-cell bitmask
   std::vector<uint32_t> range_host;   // packed (min16<<16)|max16 per brick
-  uint32_t* skip_dev = nullptr;
-  DerivedTable<skip_key> skip_table;
-  // range skipping of the intensity projections: one density bound per macro cell (vx_projection.hpp)
-  float* proj_dev = nullptr;
-  DerivedTable<proj_key> proj_table;
+  DevBuf<uint32_t> skip_dev;          // exact empty-space skipping (DVR): macro-cell bitmask
+  DevBuf<float> proj_dev;             // range skipping of the intensity projections: one density bound per macro cell
 
-  // default mode: local-majorant table (DevVolume::lmaj)
-  float* lmaj_dev = nullptr;
-  DerivedTable<lmaj_key> lmaj_table;
+  DevBuf<unsigned long long> fold_dev;   // the totals of fold_records
 
-  unsigned long long* fold_dev = nullptr;   // eight totals of fold_records
-
-  // shadowed DVR: the light grid (vx_shadow.hpp)
-  float* shadow_dev = nullptr;
-  size_t shadow_cap = 0;                     // floats allocated
-  ShadowGrid shadow{};                       // what the last build made (t == nullptr: none since the last upload)
-  DerivedTable<shadow_key> shadow_table;
-  unsigned long long* shadow_count_dev = nullptr;   // light-march samples of the last build
-  hipEvent_t shadow_ev[2] = {nullptr, nullptr};
+  DevBuf<unsigned long long> shadow_count_dev;   // light-march samples of the last light-grid build
+  StageTimer<1> shadow_timer;
   uint64_t shadow_builds = 0;
 
   // params
@@ -135,24 +162,22 @@ struct VxContext {
   // framebuffers
   uint32_t W = 0, H = 0;
   TileMap tm{};
-  float4* slab = nullptr;
+  DevBuf<float4> slab;
   size_t slab_quads = 0;
-  float4* image = nullptr;
-  float4* env_tex = nullptr;   // environment map, GL row order
-  float* env_imp = nullptr;    // importance pyramid
-  float4* env_impq = nullptr;  // the pyramid as sibling quads (sample_environment)
+  DevBuf<float4> image;
+  DevBuf<float4> env_tex;      // environment map, GL row order
+  DevBuf<float> env_imp;       // importance pyramid
+  DevBuf<float4> env_impq;     // the pyramid as sibling quads (sample_environment)
   float env_avg_w = 0.0f;
   uint32_t env_w = 0, env_h = 0;
-  uchar4* display = nullptr;
-  uint32_t display_cap = 0;  // pixels
-  uint32_t* tile_perm = nullptr;  // vx_set_tile_order: position -> tile, tile -> position (2 * n_tiles)
+  DevBuf<uchar4> display;
+  DevBuf<uint32_t> tile_perm;  // vx_set_tile_order: position -> tile, tile -> position (2 * n_tiles)
   uint32_t tile_perm_n = 0;
-  size_t slab_cap = 0, image_cap = 0;
 
   // counters / timing
-  DevCounters* dc = nullptr;   // one record per wave of the largest launch grid
+  DevBuf<DevCounters> dc;      // one record per wave of the largest launch grid
   size_t dc_waves = 0;
-  uint32_t* order = nullptr;   // launch permutation of the DVR kernel (build_order), dc_waves/4 entries
+  DevBuf<uint32_t> order;      // launch permutation of the DVR kernel (build_order), dc_waves/4 entries
   int tex_checked_res[2] = {-1, -1};  // DevVolume::ray_flags: the resolution (pixel + 0.5) / res was last tried against its reciprocal form
   bool tex_by_reciprocal[2] = {false, false};
   Switches sw;
@@ -174,161 +199,56 @@ struct VxContext {
   }
   // per-frame result slabs and counter records of multi-frame launches (vx_render_frames), pipe_slots of each in ONE
   // allocation (slot i at i * pipe_quads / i * pipe_waves)
-  float4* pipe_result_pool = nullptr;
-  DevCounters* pipe_dc_pool = nullptr;
+  DevBuf<float4> pipe_result_pool;
+  DevBuf<DevCounters> pipe_dc_pool;
   size_t pipe_quads = 0, pipe_waves = 0;
   uint32_t pipe_slots = 0;
   // the slab table the detile kernel reads (one entry per shard, on this device); slab_table_host is what it holds
-  const float4** slab_table = nullptr;
-  size_t slab_table_cap = 0;
+  DevBuf<const float4*> slab_table;
   std::vector<const float4*> slab_table_host;
   // device group (vx_create_group): member i renders shard i of members.size(); empty for a plain context
   std::vector<VxContext*> members;
   hipEvent_t done = nullptr;   // a member's: recorded after its last render, waited on by the display stream
   // slices (vx_slice): the output buffers, grown to the largest slice, and the facts of the last slice
-  float* slice_values = nullptr;
-  uchar4* slice_rgba = nullptr;
-  size_t slice_cap = 0;        // pixels of each buffer
-  hipEvent_t slice_ev[2] = {nullptr, nullptr};
+  DevBuf<float> slice_values;
+  DevBuf<uchar4> slice_rgba;
+  StageTimer<1> slice_timer;
   uint64_t slice_samples = 0;
-  double slice_ms = 0.0;
   // isosurfaces (vx_isosurface): the output buffers, grown to the largest window; the upper density bounds of range skipping
   // (its own copy of the projections' table, so that MIP's bookkeeping is never disturbed); the counts of the last call
-  float4* iso_rgba = nullptr;
-  float4* iso_hit = nullptr;
-  size_t iso_cap = 0;          // pixels of each buffer
-  float* iso_bound_dev = nullptr;
+  DevBuf<float4> iso_rgba, iso_hit;
+  DevBuf<float> iso_bound_dev;
   IsoBound iso_bound{};
-  DerivedTable<iso_key> iso_table;
-  unsigned long long* iso_count_dev = nullptr;   // ISO_NCOUNTS
-  hipEvent_t iso_ev[2] = {nullptr, nullptr};
+  DevBuf<unsigned long long> iso_count_dev;   // ISO_NCOUNTS
+  StageTimer<1> iso_timer;
   uint64_t iso_counts[ISO_NCOUNTS] = {};
-  double iso_ms = 0.0;
-  // segmentation (vx_segment): one allocation for the masks, flags, stamps, worklists, partial sums and statistics of the
-  // volume's brick grid (freed with the volume); the packed read-back and the overlay buffers grow on demand; the last result
-  void* seg_alloc = nullptr;
-  SegDev seg{};
-  bool seg_valid = false;     // a segment of the resident volume is current
-  int seg_view = VX_SEGVIEW_OFF;   // vx_set_segment_view; OFF again after an upload (free_volume)
-  uint8_t* seg_bytes = nullptr;
-  size_t seg_bytes_cap = 0;
-  uint8_t* seg_ov = nullptr;
-  size_t seg_ov_cap = 0;
-  hipEvent_t seg_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // the segment chain: the overlay of vx_slice_segment_mask, grown to the largest slice; the last vx_segment's result; the
+  // timers and launch counts the *_stats entry points report.  sed_timer / sed_launches belong to every call that rewrites
+  // the mask outright (vx_segment_edit, vx_segment_write_mask, vx_segment_threshold: vx_segment_edit_stats), not to the
+  // edit scratch.
+  DevBuf<uint8_t> seg_ov;
   VxSegmentResult seg_res{};
-  double seg_ms[3] = {0.0, 0.0, 0.0};
-  // segment edits (vx_segment_edit, vx_segment_write_mask): two scratch masks and the fill's flags, allocated by the first edit
-  // and freed with the volume; seg_pred_valid: SegDev::pred holds the predicate of a vx_segment on the resident volume
-  void* sed_alloc = nullptr;
-  uint64_t* sed_mask[2] = {nullptr, nullptr};
-  uint32_t* sed_any = nullptr;
-  bool seg_pred_valid = false;
-  hipEvent_t sed_ev[3] = {nullptr, nullptr, nullptr};
+  StageTimer<3> seg_timer;
+  StageTimer<2> sed_timer;
   uint32_t sed_launches = 0;
-  double sed_ms[2] = {0.0, 0.0};
-  // islands (vx_segment_islands): the labels (one u32 per voxel, brick-major), the root counts and their scan in one allocation
-  // made by the first call and freed with the volume; the rows and their labels grow to the largest table; the ranked table
-  // lives on the host; the dense label volume is allocated by the first vx_islands_read_labels
-  void* isl_alloc = nullptr;
-  void* isl_rows_alloc = nullptr;
-  IslDev isl{};
-  bool isl_valid = false;     // the table and the labels describe the current segment
-  std::vector<VxIsland> isl_table;
-  uint32_t* isl_dense = nullptr;
-  size_t isl_dense_cap = 0;
-  hipEvent_t isl_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  StageTimer<7> isl_timer;
   uint32_t isl_launches = 0;
-  double isl_ms[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans (freed with the
-  // volume); the vertex / cell and the triangle buffers grow to the largest mesh (freed with the volume too)
-  void* mesh_alloc = nullptr;
-  MeshDev mesh{};
-  bool mesh_valid = false;    // a mesh of the resident volume is current
-  float* mesh_verts = nullptr;
-  int32_t* mesh_cells = nullptr;
-  size_t mesh_vcap = 0;       // vertices
-  uint32_t* mesh_tris = nullptr;
-  size_t mesh_tcap = 0;       // triangles
-  uint64_t mesh_nv = 0, mesh_nt = 0;
-  hipEvent_t mesh_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  StageTimer<3> mesh_timer;
   uint32_t mesh_launches = 0;
-  double mesh_ms[3] = {0.0, 0.0, 0.0};
 };
 
 static bool is_group(const VxContext* c) { return !c->members.empty(); }
-
-#define VX_FAIL(ctx, code, ...)                       \
-  do {                                                \
-    char buf_[512];                                   \
-    snprintf(buf_, sizeof buf_, __VA_ARGS__);         \
-    (ctx)->err = buf_;                                \
-    return (code);                                    \
-  } while (0)
-
-#define VX_HIP(ctx, expr)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) VX_FAIL(ctx, VX_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 // every entry point that touches the device first makes the context's device current for the
 // calling thread (a host with several contexts / devices must not depend on its own hipSetDevice)
 #define VX_DEV(ctx) VX_HIP(ctx, hipSetDevice((ctx)->device))
 
 
+// drop the resident volume and everything derived from it (the caller has made the context's device current)
 static void free_volume(VxContext* c) {
   for (void* p : c->vol_allocs) (void)hipFree(p);
   c->vol_allocs.clear();
-  if (c->cq_alloc) (void)hipFree(c->cq_alloc);
-  if (c->bf_alloc) (void)hipFree(c->bf_alloc);
-  if (c->bu_alloc) (void)hipFree(c->bu_alloc);
-  if (c->bur_alloc) (void)hipFree(c->bur_alloc);
-  c->cq_alloc = nullptr;
-  c->bf_alloc = nullptr;
-  c->bu_alloc = c->bur_alloc = nullptr;
-  c->dv = DevVolume{};
-  c->has_volume = false;
-  c->skip_table.stale = c->proj_table.stale = c->lmaj_table.stale = c->shadow_table.stale = c->iso_table.stale = true;
-  if (c->lmaj_dev) (void)hipFree(c->lmaj_dev);
-  c->lmaj_dev = nullptr;
-  if (c->shadow_dev) (void)hipFree(c->shadow_dev);
-  c->shadow_dev = nullptr;
-  c->shadow_cap = 0;
-  c->shadow = ShadowGrid{};
-  if (c->seg_alloc) (void)hipFree(c->seg_alloc);
-  c->seg_alloc = nullptr;
-  c->seg = SegDev{};
-  c->seg_valid = false;
-  c->seg_pred_valid = false;
-  c->seg_view = VX_SEGVIEW_OFF;
-  if (c->sed_alloc) (void)hipFree(c->sed_alloc);
-  c->sed_alloc = nullptr;
-  c->sed_mask[0] = c->sed_mask[1] = nullptr;
-  c->sed_any = nullptr;
-  if (c->seg_bytes) (void)hipFree(c->seg_bytes);
-  c->seg_bytes = nullptr;
-  c->seg_bytes_cap = 0;
-  if (c->isl_alloc) (void)hipFree(c->isl_alloc);
-  if (c->isl_rows_alloc) (void)hipFree(c->isl_rows_alloc);
-  if (c->isl_dense) (void)hipFree(c->isl_dense);
-  c->isl_alloc = c->isl_rows_alloc = nullptr;
-  c->isl_dense = nullptr;
-  c->isl_dense_cap = 0;
-  c->isl = IslDev{};
-  c->isl_valid = false;
-  c->isl_table.clear();
-  if (c->mesh_alloc) (void)hipFree(c->mesh_alloc);
-  c->mesh_alloc = nullptr;
-  c->mesh = MeshDev{};
-  c->mesh_valid = false;
-  if (c->mesh_verts) (void)hipFree(c->mesh_verts);
-  if (c->mesh_cells) (void)hipFree(c->mesh_cells);
-  if (c->mesh_tris) (void)hipFree(c->mesh_tris);
-  c->mesh_verts = nullptr;
-  c->mesh_cells = nullptr;
-  c->mesh_tris = nullptr;
-  c->mesh_vcap = c->mesh_tcap = 0;
-  c->mesh_nv = c->mesh_nt = 0;
+  c->vol = VxContext::Volume{};
 }
 
 static void drain_events(VxContext* c) {
@@ -360,8 +280,7 @@ static void update_tilemap(VxContext* c) {
   t.shard_rank = c->has_params ? (uint32_t)c->params.shard_rank : 0u;
   t.tiles_per_shard = (t.n_tiles + t.shard_count - 1) / t.shard_count;
   if (c->tile_perm && c->tile_perm_n != t.n_tiles) {  // the order belongs to another tile grid
-    (void)hipFree(c->tile_perm);
-    c->tile_perm = nullptr;
+    c->tile_perm.reset();
     c->tile_perm_n = 0;
   }
   t.perm = c->tile_perm;
@@ -380,27 +299,9 @@ static int alloc_framebuffers(VxContext* c) {
   c->slab_quads = (size_t)c->tm.tiles_per_shard * 4096u;
   if (c->slab_quads == 0) return VX_OK;
   size_t px = (size_t)c->W * c->H;
-  if (c->slab_quads > c->slab_cap) {
-    if (c->slab) (void)hipFree(c->slab);
-    c->slab = nullptr;
-    c->slab_cap = 0;
-    VX_HIP(c, hipMalloc(&c->slab, c->slab_quads * sizeof(float4)));
-    c->slab_cap = c->slab_quads;
-  }
-  if (px > c->image_cap) {
-    if (c->image) (void)hipFree(c->image);
-    c->image = nullptr;
-    c->image_cap = 0;
-    VX_HIP(c, hipMalloc(&c->image, px * sizeof(float4)));
-    c->image_cap = px;
-  }
-  if (px > c->display_cap) {
-    if (c->display) (void)hipFree(c->display);
-    c->display = nullptr;
-    c->display_cap = 0;
-    VX_HIP(c, hipMalloc(&c->display, px * sizeof(uchar4)));
-    c->display_cap = (uint32_t)px;
-  }
+  if (int rc = c->slab.ensure(c, c->slab_quads)) return rc;
+  if (int rc = c->image.ensure(c, px)) return rc;
+  if (int rc = c->display.ensure(c, px)) return rc;
   VX_HIP(c, hipMemsetAsync(c->slab, 0, c->slab_quads * sizeof(float4), c->stream));
   return VX_OK;
 }
@@ -571,62 +472,58 @@ static bool proj_mode(int m) { return m == VX_MODE_MIP || m == VX_MODE_MINIP; }
 // the device table: the bound the mode tests (hi for MIP, lo for MinIP), one float per macro cell
 static int rebuild_projection_bounds(VxContext* c) {
   const VxParams& p = c->params;
-  c->proj_table.stale = true;   // until this build is complete
+  c->vol.proj_table.stale = true;   // until this build is complete
   std::vector<float> lohi;
   int level = 1;
   uint32_t md[3];
-  compute_projection_bounds(p, c->range_host.data(), c->dv.bc, c->dv.extent, lohi, level, md);
+  compute_projection_bounds(p, c->range_host.data(), c->vol.dv.bc, c->vol.dv.extent, lohi, level, md);
   const size_t n = lohi.size() / 2;
   std::vector<float> one(n);
   const int which = p.render_mode == VX_MODE_MINIP ? 0 : 1;
   for (size_t i = 0; i < n; ++i) one[i] = lohi[2 * i + which];
-  if (c->proj_dev) (void)hipFree(c->proj_dev);
-  c->proj_dev = nullptr;
-  VX_HIP(c, hipMalloc(&c->proj_dev, n * sizeof(float)));
+  if (int rc = c->proj_dev.alloc(c, n)) return rc;
   VX_HIP(c, hipMemcpyAsync(c->proj_dev, one.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   // the macro-cell grid the kernel indexes: the empty-space grid's level and dims (a function of the extent alone, so the
   // same values rebuild_skip_mask sets for this volume)
-  c->dv.skip_level = (uint32_t)level;
-  for (int a = 0; a < 3; ++a) c->dv.skip_dims[a] = md[a];
-  c->proj_table.built(p);
+  c->vol.dv.skip_level = (uint32_t)level;
+  for (int a = 0; a < 3; ++a) c->vol.dv.skip_dims[a] = md[a];
+  c->vol.proj_table.built(p);
   return VX_OK;
 }
 
 // the local majorants of the default mode, tabulated on the device with the operations of Frame::local_majorant
 static int rebuild_local_majorants(VxContext* c) {
   const VxParams& p = c->params;
-  c->lmaj_table.stale = true;   // until this build is complete
-  const size_t n = 4 * (size_t)c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2] + 1;
-  if (!c->lmaj_dev) VX_HIP(c, hipMalloc(&c->lmaj_dev, n * sizeof(float)));
-  DevVolume dv = c->dv;
+  c->vol.lmaj_table.stale = true;   // until this build is complete
+  const size_t n = 4 * (size_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] + 1;
+  if (int rc = c->vol.lmaj_dev.ensure(c, n)) return rc;
+  DevVolume dv = c->vol.dv;
   dv.lmaj = nullptr;
   hipLaunchKernelGGL(build_local_majorants, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, p, dv, c->tf,
-                     c->tf_len, c->lmaj_dev);
+                     c->tf_len, c->vol.lmaj_dev);
   VX_HIP(c, hipGetLastError());
-  c->dv.lmaj = c->lmaj_dev;
-  c->dv.lmaj_cells = (uint32_t)(n - 1);
-  c->lmaj_table.built(p);
+  c->vol.dv.lmaj = c->vol.lmaj_dev;
+  c->vol.dv.lmaj_cells = (uint32_t)(n - 1);
+  c->vol.lmaj_table.built(p);
   return VX_OK;
 }
 
 static int rebuild_skip_mask(VxContext* c) {
   const VxParams& p = c->params;
-  c->skip_table.stale = true;   // until this build is complete
+  c->vol.skip_table.stale = true;   // until this build is complete
   std::vector<uint32_t> bits;
   int level = 1;
   uint32_t md[3];
-  compute_skip_mask(p, c->range_host.data(), c->dv.bc, c->dv.extent, c->tf_host.data(), c->tf_len, bits, level, md);
-  if (c->skip_dev) (void)hipFree(c->skip_dev);
-  c->skip_dev = nullptr;
-  VX_HIP(c, hipMalloc(&c->skip_dev, bits.size() * 4));
+  compute_skip_mask(p, c->range_host.data(), c->vol.dv.bc, c->vol.dv.extent, c->tf_host.data(), c->tf_len, bits, level, md);
+  if (int rc = c->skip_dev.alloc(c, bits.size())) return rc;
   VX_HIP(c, hipMemcpyAsync(c->skip_dev, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  c->dv.skip_bits = c->skip_dev;
-  c->dv.skip_level = (uint32_t)level;
-  c->dv.skip_words = (uint32_t)bits.size();
-  for (int a = 0; a < 3; ++a) c->dv.skip_dims[a] = md[a];
-  c->skip_table.built(p);
+  c->vol.dv.skip_bits = c->skip_dev;
+  c->vol.dv.skip_level = (uint32_t)level;
+  c->vol.dv.skip_words = (uint32_t)bits.size();
+  for (int a = 0; a < 3; ++a) c->vol.dv.skip_dims[a] = md[a];
+  c->vol.skip_table.built(p);
   return VX_OK;
 }
 
@@ -634,7 +531,7 @@ static int rebuild_skip_mask(VxContext* c) {
 // fold every record array (accumulator slot and the multi-frame slots) into c->base on the device and zero it
 static int fold_counters(VxContext* c) {
   if (!c->dc || !c->dc_waves) return VX_OK;
-  if (!c->fold_dev) VX_HIP(c, hipMalloc(&c->fold_dev, 10 * sizeof(unsigned long long)));
+  if (int rc = c->fold_dev.ensure(c, 10)) return rc;
   hipLaunchKernelGGL(zero_totals, dim3(1), dim3(10), 0, c->stream, c->fold_dev);
   auto fold = [&](DevCounters* recs, size_t n) {
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
@@ -664,21 +561,17 @@ static int ensure_counters(VxContext* c, size_t waves) {
   VX_HIP(c, hipStreamSynchronize(c->stream));
   int rc = fold_counters(c);
   if (rc) return rc;
-  if (c->dc) (void)hipFree(c->dc);
-  c->dc = nullptr;
   c->dc_waves = 0;
-  VX_HIP(c, hipMalloc(&c->dc, waves * sizeof(DevCounters)));
+  if (int rc = c->dc.alloc(c, waves)) return rc;
   // on the context's stream: it is a non-blocking stream, a fill on the null stream is not ordered with the launches
   // that follow (seen under rocprofv3's counter collection: the late fill wiped the records of a launch)
   VX_HIP(c, hipMemsetAsync(c->dc, 0, waves * sizeof(DevCounters), c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   c->dc_waves = waves;
-  if (c->order) (void)hipFree(c->order);
-  c->order = nullptr;
   {
     std::vector<uint32_t> ident(waves / 4);
     for (size_t i = 0; i < ident.size(); ++i) ident[i] = (uint32_t)i;
-    VX_HIP(c, hipMalloc(&c->order, ident.size() * 4));
+    if (int rc = c->order.alloc(c, ident.size())) return rc;
     VX_HIP(c, hipMemcpy(c->order, ident.data(), ident.size() * 4, hipMemcpyHostToDevice));
     c->order_builds_left = 2;
   }
@@ -746,7 +639,7 @@ static LightMarch light_march(const VxContext* c) {
   const uint32_t s = (uint32_t)p.dvr_shadow_stride;
   lm.stride = s;
   for (int i = 0; i < 3; ++i) {
-    lm.n[i] = (c->dv.extent[i] - 1u + s - 1u) / s + 1u;   // ceil((extent - 1) / s) + 1
+    lm.n[i] = (c->vol.dv.extent[i] - 1u + s - 1u) / s + 1u;   // ceil((extent - 1) / s) + 1
     // nodes inside the box: box_lo <= s * i + 1/2 <= box_hi (prepare_render keeps the box within the volume)
     const double lo = std::ceil(((double)lm.box_lo[i] - 0.5) / s), hi = std::floor(((double)lm.box_hi[i] - 0.5) / s);
     lm.ilo[i] = (uint32_t)std::min(std::max(lo, 0.0), (double)(lm.n[i] - 1u));
@@ -756,37 +649,31 @@ static LightMarch light_march(const VxContext* c) {
 }
 // build the light grid on the context's stream (after the layouts of the launch are in place)
 static int rebuild_light_grid(VxContext* c) {
-  c->shadow_table.stale = true;   // until this build is complete
+  c->vol.shadow_table.stale = true;   // until this build is complete
   const LightMarch lm = light_march(c);
   const uint64_t nodes = (uint64_t)lm.n[0] * lm.n[1] * lm.n[2];
   if (nodes >= (1ull << 31))
     VX_FAIL(c, VX_ERR_INVALID, "shadowed DVR: a light grid of %llu nodes (stride %u) is beyond the look-up's index range; "
             "use a larger dvr_shadow_stride", (unsigned long long)nodes, lm.stride);
-  if (nodes > c->shadow_cap) {
+  if (nodes > c->vol.shadow_dev.cap) {
     VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued launch still reads the old grid
-    if (c->shadow_dev) (void)hipFree(c->shadow_dev);
-    c->shadow_dev = nullptr;
-    c->shadow_cap = 0;
-    c->shadow = ShadowGrid{};
-    VX_HIP(c, hipMalloc(&c->shadow_dev, nodes * sizeof(float)));
-    c->shadow_cap = nodes;
+    c->vol.shadow = ShadowGrid{};
+    if (int rc = c->vol.shadow_dev.alloc(c, nodes)) return rc;
   }
-  if (!c->shadow_count_dev) VX_HIP(c, hipMalloc(&c->shadow_count_dev, sizeof(unsigned long long)));
-  for (hipEvent_t& e : c->shadow_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
+  if (int rc = c->shadow_count_dev.ensure(c, 1)) return rc;
   VX_HIP(c, hipMemsetAsync(c->shadow_count_dev, 0, sizeof(unsigned long long), c->stream));
   const dim3 grid((lm.n[0] + 7u) / 8u, (lm.n[1] + 7u) / 8u, (lm.n[2] + 3u) / 4u);
   const size_t lds = c->tf_len <= TF_LDS_MAX ? (size_t)c->tf_len * sizeof(float4) : 0u;
-  VX_HIP(c, hipEventRecord(c->shadow_ev[0], c->stream));
+  if (int rc = c->shadow_timer.mark(c, 0)) return rc;
   with_layout(eff_layout(c), [&](auto tag) {
     constexpr int LAY = decltype(tag)::value;
-    hipLaunchKernelGGL((build_light_grid<LAY>), grid, dim3(256), lds, c->stream, c->params, c->dv, c->tf, c->tf_len, lm,
-                       c->shadow_dev, c->shadow_count_dev);
+    hipLaunchKernelGGL((build_light_grid<LAY>), grid, dim3(256), lds, c->stream, c->params, c->vol.dv, c->tf, c->tf_len, lm,
+                       c->vol.shadow_dev, c->shadow_count_dev);
   });
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->shadow_ev[1], c->stream));
-  ShadowGrid& g = c->shadow;
-  g.t = c->shadow_dev;
+  if (int rc = c->shadow_timer.mark(c, 1)) return rc;
+  ShadowGrid& g = c->vol.shadow;
+  g.t = c->vol.shadow_dev;
   g.inv_s = 1.0f / (float)lm.stride;
   for (int i = 0; i < 3; ++i) {
     g.n[i] = lm.n[i];
@@ -794,7 +681,7 @@ static int rebuild_light_grid(VxContext* c) {
     g.ghi[i] = (float)lm.ihi[i];
     g.gmax[i] = (float)(lm.n[i] - 1u);
   }
-  c->shadow_table.built(c->params);
+  c->vol.shadow_table.built(c->params);
   c->shadow_builds += 1;
   return VX_OK;
 }
@@ -847,11 +734,11 @@ static bool tuned_possible(const VxContext* c) {
 static bool use_lds_kernel(const VxContext* c) {
   if (!tuned_possible(c)) return false;
   if (proj_mode(c->params.render_mode))
-    return eff_layout(c) == VX_LAYOUT_BRICKF32 || (eff_layout(c) == VX_LAYOUT_BRICKU8 && c->dv.bu != nullptr);
+    return eff_layout(c) == VX_LAYOUT_BRICKF32 || (eff_layout(c) == VX_LAYOUT_BRICKU8 && c->vol.dv.bu != nullptr);
   if (eff_layout(c) == VX_LAYOUT_BRICKU8)   // the same kernel, staging from the 8-bit bricks
-    return (c->params.render_mode == VX_MODE_DVR || c->params.render_mode == VX_MODE_DVR_PHONG) && c->dv.bu != nullptr;
+    return (c->params.render_mode == VX_MODE_DVR || c->params.render_mode == VX_MODE_DVR_PHONG) && c->vol.dv.bu != nullptr;
   if (c->params.render_mode == VX_MODE_DVR) return eff_layout(c) == VX_LAYOUT_BRICKF32;
-  return c->params.render_mode == VX_MODE_DVR_PHONG && c->dv.bf != nullptr;
+  return c->params.render_mode == VX_MODE_DVR_PHONG && c->vol.dv.bf != nullptr;
 }
 static bool is_tuned(const VxContext* c) {
   const bool dvr_cq = c->params.render_mode == VX_MODE_DVR && eff_layout(c) == VX_LAYOUT_CELLQUAD;
@@ -873,7 +760,7 @@ static bool folds(Kernel kernel, int mode, uint32_t n) {
 // the dynamic LDS of a launch: the TF, the mask of the empty-space grid where the kernel stages it, the wave tiles
 static size_t lds_bytes(const VxContext* c, const LaunchPlan& lp) {
   const size_t tf = (size_t)c->tf_len * sizeof(float4);
-  const size_t mask = lp.skip ? (size_t)c->dv.skip_words * 4u : 0u;
+  const size_t mask = lp.skip ? (size_t)c->vol.dv.skip_words * 4u : 0u;
   const size_t tiles = 4u * (size_t)(lp.phong ? LdsTile<true>::FLOATS : LdsTile<false>::FLOATS) * sizeof(float);
   switch (lp.kernel) {
     case Kernel::DVR_LDS: return tf + ((mask + 15u) & ~(size_t)15u) + tiles;   // the mask in whole 16-byte rows
@@ -895,23 +782,23 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo, bool probe
     lp.kernel = !use_lds_kernel(c) ? Kernel::DVR_CQ : proj_mode(p.render_mode) ? Kernel::PROJ_LDS : Kernel::DVR_LDS;
   lp.phong = lp.kernel == Kernel::DVR_LDS && p.render_mode == VX_MODE_DVR_PHONG;
   lp.minip = lp.kernel == Kernel::PROJ_LDS && p.render_mode == VX_MODE_MINIP;
-  if (lp.shadow) lp.light = c->shadow;
+  if (lp.shadow) lp.light = c->vol.shadow;
   // SKIP: the DVR kernels test that a mask exists, the projections that their bounds are current
   if (lp.kernel == Kernel::PROJ_LDS) {
-    lp.skip = p.dvr_skip_empty && c->proj_dev && !c->proj_table.stale;
+    lp.skip = p.dvr_skip_empty && c->proj_dev && !c->vol.proj_table.stale;
     lp.bounds = lp.skip ? c->proj_dev : nullptr;
   } else {
-    lp.skip = p.dvr_skip_empty && c->dv.skip_bits;
+    lp.skip = p.dvr_skip_empty && c->vol.dv.skip_bits;
   }
   // the segment view (check_segment_view has refused every launch it does not cover): the masked instance, without skipping
-  if (c->seg_view != VX_SEGVIEW_OFF && lds_window_kernel(lp.kernel)) {
+  if (c->vol.seg_view != VX_SEGVIEW_OFF && lds_window_kernel(lp.kernel)) {
     lp.segv = true;
-    lp.segm = reinterpret_cast<const uint32_t*>(c->seg.seg);
-    lp.seg_inv = c->seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u;
+    lp.segm = reinterpret_cast<const uint32_t*>(c->vol.seg.seg);
+    lp.seg_inv = c->vol.seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u;
     lp.skip = false;
     lp.bounds = nullptr;
   }
-  lp.u8 = lp.layout == VX_LAYOUT_BRICKU8 && c->dv.bu;
+  lp.u8 = lp.layout == VX_LAYOUT_BRICKU8 && c->vol.dv.bu;
   lp.probe = probe;
   lp.order = probe ? nullptr : c->order;
   // a frame's blocks per frame slot (the LDS-window kernels take a count of 0 as 1)
@@ -927,6 +814,12 @@ template <class F>
 static void with_bool(bool b, F&& f) {
   if (b) f(std::true_type{});
   else f(std::false_type{});
+}
+// calls f(std::integral_constant<int, 6 or 26>) for a checked connectivity (the flood, the edit steps, the islands)
+template <class F>
+static void with_conn(int conn, F&& f) {
+  if (conn == 26) f(std::integral_constant<int, 26>{});
+  else f(std::integral_constant<int, 6>{});
 }
 // calls f(std::integral_constant<int, VX_MODE_*>) for render mode m
 template <class F>
@@ -948,7 +841,7 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
   if (mo.fuse && !folds(lp.kernel, lp.mode, mo.count))
     VX_FAIL(c, VX_ERR_INVALID, "render launch: running mean to fold (MultiOut::fuse) for a kernel that does not fold it");
   const VxParams& p = c->params;
-  const DevVolume& v = c->dv;
+  const DevVolume& v = c->vol.dv;
   const TileMap& tm = c->tm;
   const float4* tf = c->tf;
   const uint32_t n = c->tf_len;
@@ -1029,8 +922,8 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
 // (same bits on all three).  Not eff_layout: under AUTO it follows the render mode, and for `default` / `no_dda` it names
 // cellquad before the first render of such a mode has built it; under bricku8 the slice reads the reference textures.
 static int slice_layout(const VxContext* c) {
-  if (c->dv.bf) return VX_LAYOUT_BRICKF32;
-  if (c->dv.cq) return VX_LAYOUT_CELLQUAD;
+  if (c->vol.dv.bf) return VX_LAYOUT_BRICKF32;
+  if (c->vol.dv.cq) return VX_LAYOUT_CELLQUAD;
   return VX_LAYOUT_REFERENCE;
 }
 // launches slice_reduce<sp.reduce, the layout of slice_layout> for sp on the context's stream
@@ -1040,7 +933,7 @@ static void launch_slice(VxContext* c, const VxSliceParams& sp) {
   with_layout(slice_layout(c), [&](auto lay) {
     constexpr int LAY = decltype(lay)::value;
     auto go = [&](auto red) {
-      hipLaunchKernelGGL((slice_reduce<decltype(red)::value, LAY>), grid, dim3(256), 0, c->stream, sp, c->dv, p.volume_density_scale,
+      hipLaunchKernelGGL((slice_reduce<decltype(red)::value, LAY>), grid, dim3(256), 0, c->stream, sp, c->vol.dv, p.volume_density_scale,
                          p.volume_inv_maj, c->tf, c->tf_len, p.sample_range[0], p.sample_range[1], c->slice_values, c->slice_rgba);
     };
     if (sp.reduce == VX_SLICE_MAX) go(std::integral_constant<int, VX_SLICE_MAX>{});
@@ -1054,17 +947,15 @@ static void launch_slice(VxContext* c, const VxSliceParams& sp) {
 // of its own: building it never marks, frees or replaces the table MIP / MinIP launches read (proj_table / proj_dev).
 static int rebuild_iso_bounds(VxContext* c) {
   const VxParams& p = c->params;
-  c->iso_table.stale = true;   // until this build is complete
+  c->vol.iso_table.stale = true;   // until this build is complete
   std::vector<float> lohi;
   int level = 1;
   uint32_t md[3];
-  compute_projection_bounds(p, c->range_host.data(), c->dv.bc, c->dv.extent, lohi, level, md);
+  compute_projection_bounds(p, c->range_host.data(), c->vol.dv.bc, c->vol.dv.extent, lohi, level, md);
   const size_t n = lohi.size() / 2;
   std::vector<float> hi(n);
   for (size_t i = 0; i < n; ++i) hi[i] = lohi[2 * i + 1];
-  if (c->iso_bound_dev) (void)hipFree(c->iso_bound_dev);
-  c->iso_bound_dev = nullptr;
-  VX_HIP(c, hipMalloc(&c->iso_bound_dev, n * sizeof(float)));
+  if (int rc = c->iso_bound_dev.alloc(c, n)) return rc;
   VX_HIP(c, hipMemcpyAsync(c->iso_bound_dev, hi.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   IsoBound& b = c->iso_bound;
@@ -1072,8 +963,8 @@ static int rebuild_iso_bounds(VxContext* c) {
   b.sh = 3u + (uint32_t)level;
   b.md0 = md[0];
   b.md1 = md[1];
-  for (int a = 0; a < 3; ++a) b.cmax[a] = c->dv.extent[a] + 7u;
-  c->iso_table.built(p);
+  for (int a = 0; a < 3; ++a) b.cmax[a] = c->vol.dv.extent[a] + 7u;
+  c->vol.iso_table.built(p);
   return VX_OK;
 }
 // launches iso_first_hit<the layout of slice_layout, ip.skip> over the window (x0, y0, ww, wh) on the context's stream
@@ -1082,14 +973,14 @@ static void launch_iso(VxContext* c, const VxIsoParams& ip, uint32_t ww, uint32_
   const dim3 grid((ww + 15u) / 16u, (wh + 15u) / 16u);
   with_layout(slice_layout(c), [&](auto lay) {
     constexpr int LAY = decltype(lay)::value;
-    if (c->seg_view != VX_SEGVIEW_OFF)
-      hipLaunchKernelGGL((iso_first_hit_seg<LAY>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, c->iso_rgba, c->iso_hit,
-                         c->iso_count_dev, reinterpret_cast<const uint32_t*>(c->seg.seg), c->seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u);
+    if (c->vol.seg_view != VX_SEGVIEW_OFF)
+      hipLaunchKernelGGL((iso_first_hit_seg<LAY>), grid, dim3(256), 0, c->stream, c->params, c->vol.dv, ip, c->iso_rgba, c->iso_hit,
+                         c->iso_count_dev, reinterpret_cast<const uint32_t*>(c->vol.seg.seg), c->vol.seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u);
     else if (ip.skip)
-      hipLaunchKernelGGL((iso_first_hit<LAY, true>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, c->iso_bound, c->iso_rgba,
+      hipLaunchKernelGGL((iso_first_hit<LAY, true>), grid, dim3(256), 0, c->stream, c->params, c->vol.dv, ip, c->iso_bound, c->iso_rgba,
                          c->iso_hit, c->iso_count_dev);
     else
-      hipLaunchKernelGGL((iso_first_hit<LAY, false>), grid, dim3(256), 0, c->stream, c->params, c->dv, ip, IsoBound{}, c->iso_rgba,
+      hipLaunchKernelGGL((iso_first_hit<LAY, false>), grid, dim3(256), 0, c->stream, c->params, c->vol.dv, ip, IsoBound{}, c->iso_rgba,
                          c->iso_hit, c->iso_count_dev);
   });
 }
@@ -1118,13 +1009,7 @@ static int set_slab_table(VxContext* c, const std::vector<const float4*>& t) {
   if (t == c->slab_table_host) return VX_OK;
   c->slab_table_host.clear();
   VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued de-tile still reads the old table
-  if (t.size() > c->slab_table_cap) {
-    if (c->slab_table) (void)hipFree(c->slab_table);
-    c->slab_table = nullptr;
-    c->slab_table_cap = 0;
-    VX_HIP(c, hipMalloc(&c->slab_table, t.size() * sizeof(float4*)));
-    c->slab_table_cap = t.size();
-  }
+  if (int rc = c->slab_table.ensure(c, t.size())) return rc;
   VX_HIP(c, hipMemcpy(c->slab_table, t.data(), t.size() * sizeof(float4*), hipMemcpyHostToDevice));
   c->slab_table_host = t;
   return VX_OK;
@@ -1320,48 +1205,10 @@ void vx_destroy(VxContext* c) {
     (void)hipEventDestroy(e.b);
   }
   free_volume(c);
-  if (c->tf) (void)hipFree(c->tf);
-  if (c->env_tex) (void)hipFree(c->env_tex);
-  if (c->env_imp) (void)hipFree(c->env_imp);
-  if (c->env_impq) (void)hipFree(c->env_impq);
-  if (c->skip_dev) (void)hipFree(c->skip_dev);
-  if (c->proj_dev) (void)hipFree(c->proj_dev);
-  if (c->fold_dev) (void)hipFree(c->fold_dev);
-  if (c->shadow_count_dev) (void)hipFree(c->shadow_count_dev);
-  for (hipEvent_t e : c->shadow_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->slab) (void)hipFree(c->slab);
-  if (c->image) (void)hipFree(c->image);
-  if (c->display) (void)hipFree(c->display);
-  if (c->tile_perm) (void)hipFree(c->tile_perm);
-  if (c->dc) (void)hipFree(c->dc);
-  if (c->order) (void)hipFree(c->order);
-  if (c->pipe_result_pool) (void)hipFree(c->pipe_result_pool);
-  if (c->pipe_dc_pool) (void)hipFree(c->pipe_dc_pool);
-  if (c->slab_table) (void)hipFree(c->slab_table);
   if (c->done) (void)hipEventDestroy(c->done);
-  if (c->slice_values) (void)hipFree(c->slice_values);
-  if (c->slice_rgba) (void)hipFree(c->slice_rgba);
-  for (hipEvent_t e : c->slice_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->iso_rgba) (void)hipFree(c->iso_rgba);
-  if (c->iso_hit) (void)hipFree(c->iso_hit);
-  if (c->iso_bound_dev) (void)hipFree(c->iso_bound_dev);
-  if (c->iso_count_dev) (void)hipFree(c->iso_count_dev);
-  for (hipEvent_t e : c->iso_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->seg_ov) (void)hipFree(c->seg_ov);
-  for (hipEvent_t e : c->seg_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->sed_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->mesh_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->isl_ev)
-    if (e) (void)hipEventDestroy(e);
   if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  delete c;   // every buffer and timer the context owns, on the device made current above (vx_host.hpp)
 }
 
 const char* vx_last_error(const VxContext* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -1378,72 +1225,64 @@ int vx_set_stream(VxContext* c, void* s) {
 // Allocate the device layout the trilinear modes sample (cellquad / brickf32); returns its number of z layers
 // (apron-brick layers / brick layers) through n_layers.  The contents are filled by build_layout_layers.
 static int alloc_layout(VxContext* c, uint32_t& n_layers) {
-  if (c->cq_alloc) {
-    (void)hipFree(c->cq_alloc);
-    c->cq_alloc = nullptr;
-    c->dv.cq = nullptr;
+  if (c->vol.cq_alloc) c->vol.dv.cq = nullptr;
+  if (c->vol.bf_alloc) {
+    c->vol.dv.bf = nullptr;
+    c->vol.dv.bf_zero = 0;
   }
-  if (c->bf_alloc) {
-    (void)hipFree(c->bf_alloc);
-    c->bf_alloc = nullptr;
-    c->dv.bf = nullptr;
-    c->dv.bf_zero = 0;
-  }
-  if (c->bu_alloc) (void)hipFree(c->bu_alloc);
-  if (c->bur_alloc) (void)hipFree(c->bur_alloc);
-  c->bu_alloc = c->bur_alloc = nullptr;
-  c->dv.bu = nullptr;
-  c->dv.bu_range = nullptr;
+  for (DevBuf<void>* b : {&c->vol.cq_alloc, &c->vol.bf_alloc, &c->vol.bu_alloc, &c->vol.bur_alloc}) b->reset();
+  c->vol.dv.bu = nullptr;
+  c->vol.dv.bu_range = nullptr;
   n_layers = 0;
   c->auto_no_cq = c->auto_no_bf = false;
   if (c->layout == VX_LAYOUT_AUTO) {   // what the volume's size allows
-    const uint64_t nv = (uint64_t)c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2] * 512u;
-    const uint64_t nq = (uint64_t)(c->dv.bc[0] + 1) * (c->dv.bc[1] + 1) * (c->dv.bc[2] + 1) * CQ_BRICK_QUADS;
+    const uint64_t nv = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] * 512u;
+    const uint64_t nq = (uint64_t)(c->vol.dv.bc[0] + 1) * (c->vol.dv.bc[1] + 1) * (c->vol.dv.bc[2] + 1) * CQ_BRICK_QUADS;
     c->auto_no_bf = nv / 4u > 0xffffffffull;
     c->auto_no_cq = nq > 0xffffffffull;
   }
   if (primary_layout(c) == VX_LAYOUT_BRICKF32) {
-    uint64_t n_vox = (uint64_t)c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2] * 512u;
+    uint64_t n_vox = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] * 512u;
     // the staging loads index the layout in 16-byte units with 32 bits: 64 GiB, about 2500^3 voxels
     if (n_vox / 4u > 0xffffffffull)
       VX_FAIL(c, VX_ERR_INVALID, "volume too large for the brickf32 layout (%llu voxels): select VX_LAYOUT_REFERENCE "
               "with vx_set_layout", (unsigned long long)n_vox);
     // + one zero 16-byte chunk behind the last brick: the window staging of the LDS kernel reads it for rows and
     // chunks outside the volume (one select per load instead of a branch and a zero fill)
-    VX_HIP(c, hipMalloc(&c->bf_alloc, n_vox * sizeof(float) + 16));
-    VX_HIP(c, hipMemsetAsync((char*)c->bf_alloc + n_vox * sizeof(float), 0, 16, c->stream));
-    c->dv.bf = (const float*)c->bf_alloc;
-    c->dv.bf_zero = n_vox <= 0xfffffff0ull ? (uint32_t)n_vox : 0u;
-    n_layers = c->dv.bc[2];
+    if (int rc = c->vol.bf_alloc.alloc(c, n_vox * sizeof(float) + 16)) return rc;
+    VX_HIP(c, hipMemsetAsync((char*)c->vol.bf_alloc.p + n_vox * sizeof(float), 0, 16, c->stream));
+    c->vol.dv.bf = (const float*)c->vol.bf_alloc.p;
+    c->vol.dv.bf_zero = n_vox <= 0xfffffff0ull ? (uint32_t)n_vox : 0u;
+    n_layers = c->vol.dv.bc[2];
     return VX_OK;
   }
   if (primary_layout(c) == VX_LAYOUT_BRICKU8) {
-    const uint64_t n_bricks = (uint64_t)c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2];
+    const uint64_t n_bricks = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2];
     const uint64_t n_units = n_bricks * 128u;   // dwords of four codes; the staging indexes them with 32 bits
     if (n_units > 0xfffffff0ull)
       VX_FAIL(c, VX_ERR_INVALID, "volume too large for the bricku8 layout (%llu bricks): select VX_LAYOUT_REFERENCE "
               "with vx_set_layout", (unsigned long long)n_bricks);
     // + one zero unit behind the last brick and its {0, 0} range: rows and chunks outside the volume decode to +0
-    VX_HIP(c, hipMalloc(&c->bu_alloc, (n_units + 4u) * sizeof(uint32_t)));
-    VX_HIP(c, hipMalloc(&c->bur_alloc, (n_bricks + 1u) * sizeof(float2)));
-    VX_HIP(c, hipMemsetAsync((char*)c->bu_alloc + n_units * sizeof(uint32_t), 0, 4u * sizeof(uint32_t), c->stream));
-    VX_HIP(c, hipMemsetAsync((char*)c->bur_alloc + n_bricks * sizeof(float2), 0, sizeof(float2), c->stream));
-    c->dv.bu = (const uint32_t*)c->bu_alloc;
-    c->dv.bu_range = (const float2*)c->bur_alloc;
-    n_layers = c->dv.bc[2];
+    if (int rc = c->vol.bu_alloc.alloc(c, (n_units + 4u) * sizeof(uint32_t))) return rc;
+    if (int rc = c->vol.bur_alloc.alloc(c, (n_bricks + 1u) * sizeof(float2))) return rc;
+    VX_HIP(c, hipMemsetAsync((char*)c->vol.bu_alloc.p + n_units * sizeof(uint32_t), 0, 4u * sizeof(uint32_t), c->stream));
+    VX_HIP(c, hipMemsetAsync((char*)c->vol.bur_alloc.p + n_bricks * sizeof(float2), 0, sizeof(float2), c->stream));
+    c->vol.dv.bu = (const uint32_t*)c->vol.bu_alloc.p;
+    c->vol.dv.bu_range = (const float2*)c->vol.bur_alloc.p;
+    n_layers = c->vol.dv.bc[2];
     return VX_OK;
   }
   if (primary_layout(c) != VX_LAYOUT_CELLQUAD) return VX_OK;
-  for (int i = 0; i < 3; ++i) c->dv.cq_bc[i] = c->dv.bc[i] + 1;
-  uint64_t n_quads = (uint64_t)c->dv.cq_bc[0] * c->dv.cq_bc[1] * c->dv.cq_bc[2] * CQ_BRICK_QUADS;
+  for (int i = 0; i < 3; ++i) c->vol.dv.cq_bc[i] = c->vol.dv.bc[i] + 1;
+  uint64_t n_quads = (uint64_t)c->vol.dv.cq_bc[0] * c->vol.dv.cq_bc[1] * c->vol.dv.cq_bc[2] * CQ_BRICK_QUADS;
   // the march indexes quads with 32 bits (and bricks with 24-bit multiplies): 64 GiB, about 1550^3 voxels
   if (n_quads > 0xffffffffull)
     VX_FAIL(c, VX_ERR_INVALID,
             "volume too large for the cellquad layout (%llu quads > 2^32): select VX_LAYOUT_BRICKF32 or "
             "VX_LAYOUT_REFERENCE with vx_set_layout", (unsigned long long)n_quads);
-  VX_HIP(c, hipMalloc(&c->cq_alloc, n_quads * sizeof(float4)));
-  c->dv.cq = (const float4*)c->cq_alloc;
-  n_layers = c->dv.cq_bc[2];
+  if (int rc = c->vol.cq_alloc.alloc(c, n_quads * sizeof(float4))) return rc;
+  c->vol.dv.cq = (const float4*)c->vol.cq_alloc.p;
+  n_layers = c->vol.dv.cq_bc[2];
   return VX_OK;
 }
 
@@ -1451,29 +1290,29 @@ static int alloc_layout(VxContext* c, uint32_t& n_layers) {
 static int build_layout_layers(VxContext* c, uint32_t z0, uint32_t z1, hipStream_t st) {
   if (z1 <= z0) return VX_OK;
   if (primary_layout(c) == VX_LAYOUT_BRICKF32) {
-    const uint64_t per = (uint64_t)c->dv.bc[0] * c->dv.bc[1] * 512u;
+    const uint64_t per = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * 512u;
     const uint64_t first = per * z0, end = per * z1;
     for (uint64_t at = first; at < end;) {   // <= 2^31 threads per launch
       uint64_t n = end - at < (1ull << 31) ? end - at : (1ull << 31);
-      hipLaunchKernelGGL(build_brickf32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c->dv,
-                         (float*)c->bf_alloc, at, at + n);
+      hipLaunchKernelGGL(build_brickf32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c->vol.dv,
+                         (float*)c->vol.bf_alloc.p, at, at + n);
       at += n;
     }
   } else if (primary_layout(c) == VX_LAYOUT_BRICKU8) {
-    const uint64_t bricks_per = (uint64_t)c->dv.bc[0] * c->dv.bc[1];
+    const uint64_t bricks_per = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1];
     const uint64_t first = bricks_per * 128u * z0, end = bricks_per * 128u * z1;   // dword units, < 2^32 (alloc_layout)
-    hipLaunchKernelGGL(build_bricku8, dim3((uint32_t)((end - first + 255) / 256)), dim3(256), 0, st, c->dv,
-                       (uint32_t*)c->bu_alloc, first, end);
+    hipLaunchKernelGGL(build_bricku8, dim3((uint32_t)((end - first + 255) / 256)), dim3(256), 0, st, c->vol.dv,
+                       (uint32_t*)c->vol.bu_alloc.p, first, end);
     const uint32_t b0 = (uint32_t)(bricks_per * z0), b1 = (uint32_t)(bricks_per * z1);
-    hipLaunchKernelGGL(build_bricku8_range, dim3((b1 - b0 + 255) / 256), dim3(256), 0, st, c->dv, (float2*)c->bur_alloc,
+    hipLaunchKernelGGL(build_bricku8_range, dim3((b1 - b0 + 255) / 256), dim3(256), 0, st, c->vol.dv, (float2*)c->vol.bur_alloc.p,
                        b0, b1);
   } else if (primary_layout(c) == VX_LAYOUT_CELLQUAD) {
-    const uint64_t per = (uint64_t)c->dv.cq_bc[0] * c->dv.cq_bc[1] * CQ_BRICK_QUADS;
+    const uint64_t per = (uint64_t)c->vol.dv.cq_bc[0] * c->vol.dv.cq_bc[1] * CQ_BRICK_QUADS;
     const uint64_t first = per * z0, end = per * z1;
     for (uint64_t at = first; at < end;) {
       uint64_t n = end - at < (1ull << 31) ? end - at : (1ull << 31);
-      hipLaunchKernelGGL(build_cellquad, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c->dv,
-                         (float4*)c->cq_alloc, at, at + n);
+      hipLaunchKernelGGL(build_cellquad, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c->vol.dv,
+                         (float4*)c->vol.cq_alloc.p, at, at + n);
       at += n;
     }
   }
@@ -1484,17 +1323,17 @@ static int build_layout_layers(VxContext* c, uint32_t z0, uint32_t z1, hipStream
 // dvr_phong runs on the LDS-window kernel, which samples the brickf32 layout: a context whose primary layout is
 // cellquad gets the 4-byte-per-voxel brick layout built beside it the first time Phong is rendered
 static int ensure_brickf32(VxContext* c) {
-  if (c->dv.bf) return VX_OK;
-  const uint64_t n_vox = (uint64_t)c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2] * 512u;
+  if (c->vol.dv.bf) return VX_OK;
+  const uint64_t n_vox = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] * 512u;
   if (n_vox / 4u > 0xffffffffull) return VX_OK;   // too large: the generic kernel serves Phong
-  VX_HIP(c, hipMalloc(&c->bf_alloc, n_vox * sizeof(float) + 16));   // + the zero chunk (alloc_layout)
-  VX_HIP(c, hipMemsetAsync((char*)c->bf_alloc + n_vox * sizeof(float), 0, 16, c->stream));
-  c->dv.bf = (const float*)c->bf_alloc;
-  c->dv.bf_zero = n_vox <= 0xfffffff0ull ? (uint32_t)n_vox : 0u;
+  if (int rc = c->vol.bf_alloc.alloc(c, n_vox * sizeof(float) + 16)) return rc;   // + the zero chunk (alloc_layout)
+  VX_HIP(c, hipMemsetAsync((char*)c->vol.bf_alloc.p + n_vox * sizeof(float), 0, 16, c->stream));
+  c->vol.dv.bf = (const float*)c->vol.bf_alloc.p;
+  c->vol.dv.bf_zero = n_vox <= 0xfffffff0ull ? (uint32_t)n_vox : 0u;
   for (uint64_t at = 0; at < n_vox;) {
     uint64_t n = n_vox - at < (1ull << 31) ? n_vox - at : (1ull << 31);
-    hipLaunchKernelGGL(build_brickf32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->dv,
-                       (float*)c->bf_alloc, at, at + n);
+    hipLaunchKernelGGL(build_brickf32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->vol.dv,
+                       (float*)c->vol.bf_alloc.p, at, at + n);
     at += n;
   }
   VX_HIP(c, hipGetLastError());
@@ -1504,9 +1343,9 @@ static int ensure_brickf32(VxContext* c) {
 // the cellquad layout built beside the primary one the first time a mode that gathers from it is rendered
 // (VX_LAYOUT_AUTO: the path-traced reference modes)
 static int ensure_cellquad(VxContext* c) {
-  if (c->dv.cq) return VX_OK;
-  for (int i = 0; i < 3; ++i) c->dv.cq_bc[i] = c->dv.bc[i] + 1;
-  const uint64_t n_quads = (uint64_t)c->dv.cq_bc[0] * c->dv.cq_bc[1] * c->dv.cq_bc[2] * CQ_BRICK_QUADS;
+  if (c->vol.dv.cq) return VX_OK;
+  for (int i = 0; i < 3; ++i) c->vol.dv.cq_bc[i] = c->vol.dv.bc[i] + 1;
+  const uint64_t n_quads = (uint64_t)c->vol.dv.cq_bc[0] * c->vol.dv.cq_bc[1] * c->vol.dv.cq_bc[2] * CQ_BRICK_QUADS;
   if (c->layout == VX_LAYOUT_AUTO) {
     // AUTO builds this layout on demand, beside what is resident: only when it leaves half of the free device memory to
     // the rest of the process (19.8 GB for 1024^3 on a 288 GB MI355X: always; a volume near the layout's 64 GiB index limit
@@ -1520,12 +1359,12 @@ static int ensure_cellquad(VxContext* c) {
       return VX_OK;
     }
   }
-  VX_HIP(c, hipMalloc(&c->cq_alloc, n_quads * sizeof(float4)));
-  c->dv.cq = (const float4*)c->cq_alloc;
+  if (int rc = c->vol.cq_alloc.alloc(c, n_quads * sizeof(float4))) return rc;
+  c->vol.dv.cq = (const float4*)c->vol.cq_alloc.p;
   for (uint64_t at = 0; at < n_quads;) {
     uint64_t n = n_quads - at < (1ull << 31) ? n_quads - at : (1ull << 31);
-    hipLaunchKernelGGL(build_cellquad, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->dv,
-                       (float4*)c->cq_alloc, at, at + n);
+    hipLaunchKernelGGL(build_cellquad, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->vol.dv,
+                       (float4*)c->vol.cq_alloc.p, at, at + n);
     at += n;
   }
   VX_HIP(c, hipGetLastError());
@@ -1630,19 +1469,19 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
   for (int k = 0; k < 3; ++k) {
     mip_n[k] = (size_t)mip_size[k][0] * mip_size[k][1] * mip_size[k][2];
     if ((rc = alloc(mip_n[k] * 4, &d_mip[k]))) { free_volume(c); return rc; }
-    c->dv.mips[k] = (const uint32_t*)d_mip[k];
-    for (int i = 0; i < 3; ++i) c->dv.mip_size[k][i] = mip_size[k][i];
+    c->vol.dv.mips[k] = (const uint32_t*)d_mip[k];
+    for (int i = 0; i < 3; ++i) c->vol.dv.mip_size[k][i] = mip_size[k][i];
   }
-  c->dv.indirection = (const uint32_t*)d_ind;
-  c->dv.range = (const uint32_t*)d_range;   // u16 stream [max,min] == LE u32 (min<<16)|max
-  c->dv.atlas = (const uint8_t*)d_atlas;
+  c->vol.dv.indirection = (const uint32_t*)d_ind;
+  c->vol.dv.range = (const uint32_t*)d_range;   // u16 stream [max,min] == LE u32 (min<<16)|max
+  c->vol.dv.atlas = (const uint8_t*)d_atlas;
   for (int i = 0; i < 3; ++i) {
-    c->dv.bc[i] = ind_size[i];
-    c->dv.atlas_size[i] = atlas_size[i];
-    c->dv.extent[i] = index_extent[i];
+    c->vol.dv.bc[i] = ind_size[i];
+    c->vol.dv.atlas_size[i] = atlas_size[i];
+    c->vol.dv.extent[i] = index_extent[i];
   }
   c->range_host.assign((const uint32_t*)range, (const uint32_t*)range + nb);
-  c->skip_table.stale = c->proj_table.stale = c->iso_table.stale = true;
+  c->vol.skip_table.stale = c->vol.proj_table.stale = c->vol.iso_table.stale = true;
   c->order_builds_left = 2;
   uint32_t n_layers = 0;
   if ((rc = alloc_layout(c, n_layers))) { free_volume(c); return rc; }
@@ -1706,7 +1545,7 @@ int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t i
     free_volume(c);
     VX_FAIL(c, VX_ERR_DEVICE, "vx_upload_volume: %s", hipGetErrorString(bad));
   }
-  c->has_volume = true;
+  c->vol.has_volume = true;
   c->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
   c->upload_host_bytes = (uint64_t)atlas_bytes + (uint64_t)nb * 8u + (uint64_t)(mip_n[0] + mip_n[1] + mip_n[2]) * 4u;
   c->upload_pinned = pin_atlas.pinned ? 1 : 0;
@@ -1750,7 +1589,7 @@ int vx_set_layout(VxContext* c, int layout) {
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_layout: unknown layout %d", layout);
   if (layout == c->layout) return VX_OK;
   c->layout = layout;
-  if (c->has_volume) {
+  if (c->vol.has_volume) {
     VX_HIP(c, hipStreamSynchronize(c->stream));
     int rc = build_layout(c);
     if (rc) return rc;
@@ -1770,13 +1609,11 @@ int vx_upload_transfer(VxContext* c, const float* rgba, uint32_t length) {
     if (!std::isfinite(rgba[i]))
       VX_FAIL(c, VX_ERR_INVALID, "vx_upload_transfer: entry %zu component %zu is not finite", i / 4, i % 4);
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->tf) (void)hipFree(c->tf);
-  c->tf = nullptr;
-  VX_HIP(c, hipMalloc(&c->tf, (size_t)length * sizeof(float4)));
+  if (int rc = c->tf.alloc(c, length)) return rc;
   VX_HIP(c, hipMemcpy(c->tf, rgba, (size_t)length * sizeof(float4), hipMemcpyHostToDevice));
   c->tf_len = length;
   c->tf_host.assign(rgba, rgba + (size_t)length * 4);
-  c->skip_table.stale = c->lmaj_table.stale = c->shadow_table.stale = true;
+  c->vol.skip_table.stale = c->vol.lmaj_table.stale = c->vol.shadow_table.stale = true;
   c->order_builds_left = 2;
   return VX_OK;
 }
@@ -1786,12 +1623,9 @@ int vx_upload_environment(VxContext* c, const float* rgba, uint32_t w, uint32_t 
   if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_upload_environment(m, rgba, w, h); });
   VX_HIP(c, hipSetDevice(c->device));
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->env_tex) (void)hipFree(c->env_tex);
-  if (c->env_imp) (void)hipFree(c->env_imp);
-  if (c->env_impq) (void)hipFree(c->env_impq);
-  c->env_tex = nullptr;
-  c->env_imp = nullptr;
-  c->env_impq = nullptr;
+  c->env_tex.reset();
+  c->env_imp.reset();
+  c->env_impq.reset();
   c->env_w = c->env_h = 0;
   if (!rgba) return VX_OK;
   if (w == 0 || h == 0 || w > 16384 || h > 16384)
@@ -1799,9 +1633,9 @@ int vx_upload_environment(VxContext* c, const float* rgba, uint32_t w, uint32_t 
   std::vector<float> flipped((size_t)w * h * 4);  // UNPACK_FLIP_Y_WEBGL, environment.ts:30-32
   for (uint32_t y = 0; y < h; ++y)
     memcpy(flipped.data() + (size_t)(h - 1 - y) * w * 4, rgba + (size_t)y * w * 4, (size_t)w * 16);
-  VX_HIP(c, hipMalloc(&c->env_tex, flipped.size() * sizeof(float)));
-  VX_HIP(c, hipMalloc(&c->env_imp, (size_t)IMP_FLOATS * sizeof(float)));
-  VX_HIP(c, hipMalloc(&c->env_impq, (size_t)IMPQ_QUADS * sizeof(float4)));
+  if (int rc = c->env_tex.alloc(c, (size_t)w * h)) return rc;
+  if (int rc = c->env_imp.alloc(c, IMP_FLOATS)) return rc;
+  if (int rc = c->env_impq.alloc(c, IMPQ_QUADS)) return rc;
   VX_HIP(c, hipMemcpy(c->env_tex, flipped.data(), flipped.size() * sizeof(float), hipMemcpyHostToDevice));
   c->env_w = w;
   c->env_h = h;
@@ -1891,8 +1725,7 @@ int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
   VX_HIP(c, hipSetDevice(c->device));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   if ((w != c->W || h != c->H) && c->tile_perm) {  // a dealing order belongs to one image size
-    (void)hipFree(c->tile_perm);
-    c->tile_perm = nullptr;
+    c->tile_perm.reset();
     c->tile_perm_n = 0;
   }
   c->W = w;
@@ -1903,10 +1736,10 @@ int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
 // The segment view's refusals, in one place: a covered call (`iso`: vx_isosurface; else a render launch, after its layouts are
 // resident) with the view on fails here, before anything is launched, unless a masked instance serves it.
 static int check_segment_view(VxContext* c, const char* fn, bool iso) {
-  if (c->seg_view == VX_SEGVIEW_OFF) return VX_OK;
-  const char* view = c->seg_view == VX_SEGVIEW_ONLY ? "only" : "hide";
+  if (c->vol.seg_view == VX_SEGVIEW_OFF) return VX_OK;
+  const char* view = c->vol.seg_view == VX_SEGVIEW_ONLY ? "only" : "hide";
   if (is_group(c)) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for a device group (the segment lives on member 0)", fn, view);
-  if (!c->seg_valid)
+  if (!c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s without a current segment (vx_segment first; an upload drops it)", fn, view);
   if (iso) return VX_OK;
   const VxParams& p = c->params;
@@ -1923,7 +1756,7 @@ static int check_segment_view(VxContext* c, const char* fn, bool iso) {
 }
 
 static int prepare_render(VxContext* c) {
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
   if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
   if (!c->tf) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: no transfer function");
   if (!c->slab) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_resize not called");
@@ -1931,12 +1764,12 @@ static int prepare_render(VxContext* c) {
     VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: params.res differs from the framebuffer size");
   if (c->params.use_env > 0 && !c->env_tex)
     VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: use_env = 1 without vx_upload_environment");
-  c->dv.env_tex = c->env_tex;
-  c->dv.env_imp = c->env_imp;
-  c->dv.env_impq = c->env_impq;
-  c->dv.env_avg_w = c->env_avg_w;
-  c->dv.env_w = c->env_w;
-  c->dv.env_h = c->env_h;
+  c->vol.dv.env_tex = c->env_tex;
+  c->vol.dv.env_imp = c->env_imp;
+  c->vol.dv.env_impq = c->env_impq;
+  c->vol.dv.env_avg_w = c->env_avg_w;
+  c->vol.dv.env_w = c->env_w;
+  c->vol.dv.env_h = c->env_h;
   {
     // The box the rays are clipped to must lie inside the volume (volume.ts:32-37 clips the volume's own box, so the
     // viewer cannot ask for anything else): the trilinear look-up of the cellquad layout relies on every sample's cell
@@ -1950,9 +1783,9 @@ static int prepare_render(VxContext* c) {
       for (int i = 0; i < 3; ++i) {
         const float* m = p.density_transform_inv;
         const float q = fmaf(m[12 + i], 1.0f, fmaf(m[8 + i], w[2], fmaf(m[4 + i], w[1], m[i] * w[0])));
-        if (!(q >= -0.25f && q <= (float)c->dv.extent[i] + 0.25f))
+        if (!(q >= -0.25f && q <= (float)c->vol.dv.extent[i] + 0.25f))
           VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: volume_aabb reaches index %.3f on axis %d, outside the volume [0, %u]: "
-                  "the clip box must lie inside the volume's own box (volume.ts:32-37)", (double)q, i, c->dv.extent[i]);
+                  "the clip box must lie inside the volume's own box (volume.ts:32-37)", (double)q, i, c->vol.dv.extent[i]);
       }
     }
   }
@@ -1965,18 +1798,18 @@ static int prepare_render(VxContext* c) {
     };
     float cw[4], a[4];
     mat4(p.camera_view_inv, 0.0f, 0.0f, 0.0f, 1.0f, cw);
-    for (int i = 0; i < 3; ++i) c->dv.cam_o[i] = cw[i] / cw[3];
-    mat4(p.density_transform_inv, c->dv.cam_o[0], c->dv.cam_o[1], c->dv.cam_o[2], 1.0f, a);
-    for (int i = 0; i < 3; ++i) c->dv.cam_ipos[i] = a[i];
-    c->dv.inv_res[0] = 1.0f / (float)p.res[0];
-    c->dv.inv_res[1] = 1.0f / (float)p.res[1];
+    for (int i = 0; i < 3; ++i) c->vol.dv.cam_o[i] = cw[i] / cw[3];
+    mat4(p.density_transform_inv, c->vol.dv.cam_o[0], c->vol.dv.cam_o[1], c->vol.dv.cam_o[2], 1.0f, a);
+    for (int i = 0; i < 3; ++i) c->vol.dv.cam_ipos[i] = a[i];
+    c->vol.dv.inv_res[0] = 1.0f / (float)p.res[0];
+    c->vol.dv.inv_res[1] = 1.0f / (float)p.res[1];
     // the per-ray divisions a launch constant decides (DevVolume::ray_flags): both shortcuts are exact or not taken
     uint32_t flags = 0;
     const float* vi = p.camera_view_inv;
     if (vi[3] == 0.0f && vi[7] == 0.0f && vi[11] == 0.0f && vi[15] == 1.0f) flags |= RAY_AFFINE_VIEW;
     for (int axis = 0; axis < 2; ++axis) {
       if (c->tex_checked_res[axis] != p.res[axis]) {   // tried once per resolution, not per launch
-        const float res = (float)p.res[axis], y = c->dv.inv_res[axis];
+        const float res = (float)p.res[axis], y = c->vol.dv.inv_res[axis];
         bool same = true;
         for (int px = 0; px < p.res[axis] && same; ++px) {
           const float a = (float)px + 0.5f, q0 = a * y;
@@ -1988,16 +1821,16 @@ static int prepare_render(VxContext* c) {
       if (c->tex_by_reciprocal[axis]) flags |= (axis == 0 ? RAY_TEX_BY_RECIPROCAL_X : RAY_TEX_BY_RECIPROCAL_Y);
     }
     if (!c->sw.ray_shortcuts) flags = 0;   // diagnostic: the divisions themselves
-    c->dv.ray_flags = flags;
+    c->vol.dv.ray_flags = flags;
   }
   {
     const VxParams& p = c->params;
     const bool dvr = p.render_mode == VX_MODE_DVR || p.render_mode == VX_MODE_DVR_PHONG;
     int rc = VX_OK;
-    if (dvr && p.dvr_skip_empty && !p.debug_hits && !c->skip_table.current(p)) rc = rebuild_skip_mask(c);
-    if (!rc && proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits && !c->proj_table.current(p))
+    if (dvr && p.dvr_skip_empty && !p.debug_hits && !c->vol.skip_table.current(p)) rc = rebuild_skip_mask(c);
+    if (!rc && proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits && !c->vol.proj_table.current(p))
       rc = rebuild_projection_bounds(c);
-    if (!rc && p.render_mode == VX_MODE_DEFAULT && !p.debug_hits && !c->lmaj_table.current(p)) rc = rebuild_local_majorants(c);
+    if (!rc && p.render_mode == VX_MODE_DEFAULT && !p.debug_hits && !c->vol.lmaj_table.current(p)) rc = rebuild_local_majorants(c);
     if (rc) return rc;
   }
   {
@@ -2014,7 +1847,7 @@ static int prepare_render(VxContext* c) {
     if (rc) return rc;
   }
   if (int rc = check_segment_view(c, "vx_render_frame", false)) return rc;
-  if (shadow_on(c) && !c->shadow_table.current(c->params)) {   // after the layouts: the build samples them
+  if (shadow_on(c) && !c->vol.shadow_table.current(c->params)) {   // after the layouts: the build samples them
     int rc = rebuild_light_grid(c);
     if (rc) return rc;
   }
@@ -2073,13 +1906,11 @@ static int ensure_pipes(VxContext* c, uint32_t n) {
     if (rc) return rc;
   }
   const size_t ns = std::max(n, c->pipe_slots), waves = c->dc_waves;
-  if (c->pipe_result_pool) (void)hipFree(c->pipe_result_pool);
-  if (c->pipe_dc_pool) (void)hipFree(c->pipe_dc_pool);
-  c->pipe_result_pool = nullptr;
-  c->pipe_dc_pool = nullptr;
+  c->pipe_result_pool.reset();
+  c->pipe_dc_pool.reset();
   c->pipe_slots = 0;
-  VX_HIP(c, hipMalloc(&c->pipe_result_pool, ns * c->slab_quads * sizeof(float4)));
-  VX_HIP(c, hipMalloc(&c->pipe_dc_pool, ns * waves * sizeof(DevCounters)));
+  if (int rc = c->pipe_result_pool.alloc(c, ns * c->slab_quads)) return rc;
+  if (int rc = c->pipe_dc_pool.alloc(c, ns * waves)) return rc;
   VX_HIP(c, hipMemsetAsync(c->pipe_dc_pool, 0, ns * waves * sizeof(DevCounters), c->stream));   // ordered with the launches
   VX_HIP(c, hipStreamSynchronize(c->stream));
   c->pipe_slots = (uint32_t)ns;
@@ -2198,13 +2029,7 @@ int vx_read_display_scaled(VxContext* c, uint8_t* out, uint32_t ow, uint32_t oh,
   int rc = compose_image(c, d);
   if (rc) return rc;
   uint32_t n = ow * oh;
-  if (n > d->display_cap) {
-    if (d->display) (void)hipFree(d->display);
-    d->display = nullptr;
-    d->display_cap = 0;
-    VX_HIP(c, hipMalloc(&d->display, (size_t)n * sizeof(uchar4)));
-    d->display_cap = n;
-  }
+  if ((rc = d->display.ensure(c, n))) return rc;
   hipLaunchKernelGGL(blit_rgba8, dim3((n + 255) / 256), dim3(256), 0, d->stream, d->image, d->display, d->W, d->H,
                      ow, oh, exposure, gamma);
   VX_HIP(c, hipGetLastError());
@@ -2223,7 +2048,7 @@ int vx_probe_tile_costs(VxContext* c, uint32_t* costs, uint32_t n) {
   if (!c || !costs) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_probe_tile_costs(c->members[0], costs, n));   // every member derives the same costs
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_probe_tile_costs: no volume uploaded");
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_probe_tile_costs: no volume uploaded");
   if (!c->has_params || !c->tf || !c->W) VX_FAIL(c, VX_ERR_INVALID, "vx_probe_tile_costs: params, transfer function and size first");
   if (n != c->tm.n_tiles) VX_FAIL(c, VX_ERR_INVALID, "vx_probe_tile_costs: the image has %u tiles, not %u", c->tm.n_tiles, n);
   int rc = prepare_render(c);   // skip mask, environment pointers
@@ -2231,7 +2056,7 @@ int vx_probe_tile_costs(VxContext* c, uint32_t* costs, uint32_t n) {
   uint32_t* d = nullptr;
   VX_HIP(c, hipMalloc(&d, (size_t)n * 4));
   with_layout(eff_layout(c), [&](auto tag) {
-    hipLaunchKernelGGL((probe_tile_costs<decltype(tag)::value>), dim3(n), dim3(64), 0, c->stream, c->params, c->dv, c->tf, c->tf_len,
+    hipLaunchKernelGGL((probe_tile_costs<decltype(tag)::value>), dim3(n), dim3(64), 0, c->stream, c->params, c->vol.dv, c->tf, c->tf_len,
                        c->tm, d);
   });
   hipError_t le = hipGetLastError();
@@ -2257,15 +2082,12 @@ int vx_set_tile_order(VxContext* c, const uint32_t* perm, uint32_t n) {
       both[pos] = t;
       both[n + t] = pos;
     }
-    if (c->tile_perm) (void)hipFree(c->tile_perm);
-    c->tile_perm = nullptr;
     c->tile_perm_n = 0;
-    VX_HIP(c, hipMalloc(&c->tile_perm, both.size() * 4));
+    if (int rc = c->tile_perm.alloc(c, both.size())) return rc;
     VX_HIP(c, hipMemcpy(c->tile_perm, both.data(), both.size() * 4, hipMemcpyHostToDevice));
     c->tile_perm_n = n;
   } else {
-    if (c->tile_perm) (void)hipFree(c->tile_perm);
-    c->tile_perm = nullptr;
+    c->tile_perm.reset();
     c->tile_perm_n = 0;
   }
   update_tilemap(c);
@@ -2543,26 +2365,81 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
   return VX_OK;
 }
 
+// ---- the parameter checks the slice and segment entry points share -------------------------------------------------------
+// Each takes the entry point's name: the refusals read "<entry point>: ..." as they always did.
+
+// the preamble: a volume, the params, and the entry point's own argument
+static int check_ready(VxContext* c, const char* fn, const void* arg, const char* arg_name) {
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "%s: no volume uploaded", fn);
+  if (!c->has_params)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: vx_set_params first (volume_density_scale and volume_inv_maj come from it)", fn);
+  if (!arg) VX_FAIL(c, VX_ERR_INVALID, "%s: %s is NULL", fn, arg_name);
+  return VX_OK;
+}
+static int check_slice_size(VxContext* c, const char* fn, const VxSliceParams* sp) {
+  for (int i = 0; i < 2; ++i)
+    if (sp->size[i] < 1u || sp->size[i] > 16384u) VX_FAIL(c, VX_ERR_INVALID, "%s: size[%d] = %u outside 1 .. 16384", fn, i, sp->size[i]);
+  if (sp->slab_samples < 1u || sp->slab_samples > 4096u)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: slab_samples = %u outside 1 .. 4096", fn, sp->slab_samples);
+  return VX_OK;
+}
+static int check_slice_frame(VxContext* c, const char* fn, const VxSliceParams* sp) {
+  const struct { const char* name; const float* v; } vecs[4] = {{"origin", sp->origin}, {"du", sp->du}, {"dv", sp->dv}, {"dn", sp->dn}};
+  for (const auto& e : vecs)
+    for (int i = 0; i < 3; ++i)
+      if (!std::isfinite(e.v[i])) VX_FAIL(c, VX_ERR_INVALID, "%s: %s[%d] is not finite", fn, e.name, i);
+  return VX_OK;
+}
+static int check_band(VxContext* c, const char* fn, float lo, float hi) {
+  if (!std::isfinite(lo)) VX_FAIL(c, VX_ERR_INVALID, "%s: lo is not finite", fn);
+  if (!std::isfinite(hi)) VX_FAIL(c, VX_ERR_INVALID, "%s: hi is not finite", fn);
+  if (lo > hi) VX_FAIL(c, VX_ERR_INVALID, "%s: lo = %g > hi = %g", fn, (double)lo, (double)hi);
+  return VX_OK;
+}
+static int check_connectivity(VxContext* c, const char* fn, int conn) {
+  if (conn != 6 && conn != 26) VX_FAIL(c, VX_ERR_INVALID, "%s: connectivity = %d is not 6 or 26", fn, conn);
+  return VX_OK;
+}
+static int check_seed(VxContext* c, const char* fn, const uint32_t seed[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (seed[a] >= c->vol.dv.extent[a])
+      VX_FAIL(c, VX_ERR_INVALID, "%s: seed[%d] = %u outside the index extent %u", fn, a, seed[a], c->vol.dv.extent[a]);
+  return VX_OK;
+}
+// the voxel box [box_lo, box_hi] with VX_SEGMENT_BOX_END resolved, inside the index extent
+struct VoxelBox {
+  uint32_t lo[3], hi[3];
+};
+static int check_box(VxContext* c, const char* fn, const uint32_t box_lo[3], const uint32_t box_hi[3], VoxelBox* b) {
+  const uint32_t* E = c->vol.dv.extent;
+  for (int a = 0; a < 3; ++a) {
+    b->lo[a] = box_lo[a];
+    b->hi[a] = box_hi[a] == VX_SEGMENT_BOX_END ? E[a] - 1u : box_hi[a];
+    if (b->lo[a] > b->hi[a] || b->hi[a] >= E[a])
+      VX_FAIL(c, VX_ERR_INVALID, "%s: box axis %d [%u, %u] is empty or outside the index extent %u", fn, a, box_lo[a], box_hi[a], E[a]);
+  }
+  return VX_OK;
+}
+// bytes of the packed mask (1 bit per voxel) a caller hands over or receives
+static int check_mask_bytes(VxContext* c, const char* fn, uint64_t nbytes, size_t* want) {
+  const uint32_t* E = c->vol.dv.extent;
+  *want = (size_t)E[0] * E[1] * E[2] / 8u;
+  if (nbytes != *want)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: nbytes = %llu, the mask of %u x %u x %u voxels is %zu bytes", fn, (unsigned long long)nbytes, E[0],
+            E[1], E[2], *want);
+  return VX_OK;
+}
+
 int vx_slice(VxContext* c, const VxSliceParams* sp, float* values_out, uint8_t* rgba8_out) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_slice(c->members[0], sp, values_out, rgba8_out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: sp is NULL");
-  for (int i = 0; i < 2; ++i)
-    if (sp->size[i] < 1u || sp->size[i] > 16384u)
-      VX_FAIL(c, VX_ERR_INVALID, "vx_slice: size[%d] = %u outside 1 .. 16384", i, sp->size[i]);
-  if (sp->slab_samples < 1u || sp->slab_samples > 4096u)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: slab_samples = %u outside 1 .. 4096", sp->slab_samples);
+  if (int rc = check_ready(c, "vx_slice", sp, "sp")) return rc;
+  if (int rc = check_slice_size(c, "vx_slice", sp)) return rc;
   if (sp->reduce < VX_SLICE_MEAN || sp->reduce > VX_SLICE_MIN) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: unknown reduce %d", sp->reduce);
   if (sp->display < VX_SLICE_NONE || sp->display > VX_SLICE_TF)
     VX_FAIL(c, VX_ERR_INVALID, "vx_slice: unknown display %d", sp->display);
-  const struct { const char* name; const float* v; } vecs[4] = {{"origin", sp->origin}, {"du", sp->du}, {"dv", sp->dv}, {"dn", sp->dn}};
-  for (const auto& e : vecs)
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(e.v[i])) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: %s[%d] is not finite", e.name, i);
+  if (int rc = check_slice_frame(c, "vx_slice", sp)) return rc;
   if (sp->display == VX_SLICE_GREY &&
       !(std::isfinite(sp->window[0]) && std::isfinite(sp->window[1]) && sp->window[1] > sp->window[0]))
     VX_FAIL(c, VX_ERR_INVALID, "vx_slice: window [%g, %g] with VX_SLICE_GREY: needs finite window[0] < window[1]",
@@ -2572,30 +2449,19 @@ int vx_slice(VxContext* c, const VxSliceParams* sp, float* values_out, uint8_t* 
   if (rgba8_out && sp->display == VX_SLICE_NONE)
     VX_FAIL(c, VX_ERR_INVALID, "vx_slice: rgba8_out with display VX_SLICE_NONE (no display output)");
   const size_t px = (size_t)sp->size[0] * sp->size[1];
-  if (px > c->slice_cap) {   // (every earlier slice has completed: vx_slice synchronises)
-    if (c->slice_values) (void)hipFree(c->slice_values);
-    if (c->slice_rgba) (void)hipFree(c->slice_rgba);
-    c->slice_values = nullptr;
-    c->slice_rgba = nullptr;
-    c->slice_cap = 0;
-    VX_HIP(c, hipMalloc(&c->slice_values, px * sizeof(float)));
-    VX_HIP(c, hipMalloc(&c->slice_rgba, px * sizeof(uchar4)));
-    c->slice_cap = px;
-  }
-  for (hipEvent_t& e : c->slice_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
-  VX_HIP(c, hipEventRecord(c->slice_ev[0], c->stream));
+  // (every earlier slice has completed: vx_slice synchronises)
+  if (int rc = c->slice_values.ensure(c, px)) return rc;
+  if (int rc = c->slice_rgba.ensure(c, px)) return rc;
+  if (int rc = c->slice_timer.mark(c, 0)) return rc;
   launch_slice(c, *sp);
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->slice_ev[1], c->stream));
+  if (int rc = c->slice_timer.mark(c, 1)) return rc;
   if (values_out)
     VX_HIP(c, hipMemcpyAsync(values_out, c->slice_values, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   if (rgba8_out) VX_HIP(c, hipMemcpyAsync(rgba8_out, c->slice_rgba, px * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  float ms = 0.0f;
-  VX_HIP(c, hipEventElapsedTime(&ms, c->slice_ev[0], c->slice_ev[1]));
+  if (int rc = c->slice_timer.read(c)) return rc;
   c->slice_samples = (uint64_t)px * sp->slab_samples;
-  c->slice_ms = ms;
   return VX_OK;
 }
 
@@ -2603,7 +2469,7 @@ int vx_slice_stats(VxContext* c, uint64_t* samples, double* last_kernel_ms) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_slice_stats(c->members[0], samples, last_kernel_ms));
   if (samples) *samples = c->slice_samples;
-  if (last_kernel_ms) *last_kernel_ms = c->slice_ms;
+  if (last_kernel_ms) *last_kernel_ms = c->slice_timer.ms[0];
   return VX_OK;
 }
 
@@ -2611,7 +2477,7 @@ int vx_isosurface(VxContext* c, const VxIsoParams* ip, float* rgba_out, float* h
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_isosurface(c->members[0], ip, rgba_out, hit_out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_isosurface: no volume uploaded");
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_isosurface: no volume uploaded");
   if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: vx_set_params first (the camera, clip box and march come from it)");
   if (!ip) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: ip is NULL");
   // the march of any render mode's params: the checks vx_set_params makes for the marching modes
@@ -2637,38 +2503,28 @@ int vx_isosurface(VxContext* c, const VxIsoParams* ip, float* rgba_out, float* h
             q.window[1], q.window[2], q.window[3], W, H);
   const uint32_t ww = q.window[2] - q.window[0], wh = q.window[3] - q.window[1];
   const size_t px = (size_t)ww * wh;
-  if (px > c->iso_cap) {   // (every earlier call has completed: vx_isosurface synchronises)
-    if (c->iso_rgba) (void)hipFree(c->iso_rgba);
-    if (c->iso_hit) (void)hipFree(c->iso_hit);
-    c->iso_rgba = c->iso_hit = nullptr;
-    c->iso_cap = 0;
-    VX_HIP(c, hipMalloc(&c->iso_rgba, px * sizeof(float4)));
-    VX_HIP(c, hipMalloc(&c->iso_hit, px * sizeof(float4)));
-    c->iso_cap = px;
-  }
+  // (every earlier call has completed: vx_isosurface synchronises)
+  if (int rc = c->iso_rgba.ensure(c, px)) return rc;
+  if (int rc = c->iso_hit.ensure(c, px)) return rc;
   if (int rc = check_segment_view(c, "vx_isosurface", true)) return rc;
-  if (c->seg_view != VX_SEGVIEW_OFF) q.skip = 0;   // masked: no range skipping
-  if (q.skip && !c->iso_table.current(c->params)) {
+  if (c->vol.seg_view != VX_SEGVIEW_OFF) q.skip = 0;   // masked: no range skipping
+  if (q.skip && !c->vol.iso_table.current(c->params)) {
     const int rc = rebuild_iso_bounds(c);
     if (rc) return rc;
   }
-  if (!c->iso_count_dev) VX_HIP(c, hipMalloc(&c->iso_count_dev, ISO_NCOUNTS * sizeof(unsigned long long)));
-  for (hipEvent_t& e : c->iso_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
+  if (int rc = c->iso_count_dev.ensure(c, ISO_NCOUNTS)) return rc;
   VX_HIP(c, hipMemsetAsync(c->iso_count_dev, 0, ISO_NCOUNTS * sizeof(unsigned long long), c->stream));
-  VX_HIP(c, hipEventRecord(c->iso_ev[0], c->stream));
+  if (int rc = c->iso_timer.mark(c, 0)) return rc;
   launch_iso(c, q, ww, wh);
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->iso_ev[1], c->stream));
+  if (int rc = c->iso_timer.mark(c, 1)) return rc;
   uint64_t counts[ISO_NCOUNTS];
   VX_HIP(c, hipMemcpyAsync(counts, c->iso_count_dev, sizeof counts, hipMemcpyDeviceToHost, c->stream));
   if (rgba_out) VX_HIP(c, hipMemcpyAsync(rgba_out, c->iso_rgba, px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   if (hit_out) VX_HIP(c, hipMemcpyAsync(hit_out, c->iso_hit, px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  float ms = 0.0f;
-  VX_HIP(c, hipEventElapsedTime(&ms, c->iso_ev[0], c->iso_ev[1]));
+  if (int rc = c->iso_timer.read(c)) return rc;
   memcpy(c->iso_counts, counts, sizeof counts);
-  c->iso_ms = ms;
   return VX_OK;
 }
 
@@ -2681,7 +2537,7 @@ int vx_iso_stats(VxContext* c, uint64_t* rays, uint64_t* hits, uint64_t* samples
   if (samples) *samples = c->iso_counts[ISO_SAMPLES];
   if (refine_samples) *refine_samples = c->iso_counts[ISO_REFINE];
   if (skipped) *skipped = c->iso_counts[ISO_SKIPPED];
-  if (last_kernel_ms) *last_kernel_ms = c->iso_ms;
+  if (last_kernel_ms) *last_kernel_ms = c->iso_timer.ms[0];
   return VX_OK;
 }
 
@@ -2692,51 +2548,50 @@ int vx_iso_stats(VxContext* c, uint64_t* rays, uint64_t* hits, uint64_t* samples
 
 // the device buffers of the brick grid, carved from one allocation (sizes in DESIGN.md / INTEGRATION.md's memory bill)
 static int ensure_segment(VxContext* c) {
-  if (c->seg_alloc) return VX_OK;
-  const uint32_t nb = c->dv.bc[0] * c->dv.bc[1] * c->dv.bc[2];
-  const size_t bytes = (size_t)nb * (64u + 64u + 8u + 4u * 4u) + 16u + sizeof(SegStats);
-  VX_HIP(c, hipMalloc(&c->seg_alloc, bytes));
-  char* p = static_cast<char*>(c->seg_alloc);
-  SegDev& s = c->seg;
-  s.pred = reinterpret_cast<uint64_t*>(p);
-  p += (size_t)nb * 64u;
-  s.seg = reinterpret_cast<uint64_t*>(p);
-  p += (size_t)nb * 64u;
-  // (the masked LDS-window staging reads the dword right behind the mask for the zero chunk behind the last brick -- the first
-  // of `partial`, inside this allocation -- and drops its bits: vx_dvr_lds_march.inc)
-  s.partial = reinterpret_cast<double*>(p);
-  p += (size_t)nb * 8u;
-  s.st = reinterpret_cast<SegStats*>(p);
-  p += sizeof(SegStats);
-  s.any = reinterpret_cast<uint32_t*>(p);
-  p += (size_t)nb * 4u;
-  s.stamp = reinterpret_cast<uint32_t*>(p);
-  p += (size_t)nb * 4u;
-  s.list[0] = reinterpret_cast<uint32_t*>(p);
-  p += (size_t)nb * 4u;
-  s.list[1] = reinterpret_cast<uint32_t*>(p);
-  p += (size_t)nb * 4u;
-  s.cnt = reinterpret_cast<uint32_t*>(p);
-  for (int a = 0; a < 3; ++a) s.bc[a] = c->dv.bc[a];
+  if (c->vol.seg_alloc) return VX_OK;
+  const uint32_t nb = c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2];
+  SegDev& s = c->vol.seg;
+  const int rc = carve(c, c->vol.seg_alloc, [&](Carve& k) {
+    s.pred = k.take<uint64_t>((size_t)nb * 8u);
+    s.seg = k.take<uint64_t>((size_t)nb * 8u);
+    // `partial` stays immediately behind `seg`: the masked LDS-window staging reads the dword right behind the mask for the
+    // zero chunk behind the last brick -- the first of `partial`, inside this allocation -- and drops its bits
+    // (vx_dvr_lds_march.inc)
+    s.partial = k.take<double>(nb);
+    s.st = k.take<SegStats>();
+    s.any = k.take<uint32_t>(nb);
+    s.stamp = k.take<uint32_t>(nb);
+    s.list[0] = k.take<uint32_t>(nb);
+    s.list[1] = k.take<uint32_t>(nb);
+    s.cnt = k.take<uint32_t>(4);
+  });
+  if (rc) return rc;
+  for (int a = 0; a < 3; ++a) s.bc[a] = c->vol.dv.bc[a];
   s.nb = nb;
   return VX_OK;
 }
 
 static void launch_seg_predicate(VxContext* c, const SegPredParams& pp) {
   const VxParams& p = c->params;
-  const uint32_t blocks = std::min<uint32_t>((c->seg.nb + 3u) / 4u, 4096u);
+  const uint32_t blocks = std::min<uint32_t>((c->vol.seg.nb + 3u) / 4u, 4096u);
   with_layout(slice_layout(c), [&](auto lay) {
     constexpr int LAY = decltype(lay)::value;
-    hipLaunchKernelGGL((seg_predicate<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
-                       pp, c->seg);
+    hipLaunchKernelGGL((seg_predicate<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
+                       pp, c->vol.seg);
   });
+}
+static SegPredParams seg_pred_params(float lo, float hi, const VoxelBox& b) {
+  return SegPredParams{lo, hi, {b.lo[0], b.lo[1], b.lo[2]}, {b.hi[0], b.hi[1], b.hi[2]}};
+}
+// the brick, the z slice and the bit of a voxel
+static SegSeed seg_seed_of(const SegDev& s, const uint32_t v[3]) {
+  return SegSeed{((v[2] >> 3) * s.bc[1] + (v[1] >> 3)) * s.bc[0] + (v[0] >> 3), v[2] & 7u, 1ull << (((v[1] & 7u) << 3) | (v[0] & 7u))};
 }
 static void launch_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint32_t round) {
   const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 1024u);
-  if (conn == 26)
-    hipLaunchKernelGGL((seg_flood<26>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
-  else
-    hipLaunchKernelGGL((seg_flood<6>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
+  with_conn(conn, [&](auto k) {
+    hipLaunchKernelGGL((seg_flood<decltype(k)::value>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
+  });
 }
 // the rounds of a flood on the view s (vx_segment: the segment; vx_segment_edit: the background of fill holes), from a round-0
 // worklist that is already on the device: queued in batches of 1, 2, 4, ... SEG_CHECK_MAX, the next worklist's length read back
@@ -2765,13 +2620,13 @@ static int run_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed&
 }
 static void launch_seg_stats(VxContext* c) {
   const VxParams& p = c->params;
-  const uint32_t blocks = std::min<uint32_t>((c->seg.nb + 3u) / 4u, 4096u);
+  const uint32_t blocks = std::min<uint32_t>((c->vol.seg.nb + 3u) / 4u, 4096u);
   with_layout(slice_layout(c), [&](auto lay) {
     constexpr int LAY = decltype(lay)::value;
-    hipLaunchKernelGGL((seg_stats<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
-                       c->seg);
+    hipLaunchKernelGGL((seg_stats<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
+                       c->vol.seg);
   });
-  hipLaunchKernelGGL(seg_sum, dim3(1), dim3(1024), 0, c->stream, c->seg);
+  hipLaunchKernelGGL(seg_sum, dim3(1), dim3(1024), 0, c->stream, c->vol.seg);
 }
 static float seg_key_float(uint32_t k) {
   const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
@@ -2779,68 +2634,8 @@ static float seg_key_float(uint32_t k) {
   memcpy(&f, &u, sizeof f);
   return f;
 }
-
-int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment(c->members[0], sp, out));
-  VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: sp is NULL");
-  const uint32_t* E = c->dv.extent;
-  for (int a = 0; a < 3; ++a)
-    if (sp->seed[a] >= E[a])
-      VX_FAIL(c, VX_ERR_INVALID, "vx_segment: seed[%d] = %u outside the index extent %u", a, sp->seed[a], E[a]);
-  if (!std::isfinite(sp->lo)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: lo is not finite");
-  if (!std::isfinite(sp->hi)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: hi is not finite");
-  if (sp->lo > sp->hi) VX_FAIL(c, VX_ERR_INVALID, "vx_segment: lo = %g > hi = %g", (double)sp->lo, (double)sp->hi);
-  if (sp->connectivity != 6 && sp->connectivity != 26)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment: connectivity = %d is not 6 or 26", sp->connectivity);
-  SegPredParams pp{sp->lo, sp->hi, {sp->box_lo[0], sp->box_lo[1], sp->box_lo[2]}, {sp->box_hi[0], sp->box_hi[1], sp->box_hi[2]}};
-  for (int a = 0; a < 3; ++a) {
-    if (pp.box_hi[a] == VX_SEGMENT_BOX_END) pp.box_hi[a] = E[a] - 1u;
-    if (pp.box_lo[a] > pp.box_hi[a] || pp.box_hi[a] >= E[a])
-      VX_FAIL(c, VX_ERR_INVALID, "vx_segment: box axis %d [%u, %u] is empty or outside the index extent %u", a, sp->box_lo[a],
-              sp->box_hi[a], E[a]);
-  }
-  c->seg_valid = false;
-  c->seg_pred_valid = false;
-  c->isl_valid = false;
-  {
-    const int rc = ensure_segment(c);
-    if (rc) return rc;
-  }
-  for (hipEvent_t& e : c->seg_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
-  const SegDev& s = c->seg;
-  const uint32_t bc0 = c->dv.bc[0], bc1 = c->dv.bc[1];
-  const uint32_t sx = sp->seed[0], sy = sp->seed[1], sz = sp->seed[2];
-  const SegSeed seed{((sz >> 3) * bc1 + (sy >> 3)) * bc0 + (sx >> 3), sz & 7u, 1ull << (((sy & 7u) << 3) | (sx & 7u))};
-  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
-  const uint64_t cap = sp->max_rounds ? (uint64_t)sp->max_rounds : std::min<uint64_t>(nvox, 0xfffffffeull);
-  VX_HIP(c, hipMemsetAsync(s.seg, 0, (size_t)s.nb * 64u, c->stream));
-  VX_HIP(c, hipMemsetAsync(s.stamp, 0, (size_t)s.nb * 4u, c->stream));
-  VX_HIP(c, hipEventRecord(c->seg_ev[0], c->stream));
-  launch_seg_predicate(c, pp);
-  VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->seg_ev[1], c->stream));
-  hipLaunchKernelGGL(seg_seed, dim3(1), dim3(64), 0, c->stream, s, seed);
-  VX_HIP(c, hipGetLastError());
-  bool converged = false;
-  if (int rc = run_seg_flood(c, s, sp->connectivity, seed, cap, &converged, nullptr)) return rc;
-  VX_HIP(c, hipEventRecord(c->seg_ev[2], c->stream));
-  launch_seg_stats(c);
-  VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->seg_ev[3], c->stream));
-  SegStats st;
-  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.0f;
-    VX_HIP(c, hipEventElapsedTime(&ms, c->seg_ev[i], c->seg_ev[i + 1]));
-    c->seg_ms[i] = ms;
-  }
+// the count, bounding box and density statistics of a result; rounds, brick_visits and converged are the caller's
+static VxSegmentResult seg_result(const SegStats& st) {
   VxSegmentResult r{};
   r.count = st.count;
   if (st.count) {
@@ -2852,12 +2647,67 @@ int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
     r.d_max = seg_key_float(st.dmax);
     r.d_sum = st.sum;
   }
+  return r;
+}
+// The statistics of the mask in SegDev::seg, behind whatever wrote it on the stream: sed_reset, seg_stats / seg_sum (three
+// launches), event `done` of the caller's timer behind them, the read-back.  Ends synchronised.
+extern "C++" {   // (a template, inside the extern "C" block of the entry points)
+template <int N>
+static int seg_mask_stats(VxContext* c, StageTimer<N>& timer, int done, SegStats* st) {
+  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, c->vol.seg, 0u);
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  if (int rc = timer.mark(c, done)) return rc;
+  VX_HIP(c, hipMemcpyAsync(st, c->vol.seg.st, sizeof *st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+}
+
+int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment(c->members[0], sp, out));
+  VX_DEV(c);
+  VoxelBox box;
+  if (int rc = check_ready(c, "vx_segment", sp, "sp")) return rc;
+  if (int rc = check_seed(c, "vx_segment", sp->seed)) return rc;
+  if (int rc = check_band(c, "vx_segment", sp->lo, sp->hi)) return rc;
+  if (int rc = check_connectivity(c, "vx_segment", sp->connectivity)) return rc;
+  if (int rc = check_box(c, "vx_segment", sp->box_lo, sp->box_hi, &box)) return rc;
+  c->vol.seg_valid = false;
+  c->vol.seg_pred_valid = false;
+  c->vol.isl_valid = false;
+  if (int rc = ensure_segment(c)) return rc;
+  const SegDev& s = c->vol.seg;
+  const uint32_t* E = c->vol.dv.extent;
+  const SegSeed seed = seg_seed_of(s, sp->seed);
+  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
+  const uint64_t cap = sp->max_rounds ? (uint64_t)sp->max_rounds : std::min<uint64_t>(nvox, 0xfffffffeull);
+  VX_HIP(c, hipMemsetAsync(s.seg, 0, (size_t)s.nb * 64u, c->stream));
+  VX_HIP(c, hipMemsetAsync(s.stamp, 0, (size_t)s.nb * 4u, c->stream));
+  if (int rc = c->seg_timer.mark(c, 0)) return rc;
+  launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
+  VX_HIP(c, hipGetLastError());
+  if (int rc = c->seg_timer.mark(c, 1)) return rc;
+  hipLaunchKernelGGL(seg_seed, dim3(1), dim3(64), 0, c->stream, s, seed);
+  VX_HIP(c, hipGetLastError());
+  bool converged = false;
+  if (int rc = run_seg_flood(c, s, sp->connectivity, seed, cap, &converged, nullptr)) return rc;
+  if (int rc = c->seg_timer.mark(c, 2)) return rc;
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  if (int rc = c->seg_timer.mark(c, 3)) return rc;
+  SegStats st;
+  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  if (int rc = c->seg_timer.read(c)) return rc;
+  VxSegmentResult r = seg_result(st);
   r.rounds = st.rounds;
   r.converged = converged ? 1u : 0u;
   r.brick_visits = st.visits;
   c->seg_res = r;
-  c->seg_valid = true;
-  c->seg_pred_valid = true;
+  c->vol.seg_valid = true;
+  c->vol.seg_pred_valid = true;
   if (out) *out = r;
   return VX_OK;
 }
@@ -2866,24 +2716,16 @@ int vx_segment_read_mask(VxContext* c, uint8_t* bits, uint64_t nbytes) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_segment_read_mask(c->members[0], bits, nbytes));
   VX_DEV(c);
-  if (!c->seg_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: no current segment (vx_segment first; an upload drops it)");
+  if (!c->vol.seg_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: no current segment (vx_segment first; an upload drops it)");
   if (!bits) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: bits is NULL");
-  const uint32_t* E = c->dv.extent;
-  const size_t want = (size_t)E[0] * E[1] * E[2] / 8u;
-  if (nbytes != want)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: nbytes = %llu, the mask of %u x %u x %u voxels is %zu bytes",
-            (unsigned long long)nbytes, E[0], E[1], E[2], want);
-  if (want > c->seg_bytes_cap) {
-    if (c->seg_bytes) (void)hipFree(c->seg_bytes);
-    c->seg_bytes = nullptr;
-    c->seg_bytes_cap = 0;
-    VX_HIP(c, hipMalloc(&c->seg_bytes, want));
-    c->seg_bytes_cap = want;
-  }
+  const uint32_t* E = c->vol.dv.extent;
+  size_t want = 0;
+  if (int rc = check_mask_bytes(c, "vx_segment_read_mask", nbytes, &want)) return rc;
+  if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
   const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 8192u);
-  hipLaunchKernelGGL(seg_pack, dim3(blocks), dim3(256), 0, c->stream, c->seg, E[0], E[1], want, c->seg_bytes);
+  hipLaunchKernelGGL(seg_pack, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg, E[0], E[1], want, c->vol.seg_bytes);
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipMemcpyAsync(bits, c->seg_bytes, want, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipMemcpyAsync(bits, c->vol.seg_bytes, want, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   return VX_OK;
 }
@@ -2892,31 +2734,18 @@ int vx_slice_segment_mask(VxContext* c, const VxSliceParams* sp, uint8_t* out) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_slice_segment_mask(c->members[0], sp, out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice_segment_mask: no volume uploaded");
-  if (!c->seg_valid)
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice_segment_mask: no volume uploaded");
+  if (!c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: no current segment (vx_segment first; an upload drops it)");
   if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: sp is NULL");
   if (!out) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: out is NULL");
-  for (int i = 0; i < 2; ++i)
-    if (sp->size[i] < 1u || sp->size[i] > 16384u)
-      VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: size[%d] = %u outside 1 .. 16384", i, sp->size[i]);
-  if (sp->slab_samples < 1u || sp->slab_samples > 4096u)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: slab_samples = %u outside 1 .. 4096", sp->slab_samples);
-  const struct { const char* name; const float* v; } vecs[4] = {{"origin", sp->origin}, {"du", sp->du}, {"dv", sp->dv}, {"dn", sp->dn}};
-  for (const auto& e : vecs)
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(e.v[i])) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: %s[%d] is not finite", e.name, i);
+  if (int rc = check_slice_size(c, "vx_slice_segment_mask", sp)) return rc;
+  if (int rc = check_slice_frame(c, "vx_slice_segment_mask", sp)) return rc;
   const size_t px = (size_t)sp->size[0] * sp->size[1];
-  if (px > c->seg_ov_cap) {   // (every earlier call has completed: each one synchronises)
-    if (c->seg_ov) (void)hipFree(c->seg_ov);
-    c->seg_ov = nullptr;
-    c->seg_ov_cap = 0;
-    VX_HIP(c, hipMalloc(&c->seg_ov, px));
-    c->seg_ov_cap = px;
-  }
+  if (int rc = c->seg_ov.ensure(c, px)) return rc;   // (every earlier call has completed: each one synchronises)
   const dim3 grid((sp->size[0] + 15u) / 16u, (sp->size[1] + 15u) / 16u);
-  hipLaunchKernelGGL(seg_slice_mask, grid, dim3(256), 0, c->stream, *sp, c->seg, c->dv.extent[0], c->dv.extent[1], c->dv.extent[2],
-                     c->seg_ov);
+  hipLaunchKernelGGL(seg_slice_mask, grid, dim3(256), 0, c->stream, *sp, c->vol.seg, c->vol.dv.extent[0], c->vol.dv.extent[1],
+                     c->vol.dv.extent[2], c->seg_ov);
   VX_HIP(c, hipGetLastError());
   VX_HIP(c, hipMemcpyAsync(out, c->seg_ov, px, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -2928,16 +2757,16 @@ int vx_set_segment_view(VxContext* c, int view) {
   if (is_group(c)) return refuse_group(c, "vx_set_segment_view", "the segment lives on member 0 only");
   if (view < VX_SEGVIEW_OFF || view > VX_SEGVIEW_HIDE)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: view = %d is not VX_SEGVIEW_OFF, _ONLY or _HIDE", view);
-  if (view != VX_SEGVIEW_OFF && !c->seg_valid)
+  if (view != VX_SEGVIEW_OFF && !c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: %s without a current segment (vx_segment first; an upload drops it)",
             view == VX_SEGVIEW_ONLY ? "only" : "hide");
-  c->seg_view = view;
+  c->vol.seg_view = view;
   return VX_OK;
 }
 
 int vx_get_segment_view(VxContext* c, int* view) {
   if (!c || !view) return VX_ERR_INVALID;
-  *view = c->seg_view;
+  *view = c->vol.seg_view;
   return VX_OK;
 }
 
@@ -2946,58 +2775,36 @@ int vx_segment_stats(VxContext* c, uint32_t* rounds, uint64_t* brick_visits, dou
   if (is_group(c)) return on_member0(c, vx_segment_stats(c->members[0], rounds, brick_visits, kernel_ms));
   if (rounds) *rounds = c->seg_res.rounds;
   if (brick_visits) *brick_visits = c->seg_res.brick_visits;
-  if (kernel_ms)
-    for (int i = 0; i < 3; ++i) kernel_ms[i] = c->seg_ms[i];
+  if (kernel_ms) std::copy_n(c->seg_timer.ms, 3, kernel_ms);
   return VX_OK;
 }
 
 // ---- segment edits (vx_segment_edit, vx_segment_write_mask; kernels in vx_segedit.hpp) ---------------------------------------
 // the scratch of the edits: two masks of nb * 8 words (1 bit per voxel each) and the fill's nb "any background" flags
 static int ensure_segedit(VxContext* c) {
-  for (hipEvent_t& e : c->sed_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
-  if (c->sed_alloc) return VX_OK;
-  const size_t nb = c->seg.nb;
-  VX_HIP(c, hipMalloc(&c->sed_alloc, nb * (64u + 64u + 4u)));
-  char* p = static_cast<char*>(c->sed_alloc);
-  c->sed_mask[0] = reinterpret_cast<uint64_t*>(p);
-  c->sed_mask[1] = reinterpret_cast<uint64_t*>(p + nb * 64u);
-  c->sed_any = reinterpret_cast<uint32_t*>(p + nb * 128u);
-  return VX_OK;
+  if (c->vol.sed_alloc) return VX_OK;
+  const size_t nb = c->vol.seg.nb;
+  return carve(c, c->vol.sed_alloc, [&](Carve& k) {
+    c->vol.sed_mask[0] = k.take<uint64_t>(nb * 8u);
+    c->vol.sed_mask[1] = k.take<uint64_t>(nb * 8u);
+    c->vol.sed_any = k.take<uint32_t>(nb);
+  });
 }
 
-// the statistics of the mask in SegDev::seg, behind the edit on the stream: events, seg_stats / seg_sum, the read-back.  The
-// flood's rounds and visits are kept when `fill`.  Ends synchronised.
-static int finish_segedit(VxContext* c, bool fill, VxSegmentResult* out) {
-  const SegDev& s = c->seg;
-  VX_HIP(c, hipEventRecord(c->sed_ev[1], c->stream));
-  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 0u);
-  launch_seg_stats(c);
-  VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->sed_ev[2], c->stream));
+// The tail of every call that rewrites the mask outright (behind event 0 of sed_timer and the call's launches): the statistics
+// of the new mask, the two times vx_segment_edit_stats reports, the result.  The flood's rounds and visits are kept when `fill`;
+// `pred`: SegDev::pred now holds this mask's predicate.  Ends synchronised.
+static int finish_mask_edit(VxContext* c, bool fill, bool pred, VxSegmentResult* out) {
   SegStats st;
-  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 2; ++i) {
-    float ms = 0.0f;
-    VX_HIP(c, hipEventElapsedTime(&ms, c->sed_ev[i], c->sed_ev[i + 1]));
-    c->sed_ms[i] = ms;
-  }
-  VxSegmentResult r{};
-  r.count = st.count;
-  if (st.count) {
-    for (int a = 0; a < 3; ++a) {
-      r.bbox_lo[a] = st.lo[a];
-      r.bbox_hi[a] = st.hi[a];
-    }
-    r.d_min = seg_key_float(st.dmin);
-    r.d_max = seg_key_float(st.dmax);
-    r.d_sum = st.sum;
-  }
+  if (int rc = c->sed_timer.mark(c, 1)) return rc;
+  if (int rc = seg_mask_stats(c, c->sed_timer, 2, &st)) return rc;
+  if (int rc = c->sed_timer.read(c)) return rc;
+  VxSegmentResult r = seg_result(st);
   r.rounds = fill ? st.rounds : 0u;
   r.converged = 1u;
   r.brick_visits = fill ? st.visits : 0u;
-  c->seg_valid = true;
+  c->vol.seg_valid = true;
+  if (pred) c->vol.seg_pred_valid = true;
   if (out) *out = r;
   return VX_OK;
 }
@@ -3006,23 +2813,18 @@ static int finish_segedit(VxContext* c, bool fill, VxSegmentResult* out) {
 // scratch masks, and the last step of the edit (`last`) writes SegDev::seg itself unless it would read it, so the masked render
 // kernels, seg_pack and the overlay keep the one pointer they read at launch time.
 static void launch_sed_steps(VxContext* c, int conn, bool invert, bool band, uint32_t steps, bool last, uint64_t** cur) {
-  const SegDev& s = c->seg;
+  const SegDev& s = c->vol.seg;
   const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
   const uint64_t inv = invert ? ~0ull : 0ull;
   for (uint32_t i = 0; i < steps; ++i) {
     uint64_t* src = *cur;
-    uint64_t* dst = (last && i + 1u == steps && src != s.seg) ? s.seg : (src == c->sed_mask[0] ? c->sed_mask[1] : c->sed_mask[0]);
-    auto go = [&](auto conn_c, auto band_c) {
-      hipLaunchKernelGGL((sed_step<decltype(conn_c)::value, decltype(band_c)::value>), dim3(blocks), dim3(256), 0, c->stream, src,
-                         dst, s.pred, inv, s.bc[0], s.bc[1], s.bc[2]);
-    };
-    if (conn == 26) {
-      if (band) go(std::integral_constant<int, 26>{}, std::true_type{});
-      else go(std::integral_constant<int, 26>{}, std::false_type{});
-    } else {
-      if (band) go(std::integral_constant<int, 6>{}, std::true_type{});
-      else go(std::integral_constant<int, 6>{}, std::false_type{});
-    }
+    uint64_t* dst = (last && i + 1u == steps && src != s.seg) ? s.seg : (src == c->vol.sed_mask[0] ? c->vol.sed_mask[1] : c->vol.sed_mask[0]);
+    with_conn(conn, [&](auto conn_c) {
+      with_bool(band, [&](auto band_c) {
+        hipLaunchKernelGGL((sed_step<decltype(conn_c)::value, decltype(band_c)::value>), dim3(blocks), dim3(256), 0, c->stream, src,
+                           dst, s.pred, inv, s.bc[0], s.bc[1], s.bc[2]);
+      });
+    });
     *cur = dst;
     ++c->sed_launches;
   }
@@ -3032,31 +2834,27 @@ int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_segment_edit(c->members[0], ep, out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_edit: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!ep) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: params is NULL");
+  if (int rc = check_ready(c, "vx_segment_edit", ep, "params")) return rc;
   if (ep->op < VX_SEGEDIT_DILATE || ep->op > VX_SEGEDIT_FILL_HOLES)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: op = %d is not a VxSegmentEditOp (0 .. 4)", ep->op);
-  if (ep->connectivity != 6 && ep->connectivity != 26)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: connectivity = %d is not 6 or 26", ep->connectivity);
+  if (int rc = check_connectivity(c, "vx_segment_edit", ep->connectivity)) return rc;
   const bool fill = ep->op == VX_SEGEDIT_FILL_HOLES;
   if (fill ? ep->steps > 1u : (ep->steps < 1u || ep->steps > VX_SEGEDIT_MAX_STEPS))
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: steps = %u outside %s", ep->steps, fill ? "0 .. 1 (fill holes)" : "1 .. 1024");
   if (ep->band != 0 && ep->band != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = %d is not 0 or 1", ep->band);
   if (ep->band && ep->op != VX_SEGEDIT_DILATE)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 is for VX_SEGEDIT_DILATE only (op = %d)", ep->op);
-  if (!c->seg_valid)
+  if (!c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: no current segment (vx_segment or vx_segment_write_mask first; an upload drops it)");
-  if (ep->band && !c->seg_pred_valid)
+  if (ep->band && !c->vol.seg_pred_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
   if (int rc = ensure_segedit(c)) return rc;
-  c->isl_valid = false;
-  const SegDev& s = c->seg;
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
   const int conn = ep->connectivity;
   const uint32_t n = ep->steps;
   c->sed_launches = 0;
-  VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
   uint64_t* cur = s.seg;
   switch (ep->op) {
     case VX_SEGEDIT_DILATE: launch_sed_steps(c, conn, false, ep->band != 0, n, true, &cur); break;
@@ -3073,16 +2871,16 @@ int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult
       // the background flood on a second view: predicate ~M and the reached set in the scratch masks, the bookkeeping shared
       // with vx_segment (its predicate WORDS stay: band dilation after a fill is legal)
       SegDev f = s;
-      f.pred = c->sed_mask[0];
-      f.seg = c->sed_mask[1];
-      f.any = c->sed_any;
+      f.pred = c->vol.sed_mask[0];
+      f.seg = c->vol.sed_mask[1];
+      f.any = c->vol.sed_any;
       const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
       hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 1u);
       hipLaunchKernelGGL(sed_fill_seed, dim3(blocks), dim3(256), 0, c->stream, s.seg, f);
       VX_HIP(c, hipGetLastError());
       bool converged = false;
       uint64_t launched = 0;
-      const uint64_t nvox = (uint64_t)c->dv.extent[0] * c->dv.extent[1] * c->dv.extent[2];
+      const uint64_t nvox = (uint64_t)c->vol.dv.extent[0] * c->vol.dv.extent[1] * c->vol.dv.extent[2];
       if (int rc = run_seg_flood(c, f, conn, SegSeed{0u, 0u, 0ull}, std::min<uint64_t>(nvox, 0xfffffffeull), &converged, &launched))
         return rc;
       const size_t words = (size_t)s.nb * 8u;
@@ -3095,121 +2893,87 @@ int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult
   VX_HIP(c, hipGetLastError());
   // a single step read SegDev::seg and so wrote a scratch mask: copy it home on the stream
   if (cur != s.seg) VX_HIP(c, hipMemcpyAsync(s.seg, cur, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
-  return finish_segedit(c, fill, out);
+  return finish_mask_edit(c, fill, false, out);
 }
 
 int vx_segment_write_mask(VxContext* c, const uint8_t* bits, uint64_t nbytes, VxSegmentResult* out) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_segment_write_mask(c->members[0], bits, nbytes, out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_write_mask: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_write_mask: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!bits) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_write_mask: bits is NULL");
-  const uint32_t* E = c->dv.extent;
-  const size_t want = (size_t)E[0] * E[1] * E[2] / 8u;
-  if (nbytes != want)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_write_mask: nbytes = %llu, the mask of %u x %u x %u voxels is %zu bytes",
-            (unsigned long long)nbytes, E[0], E[1], E[2], want);
+  if (int rc = check_ready(c, "vx_segment_write_mask", bits, "bits")) return rc;
+  size_t want = 0;
+  if (int rc = check_mask_bytes(c, "vx_segment_write_mask", nbytes, &want)) return rc;
   if (int rc = ensure_segment(c)) return rc;
   if (int rc = ensure_segedit(c)) return rc;
-  if (want > c->seg_bytes_cap) {   // (every earlier call has completed: each one synchronises)
-    if (c->seg_bytes) (void)hipFree(c->seg_bytes);
-    c->seg_bytes = nullptr;
-    c->seg_bytes_cap = 0;
-    VX_HIP(c, hipMalloc(&c->seg_bytes, want));
-    c->seg_bytes_cap = want;
-  }
-  c->isl_valid = false;
-  const SegDev& s = c->seg;
-  VX_HIP(c, hipMemcpyAsync(c->seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
-  VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
+  if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
+  VX_HIP(c, hipMemcpyAsync(c->vol.seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
   const size_t words = (size_t)s.nb * 8u;
-  hipLaunchKernelGGL(sed_unpack, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream, s, E[1],
-                     c->seg_bytes);
+  hipLaunchKernelGGL(sed_unpack, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream, s,
+                     c->vol.dv.extent[1], c->vol.seg_bytes);
   VX_HIP(c, hipGetLastError());
   c->sed_launches = 1;
-  return finish_segedit(c, false, out);
+  return finish_mask_edit(c, false, false, out);
 }
 
 int vx_segment_edit_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_segment_edit_stats(c->members[0], launches, kernel_ms));
   if (launches) *launches = c->sed_launches;
-  if (kernel_ms)
-    for (int i = 0; i < 2; ++i) kernel_ms[i] = c->sed_ms[i];
+  if (kernel_ms) std::copy_n(c->sed_timer.ms, 2, kernel_ms);
   return VX_OK;
 }
 
 // ---- islands (vx_segment_threshold, vx_segment_islands, vx_islands_read*; kernels in vx_islands.hpp) ---------------------------
+// (the mask is rewritten outright: timed and counted like vx_segment_write_mask, reported by vx_segment_edit_stats)
 int vx_segment_threshold(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_segment_threshold(c->members[0], sp, out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_threshold: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: sp is NULL");
-  const uint32_t* E = c->dv.extent;
-  if (!std::isfinite(sp->lo)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: lo is not finite");
-  if (!std::isfinite(sp->hi)) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: hi is not finite");
-  if (sp->lo > sp->hi) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: lo = %g > hi = %g", (double)sp->lo, (double)sp->hi);
-  SegPredParams pp{sp->lo, sp->hi, {sp->box_lo[0], sp->box_lo[1], sp->box_lo[2]}, {sp->box_hi[0], sp->box_hi[1], sp->box_hi[2]}};
-  for (int a = 0; a < 3; ++a) {
-    if (pp.box_hi[a] == VX_SEGMENT_BOX_END) pp.box_hi[a] = E[a] - 1u;
-    if (pp.box_lo[a] > pp.box_hi[a] || pp.box_hi[a] >= E[a])
-      VX_FAIL(c, VX_ERR_INVALID, "vx_segment_threshold: box axis %d [%u, %u] is empty or outside the index extent %u", a,
-              sp->box_lo[a], sp->box_hi[a], E[a]);
-  }
+  VoxelBox box;
+  if (int rc = check_ready(c, "vx_segment_threshold", sp, "sp")) return rc;
+  if (int rc = check_band(c, "vx_segment_threshold", sp->lo, sp->hi)) return rc;
+  if (int rc = check_box(c, "vx_segment_threshold", sp->box_lo, sp->box_hi, &box)) return rc;
   if (int rc = ensure_segment(c)) return rc;
-  if (int rc = ensure_segedit(c)) return rc;   // (its events time the call, as for vx_segment_write_mask)
-  c->seg_valid = false;
-  c->seg_pred_valid = false;
-  c->isl_valid = false;
-  const SegDev& s = c->seg;
-  VX_HIP(c, hipEventRecord(c->sed_ev[0], c->stream));
-  launch_seg_predicate(c, pp);
+  c->vol.seg_valid = false;
+  c->vol.seg_pred_valid = false;
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
+  launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
   VX_HIP(c, hipGetLastError());
   // the mask = the predicate words.  SegDev::seg keeps its address: the masked render kernels read it at launch time
   VX_HIP(c, hipMemcpyAsync(s.seg, s.pred, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
   c->sed_launches = 1;
-  const int rc = finish_segedit(c, false, out);
-  if (rc == VX_OK) c->seg_pred_valid = true;
-  return rc;
+  return finish_mask_edit(c, false, true, out);
 }
 
 static int ensure_islands(VxContext* c) {
-  for (hipEvent_t& e : c->isl_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
-  if (c->isl_alloc) return VX_OK;
-  const size_t nb = c->seg.nb;
-  VX_HIP(c, hipMalloc(&c->isl_alloc, nb * (512u * 4u + 4u + 4u) + sizeof(IslHdr)));
-  char* p = static_cast<char*>(c->isl_alloc);
-  IslDev& d = c->isl;
-  d.lab = reinterpret_cast<uint32_t*>(p);
-  p += nb * 2048u;
-  d.nroots = reinterpret_cast<uint32_t*>(p);
-  p += nb * 4u;
-  d.off = reinterpret_cast<uint32_t*>(p);
-  p += nb * 4u;
-  d.hdr = reinterpret_cast<IslHdr*>(p);
-  return VX_OK;
+  if (c->vol.isl_alloc) return VX_OK;
+  const size_t nb = c->vol.seg.nb;
+  IslDev& d = c->vol.isl;
+  return carve(c, c->vol.isl_alloc, [&](Carve& k) {
+    d.lab = k.take<uint32_t>(nb * 512u);
+    d.nroots = k.take<uint32_t>(nb);
+    d.off = k.take<uint32_t>(nb);
+    d.hdr = k.take<IslHdr>();
+  });
 }
 
-// room for n rows and their labels (every earlier call has completed: each one synchronises)
+// room for n rows and their labels, 1024 at least (every earlier call has completed: each one synchronises)
 static int ensure_island_rows(VxContext* c, uint32_t n) {
-  IslDev& d = c->isl;
+  IslDev& d = c->vol.isl;
   n = std::max(n, 1u);
   if (n <= d.cap) return VX_OK;
-  if (c->isl_rows_alloc) (void)hipFree(c->isl_rows_alloc);
-  c->isl_rows_alloc = nullptr;
-  d.rows = nullptr;
-  d.newlab = nullptr;
   d.cap = 0;
   const size_t cap = std::max<size_t>(n, 1024u);
-  VX_HIP(c, hipMalloc(&c->isl_rows_alloc, cap * (sizeof(IslRow) + 4u)));
-  d.rows = static_cast<IslRow*>(c->isl_rows_alloc);
-  d.newlab = reinterpret_cast<uint32_t*>(static_cast<char*>(c->isl_rows_alloc) + cap * sizeof(IslRow));
+  const int rc = carve(c, c->vol.isl_rows_alloc, [&](Carve& k) {
+    d.rows = k.take<IslRow>(cap);
+    d.newlab = k.take<uint32_t>(cap);
+  });
+  if (rc) return rc;
   d.cap = (uint32_t)cap;
   return VX_OK;
 }
@@ -3218,24 +2982,18 @@ int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult*
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_segment_islands(c->members[0], ip, out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_segment_islands: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!ip) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: params is NULL");
+  if (int rc = check_ready(c, "vx_segment_islands", ip, "params")) return rc;
   if (ip->op < VX_ISLANDS_LABEL || ip->op > VX_ISLANDS_KEEP_AT)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: op = %d is not a VxIslandsOp (0 .. 3)", ip->op);
-  if (ip->connectivity != 6 && ip->connectivity != 26)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: connectivity = %d is not 6 or 26", ip->connectivity);
+  if (int rc = check_connectivity(c, "vx_segment_islands", ip->connectivity)) return rc;
   if (ip->op == VX_ISLANDS_KEEP_LARGEST && ip->keep == 0)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: keep = 0 (KEEP_LARGEST keeps at least one island)");
   if (ip->op == VX_ISLANDS_REMOVE_SMALL && ip->min_voxels == 0)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: min_voxels = 0 (REMOVE_SMALL needs a size of at least 1)");
-  const uint32_t* E = c->dv.extent;
+  const uint32_t* E = c->vol.dv.extent;
   if (ip->op == VX_ISLANDS_KEEP_AT)
-    for (int a = 0; a < 3; ++a)
-      if (ip->seed[a] >= E[a])
-        VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: seed[%d] = %u outside the index extent %u", a, ip->seed[a], E[a]);
-  if (!c->seg_valid)
+    if (int rc = check_seed(c, "vx_segment_islands", ip->seed)) return rc;
+  if (!c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: no current segment (vx_segment, vx_segment_threshold or vx_segment_write_mask "
                                "first; an upload drops it)");
   const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
@@ -3244,44 +3002,38 @@ int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult*
             (unsigned long long)nvox);
   if (int rc = ensure_islands(c)) return rc;
   if (int rc = ensure_island_rows(c, 1u)) return rc;
-  c->isl_valid = false;
-  const SegDev& s = c->seg;
-  const bool c26 = ip->connectivity == 26;
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
   const bool modify = ip->op != VX_ISLANDS_LABEL;
   const dim3 grid(std::min<uint32_t>((s.nb + 3u) / 4u, 16384u)), block(256);
   uint32_t launches = 0;
-  VX_HIP(c, hipMemsetAsync(c->isl.hdr, 0, sizeof(IslHdr), c->stream));
-  VX_HIP(c, hipEventRecord(c->isl_ev[0], c->stream));
-  if (c26) hipLaunchKernelGGL(isl_local<26>, grid, block, 0, c->stream, s, c->isl);
-  else hipLaunchKernelGGL(isl_local<6>, grid, block, 0, c->stream, s, c->isl);
-  VX_HIP(c, hipEventRecord(c->isl_ev[1], c->stream));
-  if (c26) hipLaunchKernelGGL(isl_merge<26>, grid, block, 0, c->stream, s, c->isl);
-  else hipLaunchKernelGGL(isl_merge<6>, grid, block, 0, c->stream, s, c->isl);
-  VX_HIP(c, hipEventRecord(c->isl_ev[2], c->stream));
-  hipLaunchKernelGGL(isl_flatten, grid, block, 0, c->stream, s, c->isl);
-  hipLaunchKernelGGL(isl_scan, dim3(1), dim3(1024), 0, c->stream, s, c->isl);
+  VX_HIP(c, hipMemsetAsync(c->vol.isl.hdr, 0, sizeof(IslHdr), c->stream));
+  StageTimer<7>& timer = c->isl_timer;
+  if (int rc = timer.mark(c, 0)) return rc;
+  with_conn(ip->connectivity, [&](auto k) { hipLaunchKernelGGL(isl_local<decltype(k)::value>, grid, block, 0, c->stream, s, c->vol.isl); });
+  if (int rc = timer.mark(c, 1)) return rc;
+  with_conn(ip->connectivity, [&](auto k) { hipLaunchKernelGGL(isl_merge<decltype(k)::value>, grid, block, 0, c->stream, s, c->vol.isl); });
+  if (int rc = timer.mark(c, 2)) return rc;
+  hipLaunchKernelGGL(isl_flatten, grid, block, 0, c->stream, s, c->vol.isl);
+  hipLaunchKernelGGL(isl_scan, dim3(1), dim3(1024), 0, c->stream, s, c->vol.isl);
   VX_HIP(c, hipGetLastError());
   launches += 4;
-  VX_HIP(c, hipEventRecord(c->isl_ev[3], c->stream));
+  if (int rc = timer.mark(c, 3)) return rc;
   // the one read-back that sizes the table: the number of islands
   IslHdr hdr{};
-  VX_HIP(c, hipMemcpyAsync(&hdr, c->isl.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipMemcpyAsync(&hdr, c->vol.isl.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   const uint32_t R = hdr.roots;
   if (int rc = ensure_island_rows(c, R)) return rc;
-  const IslDev& d = c->isl;
-  SegSeed seed{0u, 0u, 1ull};
-  if (ip->op == VX_ISLANDS_KEEP_AT) {
-    const uint32_t sx = ip->seed[0], sy = ip->seed[1], sz = ip->seed[2];
-    seed = SegSeed{((sz >> 3) * s.bc[1] + (sy >> 3)) * s.bc[0] + (sx >> 3), sz & 7u, 1ull << (((sy & 7u) << 3) | (sx & 7u))};
-  }
+  const IslDev& d = c->vol.isl;
+  const SegSeed seed = ip->op == VX_ISLANDS_KEEP_AT ? seg_seed_of(s, ip->seed) : SegSeed{0u, 0u, 1ull};
   hipLaunchKernelGGL(isl_rootid, grid, block, 0, c->stream, s, d);
   hipLaunchKernelGGL(isl_table, grid, block, 0, c->stream, s, d);
   hipLaunchKernelGGL(isl_seed_row, dim3(1), dim3(64), 0, c->stream, s, d, seed);
   VX_HIP(c, hipGetLastError());
   launches += 3;
-  VX_HIP(c, hipEventRecord(c->isl_ev[4], c->stream));
-  VX_HIP(c, hipEventSynchronize(c->isl_ev[4]));
+  if (int rc = timer.mark(c, 4)) return rc;
+  VX_HIP(c, hipEventSynchronize(timer.ev[4]));
   // the host's share: the rows come back once, are ranked by (count descending, anchor ascending), and every row's label
   // (0: dropped by the op) goes back up.  O(islands), not O(voxels).
   const auto t0 = std::chrono::steady_clock::now();
@@ -3324,45 +3076,27 @@ int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult*
   VX_HIP(c, hipMemcpyAsync(d.newlab, newlab.data(), newlab.size() * 4u, hipMemcpyHostToDevice, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));   // (newlab is pageable host memory of this frame)
   const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  VX_HIP(c, hipEventRecord(c->isl_ev[5], c->stream));
+  if (int rc = timer.mark(c, 5)) return rc;
   if (modify) {
     hipLaunchKernelGGL(isl_apply, grid, block, 0, c->stream, s, d);
     ++launches;
   }
-  VX_HIP(c, hipEventRecord(c->isl_ev[6], c->stream));
-  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 0u);
-  launch_seg_stats(c);
-  VX_HIP(c, hipGetLastError());
-  launches += 3;
-  VX_HIP(c, hipEventRecord(c->isl_ev[7], c->stream));
+  if (int rc = timer.mark(c, 6)) return rc;
   SegStats st;
-  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  static const int slot[7] = {0, 1, 2, 3, -1, 5, 6};   // kernel_ms[k] = ev[slot] .. ev[slot + 1]; 4 is the host's
-  for (int k = 0; k < 7; ++k) {
-    float ms = 0.0f;
-    if (slot[k] >= 0) VX_HIP(c, hipEventElapsedTime(&ms, c->isl_ev[slot[k]], c->isl_ev[slot[k] + 1]));
-    c->isl_ms[k] = slot[k] >= 0 ? (double)ms : host_ms;
-  }
-  if (!modify) c->isl_ms[5] = 0.0;   // (two events back to back still measure a few microseconds)
+  if (int rc = seg_mask_stats(c, timer, 7, &st)) return rc;
+  launches += 3;
+  if (int rc = timer.read(c)) return rc;
+  timer.ms[4] = host_ms;             // stage 4 is the host's share: wall time, not the events around it
+  if (!modify) timer.ms[5] = 0.0;    // (two events back to back still measure a few microseconds)
   c->isl_launches = launches;
   VxIslandsResult r{};
   r.islands = R;
   r.kept = table.size();
   r.largest = R ? rows[order[0]].count : 0u;
-  r.seg.count = st.count;
-  if (st.count) {
-    for (int a = 0; a < 3; ++a) {
-      r.seg.bbox_lo[a] = st.lo[a];
-      r.seg.bbox_hi[a] = st.hi[a];
-    }
-    r.seg.d_min = seg_key_float(st.dmin);
-    r.seg.d_max = seg_key_float(st.dmax);
-    r.seg.d_sum = st.sum;
-  }
+  r.seg = seg_result(st);
   r.seg.converged = 1u;
-  c->isl_table.swap(table);
-  c->isl_valid = true;
+  c->vol.isl_table.swap(table);
+  c->vol.isl_valid = true;
   if (out) *out = r;
   return VX_OK;
 }
@@ -3370,15 +3104,15 @@ int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult*
 int vx_islands_read(VxContext* c, uint64_t first, uint64_t n, VxIsland* out) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_islands_read(c->members[0], first, n, out));
-  if (!c->isl_valid)
+  if (!c->vol.isl_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: no current table (vx_segment_islands first; an upload and every call that "
                                "changes the segment drop it)");
-  const uint64_t have = c->isl_table.size();
+  const uint64_t have = c->vol.isl_table.size();
   if (first > have || n > have - first)
     VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: rows %llu .. %llu are beyond the %llu islands of the table",
             (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)have);
   if (n && !out) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: out is NULL");
-  if (n) memcpy(out, c->isl_table.data() + first, (size_t)n * sizeof(VxIsland));
+  if (n) memcpy(out, c->vol.isl_table.data() + first, (size_t)n * sizeof(VxIsland));
   return VX_OK;
 }
 
@@ -3386,26 +3120,20 @@ int vx_islands_read_labels(VxContext* c, uint32_t* labels, uint64_t nvoxels) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_islands_read_labels(c->members[0], labels, nvoxels));
   VX_DEV(c);
-  if (!c->isl_valid || !c->seg_valid)
+  if (!c->vol.isl_valid || !c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: no current table (vx_segment_islands first; an upload and every call "
                                "that changes the segment drop it)");
   if (!labels) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: labels is NULL");
-  const uint32_t* E = c->dv.extent;
+  const uint32_t* E = c->vol.dv.extent;
   const size_t want = (size_t)E[0] * E[1] * E[2];
   if (nvoxels != want)
     VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: nvoxels = %llu, the volume has %u x %u x %u = %zu voxels",
             (unsigned long long)nvoxels, E[0], E[1], E[2], want);
-  if (want > c->isl_dense_cap) {   // (every earlier call has completed: each one synchronises)
-    if (c->isl_dense) (void)hipFree(c->isl_dense);
-    c->isl_dense = nullptr;
-    c->isl_dense_cap = 0;
-    VX_HIP(c, hipMalloc(&c->isl_dense, want * 4u));
-    c->isl_dense_cap = want;
-  }
+  if (int rc = c->vol.isl_dense.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
   const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 16384u);
-  hipLaunchKernelGGL(isl_labels_out, dim3(blocks), dim3(256), 0, c->stream, c->seg, c->isl, E[0], E[1], want, c->isl_dense);
+  hipLaunchKernelGGL(isl_labels_out, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg, c->vol.isl, E[0], E[1], want, c->vol.isl_dense);
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipMemcpyAsync(labels, c->isl_dense, want * 4u, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipMemcpyAsync(labels, c->vol.isl_dense, want * 4u, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   return VX_OK;
 }
@@ -3414,8 +3142,7 @@ int vx_islands_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_islands_stats(c->members[0], launches, kernel_ms));
   if (launches) *launches = c->isl_launches;
-  if (kernel_ms)
-    for (int i = 0; i < 7; ++i) kernel_ms[i] = c->isl_ms[i];
+  if (kernel_ms) std::copy_n(c->isl_timer.ms, 7, kernel_ms);
   return VX_OK;
 }
 
@@ -3423,31 +3150,25 @@ int vx_islands_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
 // Five launches whatever the mesh: the inside words, the active cells with their counts, the two launches that finish the
 // exclusive scan, the emission.  The totals are read back once, between the scan and the emission, to size the outputs.
 static int ensure_mesh(VxContext* c) {
-  if (c->mesh_alloc) return VX_OK;
-  MeshDev& m = c->mesh;
+  if (c->vol.mesh_alloc) return VX_OK;
+  MeshDev& m = c->vol.mesh;
   for (int a = 0; a < 3; ++a) {
-    m.bc[a] = c->dv.bc[a];
-    m.cb[a] = c->dv.bc[a] + 1u;
+    m.bc[a] = c->vol.dv.bc[a];
+    m.cb[a] = c->vol.dv.bc[a] + 1u;
   }
   const size_t nb = (size_t)m.bc[0] * m.bc[1] * m.bc[2], ncb = (size_t)m.cb[0] * m.cb[1] * m.cb[2];
   if (ncb > 0xffffff00ull) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: %zu cell blocks are beyond the 32-bit block index", ncb);
   const size_t np = (ncb + 255u) / 256u;
-  const size_t bytes = nb * 64u + ncb * (64u + 8u + 8u) + np * 16u + sizeof(MeshStats);
-  VX_HIP(c, hipMalloc(&c->mesh_alloc, bytes));
-  char* p = static_cast<char*>(c->mesh_alloc);
-  m.inside = reinterpret_cast<uint64_t*>(p);
-  p += nb * 64u;
-  m.act = reinterpret_cast<uint64_t*>(p);
-  p += ncb * 64u;
-  m.vq = reinterpret_cast<uint2*>(p);
-  p += ncb * 8u;
-  m.off = reinterpret_cast<uint2*>(p);
-  p += ncb * 8u;
-  m.part = reinterpret_cast<uint2*>(p);
-  p += np * 8u;
-  m.poff = reinterpret_cast<uint2*>(p);
-  p += np * 8u;
-  m.st = reinterpret_cast<MeshStats*>(p);
+  const int rc = carve(c, c->vol.mesh_alloc, [&](Carve& k) {
+    m.inside = k.take<uint64_t>(nb * 8u);
+    m.act = k.take<uint64_t>(ncb * 8u);
+    m.vq = k.take<uint2>(ncb);
+    m.off = k.take<uint2>(ncb);
+    m.part = k.take<uint2>(np);
+    m.poff = k.take<uint2>(np);
+    m.st = k.take<MeshStats>();
+  });
+  if (rc) return rc;
   m.nb = (uint32_t)nb;
   m.ncb = (uint32_t)ncb;
   m.np = (uint32_t)np;
@@ -3458,53 +3179,43 @@ int vx_mesh_extract(VxContext* c, const VxMeshParams* mp, VxMeshResult* out) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_mesh_extract(c->members[0], mp, out));
   VX_DEV(c);
-  if (!c->has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_mesh_extract: no volume uploaded");
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: vx_set_params first (volume_density_scale and volume_inv_maj come from it)");
-  if (!mp) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: params is NULL");
+  if (int rc = check_ready(c, "vx_mesh_extract", mp, "params")) return rc;
   if (mp->source != VX_MESH_DENSITY && mp->source != VX_MESH_SEGMENT)
     VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: source = %d is not VX_MESH_DENSITY or VX_MESH_SEGMENT", mp->source);
   const bool segment = mp->source == VX_MESH_SEGMENT;
   if (!segment && !(std::isfinite(mp->iso) && mp->iso > 0.0f))
     VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: iso = %g is not finite and > 0", (double)mp->iso);
-  const uint32_t* E = c->dv.extent;
-  MeshBox box{{mp->box_lo[0], mp->box_lo[1], mp->box_lo[2]}, {mp->box_hi[0], mp->box_hi[1], mp->box_hi[2]}};
-  for (int a = 0; a < 3; ++a) {
-    if (box.hi[a] == VX_SEGMENT_BOX_END) box.hi[a] = E[a] - 1u;
-    if (box.lo[a] > box.hi[a] || box.hi[a] >= E[a])
-      VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: box axis %d [%u, %u] is empty or outside the index extent %u", a, mp->box_lo[a],
-              mp->box_hi[a], E[a]);
-  }
-  if (segment && !c->seg_valid)
+  VoxelBox vb;
+  if (int rc = check_box(c, "vx_mesh_extract", mp->box_lo, mp->box_hi, &vb)) return rc;
+  const MeshBox box{{vb.lo[0], vb.lo[1], vb.lo[2]}, {vb.hi[0], vb.hi[1], vb.hi[2]}};
+  if (segment && !c->vol.seg_valid)
     VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: source = VX_MESH_SEGMENT with no current segment (vx_segment or vx_segment_write_mask "
             "first; an upload drops it)");
   if (int rc = ensure_mesh(c)) return rc;
-  for (hipEvent_t& e : c->mesh_ev)
-    if (!e) VX_HIP(c, hipEventCreate(&e));
-  c->mesh_valid = false;
-  c->mesh_nv = c->mesh_nt = 0;
-  const MeshDev& m = c->mesh;
+  c->vol.mesh_valid = false;
+  c->vol.mesh_nv = c->vol.mesh_nt = 0;
+  const MeshDev& m = c->vol.mesh;
   const VxParams& p = c->params;
   const float iso = segment ? 0.5f : mp->iso;
-  VX_HIP(c, hipEventRecord(c->mesh_ev[0], c->stream));
+  if (int rc = c->mesh_timer.mark(c, 0)) return rc;
   if (segment) {
     const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)m.nb * 8u + 255u) / 256u, 8192u);
-    hipLaunchKernelGGL(mesh_inside_segment, dim3(blocks), dim3(256), 0, c->stream, c->seg.seg, box, m);
+    hipLaunchKernelGGL(mesh_inside_segment, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg.seg, box, m);
   } else {
     const uint32_t blocks = std::min<uint32_t>((m.nb + 3u) / 4u, 4096u);
     with_layout(slice_layout(c), [&](auto lay) {
       constexpr int LAY = decltype(lay)::value;
-      hipLaunchKernelGGL((mesh_inside_density<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale,
+      hipLaunchKernelGGL((mesh_inside_density<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale,
                          p.volume_inv_maj, iso, box, m);
     });
   }
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->mesh_ev[1], c->stream));
+  if (int rc = c->mesh_timer.mark(c, 1)) return rc;
   hipLaunchKernelGGL(mesh_active, dim3(m.np), dim3(256), 0, c->stream, m);
   hipLaunchKernelGGL(mesh_scan_partials, dim3(1), dim3(1024), 0, c->stream, m);
   hipLaunchKernelGGL(mesh_offsets, dim3(m.np), dim3(256), 0, c->stream, m);
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->mesh_ev[2], c->stream));
+  if (int rc = c->mesh_timer.mark(c, 2)) return rc;
   MeshStats st;
   VX_HIP(c, hipMemcpyAsync(&st, m.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
@@ -3513,47 +3224,30 @@ int vx_mesh_extract(VxContext* c, const VxMeshParams* mp, VxMeshResult* out) {
   if (nv > maxv || nt > maxt)
     VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: the mesh has %llu vertices and %llu triangles, more than max_vertices = %llu or "
             "max_triangles = %llu", (unsigned long long)nv, (unsigned long long)nt, (unsigned long long)maxv, (unsigned long long)maxt);
-  if (nv > c->mesh_vcap) {   // (every earlier call has completed: each one synchronises)
-    if (c->mesh_verts) (void)hipFree(c->mesh_verts);
-    if (c->mesh_cells) (void)hipFree(c->mesh_cells);
-    c->mesh_verts = nullptr;
-    c->mesh_cells = nullptr;
-    c->mesh_vcap = 0;
-    VX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->mesh_verts), (size_t)nv * 12u));
-    VX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->mesh_cells), (size_t)nv * 12u));
-    c->mesh_vcap = (size_t)nv;
-  }
-  if (nt > c->mesh_tcap) {
-    if (c->mesh_tris) (void)hipFree(c->mesh_tris);
-    c->mesh_tris = nullptr;
-    c->mesh_tcap = 0;
-    VX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->mesh_tris), (size_t)nt * 12u));
-    c->mesh_tcap = (size_t)nt;
-  }
+  // three values per vertex and per triangle (every earlier call has completed: each one synchronises)
+  if (int rc = c->vol.mesh_verts.ensure(c, (size_t)nv * 3u)) return rc;
+  if (int rc = c->vol.mesh_cells.ensure(c, (size_t)nv * 3u)) return rc;
+  if (int rc = c->vol.mesh_tris.ensure(c, (size_t)nt * 3u)) return rc;
   {
     const uint32_t blocks = std::min<uint32_t>((m.ncb + 3u) / 4u, 4096u);
     if (segment)   // no voxel is read: one instance serves every layout
-      hipLaunchKernelGGL((mesh_emit<LAYOUT_REF, true>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
-                         iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->mesh_verts, c->mesh_cells, c->mesh_tris);
+      hipLaunchKernelGGL((mesh_emit<LAYOUT_REF, true>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
+                         iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->vol.mesh_verts, c->vol.mesh_cells, c->vol.mesh_tris);
     else
       with_layout(slice_layout(c), [&](auto lay) {
         constexpr int LAY = decltype(lay)::value;
-        hipLaunchKernelGGL((mesh_emit<LAY, false>), dim3(blocks), dim3(256), 0, c->stream, c->dv, p.volume_density_scale, p.volume_inv_maj,
-                           iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->mesh_verts, c->mesh_cells, c->mesh_tris);
+        hipLaunchKernelGGL((mesh_emit<LAY, false>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
+                           iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->vol.mesh_verts, c->vol.mesh_cells, c->vol.mesh_tris);
       });
   }
   VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipEventRecord(c->mesh_ev[3], c->stream));
+  if (int rc = c->mesh_timer.mark(c, 3)) return rc;
   VX_HIP(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 3; ++i) {
-    float ms = 0.0f;
-    VX_HIP(c, hipEventElapsedTime(&ms, c->mesh_ev[i], c->mesh_ev[i + 1]));
-    c->mesh_ms[i] = ms;
-  }
+  if (int rc = c->mesh_timer.read(c)) return rc;
   c->mesh_launches = 5u;
-  c->mesh_nv = nv;
-  c->mesh_nt = nt;
-  c->mesh_valid = true;
+  c->vol.mesh_nv = nv;
+  c->vol.mesh_nt = nt;
+  c->vol.mesh_valid = true;
   if (out) {
     VxMeshResult r{};
     r.vertices = nv;
@@ -3574,12 +3268,12 @@ int vx_mesh_read(VxContext* c, float* verts_xyz, int32_t* cells_xyz, uint32_t* t
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_mesh_read(c->members[0], verts_xyz, cells_xyz, tris));
   VX_DEV(c);
-  if (!c->mesh_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_read: no current mesh (vx_mesh_extract first; an upload drops it)");
-  if (verts_xyz && c->mesh_nv)
-    VX_HIP(c, hipMemcpyAsync(verts_xyz, c->mesh_verts, (size_t)c->mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
-  if (cells_xyz && c->mesh_nv)
-    VX_HIP(c, hipMemcpyAsync(cells_xyz, c->mesh_cells, (size_t)c->mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
-  if (tris && c->mesh_nt) VX_HIP(c, hipMemcpyAsync(tris, c->mesh_tris, (size_t)c->mesh_nt * 12u, hipMemcpyDeviceToHost, c->stream));
+  if (!c->vol.mesh_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_read: no current mesh (vx_mesh_extract first; an upload drops it)");
+  if (verts_xyz && c->vol.mesh_nv)
+    VX_HIP(c, hipMemcpyAsync(verts_xyz, c->vol.mesh_verts, (size_t)c->vol.mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
+  if (cells_xyz && c->vol.mesh_nv)
+    VX_HIP(c, hipMemcpyAsync(cells_xyz, c->vol.mesh_cells, (size_t)c->vol.mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
+  if (tris && c->vol.mesh_nt) VX_HIP(c, hipMemcpyAsync(tris, c->vol.mesh_tris, (size_t)c->vol.mesh_nt * 12u, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   return VX_OK;
 }
@@ -3588,22 +3282,21 @@ int vx_mesh_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_mesh_stats(c->members[0], launches, kernel_ms));
   if (launches) *launches = c->mesh_launches;
-  if (kernel_ms)
-    for (int i = 0; i < 3; ++i) kernel_ms[i] = c->mesh_ms[i];
+  if (kernel_ms) std::copy_n(c->mesh_timer.ms, 3, kernel_ms);
   return VX_OK;
 }
 
-// test hook (not part of the reference boundary): the device's unorm8 decode table
 int vx_shadow_stats(VxContext* c, uint64_t* builds, uint64_t* light_samples, double* last_build_ms) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_shadow_stats(c->members[0], builds, light_samples, last_build_ms));
   VX_DEV(c);
   unsigned long long n = 0;
-  float ms = 0.0f;
+  double ms = 0.0;
   if (c->shadow_builds) {
     VX_HIP(c, hipStreamSynchronize(c->stream));
     VX_HIP(c, hipMemcpy(&n, c->shadow_count_dev, sizeof n, hipMemcpyDeviceToHost));
-    VX_HIP(c, hipEventElapsedTime(&ms, c->shadow_ev[0], c->shadow_ev[1]));
+    if (int rc = c->shadow_timer.read(c)) return rc;
+    ms = c->shadow_timer.ms[0];
   }
   if (builds) *builds = c->shadow_builds;
   if (light_samples) *light_samples = n;
@@ -3615,16 +3308,17 @@ int vx_debug_read_shadow_grid(VxContext* c, float* out, uint32_t dims_out[3]) {
   if (!c || !dims_out) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_debug_read_shadow_grid(c->members[0], out, dims_out));
   VX_DEV(c);
-  if (!c->shadow.t) VX_FAIL(c, VX_ERR_INVALID, "vx_debug_read_shadow_grid: no light grid built since the last upload");
-  for (int i = 0; i < 3; ++i) dims_out[i] = c->shadow.n[i];
+  if (!c->vol.shadow.t) VX_FAIL(c, VX_ERR_INVALID, "vx_debug_read_shadow_grid: no light grid built since the last upload");
+  for (int i = 0; i < 3; ++i) dims_out[i] = c->vol.shadow.n[i];
   if (out) {
     VX_HIP(c, hipStreamSynchronize(c->stream));
-    VX_HIP(c, hipMemcpy(out, c->shadow.t, (size_t)c->shadow.n[0] * c->shadow.n[1] * c->shadow.n[2] * sizeof(float),
+    VX_HIP(c, hipMemcpy(out, c->vol.shadow.t, (size_t)c->vol.shadow.n[0] * c->vol.shadow.n[1] * c->vol.shadow.n[2] * sizeof(float),
                         hipMemcpyDeviceToHost));
   }
   return VX_OK;
 }
 
+// test hook (not part of the reference boundary): the device's unorm8 decode table
 int vx_debug_unorm_table(VxContext* c, float* out256) {
   if (!c || !out256) return VX_ERR_INVALID;
   if (is_group(c)) return on_member0(c, vx_debug_unorm_table(c->members[0], out256));
