@@ -14,10 +14,11 @@ import numpy as np
 import pytest
 
 from tests import closed_form as CF
+from tests import common
 
 F32 = np.float32
 EPS32 = 2.0 ** -24                      # unit roundoff of binary32
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1}
+LAYOUTS = {k: common.LAYOUTS[k] for k in ("brickf32", "bricku8", "reference", "cellquad")}
 
 
 def _normalised(v):

@@ -15,8 +15,7 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
+from tests.common import NAPI, ROOT
 VX_ERR_INVALID = 1
 
 

@@ -21,11 +21,6 @@ pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def _grid_msg(og):
-    """oracle BrickGrid -> object with the WasmWorkerMessageDicomReturn fields"""
-    return og
-
-
 def _renderer(og, tf, L, p_src, layout):
     from volxel_amd import Volxel3DRenderer, _abi
     r = Volxel3DRenderer(p_src.res[0], p_src.res[1], layout=layout)

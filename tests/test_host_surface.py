@@ -13,8 +13,7 @@ import zipfile
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
+from tests.common import NAPI
 
 REFERENCE_METHODS = {   # viewer.ts line -> (python name, javascript name)
     963: ("restart_from_files", "restartFromFiles"), 977: ("restart_from_zip", "restartFromZip"),

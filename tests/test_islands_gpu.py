@@ -9,26 +9,22 @@ alone; staleness, refusals, a device group and the JS host."""
 import ctypes as C
 import json
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import islands_ref as IR
 from tests import segment_ref as SG
-from tests.test_segedit_gpu import _same_stats, _shape, _uploaded_shapes
-from tests.test_segment_gpu import (CHAINS, F32_MAX, LAYOUTS, NAPI, _densities, _grid, _odd, _renderer, _resolve, _serpentine,
-                                    _tube, _upload)
+from tests.common import F32_MAX, LAYOUTS, densities, grid, renderer, segment_volumes, upload_volume
+from tests.js_host import dump_grid, run_node
+from tests.shapes import CHAINS, resolve, same_stats, shape_of, uploaded_shapes
 
 CONNS = (6, 26)
 
 
 @pytest.fixture(scope="module")
 def volumes():
-    from tests.common import small_noise
-    from volxel_amd import synth
-    return {"noise": _grid(*small_noise(64)), "phantom": _grid(*synth.ct_phantom(64)), "odd": _grid(*_odd()),
-            "serpentine": _grid(*_serpentine()), "tube": _grid(*_tube())}
+    return segment_volumes()
 
 
 def _rows(table):
@@ -53,7 +49,7 @@ def _check_labelling(r, m, conn, d=None):
     assert np.array_equal(r.segment_mask(), m)                    # LABEL changes nothing
     assert isl.segment.count == int(m.sum()) and isl.segment.rounds == 0 and isl.segment.brick_visits == 0 and isl.segment.converged
     if d is not None:
-        _same_stats(isl.segment, m, d)
+        same_stats(isl.segment, m, d)
     return isl, want
 
 
@@ -72,7 +68,7 @@ def _check_op(r, m, conn, d, op, table=None, **kw):
             s = r.keep_island_at(kw["seed"], conn)
         assert np.array_equal(SG.packed(r.segment_mask()), SG.packed(nm)), (op, conn, kw)
         assert (s.islands, s.kept, s.largest) == (before, kept, largest), (op, conn, kw, s)
-        _same_stats(s, nm, d)
+        same_stats(s, nm, d)
         assert s.rounds == 0 and s.brick_visits == 0
         assert _struct_rows(r.island_table()) == nt.rows()
         assert np.array_equal(r.island_labels(), nt.labels)
@@ -111,16 +107,16 @@ THRESHOLDS = {"noise_q90": ("noise", "q0.9", None, None), "noise_band_box": ("no
 def test_threshold_is_the_predicate(volumes, case, layout):
     vol, lo, hi, box = THRESHOLDS[case]
     g = volumes[vol]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities(vol, g, p)
-        _, lo_v, hi_v, pred = _resolve(d, (0, 0, 0), lo, hi, box)
+        d = densities(vol, g, p)
+        _, lo_v, hi_v, pred = resolve(d, (0, 0, 0), lo, hi, box)
         s1 = r.threshold(lo_v, hi_v, box=box)
         m1 = r.segment_mask()
         s2 = r.threshold(lo_v, hi_v, box=box)
         assert np.array_equal(SG.packed(m1), SG.packed(pred)) and np.array_equal(r.segment_mask(), pred)
-        _same_stats(s1, pred, d)
+        same_stats(s1, pred, d)
         assert s1.count > 0 and s1.rounds == 0 and s1.brick_visits == 0 and s1.d_sum == s2.d_sum
     finally:
         r.close()
@@ -131,11 +127,11 @@ def test_threshold_is_the_predicate(volumes, case, layout):
 def test_band_dilation_after_threshold_is_that_after_segment(volumes, conn):
     from tests import segedit_ref as ER
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
-        seed, lo_v, hi_v, pred = _resolve(d, "max", "q0.7", None, None)
+        d = densities("noise", g, p)
+        seed, lo_v, hi_v, pred = resolve(d, "max", "q0.7", None, None)
         start = ER.edit(SG.component(pred, seed, conn), "erode", conn, 1)
         r.segment(seed, lo_v, hi_v, connectivity=conn)
         r.set_segment_mask(start)
@@ -157,10 +153,10 @@ def test_band_dilation_after_threshold_is_that_after_segment(volumes, conn):
 @pytest.mark.parametrize("conn", CONNS)
 def test_islands_of_thresholded_noise(volumes, layout, conn):
     g = volumes["noise"]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
+        d = densities("noise", g, p)
         for q, n6, n26 in ((0.9, 91, 68), (0.7, 47, 23)):
             lo = float(np.quantile(d, q))
             r.threshold(lo)
@@ -178,13 +174,13 @@ def test_islands_of_thresholded_noise(volumes, layout, conn):
 @pytest.mark.parametrize("conn", CONNS)
 def test_islands_of_uploaded_masks(volumes, layout, conn):
     g = volumes["odd"]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("odd", g, p)
-        shape = _shape(g)
+        d = densities("odd", g, p)
+        shape = shape_of(g)
         salt = _salt(shape)
-        for name, m in (("salt", salt), ("shapes", _uploaded_shapes(shape)), ("checkerboard", _checkerboard(shape)),
+        for name, m in (("salt", salt), ("shapes", uploaded_shapes(shape)), ("checkerboard", _checkerboard(shape)),
                         ("empty", np.zeros(shape, dtype=bool)), ("full", np.ones(shape, dtype=bool))):
             r.set_segment_mask(m)
             isl, _ = _check_labelling(r, m, conn, d)
@@ -205,10 +201,10 @@ def test_islands_of_uploaded_masks(volumes, layout, conn):
 @pytest.mark.parametrize("vol", ["phantom", "serpentine", "tube"])
 def test_islands_of_the_phantom_the_serpentine_and_the_tube(volumes, vol, conn):
     g = volumes[vol]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities(vol, g, p)
+        d = densities(vol, g, p)
         lo = 0.75 if vol == "phantom" else float(d.max()) / 2
         r.threshold(lo)
         isl, want = _check_labelling(r, SG.predicate(d, lo, F32_MAX), conn, d)
@@ -227,8 +223,8 @@ def test_diagonal_chains_are_whole_under_26_and_voxels_under_6(chain):
     pts = [CHAINS[chain](k) for k in range(40)]
     for x, y, z in pts:
         v[z, y, x] = 3000
-    g = _grid(v, (1.0, 1.0, 1.0))
-    r = _renderer(g)
+    g = grid(v, (1.0, 1.0, 1.0))
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
         d = SG.densities(g, p.volume_density_scale, p.volume_inv_maj)
@@ -249,11 +245,11 @@ def test_diagonal_chains_are_whole_under_26_and_voxels_under_6(chain):
 def test_launch_count_does_not_depend_on_the_mask(volumes):
     """the serpentine (6 472 rounds of the flood), thousands of specks and the empty mask: the same number of launches"""
     g = volumes["serpentine"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("serpentine", g, p)
-        shape = _shape(g)
+        d = densities("serpentine", g, p)
+        shape = shape_of(g)
         path = SG.predicate(d, float(d.max()) / 2, F32_MAX)
         masks = {"serpentine": path, "noise": _salt(shape, seed=5, p=0.2), "empty": np.zeros(shape, dtype=bool)}
         for conn in CONNS:
@@ -296,12 +292,12 @@ def _op_cases(want, m):
 def test_every_op_matches_the_restatement(volumes, start, conn):
     vol = "noise" if start == "noise_q90" else "odd"
     g = volumes[vol]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities(vol, g, p)
-        shape = _shape(g)
-        m = {"noise_q90": lambda: _noise_mask(d, 0.9), "salt": lambda: _salt(shape), "shapes": lambda: _uploaded_shapes(shape),
+        d = densities(vol, g, p)
+        shape = shape_of(g)
+        m = {"noise_q90": lambda: _noise_mask(d, 0.9), "salt": lambda: _salt(shape), "shapes": lambda: uploaded_shapes(shape),
              "empty": lambda: np.zeros(shape, dtype=bool)}[start]()
         want = IR.islands(m, conn)
         changed = 0
@@ -318,11 +314,11 @@ def test_every_op_matches_the_restatement(volumes, start, conn):
 def test_every_layout_gives_the_same_ops(volumes, layout):
     """only the statistics read the volume"""
     g = volumes["odd"]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("odd", g, p)
-        m = _uploaded_shapes(_shape(g))
+        d = densities("odd", g, p)
+        m = uploaded_shapes(shape_of(g))
         for conn in CONNS:
             want = IR.islands(m, conn)
             for op, kw in (("keep_largest", dict(keep=2)), ("remove_small", dict(min_voxels=4)),
@@ -336,10 +332,10 @@ def test_every_layout_gives_the_same_ops(volumes, layout):
 @pytest.mark.parametrize("conn", CONNS)
 def test_keep_largest_of_a_threshold_is_the_segment_of_its_anchor(volumes, conn):
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
+        d = densities("noise", g, p)
         lo = float(np.quantile(d, 0.7))
         r.threshold(lo)
         anchor = r.islands(conn).table[0]["anchor"]
@@ -371,7 +367,7 @@ def test_views_overlay_pick_and_mesh_see_the_new_mask(volumes):
         r.segment_view = "off"
         return img, ov, pk, mesh
 
-    r = _renderer(g, layout=LAYOUTS["brickf32"])
+    r = renderer(g, layout=LAYOUTS["brickf32"], dvr_jitter=False)
     try:
         r.bind_uniforms()
         r.threshold(0.75)
@@ -395,7 +391,7 @@ def test_views_overlay_pick_and_mesh_see_the_new_mask(volumes):
 @pytest.mark.gpu
 def test_rendering_is_left_alone_with_the_view_off(volumes):
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         r.bind_uniforms()
         r.segment((10, 10, 10), 0.2, connectivity=26)
@@ -428,7 +424,7 @@ def test_rendering_is_left_alone_with_the_view_off(volumes):
 def test_every_change_of_the_segment_drops_the_table(volumes):
     from volxel_amd.renderer import VolxelError
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         r.bind_uniforms()
         m = _salt((64, 64, 64), seed=2)
@@ -478,10 +474,10 @@ def test_refusals_change_nothing(volumes):
         assert lib.vx_segment_threshold(ctx, C.byref(t), C.byref(sres)) == 3
         assert lib.vx_islands_stats(ctx, None, None) == 0
         assert lib.vx_islands_read(ctx, 0, 0, rows) == 1 and b"no current table" in err()
-        assert _upload(lib, ctx, g) == 0
+        assert upload_volume(lib, ctx, g) == 0
         assert lib.vx_segment_islands(ctx, C.byref(q), C.byref(res)) == 1 and b"vx_set_params" in err()
         assert lib.vx_segment_threshold(ctx, C.byref(t), None) == 1 and b"vx_set_params" in err()
-        r = _renderer(g)
+        r = renderer(g, dvr_jitter=False)
         try:
             p = r.bind_uniforms()
         finally:
@@ -564,8 +560,8 @@ def test_device_group_runs_the_islands_on_member0(volumes):
         finally:
             r.close()
 
-    a = run(_renderer(g))
-    b = run(_renderer(g, devices=[0, 0]))
+    a = run(renderer(g, dvr_jitter=False))
+    b = run(renderer(g, devices=[0, 0], dvr_jitter=False))
     want = IR.islands(m, 26)
     assert a[2] == b[2] == want.rows() and np.array_equal(a[3], b[3]) and np.array_equal(a[1], b[1])
     assert np.array_equal(a[5], b[5]) and np.array_equal(a[5], IR.apply(m, "remove_small", 26, min_voxels=4)[0]) and a[6] == b[6]
@@ -578,14 +574,12 @@ def test_device_group_runs_the_islands_on_member0(volumes):
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 def test_js_host_islands_have_the_python_bits(volumes, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
-    from volxel_amd import BENCHMARK_SETTINGS
     g = volumes["noise"]
     m = _salt((64, 64, 64), seed=6, p=0.08)
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
+        d = densities("noise", g, p)
         lo = float(np.quantile(d, 0.9))
         t = r.threshold(lo)
         tm = r.segment_mask()
@@ -601,35 +595,11 @@ def test_js_host_islands_have_the_python_bits(volumes, tmp_path):
         m3 = r.segment_mask()
     finally:
         r.close()
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, g.indirection_size)), "rangeSize": list(map(int, g.range_size)),
-        "atlasSize": list(map(int, g.atlas_size)), "indexExtent": list(map(int, g.index_extent)),
-        "minMaj": list(map(float, g.min_maj)), "transform": list(map(float, g.transform)),
-        "mips": [list(map(int, sz)) for _, sz in g.range_mipmaps]}))
-    np.asarray(g.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(g.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(g.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (mm, _) in enumerate(g.range_mipmaps):
-        np.asarray(mm, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
+    dump_grid(tmp_path, g)
     SG.packed(m).tofile(tmp_path / "in.bin")
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
     (tmp_path / "args.json").write_text(json.dumps({"lo": lo}))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
+    body = r"""
 const a = JSON.parse(fs.readFileSync(path.join(dir, 'args.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
-const save = (f, m) => fs.writeFileSync(path.join(dir, f), Buffer.from(m.buffer, m.byteOffset, m.byteLength));
 let refused = 0;
 try { r.islandLabels(); } catch (e) { refused += /no current table/.test(String(e)) ? 1 : 0; }
 const t = r.threshold(a.lo);
@@ -652,10 +622,7 @@ console.log(JSON.stringify({ t, isl: { count: isl.count, largest: isl.largest, s
   s1, s2, s3, label, modify: r.islandsStats(), refused }));
 r.dispose();
 """
-    (tmp_path / "run.js").write_text(script)
-    out = subprocess.run(["node", str(tmp_path / "run.js"), NAPI, str(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    js = json.loads(out.stdout.strip().splitlines()[-1])
+    js = run_node(tmp_path, body)
     rdm = lambda f: SG.unpacked(np.fromfile(tmp_path / f, dtype=np.uint8), (64, 64, 64))
     assert np.array_equal(rdm("tm.bin"), tm) and np.array_equal(rdm("m1.bin"), m1) and np.array_equal(rdm("m2.bin"), m2)
     assert np.array_equal(rdm("m3.bin"), m3)

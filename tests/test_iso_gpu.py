@@ -3,57 +3,36 @@ against the NumPy restatement (tests/iso_ref.py) -- hit buffer and counters bit 
 and picking against the full image, the float64 pins of tests/test_iso_host.py on the device, rendering left alone, device
 groups, the refusals, the JS host and config 2 (the CT phantom at 1080p) at a bone threshold."""
 import ctypes as C
-import json
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import iso_ref as IR
-from tests import test_iso_host as IH
+from tests.common import F32, LAYOUTS, bits, grid, renderer, small_noise, upload_volume
+from tests.js_host import dump_grid, run_node
+from tests.shapes import ISO_CASES, ISO_COLOUR, ISO_PHONG, SPACINGS, Field, iso_params
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
-F32 = np.float32
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1, "auto": 3}
 COLOUR = (0.9, 0.6, 0.4)
 PHONG = (0.2, 0.6, 0.5, 24.0)
 W, H = 64, 48
 
 
-def _grid(vox, sp):
-    from volxel_amd import read_u16_stack_to_grid
-    return read_u16_stack_to_grid(vox, sp)
-
-
 @pytest.fixture(scope="module")
 def noise():
-    from tests.common import small_noise
-    return _grid(*small_noise(64))
+    return grid(*small_noise(64))
 
 
 @pytest.fixture(scope="module")
 def phantom():
     """config 2's CT phantom at 64^3: air around the body, where range skipping passes samples over"""
     from volxel_amd import synth
-    return _grid(*synth.ct_phantom(64))
+    return grid(*synth.ct_phantom(64))
 
 
-def _renderer(g, layout=None, devices=None, mode="dvr", w=W, h=H):
-    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
-    r = Volxel3DRenderer(w, h, device=None if devices else 0, layout=layout, devices=devices)
-    r.setup_from_grid(g)
-    r.restore_settings(BENCHMARK_SETTINGS)
-    r.settings.render_mode = mode
-    r.settings.dvr_jitter = False
-    r.settings.volume_clip_min, r.settings.volume_clip_max = (0.1, 0.0, 0.05), (0.9, 0.85, 1.0)
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+def _renderer(g, layout=None, devices=None, mode="dvr"):
+    return renderer(g, layout, devices, mode, (W, H), dvr_jitter=False, volume_clip_min=(0.1, 0.0, 0.05),
+                    volume_clip_max=(0.9, 0.85, 1.0))
 
 
 def _stats(r):
@@ -68,7 +47,7 @@ def _check(r, g, iso, skip, refine=8, window=None, lib=None):
     bound = IR.bound_table(lib, g, p) if skip else None
     want_rgba, want_hit, want_counts, per = IR.isosurface(p, g, iso, color=COLOUR, phong=PHONG, refine=refine, window=window,
                                                           bound=bound)
-    assert np.array_equal(_bits(hit), _bits(want_hit))
+    assert np.array_equal(bits(hit), bits(want_hit))
     assert st == want_counts, (st, want_counts)
     assert float(np.abs(rgba - want_rgba).max()) <= 1e-5
     return rgba, hit, st, per
@@ -110,7 +89,7 @@ def test_skipping_gives_the_same_bits(noise):
             sa = _stats(r)
             b_rgba, b_hit = r.isosurface(iso, skip=True)
             sb = _stats(r)
-            assert np.array_equal(_bits(a_hit), _bits(b_hit)) and np.array_equal(_bits(a_rgba), _bits(b_rgba))
+            assert np.array_equal(bits(a_hit), bits(b_hit)) and np.array_equal(bits(a_rgba), bits(b_rgba))
             assert sa["samples"] + sa["skipped"] == sb["samples"] + sb["skipped"] and sa["skipped"] == 0
             assert (sa["rays"], sa["hits"], sa["refine_samples"]) == (sb["rays"], sb["hits"], sb["refine_samples"])
     finally:
@@ -127,20 +106,20 @@ def test_window_and_pick_reproduce_the_image(noise):
         wr, wh = r.isosurface(0.4, refine=16, window=win)
         x0, y0, x1, y1 = win
         assert wr.shape == (y1 - y0, x1 - x0, 4)
-        assert np.array_equal(_bits(wr), _bits(rgba[y0:y1, x0:x1])) and np.array_equal(_bits(wh), _bits(hit[y0:y1, x0:x1]))
+        assert np.array_equal(bits(wr), bits(rgba[y0:y1, x0:x1])) and np.array_equal(bits(wh), bits(hit[y0:y1, x0:x1]))
         assert _stats(r)["rays"] < full["rays"]
         f = hit[..., 3] >= 0
         ys, xs = np.nonzero(f)
         for i in np.linspace(0, len(xs) - 1, 6).astype(int):
             pt = r.pick(int(xs[i]), int(ys[i]), 0.4)
-            assert pt is not None and np.array_equal(np.asarray(pt, F32).view(np.uint32), _bits(hit[ys[i], xs[i], :3]))
+            assert pt is not None and np.array_equal(np.asarray(pt, F32).view(np.uint32), bits(hit[ys[i], xs[i], :3]))
         ym, xm = np.nonzero(~f)
         assert len(xm) and r.pick(int(xm[0]), int(ym[0]), 0.4) is None
     finally:
         r.close()
 
 
-def _raw(r, p, iso, refine, skip, color=IH.COLOUR, phong=IH.PHONG):
+def _raw(r, p, iso, refine, skip, color=ISO_COLOUR, phong=ISO_PHONG):
     from volxel_amd import _abi
     q = _abi.VxIsoParams()
     q.iso = iso
@@ -157,19 +136,19 @@ def _raw(r, p, iso, refine, skip, color=IH.COLOUR, phong=IH.PHONG):
 @pytest.fixture(scope="module")
 def fields():
     from oracle import oracle as O
-    return {(k, sp): IH.PP.Field(O, k, IH.PP.SPACINGS[sp]) for k in ("flat", "ramp", "bowl") for sp in IH.PP.SPACINGS}
+    return {(k, sp): Field(O, k, SPACINGS[sp]) for k in ("flat", "ramp", "bowl") for sp in SPACINGS}
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", sorted(IH.CASES))
+@pytest.mark.parametrize("name", sorted(ISO_CASES))
 def test_device_meets_the_float64_pins(fields, name):
     """the cases of tests/test_iso_host.py on layouts 0, 1, 2 and 4, skipping off and on: the device's hit buffer is the
     restatement's bit for bit, so it meets the tier-2 and tier-1 bounds the host file holds the restatement to"""
     from volxel_amd import Volxel3DRenderer
-    case = IH.CASES[name]
+    case = ISO_CASES[name]
     fd = fields[case.kind, case.spacing]
-    p = IH._params(case, fd)
-    want_rgba, want_hit, counts, per = IR.isosurface(p, fd.grid, case.iso, color=IH.COLOUR, phong=case.phong, refine=case.refine)
+    p = iso_params(case, fd)
+    want_rgba, want_hit, counts, per = IR.isosurface(p, fd.grid, case.iso, color=ISO_COLOUR, phong=case.phong, refine=case.refine)
     for layout in (0, 1, 2, 4):
         for skip in (False, True):
             r = Volxel3DRenderer(int(p.res[0]), int(p.res[1]), layout=layout)
@@ -180,7 +159,7 @@ def test_device_meets_the_float64_pins(fields, name):
                 st = _stats(r)
             finally:
                 r.close()
-            assert np.array_equal(_bits(hit), _bits(want_hit)), (layout, skip)
+            assert np.array_equal(bits(hit), bits(want_hit)), (layout, skip)
             assert float(np.abs(rgba - want_rgba).max()) <= 1e-5, (layout, skip)
             assert st["hits"] == counts["hits"] and st["samples"] + st["skipped"] == counts["samples"]
 
@@ -204,7 +183,7 @@ def test_isosurface_leaves_rendering_alone(noise):
 
     a, ca = run(False)
     b, cb = run(True)
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(bits(a), bits(b))
     assert ca == cb and ca[0] > 0
 
 
@@ -220,13 +199,12 @@ def test_group_gives_the_single_context_bits(noise):
     finally:
         one.close()
         grp.close()
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1])) and sa == sb
+    assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])) and sa == sb
 
 
 @pytest.mark.gpu
 def test_refusals(noise):
     from volxel_amd import _abi
-    from tests.test_slice_gpu import _upload
     lib = _abi.load_library()
     q = _abi.VxIsoParams()
     q.iso, q.refine, q.skip = 0.5, 4, 1
@@ -235,7 +213,7 @@ def test_refusals(noise):
     try:
         assert lib.vx_isosurface(ctx, C.byref(q), None, None) == 3                    # VX_ERR_NO_VOLUME
         assert lib.vx_iso_stats(ctx, None, None, None, None, None, None) == 0
-        assert _upload(lib, ctx, noise) == 0
+        assert upload_volume(lib, ctx, noise) == 0
         assert lib.vx_isosurface(ctx, C.byref(q), None, None) == 1 and b"vx_set_params" in lib.vx_last_error(ctx)
         r = _renderer(noise)
         try:
@@ -276,7 +254,7 @@ def test_config2_bone_at_1080p():
     """config 2 (the 256^3 CT phantom, spacing (0.7, 0.7, 1.0)) at 1920 x 1080 at a bone threshold: a 96 x 64 crop of the full
     image, centred on the bone, against the restatement, bit for bit"""
     from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer, synth
-    g = _grid(*synth.ct_phantom(256))
+    g = grid(*synth.ct_phantom(256))
     r = Volxel3DRenderer(1920, 1080, device=0)
     try:
         r.setup_from_grid(g)
@@ -296,7 +274,7 @@ def test_config2_bone_at_1080p():
     finally:
         r.close()
     x0, y0, x1, y1 = win
-    assert np.array_equal(_bits(hit[y0:y1, x0:x1]), _bits(want_hit))
+    assert np.array_equal(bits(hit[y0:y1, x0:x1]), bits(want_hit))
     assert float(np.abs(rgba[y0:y1, x0:x1] - want_rgba).max()) <= 1e-5
     assert per["found"].sum() > 100 and st["hits"] == len(xs)
 
@@ -304,8 +282,6 @@ def test_config2_bone_at_1080p():
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 def test_js_host_isosurface_has_the_python_bits(noise, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
-    from volxel_amd import BENCHMARK_SETTINGS
     r = _renderer(noise)
     try:
         want_rgba, want_hit = r.isosurface(0.4, color=COLOUR, phong=PHONG, refine=6)
@@ -314,31 +290,8 @@ def test_js_host_isosurface_has_the_python_bits(noise, tmp_path):
         pt = r.pick(32, 24, 0.4)
     finally:
         r.close()
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, noise.indirection_size)), "rangeSize": list(map(int, noise.range_size)),
-        "atlasSize": list(map(int, noise.atlas_size)), "indexExtent": list(map(int, noise.index_extent)),
-        "minMaj": list(map(float, noise.min_maj)), "transform": list(map(float, noise.transform)),
-        "mips": [list(map(int, s)) for _, s in noise.range_mipmaps]}))
-    np.asarray(noise.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(noise.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(noise.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (m, _) in enumerate(noise.range_mipmaps):
-        np.asarray(m, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
+    dump_grid(tmp_path, noise)
+    body = r"""
 r.settings.volumeClipMin = [0.1, 0.0, 0.05]; r.settings.volumeClipMax = [0.9, 0.85, 1.0];
 const a = r.isosurface(0.4, { color: [0.9, 0.6, 0.4], phong: [0.2, 0.6, 0.5, 24.0], refine: 6 });
 const st = r.isoStats();
@@ -351,13 +304,12 @@ fs.writeFileSync(path.join(dir, 'whit.bin'), Buffer.from(w.hit.buffer));
 console.log(JSON.stringify({ st, size: [a.width, a.height, w.width, w.height], pt: pt === null ? null : Array.from(new Float32Array(pt)) }));
 r.dispose();
 """
-    (tmp_path / "s.js").write_text(script)
-    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    out = run_node(tmp_path, body)
     assert out["size"] == [64, 48, 26, 14]
-    assert np.array_equal(np.fromfile(tmp_path / "rgba.bin", dtype=np.uint32), _bits(want_rgba).reshape(-1))
-    assert np.array_equal(np.fromfile(tmp_path / "hit.bin", dtype=np.uint32), _bits(want_hit).reshape(-1))
-    assert np.array_equal(np.fromfile(tmp_path / "wrgba.bin", dtype=np.uint32), _bits(win_rgba).reshape(-1))
-    assert np.array_equal(np.fromfile(tmp_path / "whit.bin", dtype=np.uint32), _bits(win_hit).reshape(-1))
+    assert np.array_equal(np.fromfile(tmp_path / "rgba.bin", dtype=np.uint32), bits(want_rgba).reshape(-1))
+    assert np.array_equal(np.fromfile(tmp_path / "hit.bin", dtype=np.uint32), bits(want_hit).reshape(-1))
+    assert np.array_equal(np.fromfile(tmp_path / "wrgba.bin", dtype=np.uint32), bits(win_rgba).reshape(-1))
+    assert np.array_equal(np.fromfile(tmp_path / "whit.bin", dtype=np.uint32), bits(win_hit).reshape(-1))
     st = out["st"]
     assert [st[k] for k in ("rays", "hits", "samples", "refineSamples", "skipped")] == \
         [want_st[k] for k in ("rays", "hits", "samples", "refine_samples", "skipped")]

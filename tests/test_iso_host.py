@@ -22,15 +22,13 @@ import pytest
 
 from tests import closed_form as CF
 from tests import iso_ref as IR
-from tests import test_phong_pins as PP
+from tests.common import F32, NAPI, ROOT
+from tests.shapes import ISO_CASES as CASES
+from tests.shapes import ISO_COLOUR as COLOUR
+from tests.shapes import ISO_PHONG as PHONG
+from tests.shapes import RAMP_M, SPACINGS, Field, field_rays, iso_params, phong_case, true_grad
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
-F32 = np.float32
 EPS32 = 2.0 ** -24
-COLOUR = (0.8, 0.5, 0.3)
-PHONG = (0.3, 0.7, 0.4, 32.0)
-L_OBL = (-0.4, -0.75, 0.53)
 
 
 # ---- the boundary ------------------------------------------------------------------------------------------------------
@@ -114,44 +112,14 @@ console.log(JSON.stringify({ methods: Object.getOwnPropertyNames(v.Volxel3DDicom
 
 
 # ---- closed forms of the restatement ------------------------------------------------------------------------------------
-class IsoCase:
-    def __init__(self, kind, spacing, iso, eye_off, refine=8, step=0.5, ortho=None, max_steps=1 << 20, light=L_OBL,
-                 phong=PHONG):
-        self.kind, self.spacing, self.iso, self.eye_off = kind, spacing, iso, eye_off
-        self.refine, self.step, self.ortho, self.max_steps = refine, step, ortho, max_steps
-        self.light, self.phong = light, phong
-
-
-CASES = {
-    "ramp_iso_persp": IsoCase("ramp", "iso", 0.5, (0.3, 0.25, -0.6)),
-    "ramp_aniso_ortho_r4": IsoCase("ramp", "aniso", 0.45, (-0.2, 0.3, -0.6), refine=4, step=0.25, ortho=0.25),
-    "ramp_iso_r0_step2": IsoCase("ramp", "iso", 0.55, (0.35, -0.2, -0.55), refine=0, step=2.0),
-    "ramp_aniso_maxsteps": IsoCase("ramp", "aniso", 0.6, (0.3, 0.25, -0.6), max_steps=12),
-    "ramp_iso_r16": IsoCase("ramp", "iso", 0.5, (-0.3, -0.25, -0.6), refine=16),
-    "bowl_iso_persp": IsoCase("bowl", "iso", 0.6, (0.3, 0.25, -0.6)),
-    "bowl_aniso_ortho": IsoCase("bowl", "aniso", 0.7, (-0.25, 0.3, -0.6), step=0.125, ortho=0.12),
-    "bowl_aniso_r2": IsoCase("bowl", "aniso", 0.55, (0.5, 0.1, -0.4), refine=2),
-    "flat_iso_caps": IsoCase("flat", "iso", 0.25, (0.3, 0.25, -0.6)),
-    "flat_aniso_misses": IsoCase("flat", "aniso", 0.75, (0.3, 0.25, -0.6), ortho=0.3),
-}
-
-
 @pytest.fixture(scope="module")
 def fields():
     from oracle import oracle as O
-    return {(k, sp): PP.Field(O, k, PP.SPACINGS[sp]) for k in ("flat", "ramp", "bowl") for sp in PP.SPACINGS}
-
-
-def _phong_case(case, fd):
-    return PP.Case(fd, case.eye_off, case.light, case.phong, step=case.step, ortho=case.ortho, max_steps=case.max_steps)
-
-
-def _params(case, fd):
-    return PP._params(_phong_case(case, fd), "dvr")
+    return {(k, sp): Field(O, k, SPACINGS[sp]) for k in ("flat", "ramp", "bowl") for sp in SPACINGS}
 
 
 def _ref(case, fd, **kw):
-    p = _params(case, fd)
+    p = iso_params(case, fd)
     args = dict(color=COLOUR, phong=case.phong, refine=case.refine)
     args.update(kw)
     return p, IR.isosurface(p, fd.grid, case.iso, **args)
@@ -167,7 +135,7 @@ class Model:
     half_minus (s* +- 1/2), flip (n = +g/|g|), cap_gradient (a cap shaded with the field's gradient instead of -d)."""
 
     def __init__(self, case, fd, variant=None):
-        o, d = PP._rays(_phong_case(case, fd))
+        o, d = field_rays(phong_case(case, fd))
         o = np.broadcast_to(o, d.shape)
         lo_box, hi_box = CF.world_box(fd.ext, fd.spacing, *fd.clip())
         dt, x, n, valid, pos = CF.march_samples(o, d, lo_box, hi_box, fd.ipw, case.step, case.max_steps)
@@ -281,7 +249,7 @@ class Model:
 
 def _ref_normal(case, fd, per):
     """the restatement's normal, from its rule (the same bits as its shading uses): the fp32 central difference, or -d"""
-    p = _params(case, fd)
+    p = iso_params(case, fd)
     vol = IR.NP.NpVolume(fd.grid)
     hit, n, q0, dq = IR.rays(p)
     o, d, _, _ = IR.world_rays(p)
@@ -361,7 +329,7 @@ def _analytic(case, fd, m, hit, per):
     d = m.d
     eps = fd.eps() + fd.curvature() + float(m.g.sum()) * m.dq + 2.0 ** -20
     if case.kind == "ramp":
-        slope = np.abs(fd.b * (d @ PP.RAMP_M))                # density per world unit along the ray
+        slope = np.abs(fd.b * (d @ RAMP_M))                # density per world unit along the ray
         err = np.abs(fd.f(w) - case.iso) / np.maximum(slope, 1e-300)
     else:
         R = math.sqrt((fd.A - case.iso) / fd.B)
@@ -389,7 +357,7 @@ def test_reference_hits_the_analytic_surface(fields, refs, name):
     w = hit[..., :3].astype(np.float64)
     exact = fd.normal(w)
     q = CF.world_to_index(w, fd.ext, fd.spacing) - 0.5
-    true_g = PP.Model._true_grad(fd, q)
+    true_g = true_grad(fd, q)
     dn = np.minimum(2.0, 2.0 * 2.0 * fd.eps() * np.linalg.norm(fd.ipw) / np.maximum(true_g, 1e-300)) + m.dn
     ok = np.linalg.norm(nrm - exact, axis=-1) <= dn
     assert ok[sel].all(), int((~ok & sel).sum())

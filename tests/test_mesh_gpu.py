@@ -6,15 +6,14 @@ box on a brick boundary.  Two calls and every layout return the same raw bytes; 
 rendering, the counters, the segment, its view and pick are left alone; refusals, staleness after an upload, a device group,
 the JS host and the world-space conventions."""
 import ctypes as C
-import json
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import mesh_ref as MR
 from tests import segment_ref as SG
-from tests.test_segment_gpu import (F32, LAYOUTS, NAPI, _densities, _grid, _odd, _renderer, _serpentine, _tube, _upload)
+from tests.common import F32, LAYOUTS, densities, grid, renderer, segment_volumes, upload_volume
+from tests.js_host import dump_grid, run_node
 
 BOXES = {"whole": None, "interior": ((5, 9, 3), (40, 30, 37)), "one_voxel": ((17, 18, 19), (17, 18, 19)),
          "brick_boundary": ((8, 16, 0), (23, 31, 15))}
@@ -22,10 +21,7 @@ BOXES = {"whole": None, "interior": ((5, 9, 3), (40, 30, 37)), "one_voxel": ((17
 
 @pytest.fixture(scope="module")
 def volumes():
-    from tests.common import small_noise
-    from volxel_amd import synth
-    return {"noise": _grid(*small_noise(64)), "phantom": _grid(*synth.ct_phantom(64)), "odd": _grid(*_odd()),
-            "serpentine": _grid(*_serpentine()), "tube": _grid(*_tube())}
+    return segment_volumes()
 
 
 def _raw(r, **kw):
@@ -62,9 +58,9 @@ def _isos(d):
 @pytest.mark.parametrize("vol", ["noise", "phantom", "odd"])
 def test_density_meshes_match_the_restatement_bit_for_bit(volumes, vol, layout):
     g = volumes[vol]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
-        d = _densities(vol, g, r.bind_uniforms())
+        d = densities(vol, g, r.bind_uniforms())
         Z, Y, X = d.shape
         isos = _isos(d)
         assert (d == F32(isos[1])).any()
@@ -103,9 +99,9 @@ def _touching_all_faces(shape):
 @pytest.mark.parametrize("layout", sorted(LAYOUTS))
 def test_segment_meshes_match_the_restatement_bit_for_bit(volumes, layout):
     g = volumes["noise"]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
-        d = _densities("noise", g, r.bind_uniforms())
+        d = densities("noise", g, r.bind_uniforms())
         lo = float(np.quantile(d, 0.7))
         z, y, x = np.unravel_index(int(np.argmax(d)), d.shape)
         s = r.segment((int(x), int(y), int(z)), lo, connectivity=26)
@@ -130,9 +126,9 @@ def test_segment_meshes_match_the_restatement_bit_for_bit(volumes, layout):
 @pytest.mark.parametrize("vol", ["serpentine", "tube"])
 def test_thin_and_long_volumes(volumes, vol):
     g = volumes[vol]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
-        d = _densities(vol, g, r.bind_uniforms())
+        d = densities(vol, g, r.bind_uniforms())
         iso = float(d.max()) / 2
         _same(_raw(r, iso=iso), MR.extract_density(d, iso), vol)
         _same_result(r.last_mesh_result, d >= F32(iso), None)
@@ -145,9 +141,9 @@ def test_every_layout_returns_the_same_raw_arrays_and_the_launch_count_is_consta
     g = volumes["phantom"]
     raws, launches = {}, set()
     for layout in sorted(LAYOUTS):
-        r = _renderer(g, layout=LAYOUTS[layout])
+        r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
         try:
-            d = _densities("phantom", g, r.bind_uniforms())
+            d = densities("phantom", g, r.bind_uniforms())
             out = []
             for iso in (0.75, 0.3, float(d.max()) * 2):
                 out.append(_raw(r, iso=iso))
@@ -167,7 +163,7 @@ def test_every_layout_returns_the_same_raw_arrays_and_the_launch_count_is_consta
 @pytest.mark.gpu
 def test_rendering_the_segment_its_view_and_pick_are_left_alone(volumes):
     g = volumes["phantom"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         r.bind_uniforms()
         s0 = r.segment((32, 32, 32), 0.3, connectivity=26)
@@ -224,9 +220,9 @@ def test_refusals_limits_and_staleness(volumes):
 
     try:
         refused(3, "no volume")
-        assert _upload(lib, ctx, g) == 0
+        assert upload_volume(lib, ctx, g) == 0
         refused(1, "vx_set_params")
-        r = _renderer(g)
+        r = renderer(g, dvr_jitter=False)
         try:
             p = r.bind_uniforms()
         finally:
@@ -268,7 +264,7 @@ def test_refusals_limits_and_staleness(volumes):
         assert lib.vx_mesh_extract(ctx, C.byref(q), None) == 0
         assert lib.vx_mesh_read(ctx, None, None, None) == 0
         # an upload drops the mesh
-        assert _upload(lib, ctx, g) == 0
+        assert upload_volume(lib, ctx, g) == 0
         refused(1, "no current mesh", lambda: lib.vx_mesh_read(ctx, None, None, None))
         assert lib.vx_mesh_extract(ctx, C.byref(q), C.byref(res)) == 0 and (int(res.vertices), int(res.triangles)) == (nv, nt)
     finally:
@@ -277,7 +273,7 @@ def test_refusals_limits_and_staleness(volumes):
 
 @pytest.mark.gpu
 def test_python_refusals_on_a_live_renderer(volumes):
-    r = _renderer(volumes["noise"])
+    r = renderer(volumes["noise"], dvr_jitter=False)
     try:
         with pytest.raises(ValueError, match="box"):
             r.extract_mesh(0.3, box=((0, 0, 0), (64, 5, 5)))
@@ -293,14 +289,14 @@ def test_python_refusals_on_a_live_renderer(volumes):
 @pytest.mark.gpu
 def test_device_group_runs_the_mesher_on_member0(volumes):
     g = volumes["noise"]
-    one = _renderer(g)
+    one = renderer(g, dvr_jitter=False)
     try:
         want = _raw(one, iso=0.3)
         one.segment((10, 10, 10), 0.2, connectivity=26)
         want_s = _raw(one, segment=True)
     finally:
         one.close()
-    grp = _renderer(g, devices=[0, 0])
+    grp = renderer(g, devices=[0, 0], dvr_jitter=False)
     try:
         got = _raw(grp, iso=0.3)
         grp.segment((10, 10, 10), 0.2, connectivity=26)
@@ -321,8 +317,8 @@ def _ball(n=64):
 
 @pytest.mark.gpu
 def test_world_space_agrees_with_voxel_index_and_pick():
-    g = _grid(*_ball())
-    r = _renderer(g, w=96, h=96)
+    g = grid(*_ball())
+    r = renderer(g, size=(96, 96), dvr_jitter=False)
     try:
         d = SG.densities(g, r.bind_uniforms().volume_density_scale, r.bind_uniforms().volume_inv_maj)
         iso = float(d.max()) * 0.75
@@ -353,11 +349,9 @@ def test_world_space_agrees_with_voxel_index_and_pick():
 
 @pytest.mark.gpu
 def test_js_host_has_the_python_arrays_and_stl_bytes(volumes, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
-    from volxel_amd import BENCHMARK_SETTINGS
     g = volumes["noise"]
     box = ((2, 3, 4), (50, 60, 61))
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         m = r.extract_mesh(0.3, space="voxel", box=box)
         m.write_stl(tmp_path / "py.stl")
@@ -366,32 +360,8 @@ def test_js_host_has_the_python_arrays_and_stl_bytes(volumes, tmp_path):
         launches = r.mesh_stats()[0]
     finally:
         r.close()
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, g.indirection_size)), "rangeSize": list(map(int, g.range_size)),
-        "atlasSize": list(map(int, g.atlas_size)), "indexExtent": list(map(int, g.index_extent)),
-        "minMaj": list(map(float, g.min_maj)), "transform": list(map(float, g.transform)),
-        "mips": [list(map(int, sz)) for _, sz in g.range_mipmaps]}))
-    np.asarray(g.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(g.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(g.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (mm, _) in enumerate(g.range_mipmaps):
-        np.asarray(mm, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
-const save = (f, m) => fs.writeFileSync(path.join(dir, f), Buffer.from(m.buffer, m.byteOffset, m.byteLength));
+    dump_grid(tmp_path, g)
+    body = r"""
 const m = r.extractMesh({ iso: 0.3, space: 'voxel', box: [[2, 3, 4], [50, 60, 61]] });
 save('v.bin', m.vertices); save('c.bin', m.cells); save('t.bin', m.triangles);
 fs.writeFileSync(path.join(dir, 'js.stl'), r.meshToStl(m));
@@ -405,8 +375,7 @@ try { r.extractMesh({ iso: 0.3, segment: true }); } catch (e) { both = String(e.
 console.log(JSON.stringify({ st: r.meshStats(), refused, both }));
 r.dispose();
 """
-    (tmp_path / "s.js").write_text(script)
-    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    out = run_node(tmp_path, body)
     assert np.array_equal(np.fromfile(tmp_path / "v.bin", dtype=np.float64).reshape(-1, 3), m.vertices)
     assert np.array_equal(np.fromfile(tmp_path / "c.bin", dtype=np.int32).reshape(-1, 3), m.cells)
     assert np.array_equal(np.fromfile(tmp_path / "t.bin", dtype=np.uint32).reshape(-1, 3), m.triangles)

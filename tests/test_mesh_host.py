@@ -18,9 +18,8 @@ import numpy as np
 import pytest
 
 from tests import mesh_ref as MR
-
-F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.common import F32, ROOT
+from tests.shapes import odd
 BALL_VOLUME_ERR = {32: 0.012397, 64: 0.003105, 128: 0.000776}
 BALL_AREA_ERR = {32: 0.006750, 64: 0.001652, 128: 0.000415}
 SEGMENT_VOLUME_ERR = {32: 0.026843, 64: 0.009019, 128: 0.001542}
@@ -48,8 +47,7 @@ def _phantom():
 
 
 def _odd_field():
-    from tests.test_segment_gpu import _odd
-    v, _ = _odd()
+    v, _ = odd()
     out = np.zeros((48, 32, 40), dtype=F32)
     out[:45, :29, :37] = v.astype(F32) / F32(4095)
     return out

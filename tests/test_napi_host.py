@@ -10,8 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
+from tests.common import NAPI, ROOT
 
 pytestmark = pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 

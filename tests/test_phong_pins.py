@@ -23,117 +23,13 @@ import numpy as np
 import pytest
 
 from tests import closed_form as CF
+from tests import common
+from tests.shapes import DIMS, FIELD_RES, SPACINGS, Case, Field, field_params, field_rays, true_grad
 
 EPS32 = 2.0 ** -24
-LAYOUTS = {"reference": 0, "cellquad": 1, "brickf32": 2, "bricku8": 4}
-W, H = 40, 30
+LAYOUTS = {k: common.LAYOUTS[k] for k in ("reference", "cellquad", "brickf32", "bricku8")}
+W, H = FIELD_RES
 COLOUR = np.array([0.8, 0.5, 0.3])
-SPACINGS = {"iso": (1.0, 1.0, 1.0), "aniso": (0.5, 0.75, 1.25)}
-DIMS = (21, 29, 33)                     # z, y, x: ragged, padded to a 64^3 index extent
-VMAX = 4095
-
-
-def _normalised(v):
-    v = np.asarray(v, float)
-    return v / np.linalg.norm(v)
-
-
-def _ext(spacing):
-    return (64, 64, 64)
-
-
-def _data_world(spacing):
-    """(centre, half extent) of the data's box in world space"""
-    ext = _ext(spacing)
-    lo = CF.index_to_world(np.zeros(3), ext, spacing)
-    hi = CF.index_to_world(np.array(DIMS[::-1], float), ext, spacing)
-    return 0.5 * (lo + hi), 0.5 * (hi - lo)
-
-
-RAMP_M = _normalised((0.48, -0.6, 0.64))
-
-
-class Field:
-    """a field given in world space, its u16 stack (code VMAX = density 1) and the oracle's decoded voxels"""
-
-    def __init__(self, oracle, kind, spacing):
-        self.kind, self.spacing = kind, np.asarray(spacing, float)
-        self.ext = _ext(spacing)
-        self.ipw = CF.index_per_world(spacing, self.ext)
-        self.c, _ = _data_world(spacing)
-        z, y, x = np.meshgrid(*[np.arange(n) for n in DIMS], indexing="ij")
-        w = CF.index_to_world(np.stack([x + 0.5, y + 0.5, z + 0.5], axis=-1), self.ext, spacing)
-        if kind == "flat":
-            ideal = np.full(DIMS, 0.5)
-            vox = np.full(DIMS, 2000, np.uint16)
-            vox[-1, -1, -1] = 4000
-            self.grid = oracle.BrickGrid(vox, tuple(spacing))
-            self.ideal = ideal
-            self.dec = CF.decode(oracle, self.grid)
-            self.cut = 0.25
-            self.margin = (9, 9, 9)             # voxels: keeps the gradient taps clear of the brick of the brighter corner
-            return
-        if kind == "ramp":
-            self.b = 0.4 / float(np.abs((w - self.c) @ RAMP_M).max())
-            self.cut = 0.5                      # the iso-plane through the data's centre
-        else:
-            # the ball f >= cut has world radius R, R - 2 voxels inside the data on every axis; f stays positive to 1.6 R
-            self.R = float(((np.array(DIMS[::-1]) / 2.0 - 3.0) / self.ipw).min())
-            self.A, self.B, self.cut = 0.95, 0.35 / self.R ** 2, 0.6
-        self.ideal = self.f(w)
-        assert self.ideal.min() > 0.0 if kind == "ramp" else True
-        self.grid = oracle.BrickGrid(np.round(np.clip(self.ideal, 0.0, 1.0) * VMAX).astype(np.uint16), tuple(spacing),
-                                     max_value=VMAX)
-        self.dec = CF.decode(oracle, self.grid)
-        self.margin = (2, 2, 2)
-
-    def f(self, w):
-        if self.kind == "ramp":
-            return 0.5 + self.b * ((w - self.c) @ RAMP_M)
-        return self.A - self.B * ((w - self.c) ** 2).sum(axis=-1)
-
-    def normal(self, w):
-        """the exact outward normal -grad f / |grad f|"""
-        if self.kind == "ramp":
-            return np.broadcast_to(-RAMP_M, w.shape)
-        r = w - self.c
-        return r / np.maximum(np.linalg.norm(r, axis=-1, keepdims=True), 1e-300)
-
-    def clip(self):
-        """the clip box as fractions of the index extent: the data with `margin` voxels off every face (taps included)"""
-        d = np.array(DIMS[::-1], float)
-        m = np.array(self.margin, float)
-        if self.kind == "bowl":          # the ball and 1.5 voxels around it
-            lo = self.c - (self.R + 1.5 / self.ipw)
-            hi = self.c + (self.R + 1.5 / self.ipw)
-            return tuple(CF.world_to_index(lo, self.ext, self.spacing) / 64.0), tuple(CF.world_to_index(hi, self.ext, self.spacing) / 64.0)
-        return tuple(m / 64.0), tuple((d - m) / 64.0)
-
-    def eps(self):
-        """the codec's voxel error over the data: max |decode - ideal|"""
-        nz, ny, nx = DIMS
-        return float(np.abs(self.dec[:nz, :ny, :nx] - np.round(np.clip(self.ideal, 0, 1) * VMAX) / VMAX).max()
-                     + 0.5 / VMAX)
-
-    def curvature(self):
-        """the trilinear's largest error on the field, sum_a a_a / 4, a_a the index-space quadratic coefficient"""
-        if self.kind != "bowl":
-            return 0.0
-        return float((self.B / self.ipw ** 2).sum() / 4.0)
-
-
-class Case:
-    def __init__(self, field, eye_off, light, phong, step=0.5, alpha=0.08, ortho=None, max_steps=1 << 20, ert_eps=1e-4,
-                 env=False, look_off=(0.0, 0.0, 0.0), inside=False):
-        self.look = field.c + np.asarray(look_off, float)
-        # inside: the eye sits at eye_off from the data's centre, inside the clip box
-        self.eye = (field.c if inside else self.look) + np.asarray(eye_off, float)
-        if light is None:      # the light shines toward the camera from a little off the view axis
-            light = -_normalised(-_normalised(eye_off) + np.array([0.12, 0.06, 0.0]))
-        self.field, self.light = field, _normalised(light)
-        self.phong, self.step, self.alpha, self.ortho = phong, step, alpha, ortho
-        self.max_steps, self.ert_eps, self.env = max_steps, ert_eps, env
-        self.inside = inside
 
 
 def _cases(fields):
@@ -161,13 +57,6 @@ def _cases(fields):
     }
 
 
-def _rays(case):
-    if case.ortho is None:
-        (d,), _ = CF.camera_rays(case.eye, case.look, W, H)
-        return np.broadcast_to(case.eye, d.shape), d
-    return CF.ortho_rays(case.eye, case.look, W, H, case.ortho)
-
-
 def _gain(env):
     """K = albedo mis f_p Le (fragment.frag:94-97): mis = 1 / (1 + f_p^2) with the environment shown, else 1"""
     f_p = 1.0 / (4.0 * math.pi)
@@ -183,7 +72,7 @@ class Model:
 
     def __init__(self, case, analytic=False, variant=None):
         fd, self.case = case.field, case
-        o, d = _rays(case)
+        o, d = field_rays(case)
         self.d = d
         lo, hi = CF.world_box(fd.ext, fd.spacing, *fd.clip())
         dt, x, n, valid, pos = CF.march_samples(o, d, lo, hi, fd.ipw, case.step, case.max_steps)
@@ -267,7 +156,7 @@ class Model:
             # 2 G_true by 2 eps ipw_i per axis; the trilinear of the field adds its curvature term to the density
             eps = fd.eps()
             err_G = 2.0 * eps * np.linalg.norm(fd.ipw) * np.ones(q.shape[:-1])
-            dn = np.minimum(2.0, 2.0 * err_G / np.maximum(self._true_grad(fd, q), 1e-300))
+            dn = np.minimum(2.0, 2.0 * err_G / np.maximum(true_grad(fd, q), 1e-300))
             d_band = eps + fd.curvature() + float(g.sum()) * dq + 4 * EPS32
         else:
             # fp32: each trilinear within 8 ulps of 1, D_i within 2^-20; a position error dq moves D_i by at most
@@ -313,34 +202,12 @@ class Model:
         # every sample it has: its count may differ by up to n + 1
         self.count_slack = int((n + 1)[~self.exact_count].sum())
 
-    @staticmethod
-    def _true_grad(fd, q):
-        """|2 grad_w f| in units of D ipw: the ramp's 2 b, the bowl's 4 B |w - c| (the device's D = 2 df/dindex)"""
-        w = CF.index_to_world(q + 0.5, fd.ext, fd.spacing)
-        if fd.kind == "ramp":
-            return 2.0 * fd.b * np.ones(q.shape[:-1])
-        if fd.kind == "bowl":
-            return 4.0 * fd.B * np.linalg.norm(w - fd.c, axis=-1)
-        return np.zeros(q.shape[:-1])
-
     def check(self, img):
         """per pixel and channel |img - model| <= tol; returns observed / allowed"""
         err = np.abs(img[..., :3].astype(np.float64) - self.img)
         ok = err <= self.tol[..., None]
         assert ok.all(), (int((~ok).sum()), float((err / self.tol[..., None]).max()))
         return float((err / self.tol[..., None]).max())
-
-
-def _params(case, mode, skip=False):
-    from tests.common import make_scene
-    fd = case.field
-    lo, hi = fd.clip()
-    _, _, _, _, p = make_scene(fd.grid, W, H, mode, cam_pos=tuple(case.eye), look_at=tuple(case.look), clip_min=lo,
-                               clip_max=hi, ortho=case.ortho, show_environment=case.env, use_env=False,
-                               light_dir=tuple(case.light), dvr_step_voxels=case.step, dvr_max_steps=case.max_steps,
-                               dvr_ert_epsilon=case.ert_eps, dvr_jitter=False, dvr_skip_empty=skip,
-                               sample_range=(fd.cut, 1.0), phong=case.phong)
-    return p
 
 
 def _case_tf(case, L=16):
@@ -374,7 +241,7 @@ def test_phong_scene_geometry_is_hand_derived(fields):
     """the hand-written maps equal the uniforms: density_transform_inv's diagonal is index per world (S / spacing),
     volume_maj = volume_density_scale = S, and the clip box, camera and light reach the uniforms as given"""
     for (kind, sp), fd in fields.items():
-        p = _params(Case(fd, (0.3, 0.25, -0.6), (0.0, -1.0, 0.0), (0.3, 0.7, 0.4, 32.0)), "dvr_phong")
+        p = field_params(Case(fd, (0.3, 0.25, -0.6), (0.0, -1.0, 0.0), (0.3, 0.7, 0.4, 32.0)), "dvr_phong")
         m = np.asarray(p.density_transform_inv[:], dtype=np.float64).reshape(4, 4).T
         assert np.allclose(np.diag(m)[:3], fd.ipw, rtol=1e-7, atol=0)
         S = CF.world_scale(fd.ext, fd.spacing)
@@ -437,7 +304,7 @@ def test_phong_oracle_meets_closed_form(cases, models, name):
     Counters: samples per ray and grad_samples exactly, except on the rays with an ambiguous decision above."""
     from oracle import oracle as O
     c, m = cases[name], models[name]
-    p = _params(c, "dvr_phong")
+    p = field_params(c, "dvr_phong")
     img, oc, per_ray = O.render(p, c.field.grid, _case_tf(c), 16, ray_samples=True)
     margin = m.check(img)
     assert float(m.img.max()) > 0.02, "the case shows nothing"
@@ -466,8 +333,8 @@ def test_phong_flat_field_equals_dvr_on_the_oracle(fields, spacing):
         c = _cases(fields)[name]
         if c.field is not fields["flat", spacing]:
             continue
-        a, ca = O.render(_params(c, "dvr"), c.field.grid, _case_tf(c), 16)
-        b, cb = O.render(_params(c, "dvr_phong"), c.field.grid, _case_tf(c), 16)
+        a, ca = O.render(field_params(c, "dvr"), c.field.grid, _case_tf(c), 16)
+        b, cb = O.render(field_params(c, "dvr_phong"), c.field.grid, _case_tf(c), 16)
         assert np.array_equal(a, b)
         assert cb.grad_samples == cb.samples == ca.samples > 100
 
@@ -501,7 +368,7 @@ def _render(case, mode, layout, skip):
     try:
         r.setup_from_grid(fd.grid)
         r.change_transfer_func(_case_tf(case), 16)
-        r._check(r._lib.vx_set_params(r._ctx, C.byref(_params(case, mode, skip))))
+        r._check(r._lib.vx_set_params(r._ctx, C.byref(field_params(case, mode, skip))))
         r.reset_counters()
         r._check(r._lib.vx_render_frame(r._ctx, 0, 0.0))
         return r.read_accum(), r.counters()

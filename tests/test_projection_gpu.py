@@ -6,58 +6,33 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import common
 from tests import projection_ref as PR
+from tests.common import bits, frame, grid, renderer, small_noise
 
 W, H = 96, 64
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1}
+LAYOUTS = {k: common.LAYOUTS[k] for k in ("brickf32", "bricku8", "reference", "cellquad")}
 MODES = ("mip", "minip")
-
-
-def _grid(vox, sp):
-    from volxel_amd import read_u16_stack_to_grid
-    return read_u16_stack_to_grid(vox, sp)
+SETTINGS = dict(volume_clip_min=(0.25, 0.0, 0.0), volume_clip_max=(1.0, 1.0, 0.75), dvr_step_voxels=0.5, dvr_jitter=False,
+                dvr_skip_empty=False, max_samples=1 << 20)
 
 
 @pytest.fixture(scope="module")
 def noise():
-    from tests.common import small_noise
-    return _grid(*small_noise(64))
+    return grid(*small_noise(64))
 
 
 @pytest.fixture(scope="module")
 def ct():
     from volxel_amd import synth
-    return _grid(*synth.ct_phantom(64))
+    return grid(*synth.ct_phantom(64))
 
 
-def _scene(g, mode, layout=None, size=(W, H), **kw):
-    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
-    devices = kw.pop("devices", None)
-    r = Volxel3DRenderer(size[0], size[1], device=None if devices else 0, layout=layout, devices=devices)
-    r.setup_from_grid(g)
-    r.restore_settings(BENCHMARK_SETTINGS)
-    s = r.settings
-    s.render_mode = mode
-    s.volume_clip_min = (0.25, 0.0, 0.0)
-    s.volume_clip_max = (1.0, 1.0, 0.75)
-    s.dvr_step_voxels = 0.5
-    s.dvr_jitter = False
-    s.dvr_skip_empty = False
-    s.max_samples = 1 << 20
-    for k, v in kw.items():
-        setattr(s, k, v)
+def _scene(g, mode, layout=None, size=(W, H), devices=None, **kw):
+    r = renderer(g, layout, devices, mode, size, **SETTINGS)
+    for k, v in kw.items():     # after the pinned ones: a test may set one of them again
+        setattr(r.settings, k, v)
     return r
-
-
-def _frame(r, frames=1, in_flight=1):
-    r.restart_rendering()
-    r.reset_counters()
-    r.render(frames=frames, in_flight=in_flight)
-    return r.read_accum(), r.counters()
-
-
-def _bits(a):
-    return a.view(np.uint32)
 
 
 @pytest.mark.gpu
@@ -66,7 +41,7 @@ def _bits(a):
 def test_image_matches_reference(noise, layout, mode):
     r = _scene(noise, mode, layout=LAYOUTS[layout])
     try:
-        img, c = _frame(r)
+        img, c = frame(r)
         tf, L = r._tf
         want, n, ntf, rays = PR.projection_image(r._params, noise, tf, L, minip=mode == "minip")
     finally:
@@ -85,12 +60,12 @@ def test_range_skipping_is_exact(request, scene, layout, mode):
     g = request.getfixturevalue(scene)
     r = _scene(g, mode, layout=LAYOUTS[layout])
     try:
-        off, c_off = _frame(r)
+        off, c_off = frame(r)
         r.settings.dvr_skip_empty = True
-        on, c_on = _frame(r)
+        on, c_on = frame(r)
     finally:
         r.close()
-    assert np.array_equal(_bits(on), _bits(off))
+    assert np.array_equal(bits(on), bits(off))
     assert c_off.skip_steps == 0
     assert c_on.samples + c_on.skip_steps == c_off.samples
     assert c_on.tf_samples == c_off.tf_samples and c_on.rays == c_off.rays
@@ -108,21 +83,21 @@ def test_kernels_and_launch_shapes_agree(ct, monkeypatch, layout, mode):
     kw = dict(dvr_jitter=True, dvr_skip_empty=True)
     r = _scene(ct, mode, layout=LAYOUTS[layout], **kw)
     try:
-        a, ca = _frame(r, 66, 32)
-        b, cb = _frame(r, 66, 1)
+        a, ca = frame(r, 66, 32)
+        b, cb = frame(r, 66, 1)
     finally:
         r.close()
     monkeypatch.setenv("VX_DVR_KERNEL", "generic")
     gr = _scene(ct, mode, layout=LAYOUTS[layout], **kw)
     try:
-        g, cg = _frame(gr, 66, 32)
+        g, cg = frame(gr, 66, 32)
     finally:
         gr.close()
     assert ca.max_launch_frames == 32 and cb.max_launch_frames == 1
     if layout == "brickf32":
         assert ca.merge_launches == 0      # the kernel folded the running mean itself
-    assert np.array_equal(_bits(a), _bits(b))
-    assert np.array_equal(_bits(a), _bits(g))
+    assert np.array_equal(bits(a), bits(b))
+    assert np.array_equal(bits(a), bits(g))
     assert ca.samples + ca.skip_steps == cb.samples + cb.skip_steps == cg.samples + cg.skip_steps
     assert cg.skip_steps == 0 and ca.tf_samples == cg.tf_samples
 
@@ -134,12 +109,12 @@ def test_group_matches_one_context(ct, mode):
     one = _scene(ct, mode, **kw)
     grp = _scene(ct, mode, devices=[0, 0, 0], **kw)
     try:
-        a, ca = _frame(one, 32, 32)
-        b, cb = _frame(grp, 32, 32)
+        a, ca = frame(one, 32, 32)
+        b, cb = frame(grp, 32, 32)
     finally:
         one.close()
         grp.close()
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(bits(a), bits(b))
     assert (ca.samples, ca.skip_steps, ca.rays, ca.tf_samples, ca.pixels) == \
         (cb.samples, cb.skip_steps, cb.rays, cb.tf_samples, cb.pixels)
 
@@ -175,10 +150,10 @@ def test_refusals(noise):
 def test_full_size_ct(mode):
     """BASELINE config 2 (256^3 CT phantom) at 1920x1080, skipping on, on a centred 160 x 96 crop"""
     from volxel_amd import synth
-    g = _grid(*synth.ct_phantom(256))
+    g = grid(*synth.ct_phantom(256))
     r = _scene(g, mode, size=(1920, 1080), dvr_skip_empty=True)
     try:
-        img, c = _frame(r)
+        img, c = frame(r)
         tf, L = r._tf
         win = (880, 492, 1040, 588)
         want, n, ntf, rays = PR.projection_image(r._params, g, tf, L, minip=mode == "minip", window=win)

@@ -12,8 +12,7 @@ import pytest
 from oracle import np_oracle as NP
 from tests import projection_ref as PR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = np.float32
+from tests.common import F32, ROOT, oracle_grid
 
 
 def test_header_modes_match_abi():
@@ -61,11 +60,6 @@ def test_js_render_mode_table_carries_the_modes():
     assert "mip: 5; minip: 6" in dts
 
 
-def _grid(vox, sp=(1.0, 1.0, 1.0)):
-    from oracle import oracle as O
-    return O.BrickGrid(vox, sp)
-
-
 def _tf():
     from tests.common import benchmark_tf
     return benchmark_tf()
@@ -76,7 +70,7 @@ def test_constant_volume_gives_tf_of_the_constant(minip):
     from tests.common import make_scene
     vox = np.full((64, 64, 64), 1000, dtype=np.uint16)   # (64^3: the index space is the data's)
     vox[0, 0, 0] = 4095      # outside the clip box: the constant normalises to 1000 / 4095, inside the sample range
-    g = _grid(vox)
+    g = oracle_grid(vox)
     tf, L = _tf()
     s, cam, vol, ds, p = make_scene(g, 24, 16, "mip", sample_range=(0.0, 1.0), clip_min=(0.25, 0.25, 0.25),
                                     clip_max=(0.75, 0.75, 0.75))
@@ -95,7 +89,7 @@ def test_axis_ramp_under_the_ortho_camera_gives_its_last_and_first_samples():
     from tests.common import make_scene
     z = np.arange(64, dtype=np.float64)
     vox = np.broadcast_to((100 + 30 * z)[:, None, None], (64, 64, 64)).astype(np.uint16).copy()
-    g = _grid(vox)
+    g = oracle_grid(vox)
     tf, L = _tf()
     s, cam, vol, ds, p = make_scene(g, 16, 16, "mip", cam_pos=(0.0, 0.0, -1.0), look_at=(0.0, 0.0, 0.0), ortho=0.2,
                                     sample_range=(0.0, 1.0), clip_min=(0.2, 0.2, 0.2), clip_max=(0.8, 0.8, 0.8))
@@ -150,7 +144,7 @@ def _check_bounds(lib, g, p, per_axis=9):
 
 def test_bounds_hold_on_small_noise(native_lib):
     from tests.common import make_scene, small_noise
-    g = _grid(*small_noise(64))
+    g = oracle_grid(*small_noise(64))
     p = make_scene(g, 8, 8, "mip")[4]
     b, n = _check_bounds(native_lib, g, p)
     assert n > 100000
@@ -164,7 +158,7 @@ def test_bounds_hold_at_the_range_limits(native_lib):
     vox = np.where(rs.random((48, 40, 56)) < 0.5, 0, 4095).astype(np.uint16)
     vox[:, :, :8] = 4095
     vox[20:, 8:16, :] = rs.integers(3000, 3100, size=vox[20:, 8:16, :].shape)
-    g = _grid(vox, (1.0, 1.0, 1.0))
+    g = oracle_grid(vox, (1.0, 1.0, 1.0))
     for mult in (1.0, 37.0, 1e-3):
         p = make_scene(g, 8, 8, "mip", density_multiplier=mult)[4]
         _check_bounds(native_lib, g, p, per_axis=5)
@@ -172,7 +166,7 @@ def test_bounds_hold_at_the_range_limits(native_lib):
 
 def test_bounds_do_not_skip_without_a_positive_scale(native_lib):
     from tests.common import make_scene, small_noise
-    g = _grid(*small_noise(32))
+    g = oracle_grid(*small_noise(32))
     p = make_scene(g, 8, 8, "mip")[4]
     p.volume_density_scale = 0.0
     b, _ = _bounds(native_lib, g, p)

@@ -7,15 +7,15 @@ alone; refusals, staleness after an upload, device groups and the JS host."""
 import ctypes as C
 import json
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import segedit_ref as ER
 from tests import segment_ref as SG
-from tests.test_segment_gpu import (CASES, F32, LAYOUTS, NAPI, _densities, _grid, _odd, _renderer, _resolve,
-                                    _serpentine, _tube, _upload)
+from tests.common import F32, LAYOUTS, densities, frame, renderer, segment_volumes, upload_volume
+from tests.js_host import dump_grid, run_node
+from tests.shapes import CASES, resolve, same_stats, shape_of, uploaded_shapes
 
 STEPS = (1, 2, 3, 8, 9, 17)   # past one brick (8) and past two (17)
 STEP_OPS = ("dilate", "erode", "open", "close")
@@ -23,23 +23,7 @@ STEP_OPS = ("dilate", "erode", "open", "close")
 
 @pytest.fixture(scope="module")
 def volumes():
-    from tests.common import small_noise
-    from volxel_amd import synth
-    return {"noise": _grid(*small_noise(64)), "phantom": _grid(*synth.ct_phantom(64)), "odd": _grid(*_odd()),
-            "serpentine": _grid(*_serpentine()), "tube": _grid(*_tube())}
-
-
-def _shape(g):
-    X, Y, Z = (int(e) for e in g.index_extent)
-    return (Z, Y, X)
-
-
-def _same_stats(s, mask, d):
-    st = SG.stats(mask, d)
-    assert s.count == st["count"] and s.bbox_lo == st["bbox_lo"] and s.bbox_hi == st["bbox_hi"], (s, st)
-    assert F32(s.d_min) == F32(st["d_min"]) and F32(s.d_max) == F32(st["d_max"]), (s, st)
-    assert abs(s.d_sum - st["d_sum"]) <= 1e-9 * abs(st["d_sum"]), (s.d_sum, st["d_sum"])
-    assert s.converged
+    return segment_volumes()
 
 
 def _edit_twice(r, start, d, op, conn, n=1, band=None):
@@ -51,7 +35,7 @@ def _edit_twice(r, start, d, op, conn, n=1, band=None):
         s = r.segment_edit(op, steps=1 if op == "fill_holes" else n, connectivity=conn, band=band is not None)
         m = r.segment_mask()
         assert np.array_equal(SG.packed(m), SG.packed(want)), (op, conn, n, int(m.sum()), int(want.sum()))
-        _same_stats(s, want, d)
+        same_stats(s, want, d)
         if op != "fill_holes":
             assert s.rounds == 0 and s.brick_visits == 0
         got.append(s)
@@ -60,25 +44,7 @@ def _edit_twice(r, start, d, op, conn, n=1, band=None):
     return got[0], want
 
 
-def _uploaded_shapes(shape):
-    """shapes that cross brick faces, edges and corners and touch all six faces of the volume: blobs (wrapped noise), cubes in
-    two opposite corners of the volume, a box around the brick corner (8, 8, 8), a diagonal chain through brick corners, a
-    hollow shell across several bricks and a one-voxel plate on the brick face z = 16"""
-    Z, Y, X = shape
-    m = ER.blobs(shape, seed=11, sigma=2.0, q=0.8)
-    m[:3, :3, :3] = True
-    m[Z - 4:, Y - 4:, X - 4:] = True
-    m[6:11, 6:11, 6:11] = True
-    for k in range(min(shape) - 2):
-        m[k + 1, k, k] = True
-    m |= ER.shell(shape, (13, 5, 19), (27, 26, 37))
-    m[16, 9:23, 3:X - 2] = True
-    for a in range(3):   # all six faces
-        assert m.take(0, axis=a).any() and m.take(-1, axis=a).any()
-    return m
-
-
-# (volume, its vx_segment case of tests/test_segment_gpu.py -- or None: a mask built on the host).  The stack with odd sides is
+# (volume, its vx_segment case of tests/shapes.py -- or None: a mask built on the host).  The stack with odd sides is
 # mostly padding, so its case there (lo = the 0.55 quantile = 0) is the whole volume, which no edit changes: q0.9 here.
 STARTS = {"noise": ("noise", CASES["noise_q70"]), "phantom": ("phantom", CASES["phantom_bone"]),
           "odd": ("odd", ("odd", "max", "q0.9", None, None)), "tube": ("tube", CASES["tube"]),
@@ -89,11 +55,11 @@ def _start(r, g, name):
     """the start mask of STARTS[name] (from vx_segment, or built on the host) and the densities"""
     vol, case = STARTS[name]
     p = r.bind_uniforms()
-    d = _densities(vol, g, p)
+    d = densities(vol, g, p)
     if case is None:
-        return _uploaded_shapes(_shape(g)), d
+        return uploaded_shapes(shape_of(g)), d
     _, seed, lo, hi, box = case
-    seed, lo_v, hi_v, _ = _resolve(d, seed, lo, hi, box)
+    seed, lo_v, hi_v, _ = resolve(d, seed, lo, hi, box)
     s = r.segment(seed, lo_v, hi_v, connectivity=6, box=box)
     assert s.count > 0
     return r.segment_mask(), d
@@ -104,13 +70,13 @@ def _start(r, g, name):
 @pytest.mark.parametrize("conn", [6, 26])
 def test_every_op_matches_the_restatement(volumes, start, conn):
     g = volumes[STARTS[start][0]]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         m0, d = _start(r, g, start)
         if STARTS[start][1] is not None:   # straight from vx_segment, without an upload in between
             s = r.segment_edit("dilate", steps=2, connectivity=conn)
             assert np.array_equal(r.segment_mask(), ER.edit(m0, "dilate", conn, 2))
-            _same_stats(s, ER.edit(m0, "dilate", conn, 2), d)
+            same_stats(s, ER.edit(m0, "dilate", conn, 2), d)
         changed = 0
         for op in STEP_OPS:
             for n in STEPS:
@@ -129,7 +95,7 @@ def test_every_op_matches_the_restatement(volumes, start, conn):
 def test_every_layout_gives_the_same_edit(volumes, layout):
     """only the statistics read the volume"""
     g = volumes["odd"]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         m0, d = _start(r, g, "odd")
         for op, conn, n in (("close", 26, 3), ("erode", 6, 2), ("dilate", 26, 9), ("fill_holes", 6, 1)):
@@ -143,11 +109,11 @@ def test_every_layout_gives_the_same_edit(volumes, layout):
 def test_band_dilation(volumes, conn):
     from volxel_amd import VolxelError
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
-        seed, lo, hi, pred = _resolve(d, "max", "q0.6", "q0.95", ((3, 0, 5), (60, 50, 63)))
+        d = densities("noise", g, p)
+        seed, lo, hi, pred = resolve(d, "max", "q0.6", "q0.95", ((3, 0, 5), (60, 50, 63)))
         box = ((3, 0, 5), (60, 50, 63))
         r.segment(seed, lo, hi, connectivity=6, box=box)
         m = r.segment_mask()
@@ -163,7 +129,7 @@ def test_band_dilation(volumes, conn):
             assert np.array_equal(got, want) and not (got & ~pred).any() and got.sum() > core.sum()
             if n >= 3:   # (one 6-step from a core eroded by 2 stays inside the old segment, hence inside P)
                 assert not np.array_equal(want, ER.edit(core, "dilate", conn, n))   # the band matters here
-            _same_stats(s, want, d)
+            same_stats(s, want, d)
         # after a fill: the predicate words of vx_segment survive the fill's own flood
         r.set_segment_mask(core)
         r.segment_edit("fill_holes", connectivity=conn)
@@ -197,11 +163,11 @@ def test_band_dilation(volumes, conn):
 @pytest.mark.gpu
 def test_write_read_round_trip_and_the_trivial_masks(volumes):
     g = volumes["odd"]                         # a 37 x 29 x 45 stack: the padding behind it is part of the mask
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("odd", g, p)
-        shape = _shape(g)
+        d = densities("odd", g, p)
+        shape = shape_of(g)
         assert shape[0] > 45 and shape[1] > 29 and shape[2] > 37
         m = np.random.default_rng(3).random(shape) < 0.37
         s = r.set_segment_mask(m)              # on a context that never ran vx_segment
@@ -209,7 +175,7 @@ def test_write_read_round_trip_and_the_trivial_masks(volumes):
         assert r._lib.vx_segment_read_mask(r._ctx, bits.ctypes.data, bits.size) == 0
         assert np.array_equal(bits, SG.packed(m))
         assert m[45:].any() and m[:, 29:].any() and m[:, :, 37:].any()
-        _same_stats(s, m, d)
+        same_stats(s, m, d)
         assert s.rounds == 0 and s.brick_visits == 0
         assert r.set_segment_mask(m).d_sum == s.d_sum
         zero, one = np.zeros(shape, dtype=bool), np.ones(shape, dtype=bool)
@@ -233,10 +199,10 @@ def test_fill_holes_on_the_phantoms_soft_tissue_and_the_serpentine(volumes, conn
     from volxel_amd import synth
     vox, _ = synth.ct_phantom(64)
     g = volumes["phantom"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("phantom", g, p)
+        d = densities("phantom", g, p)
         lo, hi = float(d[vox >= 1000].min()), float(d[vox <= 1300].max())     # raw 1000 .. 1300: d is monotone in the raw value
         a = r.segment((32, 32, 32), lo, hi, connectivity=conn)
         m = r.segment_mask()
@@ -247,17 +213,17 @@ def test_fill_holes_on_the_phantoms_soft_tissue_and_the_serpentine(volumes, conn
         assert np.array_equal(f, want)
         assert b.count - a.count == 8538 and (b.bbox_lo, b.bbox_hi) == (a.bbox_lo, a.bbox_hi)   # lungs, spine and ribs
         assert b.rounds > 0 and b.brick_visits > 0 and b.converged
-        _same_stats(b, want, d)
+        same_stats(b, want, d)
         assert f[32, 32, 47] and not m[32, 32, 47]                              # inside a lung
         c = r.segment_edit("fill_holes", connectivity=conn)                     # idempotent
         assert c.count == b.count and np.array_equal(r.segment_mask(), f)
     finally:
         r.close()
     g = volumes["serpentine"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("serpentine", g, p)
+        d = densities("serpentine", g, p)
         a = r.segment((0, 0, 0), float(d.max()) / 2, connectivity=conn)
         m = r.segment_mask()
         b = r.segment_edit("fill_holes", connectivity=conn)
@@ -274,12 +240,12 @@ def test_overlay_views_and_pick_read_the_edited_mask(volumes):
 
     def bone(r):
         p = r.bind_uniforms()
-        d = _densities("phantom", g, p)
-        seed, lo, hi, _ = _resolve(d, "max", 0.75, None, None)
+        d = densities("phantom", g, p)
+        seed, lo, hi, _ = resolve(d, "max", 0.75, None, None)
         r.segment(seed, lo, connectivity=6)
         return d
 
-    r = _renderer(g, layout=LAYOUTS["brickf32"])
+    r = renderer(g, layout=LAYOUTS["brickf32"], dvr_jitter=False)
     images = {}
     try:
         bone(r)
@@ -308,7 +274,7 @@ def test_overlay_views_and_pick_read_the_edited_mask(volumes):
         assert any(not m0[v[2], v[1], v[0]] for v in vis)
     finally:
         r.close()
-    r = _renderer(g, layout=LAYOUTS["brickf32"])
+    r = renderer(g, layout=LAYOUTS["brickf32"], dvr_jitter=False)
     try:
         r.set_segment_mask(em)                 # a fresh renderer: the same mask installed from the host
         r.segment_view = "only"
@@ -329,23 +295,23 @@ def test_segment_view_of_an_edited_mask_matches_the_segview_restatement(volumes,
     """one small case against tests/segview_ref.py: the MIP of the view of an edited mask is, bit for bit, the projection of
     the volume whose hidden voxels decode to 0, with its counters"""
     from tests import segview_ref as SV
-    from tests.test_segview_gpu import _frame, _scene
     g = volumes["noise"]
-    r = _scene(g, "mip", layout=LAYOUTS["brickf32"], dvr_skip_empty=True, use_env=False, show_environment=False)
+    r = renderer(g, layout=LAYOUTS["brickf32"], mode="mip", size=(96, 64), dvr_step_voxels=0.5, dvr_jitter=False,
+                 max_samples=1 << 20, sample_range=(0.0, 1.0), dvr_skip_empty=True, use_env=False, show_environment=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
+        d = densities("noise", g, p)
         lo, hi = float(np.quantile(d, 0.6)), float(np.quantile(d, 0.95))
         z, y, x = np.unravel_index(int(np.argmax(np.where(SG.predicate(d, lo, hi), d, -np.inf))), d.shape)
         r.segment((int(x), int(y), int(z)), lo, hi, connectivity=6)
         m0 = r.segment_mask()
         r.segment_view = view
-        before = _frame(r).copy()
+        before = frame(r)[0].copy()
         r.segment_edit("close", steps=2, connectivity=26)
         em = r.segment_mask()
         assert np.array_equal(em, ER.edit(m0, "close", 26, 2)) and (em ^ m0).any()
         assert r.frame_index == 0                       # the host restarted accumulation: the picture changed
-        img = _frame(r)
+        img = frame(r)[0]
         c = r.counters()
         tf, L = r._tf
         want, n, ntf, rays = SV.projection_image(r._params, g, tf, L, em, view)
@@ -359,7 +325,7 @@ def test_segment_view_of_an_edited_mask_matches_the_segview_restatement(volumes,
 @pytest.mark.gpu
 def test_rendering_is_left_alone_with_the_view_off(volumes):
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         r.bind_uniforms()
         r.segment((10, 10, 10), 0.2, connectivity=26)
@@ -406,10 +372,10 @@ def test_refusals_leave_the_segment_alone(volumes):
         assert lib.vx_segment_edit(ctx, C.byref(q), C.byref(res)) == 3                                   # VX_ERR_NO_VOLUME
         assert lib.vx_segment_write_mask(ctx, bits.ctypes.data, nbytes, C.byref(res)) == 3
         assert lib.vx_segment_edit_stats(ctx, None, None) == 0
-        assert _upload(lib, ctx, g) == 0
+        assert upload_volume(lib, ctx, g) == 0
         assert lib.vx_segment_edit(ctx, C.byref(q), C.byref(res)) == 1 and b"vx_set_params" in lib.vx_last_error(ctx)
         assert lib.vx_segment_write_mask(ctx, bits.ctypes.data, nbytes, None) == 1 and b"vx_set_params" in lib.vx_last_error(ctx)
-        r = _renderer(g)
+        r = renderer(g, dvr_jitter=False)
         try:
             p = r.bind_uniforms()
         finally:
@@ -456,7 +422,7 @@ def test_refusals_leave_the_segment_alone(volumes):
         assert lib.vx_segment_read_mask(ctx, back.ctypes.data, nbytes) == 0
         assert np.array_equal(back, SG.packed(ER.edit(filled, "dilate", 6, 1)))
         # an upload drops segment, predicate and scratch
-        assert _upload(lib, ctx, g) == 0
+        assert upload_volume(lib, ctx, g) == 0
         assert lib.vx_segment_edit(ctx, C.byref(q), C.byref(res)) == 1 and b"no current segment" in lib.vx_last_error(ctx)
         assert lib.vx_segment_write_mask(ctx, bits.ctypes.data, nbytes, C.byref(res)) == 0 and res.count == count
         assert lib.vx_segment_edit(ctx, C.byref(q), C.byref(res)) == 0
@@ -467,7 +433,7 @@ def test_refusals_leave_the_segment_alone(volumes):
 @pytest.mark.gpu
 def test_python_refusals_on_a_live_renderer(volumes):
     from volxel_amd import VolxelError
-    r = _renderer(volumes["noise"])
+    r = renderer(volumes["noise"], dvr_jitter=False)
     try:
         with pytest.raises(VolxelError, match="no current segment"):
             r.segment_edit("dilate")
@@ -483,7 +449,7 @@ def test_python_refusals_on_a_live_renderer(volumes):
 def test_device_group_runs_the_edits_on_member0(volumes):
     g = volumes["noise"]
     m = ER.blobs((64, 64, 64), seed=8)
-    r1 = _renderer(g)
+    r1 = renderer(g, dvr_jitter=False)
     try:
         a0 = r1.set_segment_mask(m)
         a1 = r1.segment_edit("close", steps=3, connectivity=26)
@@ -492,7 +458,7 @@ def test_device_group_runs_the_edits_on_member0(volumes):
         fa = r1.segment_mask()
     finally:
         r1.close()
-    r2 = _renderer(g, devices=[0, 0])
+    r2 = renderer(g, devices=[0, 0], dvr_jitter=False)
     try:
         b0 = r2.set_segment_mask(m)
         b1 = r2.segment_edit("close", steps=3, connectivity=26)
@@ -511,15 +477,13 @@ def test_device_group_runs_the_edits_on_member0(volumes):
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 def test_js_host_edits_have_the_python_bits(volumes, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
-    from volxel_amd import BENCHMARK_SETTINGS
     g = volumes["noise"]
     m = ER.blobs((64, 64, 64), seed=4)
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
-        seed, lo, _, _ = _resolve(d, "max", "q0.6", None, None)
+        d = densities("noise", g, p)
+        seed, lo, _, _ = resolve(d, "max", "q0.6", None, None)
         r.segment(seed, lo, connectivity=6)
         s1 = r.segment_edit("dilate", steps=3, connectivity=26)
         m1 = r.segment_mask()
@@ -528,35 +492,11 @@ def test_js_host_edits_have_the_python_bits(volumes, tmp_path):
         s3 = r.set_segment_mask(m)
     finally:
         r.close()
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, g.indirection_size)), "rangeSize": list(map(int, g.range_size)),
-        "atlasSize": list(map(int, g.atlas_size)), "indexExtent": list(map(int, g.index_extent)),
-        "minMaj": list(map(float, g.min_maj)), "transform": list(map(float, g.transform)),
-        "mips": [list(map(int, sz)) for _, sz in g.range_mipmaps]}))
-    np.asarray(g.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(g.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(g.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (mm, _) in enumerate(g.range_mipmaps):
-        np.asarray(mm, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
+    dump_grid(tmp_path, g)
     SG.packed(m).tofile(tmp_path / "in.bin")
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
     (tmp_path / "args.json").write_text(json.dumps({"seed": list(seed), "lo": lo}))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
+    body = r"""
 const a = JSON.parse(fs.readFileSync(path.join(dir, 'args.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
-const save = (f, m) => fs.writeFileSync(path.join(dir, f), Buffer.from(m.buffer, m.byteOffset, m.byteLength));
 r.segment(a.seed, a.lo, { connectivity: 6 });
 const s1 = r.segmentEdit('dilate', { steps: 3, connectivity: 26 });
 save('m1.bin', r.segmentMask());
@@ -569,8 +509,7 @@ try { r.segmentEdit('erode', { band: true }); } catch (e) { refused = String(e.m
 console.log(JSON.stringify({ s1, s2, s3, st: r.segmentEditStats(), refused }));
 r.dispose();
 """
-    (tmp_path / "s.js").write_text(script)
-    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    out = run_node(tmp_path, body)
     assert np.array_equal(np.fromfile(tmp_path / "m1.bin", dtype=np.uint8), SG.packed(m1))
     assert np.array_equal(np.fromfile(tmp_path / "m2.bin", dtype=np.uint8), SG.packed(m2))
     assert np.array_equal(np.fromfile(tmp_path / "m3.bin", dtype=np.uint8), SG.packed(m))

@@ -11,9 +11,8 @@ import pytest
 from scipy import ndimage
 
 from tests import segedit_ref as ER
-from tests.test_segment_host import _offsets, _shell
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.common import ROOT
+from tests.shapes import offsets, renderer_shell
 
 
 # ---- the two restatements -----------------------------------------------------------------------------------------------
@@ -146,7 +145,7 @@ def test_edit_params_layout_matches_the_c_compiler(tmp_path):
     assert VxSegmentEditParams is _abi.VxSegmentEditParams
     names = [f[0] for f in VxSegmentEditParams._fields_]
     assert names == ["op", "connectivity", "steps", "band"]
-    got = _offsets(tmp_path, "VxSegmentEditParams", names)
+    got = offsets(tmp_path, "VxSegmentEditParams", names)
     assert got == [C.sizeof(VxSegmentEditParams)] + [getattr(VxSegmentEditParams, n).offset for n in names]
     assert got == [16, 0, 4, 8, 12]
 
@@ -188,11 +187,11 @@ def test_c_refusals_without_a_context(native_lib):
 ])
 def test_python_refusals_of_segment_edit(kw, word):
     with pytest.raises(ValueError, match=word):
-        _shell().segment_edit(**kw)
+        renderer_shell().segment_edit(**kw)
 
 
 def test_python_refusals_of_set_segment_mask():
-    r = _shell((16, 16, 24))
+    r = renderer_shell((16, 16, 24))
     with pytest.raises(ValueError, match="shape"):
         r.set_segment_mask(np.zeros((16, 16, 24), dtype=bool))        # (X, Y, Z) order instead of (Z, Y, X)
     with pytest.raises(ValueError, match="shape"):

@@ -6,132 +6,26 @@ segment on config 2's bone, rendering left alone, staleness after an upload, dev
 import ctypes as C
 import json
 import math
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import segment_ref as SG
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
-F32 = np.float32
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1, "auto": 3}
-F32_MAX = float(np.finfo(np.float32).max)
-
-
-def _grid(vox, sp):
-    from volxel_amd import read_u16_stack_to_grid
-    return read_u16_stack_to_grid(vox, sp)
-
-
-def _serpentine():
-    """a one-voxel-wide path: rows along x at every other y, joined at alternating ends, in every other z layer, the layers
-    joined at the end of their last row; no two parts of it closer than 2 voxels except along the path, so it is one path under
-    6 and 26 alike, and it crosses brick faces hundreds of times"""
-    X, Y, Z = 48, 40, 16
-    v = np.zeros((Z, Y, X), dtype=np.uint16)
-    x = 0
-    rows, layers = list(range(0, Y, 2)), list(range(0, Z, 2))
-    for li, z in enumerate(layers):
-        order = rows if li % 2 == 0 else rows[::-1]
-        for ri, y in enumerate(order):
-            xe = X - 1 if x == 0 else 0
-            v[z, y, min(x, xe):max(x, xe) + 1] = 3000
-            x = xe
-            if ri + 1 < len(order):
-                v[z, (y + order[ri + 1]) // 2, x] = 3000
-        if li + 1 < len(layers):
-            v[z + 1, order[-1], x] = 3000
-    return v, (1.0, 1.0, 1.0)
-
-
-def _tube():
-    """1040 x 16 x 24: a noisy tube along x through 130 bricks, with noise below the threshold around it"""
-    X, Y, Z = 1040, 16, 24
-    z, y, x = np.meshgrid(np.arange(Z), np.arange(Y), np.arange(X), indexing="ij")
-    r2 = (y - 7.5 - 3 * np.sin(x / 40.0)) ** 2 + (z - 11.5 - 4 * np.cos(x / 55.0)) ** 2
-    rng = np.random.default_rng(5)
-    v = np.where(r2 < 16, 2500, 600) + rng.integers(0, 300, size=r2.shape)
-    return v.astype(np.uint16), (0.5, 0.5, 0.8)
-
-
-def _odd():
-    """a 37 x 29 x 45 stack: the builder pads it to 40 x 32 x 48 (index_extent is always 8 x the brick grid, so no brick is
-    partial), and the padding is part of the volume the segment runs over"""
-    from volxel_amd import synth
-    v, _ = synth.value_noise(48, seed=3, zero_quantile=0.3)
-    return np.ascontiguousarray(v[:45, :29, :37]), (1.0, 1.2, 0.9)
-
+from tests.common import F32, F32_MAX, LAYOUTS, densities, grid, renderer, segment_volumes, upload_volume
+from tests.js_host import dump_grid, run_node
+from tests.shapes import CASES, CHAINS, resolve
 
 @pytest.fixture(scope="module")
 def volumes():
-    from tests.common import small_noise
-    from volxel_amd import synth
-    return {"noise": _grid(*small_noise(64)), "phantom": _grid(*synth.ct_phantom(64)), "odd": _grid(*_odd()),
-            "serpentine": _grid(*_serpentine()), "tube": _grid(*_tube())}
-
-
-def _renderer(g, layout=None, devices=None, w=64, h=48):
-    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
-    r = Volxel3DRenderer(w, h, device=None if devices else 0, layout=layout, devices=devices)
-    r.setup_from_grid(g)
-    r.restore_settings(BENCHMARK_SETTINGS)
-    r.settings.render_mode = "dvr"
-    r.settings.dvr_jitter = False
-    return r
-
-
-_D = {}
-
-
-def _densities(name, g, p):
-    key = (name, float(p.volume_density_scale), float(p.volume_inv_maj))
-    if key not in _D:
-        _D[key] = SG.densities(g, p.volume_density_scale, p.volume_inv_maj)
-    return _D[key]
-
-
-# (volume, seed rule, lo, hi, box): lo / hi as quantiles of d ("q0.6") or values; seed: the voxel of the largest d in the
-# predicate, or a fixed voxel
-CASES = {
-    "noise_q60": ("noise", "max", "q0.6", None, None),     # small_noise is half zeros: q0.5 would be lo = 0, the whole volume
-    "noise_q70": ("noise", "max", "q0.7", None, None),
-    "noise_q90": ("noise", "max", "q0.9", None, None),
-    "noise_band": ("noise", "max", "q0.6", "q0.95", ((3, 0, 5), (60, 50, 63))),
-    "phantom_bone": ("phantom", "max", 0.75, None, None),
-    "phantom_air": ("phantom", (0, 0, 0), 0.0, 0.05, None),
-    "odd": ("odd", "max", "q0.55", None, None),
-    "serpentine": ("serpentine", (0, 0, 0), "half", None, None),
-    "tube": ("tube", (0, 8, 12), "half", None, None),
-}
-
-
-def _resolve(d, seed, lo, hi, box):
-    def val(v):
-        if v is None:
-            return F32_MAX
-        if isinstance(v, str) and v.startswith("q"):
-            return float(np.quantile(d, float(v[1:])))
-        if v == "half":
-            return float(d.max()) / 2
-        return float(v)
-    lo_v, hi_v = val(lo), val(hi)
-    p = SG.predicate(d, lo_v, hi_v, box)
-    if seed == "max":
-        dd = np.where(p, d, -np.inf)
-        z, y, x = np.unravel_index(int(np.argmax(dd)), d.shape)
-        seed = (int(x), int(y), int(z))
-    return seed, lo_v, hi_v, p
+    return segment_volumes()
 
 
 def _check_against_ref(r, name, g, case, conn):
     vol, seed, lo, hi, box = CASES[case]
     p = r.bind_uniforms()
-    d = _densities(vol, g, p)
-    seed, lo_v, hi_v, pred = _resolve(d, seed, lo, hi, box)
+    d = densities(vol, g, p)
+    seed, lo_v, hi_v, pred = resolve(d, seed, lo, hi, box)
     want = SG.component(pred, seed, conn)
     st = SG.stats(want, d)
     s1 = r.segment(seed, lo_v, hi_v, connectivity=conn, box=box)
@@ -154,7 +48,7 @@ def _check_against_ref(r, name, g, case, conn):
 @pytest.mark.parametrize("conn", [6, 26])
 def test_segment_matches_the_restatement(volumes, case, layout, conn):
     g = volumes[CASES[case][0]]
-    r = _renderer(g, layout=LAYOUTS[layout])
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         s, want, _, _ = _check_against_ref(r, CASES[case][0], g, case, conn)
     finally:
@@ -166,20 +60,6 @@ def test_segment_matches_the_restatement(volumes, case, layout, conn):
         assert s.bbox_lo[0] == 0 and s.bbox_hi[0] == 1039
 
 
-# one-voxel chains whose only links are diagonal (no two voxels share a face), 40 long in a 40^3 volume (5 bricks a side): each
-# step of a chain changes two or three coordinates at once, and 39 = 8 * 5 - 1 makes the reversed coordinate cross a brick
-# boundary at the same step as the others.  So every brick-to-brick step is across a brick edge (two coordinates) or a brick
-# corner (three), never a face: only the 12 edge and 8 corner directions of the 26-flood can follow them.  The seed is the
-# middle voxel, so the flood runs both ways and each chain uses both opposite directions of its edge / corner.
-CHAINS = {
-    "corner+++": lambda k: (k, k, k), "corner+-+": lambda k: (k, 39 - k, k), "corner-++": lambda k: (39 - k, k, k),
-    "corner++-": lambda k: (k, k, 39 - k),
-    "edge_xy++": lambda k: (k, k, 20), "edge_xy+-": lambda k: (k, 39 - k, 20),
-    "edge_xz++": lambda k: (k, 20, k), "edge_xz+-": lambda k: (k, 20, 39 - k),
-    "edge_yz++": lambda k: (20, k, k), "edge_yz+-": lambda k: (20, k, 39 - k),
-}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("chain", sorted(CHAINS))
 @pytest.mark.parametrize("layout", sorted(LAYOUTS))
@@ -188,8 +68,8 @@ def test_diagonal_chains_cross_brick_edges_and_corners(chain, layout):
     pts = [CHAINS[chain](k) for k in range(40)]
     for x, y, z in pts:
         v[z, y, x] = 3000
-    g = _grid(v, (1.0, 1.0, 1.0))
-    r = _renderer(g, layout=LAYOUTS[layout])
+    g = grid(v, (1.0, 1.0, 1.0))
+    r = renderer(g, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         p = r.bind_uniforms()
         d = SG.densities(g, p.volume_density_scale, p.volume_inv_maj)
@@ -217,7 +97,7 @@ def test_box_edges_and_the_one_voxel_box(volumes):
     """box = ((0, 0, 0), (0, 0, 0)) is the voxel at the origin, not the whole volume; VX_SEGMENT_BOX_END reaches the far face"""
     from volxel_amd import _abi
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         one = r.segment((0, 0, 0), 0.0, box=((0, 0, 0), (0, 0, 0)))
         m = r.segment_mask()
@@ -241,10 +121,10 @@ def test_density_is_trilinear_at_voxel_centres(volumes):
     """the slice at an axial plane with one sample through voxel centres shows d(i) bit for bit"""
     from volxel_amd import mpr
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         vals = r.slice(mpr.axial(r, 17))
-        d = _densities("noise", g, r._params)
+        d = densities("noise", g, r._params)
     finally:
         r.close()
     assert np.array_equal(vals.view(np.uint32), d[17].view(np.uint32))
@@ -253,10 +133,10 @@ def test_density_is_trilinear_at_voxel_centres(volumes):
 @pytest.mark.gpu
 def test_round_cap_gives_a_connected_subset(volumes):
     g = volumes["serpentine"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("serpentine", g, p)
+        d = densities("serpentine", g, p)
         lo = float(d.max()) / 2
         full = r.segment((0, 0, 0), lo)
         fm = r.segment_mask()
@@ -275,7 +155,7 @@ def test_round_cap_gives_a_connected_subset(volumes):
 def test_slice_overlay_matches_the_restatement(volumes, conn):
     from volxel_amd import mpr
     g = volumes["phantom"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         s, want, _, _ = _check_against_ref(r, "phantom", g, "phantom_bone", conn)
         sps = [mpr.axial(r, 30), mpr.coronal(r, 40), mpr.sagittal(r, 20),
@@ -294,7 +174,7 @@ def test_slice_overlay_matches_the_restatement(volumes, conn):
 def test_pick_voxel_index_segment_on_config2_bone():
     """config 2 (the 256^3 CT phantom, spacing (0.7, 0.7, 1.0)): pick a point of the spine, take its nearest voxel as the seed"""
     from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer, synth
-    g = _grid(*synth.ct_phantom(256))
+    g = grid(*synth.ct_phantom(256))
     r = Volxel3DRenderer(480, 270, device=0)
     try:
         r.setup_from_grid(g)
@@ -331,7 +211,7 @@ def test_pick_voxel_index_segment_on_config2_bone():
 @pytest.mark.gpu
 def test_rendering_is_left_alone(volumes):
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         r.bind_uniforms()
         r.reset_counters()
@@ -360,7 +240,7 @@ def test_rendering_is_left_alone(volumes):
 def test_upload_makes_the_segment_stale(volumes):
     from volxel_amd import VolxelError, mpr
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         s = r.segment((5, 5, 5), 0.0, connectivity=6)
         assert s.count == 64 ** 3                       # lo = 0 admits every voxel (densities are >= 0)
@@ -377,16 +257,16 @@ def test_upload_makes_the_segment_stale(volumes):
 @pytest.mark.gpu
 def test_device_group_gives_member0_bits(volumes):
     g = volumes["noise"]
-    r1 = _renderer(g)
+    r1 = renderer(g, dvr_jitter=False)
     try:
         p = r1.bind_uniforms()
-        d = _densities("noise", g, p)
-        seed, lo, hi, _ = _resolve(d, "max", "q0.7", None, None)
+        d = densities("noise", g, p)
+        seed, lo, hi, _ = resolve(d, "max", "q0.7", None, None)
         a = r1.segment(seed, lo, connectivity=26)
         ma = r1.segment_mask()
     finally:
         r1.close()
-    r2 = _renderer(g, devices=[0, 0])
+    r2 = renderer(g, devices=[0, 0], dvr_jitter=False)
     try:
         b = r2.segment(seed, lo, connectivity=26)
         mb = r2.segment_mask()
@@ -396,18 +276,6 @@ def test_device_group_gives_member0_bits(volumes):
     assert np.array_equal(ma, mb)
     assert (a.count, a.bbox_lo, a.bbox_hi, a.d_min, a.d_max, a.d_sum) == (b.count, b.bbox_lo, b.bbox_hi, b.d_min, b.d_max, b.d_sum)
     assert st[0] == b.rounds and st[1] == b.brick_visits and all(t >= 0 for t in st[2:])
-
-
-def _upload(lib, ctx, g):
-    u3 = lambda t: (C.c_uint32 * 3)(*[int(x) for x in t])
-    ind = np.ascontiguousarray(g.indirection, dtype=np.uint32)
-    rng = np.ascontiguousarray(g.range, dtype=np.uint16)
-    atl = np.ascontiguousarray(g.atlas, dtype=np.uint8)
-    mips = [np.ascontiguousarray(m, dtype=np.uint16) for m, _ in g.range_mipmaps]
-    mp = (C.c_void_p * 3)(*[m.ctypes.data for m in mips])
-    ms = (C.c_uint32 * 9)(*[int(x) for _, s in g.range_mipmaps for x in s])
-    return lib.vx_upload_volume(ctx, ind.ctypes.data, u3(g.indirection_size), rng.ctypes.data, u3(g.range_size),
-                                atl.ctypes.data, u3(g.atlas_size), 3, mp, C.cast(ms, C.c_void_p), u3(g.index_extent))
 
 
 @pytest.mark.gpu
@@ -426,10 +294,10 @@ def test_refusals(volumes):
     try:
         assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 3                    # VX_ERR_NO_VOLUME
         assert lib.vx_segment_stats(ctx, None, None, None) == 0
-        assert _upload(lib, ctx, g) == 0
+        assert upload_volume(lib, ctx, g) == 0
         assert lib.vx_segment(ctx, C.byref(q), C.byref(res)) == 1 and b"vx_set_params" in lib.vx_last_error(ctx)
         assert lib.vx_segment_read_mask(ctx, bits.ctypes.data, nbytes) == 1 and b"no current segment" in lib.vx_last_error(ctx)
-        r = _renderer(g)
+        r = renderer(g, dvr_jitter=False)
         try:
             p = r.bind_uniforms()
             sp = mpr.axial(r, 3)
@@ -493,14 +361,13 @@ def test_refusals(volumes):
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 def test_js_host_segment_has_the_python_bits(volumes, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
-    from volxel_amd import BENCHMARK_SETTINGS, mpr
+    from volxel_amd import mpr
     g = volumes["noise"]
-    r = _renderer(g)
+    r = renderer(g, dvr_jitter=False)
     try:
         p = r.bind_uniforms()
-        d = _densities("noise", g, p)
-        seed, lo, _, _ = _resolve(d, "max", "q0.6", None, None)
+        d = densities("noise", g, p)
+        seed, lo, _, _ = resolve(d, "max", "q0.6", None, None)
         s = r.segment(seed, lo, connectivity=26, box=((2, 3, 4), (60, 61, 62)))
         m = r.segment_mask()
         sl = r.slice_mask(mpr.axial(r, seed[2]))
@@ -508,33 +375,10 @@ def test_js_host_segment_has_the_python_bits(volumes, tmp_path):
         vi = [r.voxel_index(pt) for pt in w]
     finally:
         r.close()
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, g.indirection_size)), "rangeSize": list(map(int, g.range_size)),
-        "atlasSize": list(map(int, g.atlas_size)), "indexExtent": list(map(int, g.index_extent)),
-        "minMaj": list(map(float, g.min_maj)), "transform": list(map(float, g.transform)),
-        "mips": [list(map(int, sz)) for _, sz in g.range_mipmaps]}))
-    np.asarray(g.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(g.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(g.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (mm, _) in enumerate(g.range_mipmaps):
-        np.asarray(mm, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
+    dump_grid(tmp_path, g)
     (tmp_path / "args.json").write_text(json.dumps({"seed": list(seed), "lo": lo, "w": list(w)}))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
+    body = r"""
 const a = JSON.parse(fs.readFileSync(path.join(dir, 'args.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
 const s = r.segment(a.seed, a.lo, { connectivity: 26, box: [[2, 3, 4], [60, 61, 62]] });
 const m = r.segmentMask();
 const sl = r.sliceMask(r.axial(a.seed[2]));
@@ -544,8 +388,7 @@ fs.writeFileSync(path.join(dir, 'slice.bin'), Buffer.from(sl.mask.buffer, sl.mas
 console.log(JSON.stringify({ s, st, vi: a.w.map((p) => r.voxelIndex(p)), size: [sl.width, sl.height] }));
 r.dispose();
 """
-    (tmp_path / "s.js").write_text(script)
-    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    out = run_node(tmp_path, body)
     assert np.array_equal(np.fromfile(tmp_path / "mask.bin", dtype=np.uint8), SG.packed(m))
     assert out["size"] == [64, 64]
     assert np.array_equal(np.fromfile(tmp_path / "slice.bin", dtype=np.uint8).reshape(64, 64), sl.astype(np.uint8))

@@ -6,38 +6,22 @@ import ctypes as C
 import math
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import segment_ref as SG
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32 = np.float32
-F32_MAX = float(np.finfo(np.float32).max)
+from tests.common import F32, F32_MAX, NAPI, ROOT
+from tests.shapes import offsets, renderer_shell
 
 
 # ---- the boundary ------------------------------------------------------------------------------------------------------
-def _offsets(tmp_path, name, fields):
-    src = tmp_path / f"{name}.c"
-    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "volxel_hip.h"\n'
-                   'int main(void) { printf("%u' + " %u" * len(fields) + '\\n", (unsigned)sizeof(' + name + ')'
-                   + "".join(f", (unsigned)offsetof({name}, {n})" for n in fields) + "); return 0; }\n")
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    if cc is None:
-        pytest.skip("no C compiler")
-    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / name)])
-    return [int(x) for x in subprocess.check_output([str(tmp_path / name)]).split()]
-
-
 def test_segment_params_layout_matches_the_c_compiler(tmp_path):
     from volxel_amd import _abi, VxSegmentParams
     assert VxSegmentParams is _abi.VxSegmentParams
     names = [f[0] for f in VxSegmentParams._fields_]
     assert names == ["seed", "lo", "hi", "connectivity", "box_lo", "box_hi", "max_rounds"]
-    got = _offsets(tmp_path, "VxSegmentParams", names)
+    got = offsets(tmp_path, "VxSegmentParams", names)
     assert got == [C.sizeof(VxSegmentParams)] + [getattr(VxSegmentParams, n).offset for n in names]
     assert got[0] == 4 * (3 + 2 + 1 + 3 + 3 + 1)
 
@@ -47,7 +31,7 @@ def test_segment_result_layout_matches_the_c_compiler(tmp_path):
     assert VxSegmentResult is _abi.VxSegmentResult
     names = [f[0] for f in VxSegmentResult._fields_]
     assert names == ["count", "bbox_lo", "bbox_hi", "d_min", "d_max", "d_sum", "rounds", "converged", "brick_visits"]
-    got = _offsets(tmp_path, "VxSegmentResult", names)
+    got = offsets(tmp_path, "VxSegmentResult", names)
     assert got == [C.sizeof(VxSegmentResult)] + [getattr(VxSegmentResult, n).offset for n in names]
     assert got == [64, 0, 8, 20, 32, 36, 40, 48, 52, 56]
 
@@ -72,10 +56,9 @@ def test_c_refusals_without_a_context(native_lib):
 
 
 def test_js_host_carries_the_segment_calls():
-    napi = os.path.join(ROOT, "volxel_amd", "napi")
-    c = open(os.path.join(napi, "volxel_napi.c")).read()
-    js = open(os.path.join(napi, "viewer.js")).read()
-    dts = open(os.path.join(napi, "index.d.ts")).read()
+    c = open(os.path.join(NAPI, "volxel_napi.c")).read()
+    js = open(os.path.join(NAPI, "viewer.js")).read()
+    dts = open(os.path.join(NAPI, "index.d.ts")).read()
     for fn in ("vx_segment(", "vx_segment_read_mask(", "vx_slice_segment_mask(", "vx_segment_stats("):
         assert fn in c
     for m in ("segment(", "segmentMask(", "sliceMask(", "voxelIndex(", "segmentStats("):
@@ -83,15 +66,6 @@ def test_js_host_carries_the_segment_calls():
 
 
 # ---- Python-side refusals (no device: a renderer shell with a volume description) -------------------------------------
-def _shell(ext=(16, 16, 24)):
-    from volxel_amd import Volxel3DRenderer
-    from volxel_amd.scene import Grid, Volume
-    r = Volxel3DRenderer.__new__(Volxel3DRenderer)
-    r._ctx = None
-    r.volume = Volume(Grid(min_maj=(0.0, 1.0), index_extent=np.asarray(ext, float), transform=np.eye(4)))
-    return r
-
-
 @pytest.mark.parametrize("kw, word", [
     (dict(seed=(16, 0, 0), lo=0.1), "seed"), (dict(seed=(0, 0, -1), lo=0.1), "seed"), (dict(seed=(0.5, 0, 0), lo=0.1), "seed"),
     (dict(seed=(0, 0), lo=0.1), "seed"), (dict(seed=(1, 1, 1), lo=float("nan")), "finite"),
@@ -104,12 +78,12 @@ def _shell(ext=(16, 16, 24)):
 ])
 def test_python_refusals(kw, word):
     with pytest.raises(ValueError, match=word):
-        _shell().segment(**kw)
+        renderer_shell().segment(**kw)
 
 
 def test_python_refusals_of_slice_mask_and_voxel_index():
     from volxel_amd import mpr
-    r = _shell()
+    r = renderer_shell()
     sp = mpr.axial(r, 3)
     sp.slab_samples = 0
     with pytest.raises(ValueError, match="slab_samples"):
@@ -240,7 +214,7 @@ def test_overlay_restatement_on_an_axial_plane():
     from volxel_amd import mpr
     rng = np.random.default_rng(3)
     m = rng.random((16, 16, 24)) < 0.4                            # (Z, Y, X)
-    r = _shell((24, 16, 16))
+    r = renderer_shell((24, 16, 16))
     sp = mpr.axial(r, 5)
     assert np.array_equal(SG.overlay(sp, m), m[5])
     sp.slab_samples, sp.dn[2] = 3, 1.0                            # a slab over z = 5, 6, 7

@@ -9,64 +9,38 @@ Against the restatement (tests/segview_ref.py) on value noise with a ragged band
 the isosurface bit for bit, DVR within the deterministic-DVR tolerance (2e-6).  Then the refusals, the state rules, slices left
 alone and the JS host."""
 import json
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import common
 from tests import segview_ref as SV
+from tests.common import F32_MAX, bits, frame, grid, renderer, small_noise
+from tests.js_host import dump_grid, run_node
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
 W, H = 96, 64
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "auto": 3}
+LAYOUTS = {k: common.LAYOUTS[k] for k in ("brickf32", "bricku8", "auto")}
 MODES = ("dvr", "dvr_phong", "mip", "minip")
-F32_MAX = float(np.finfo(np.float32).max)
-
-
-def _grid(vox, sp=(1.0, 1.0, 1.0)):
-    from volxel_amd import read_u16_stack_to_grid
-    return read_u16_stack_to_grid(vox, sp)
+# sample_range: every density of both blobs is in range, B shows unless a view hides it
+SETTINGS = dict(dvr_step_voxels=0.5, dvr_jitter=False, max_samples=1 << 20, sample_range=(0.0, 1.0))
 
 
 @pytest.fixture(scope="module")
 def scenes():
     ab, a, _ = SV.blobs()
-    from tests.common import small_noise
     # the background: no voxel inside CLIP_BACK (a volume must have one voxel above 0; this one, at the far corner, is clipped away
     # and shares A+B's largest value)
     zero = np.zeros_like(ab)
     zero[63, 63, 63] = ab.max()
-    return {"ab": _grid(ab), "a": _grid(a), "zero": _grid(zero), "noise": _grid(*small_noise(64)), "ab_raw": ab, "a_raw": a}
+    return {"ab": grid(ab), "a": grid(a), "zero": grid(zero), "noise": grid(*small_noise(64)), "ab_raw": ab, "a_raw": a}
 
 
 CLIP_BACK = (40.0 / 64.0, 1.0, 1.0)   # volume_clip_max that leaves brick columns x 5 .. 7 out
 
 
-def _scene(g, mode, layout=None, jitter=False, **kw):
-    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
-    devices = kw.pop("devices", None)
-    r = Volxel3DRenderer(W, H, device=None if devices else 0, layout=layout, devices=devices)
-    r.setup_from_grid(g)
-    r.restore_settings(BENCHMARK_SETTINGS)
-    s = r.settings
-    s.render_mode = mode
-    s.dvr_step_voxels = 0.5
-    s.dvr_jitter = jitter
-    s.max_samples = 1 << 20
-    s.sample_range = (0.0, 1.0)   # every density of both blobs is in range: B shows unless a view hides it
-    for k, v in kw.items():
-        setattr(s, k, v)
-    return r
-
-
-def _frame(r, frames=1, in_flight=1):
-    r.restart_rendering()
-    r.reset_counters()
-    r.render(frames=frames, in_flight=in_flight)
-    return r.read_accum()
+def _scene(g, mode, layout=None, jitter=False, devices=None, **kw):
+    return renderer(g, layout, devices, mode, (W, H), **{**SETTINGS, "dvr_jitter": jitter}, **kw)
 
 
 def _seed_of(raw, xlo, xhi):
@@ -89,10 +63,6 @@ def _iso(r):
     return rgba, hit, r.iso_stats()[:5]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 # ---- restatement-free pins ----------------------------------------------------------------------------------------------------
 
 @pytest.mark.gpu
@@ -103,17 +73,17 @@ def test_two_blobs_equal_a_alone(scenes, layout, mode):
     plain = _scene(scenes["a"], mode, layout=LAYOUTS[layout], jitter=True)
     masked = _scene(scenes["ab"], mode, layout=LAYOUTS[layout], jitter=True)
     try:
-        want = {n: _frame(plain, n, in_flight=32) for n in (1, 3, 32)}
+        want = {n: frame(plain, n, in_flight=32)[0] for n in (1, 3, 32)}
         assert float(want[32][..., :3].max()) > 0.0
         for view, (xlo, xhi) in (("only", (0, 24)), ("hide", (32, 64))):
             _segment_blob(masked, ab, xlo, xhi)
             masked.segment_view = view
             for n in (1, 3, 32):
-                got = _frame(masked, n, in_flight=32)
-                assert np.array_equal(_bits(got), _bits(want[n])), (view, n, float(np.abs(got - want[n]).max()))
+                got = frame(masked, n, in_flight=32)[0]
+                assert np.array_equal(bits(got), bits(want[n])), (view, n, float(np.abs(got - want[n]).max()))
         masked.segment_view = "off"
         if mode != "minip":   # (MinIP is TF(0) on every ray of this scene: the blobs are surrounded by zeros)
-            assert not np.array_equal(_frame(masked, 1), want[1])   # B is visible again
+            assert not np.array_equal(frame(masked, 1)[0], want[1])   # B is visible again
     finally:
         plain.close()
         masked.close()
@@ -134,7 +104,7 @@ def test_two_blobs_isosurface_and_pick(scenes, layout):
             _segment_blob(masked, ab, xlo, xhi)
             masked.segment_view = view
             rgba, hit, counts = _iso(masked)
-            assert np.array_equal(_bits(rgba), _bits(w_rgba)) and np.array_equal(_bits(hit), _bits(w_hit)), view
+            assert np.array_equal(bits(rgba), bits(w_rgba)) and np.array_equal(bits(hit), bits(w_hit)), view
             # no range skipping under a view: every sample the plain launch passed over is evaluated
             assert counts[4] == 0 and counts[:2] + counts[3:4] == w_counts[:2] + w_counts[3:4], (counts, w_counts)
             assert counts[2] == w_counts[2] + w_counts[4], (counts, w_counts)
@@ -152,21 +122,21 @@ def test_empty_and_whole_segments(scenes, layout, mode):
     r = _scene(scenes["ab"], mode, layout=LAYOUTS[layout], jitter=True, volume_clip_max=CLIP_BACK)
     z = _scene(scenes["zero"], mode, layout=LAYOUTS[layout], jitter=True, volume_clip_max=CLIP_BACK)
     try:
-        plain = _frame(r, 3, in_flight=32)
-        background = _frame(z, 3, in_flight=32)
+        plain = frame(r, 3, in_flight=32)[0]
+        background = frame(z, 3, in_flight=32)[0]
         if mode != "minip":   # (MinIP of A+B meets a zero on every ray: it is the background too)
             assert not np.array_equal(plain, background)
         s = r.segment(_seed_of(ab, 0, 64), 1e30)              # lo above every density: empty
         assert s.count == 0
         r.segment_view = "hide"
-        assert np.array_equal(_bits(_frame(r, 3, in_flight=32)), _bits(plain))
+        assert np.array_equal(bits(frame(r, 3, in_flight=32)[0]), bits(plain))
         r.segment_view = "only"
-        assert np.array_equal(_bits(_frame(r, 3, in_flight=32)), _bits(background))
+        assert np.array_equal(bits(frame(r, 3, in_flight=32)[0]), bits(background))
         s = r.segment((0, 0, 0), -F32_MAX)                    # every voxel: the whole volume
         assert s.count == ab.size
-        assert np.array_equal(_bits(_frame(r, 3, in_flight=32)), _bits(plain))
+        assert np.array_equal(bits(frame(r, 3, in_flight=32)[0]), bits(plain))
         r.segment_view = "hide"
-        assert np.array_equal(_bits(_frame(r, 3, in_flight=32)), _bits(background))
+        assert np.array_equal(bits(frame(r, 3, in_flight=32)[0]), bits(background))
     finally:
         r.close()
         z.close()
@@ -200,21 +170,21 @@ def test_device_matches_restatement(scenes, layout, conn):
             r.segment_view = view
             for mode in ("mip", "minip"):
                 r.settings.render_mode = mode
-                img = _frame(r)
+                img = frame(r)[0]
                 c = r.counters()
                 tf, L = r._tf
                 want, n, ntf, rays = SV.projection_image(r._params, g, tf, L, m, view, minip=mode == "minip")
                 assert np.array_equal(img, want), (view, mode, float(np.abs(img - want).max()))
                 assert c.samples == n and c.skip_steps == 0 and c.tf_samples == ntf and c.rays == rays
             r.settings.render_mode = "dvr"
-            img = _frame(r)
+            img = frame(r)[0]
             tf, L = r._tf
             want, _ = SV.dvr_image(r._params, g, tf, L, m, view)
             assert np.abs(img - want).max() <= 2e-6, (view, float(np.abs(img - want).max()))
             rgba, hit = r.isosurface(0.45, skip=True)
             counts = r.iso_stats()[:5]
             w_rgba, w_hit, wc, _ = SV.isosurface(r._params, g, 0.45, m, view)
-            assert np.array_equal(_bits(hit), _bits(w_hit)), view
+            assert np.array_equal(bits(hit), bits(w_hit)), view
             assert counts == (wc["rays"], wc["hits"], wc["samples"], wc["refine_samples"], 0), (counts, wc)
             assert np.abs(rgba - w_rgba).max() <= 1e-5
     finally:
@@ -246,31 +216,31 @@ def test_refusals(scenes):
         assert rc != 0 and b"is not VX_SEGVIEW_OFF" in r._lib.vx_last_error(r._ctx)
         _segment_blob(r, ab, 0, 24)
         r.segment_view = "hide"
-        _frame(r)
+        frame(r)
         for mode in ("default", "no_dda", "raymarch"):
             r.settings.render_mode = mode
-            _refused(lambda: _frame(r), "path-traced render mode")
+            _refused(lambda: frame(r), "path-traced render mode")
         r.settings.render_mode = "dvr"
         r.settings.debug_hits = True
-        _refused(lambda: _frame(r), "debug_hits")
+        _refused(lambda: frame(r), "debug_hits")
         r.settings.debug_hits = False
         r.settings.use_env = False
         r.settings.dvr_shadow_stride = 2
-        _refused(lambda: _frame(r), "shadowed DVR")
+        _refused(lambda: frame(r), "shadowed DVR")
         r.settings.dvr_shadow_stride = 0
         r.settings.dvr_ert_epsilon = 1.0
-        _refused(lambda: _frame(r), "no LDS-window kernel")
+        _refused(lambda: frame(r), "no LDS-window kernel")
         r.settings.dvr_ert_epsilon = 1e-4
         for lay in (0, 1):   # reference, cellquad
             r.set_layout(lay)
-            _refused(lambda: _frame(r), "no LDS-window kernel")
+            _refused(lambda: frame(r), "no LDS-window kernel")
         r.set_layout(2)
-        _frame(r)
+        frame(r)
         _iso(r)
         # an upload drops the segment and resets the view: renders go on
         r.setup_from_grid(scenes["ab"])
         assert r.segment_view == "off"
-        _frame(r)
+        frame(r)
         _refused(lambda: setv("hide"), "without a current segment")
     finally:
         r.close()
@@ -293,11 +263,11 @@ def test_new_segment_changes_image_and_slices_stay(scenes):
         sl_plain = r.slice(sp)
         _segment_blob(r, ab, 0, 24)
         r.segment_view = "hide"
-        hide_a = _frame(r)
+        hide_a = frame(r)[0]
         assert np.array_equal(r.slice(sp), sl_plain)           # slices keep the unmasked data
         _segment_blob(r, ab, 32, 64)
         assert r.frame_index == 0                              # segment() restarted accumulation under a view
-        hide_b = _frame(r)
+        hide_b = frame(r)[0]
         assert not np.array_equal(hide_a, hide_b)
         assert np.array_equal(r.slice(sp), sl_plain)
     finally:
@@ -307,8 +277,6 @@ def test_new_segment_changes_image_and_slices_stay(scenes):
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 def test_js_host_segment_view_has_the_python_bits(scenes, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
-    from volxel_amd import BENCHMARK_SETTINGS
     ab = scenes["ab_raw"]
     g = scenes["ab"]
     seed = _seed_of(ab, 32, 64)
@@ -320,33 +288,10 @@ def test_js_host_segment_view_has_the_python_bits(scenes, tmp_path):
         want = r.read_accum()
     finally:
         r.close()
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, g.indirection_size)), "rangeSize": list(map(int, g.range_size)),
-        "atlasSize": list(map(int, g.atlas_size)), "indexExtent": list(map(int, g.index_extent)),
-        "minMaj": list(map(float, g.min_maj)), "transform": list(map(float, g.transform)),
-        "mips": [list(map(int, sz)) for _, sz in g.range_mipmaps]}))
-    np.asarray(g.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(g.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(g.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (mm, _) in enumerate(g.range_mipmaps):
-        np.asarray(mm, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
-    (tmp_path / "args.json").write_text(json.dumps({"seed": list(seed), "w": W, "h": H}))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
+    dump_grid(tmp_path, g)
+    (tmp_path / "args.json").write_text(json.dumps({"seed": list(seed)}))
+    body = r"""
 const a = JSON.parse(fs.readFileSync(path.join(dir, 'args.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: a.w, height: a.h });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
 r.settings.dvrStepVoxels = 0.5;
 r.settings.dvrJitter = false;
 r.settings.maxSamples = 1 << 20;
@@ -364,8 +309,7 @@ r.setupFromGrid(grid);
 console.log(JSON.stringify({ before, refused, view, after: r.segmentView }));
 r.dispose();
 """
-    (tmp_path / "s.js").write_text(script)
-    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    out = run_node(tmp_path, body, size=(W, H))
     assert out == {"before": "off", "refused": True, "view": "hide", "after": "off"}, out
     got = np.fromfile(tmp_path / "img.bin", dtype=np.float32).reshape(want.shape)
-    assert np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(bits(got), bits(want))

@@ -13,20 +13,14 @@ from tests import iso_ref as IR
 from tests import projection_ref as PR
 from tests import segview_ref as SV
 
-F32 = np.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _grid(vox, sp=(1.0, 1.0, 1.0)):
-    from oracle import oracle as O
-    return O.BrickGrid(vox, sp)
+from tests.common import F32, ROOT, oracle_grid
 
 
 @pytest.fixture(scope="module")
 def two():
     ab, a, _ = SV.blobs()
     x = np.arange(ab.shape[2])[None, None, :]
-    return {"ab": _grid(ab), "a": _grid(a), "raw": ab, "seg_a": (ab > 0) & (x < 24), "seg_b": (ab > 0) & (x >= 32)}
+    return {"ab": oracle_grid(ab), "a": oracle_grid(a), "raw": ab, "seg_a": (ab > 0) & (x < 24), "seg_b": (ab > 0) & (x >= 32)}
 
 
 def _coords(shape):

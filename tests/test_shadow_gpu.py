@@ -6,36 +6,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests import common
 from tests import shadow_ref as SR
+from tests.common import frame, renderer
 
 W, H = 96, 64
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1}
+LAYOUTS = {k: common.LAYOUTS[k] for k in ("brickf32", "bricku8", "reference", "cellquad")}
+SETTINGS = dict(use_env=False, show_environment=False, volume_clip_min=(0.25, 0.0, 0.0), volume_clip_max=(1.0, 1.0, 0.75),
+                dvr_shadow_stride=2, sync_light_dir=False, max_samples=1 << 20)
 
 
-def _scene(g, layout=None, stride=2, size=(W, H), **kw):
-    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
-    r = Volxel3DRenderer(size[0], size[1], device=0 if "devices" not in kw else None, layout=layout, devices=kw.pop("devices", None))
-    r.setup_from_grid(g)
-    r.restore_settings(BENCHMARK_SETTINGS)
-    s = r.settings
-    s.render_mode = "dvr"
-    s.use_env = False
-    s.show_environment = False
-    s.volume_clip_min = (0.25, 0.0, 0.0)
-    s.volume_clip_max = (1.0, 1.0, 0.75)
-    s.dvr_shadow_stride = stride
-    s.sync_light_dir = False
-    s.max_samples = 1 << 20
-    for k, v in kw.items():
-        setattr(s, k, v)
-    return r
-
-
-def _frame(r, frames=1, in_flight=1):
-    r.restart_rendering()
-    r.reset_counters()
-    r.render(frames=frames, in_flight=in_flight)
-    return r.read_accum(), r.counters()
+def _scene(g, layout=None, stride=2, size=(W, H), devices=None, **kw):
+    return renderer(g, layout, devices, "dvr", size, **{**SETTINGS, "dvr_shadow_stride": stride}, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -55,7 +37,7 @@ LIGHTS = {"axis": (0.0, 0.0, -1.0), "oblique1": (-0.48, -0.6, -0.64), "oblique2"
 def test_light_grid_matches_reference(noise, stride, light):
     r = _scene(noise, stride=stride, light_dir=LIGHTS[light])
     try:
-        _frame(r)
+        frame(r)
         got = r.read_shadow_grid()
         builds, light_samples, ms = r.shadow_stats()
         tf, L = r._tf
@@ -78,9 +60,9 @@ def test_shadowed_image_matches_reference(noise, layout, ert):
     eps = 1e-4 if ert == "ert" else 2.0
     r = _scene(noise, layout=LAYOUTS[layout], stride=2, dvr_ert_epsilon=eps, light_dir=LIGHTS["oblique1"])
     try:
-        img, c = _frame(r)
+        img, c = frame(r)
         r.settings.dvr_shadow_stride = 0
-        plain, c0 = _frame(r)
+        plain, c0 = frame(r)
         tf, L = r._tf
         p = r._params
         p.dvr_shadow_stride = 2
@@ -102,8 +84,8 @@ def test_launch_shapes_are_bit_identical(noise, layout):
     for skip in (True, False):
         r = _scene(noise, layout=LAYOUTS[layout], stride=2, dvr_jitter=True, dvr_skip_empty=skip)
         try:
-            a, ca = _frame(r, 64, 32)
-            b, cb = _frame(r, 64, 1)
+            a, ca = frame(r, 64, 32)
+            b, cb = frame(r, 64, 1)
         finally:
             r.close()
         assert ca.max_launch_frames == 32 and cb.max_launch_frames == 1
@@ -117,8 +99,8 @@ def test_group_matches_one_context(noise):
     one = _scene(noise, stride=2, size=(256, 192), dvr_jitter=True)
     grp = _scene(noise, stride=2, size=(256, 192), dvr_jitter=True, devices=[0, 0, 0])
     try:
-        a, ca = _frame(one, 32, 32)
-        b, cb = _frame(grp, 32, 32)
+        a, ca = frame(one, 32, 32)
+        b, cb = frame(grp, 32, 32)
         assert grp.shadow_stats()[0] == 1 and grp.read_shadow_grid().shape == one.read_shadow_grid().shape
     finally:
         one.close()
@@ -131,33 +113,33 @@ def test_group_matches_one_context(noise):
 def test_rebuild_rules(noise):
     r = _scene(noise, stride=2, light_dir=LIGHTS["oblique1"])
     try:
-        _frame(r)
+        frame(r)
         assert r.shadow_stats()[0] == 1
         r.camera.pos = r.camera.pos + np.array([0.05, -0.02, 0.03])      # a camera move does not rebuild
-        _frame(r)
-        _frame(r)
+        frame(r)
+        frame(r)
         assert r.shadow_stats()[0] == 1
         r.settings.light_dir = LIGHTS["oblique2"]                       # light
-        after_light, _ = _frame(r)
+        after_light, _ = frame(r)
         assert r.shadow_stats()[0] == 2
         cam = (r.camera.pos.copy(), r.camera.view.copy())
         tf, L = r._tf
         r.change_transfer_func(tf.copy(), L)                            # TF upload
-        _frame(r)
+        frame(r)
         assert r.shadow_stats()[0] == 3
         r.setup_from_grid(noise)                                        # volume upload
         r.settings.dvr_shadow_stride = 2
-        _frame(r)
+        frame(r)
         assert r.shadow_stats()[0] == 4
         r.settings.dvr_shadow_stride = 4                                # stride
-        _frame(r)
+        frame(r)
         assert r.shadow_stats()[0] == 5
     finally:
         r.close()
     fresh = _scene(noise, stride=2, light_dir=LIGHTS["oblique2"])      # after the light change: what a fresh context renders
     try:
         fresh.camera.pos, fresh.camera.view = cam
-        want, _ = _frame(fresh)
+        want, _ = frame(fresh)
     finally:
         fresh.close()
     assert np.array_equal(after_light.view(np.uint32), want.view(np.uint32))
@@ -190,9 +172,9 @@ def test_refusals_and_path_modes_ignore_the_stride(noise):
         for mode in ("default", "no_dda", "raymarch"):
             r.settings.render_mode = mode
             r.settings.dvr_shadow_stride = 0
-            a, ca = _frame(r, 2, 1)
+            a, ca = frame(r, 2, 1)
             r.settings.dvr_shadow_stride = 2
-            b, cb = _frame(r, 2, 1)
+            b, cb = frame(r, 2, 1)
             assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), mode
             assert (ca.samples, ca.rays) == (cb.samples, cb.rays), mode
         assert r.shadow_stats()[0] == 0
@@ -235,12 +217,12 @@ def test_shadowed_dvr_is_closer_to_the_path_tracer():
         r.camera.view = np.array([0.0, 0.0, 0.0])
         s.render_mode = "raymarch"
         s.max_samples = 100000
-        mean, _ = _frame(r, 384, 32)
+        mean, _ = frame(r, 384, 32)
         s.render_mode = "dvr"
         s.dvr_shadow_stride = 0
-        plain, _ = _frame(r)
+        plain, _ = frame(r)
         s.dvr_shadow_stride = 1
-        shad, _ = _frame(r)
+        shad, _ = frame(r)
     finally:
         r.close()
     lum = lambda im: im[..., :3].mean(axis=-1)

@@ -13,8 +13,7 @@ import pytest
 from oracle import np_oracle as NP
 from tests import shadow_ref as SR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
+from tests.common import NAPI, ROOT
 F32 = np.float32
 
 

@@ -3,54 +3,29 @@ oblique thin and thick slabs of every reduction under every layout against the N
 tolerance 0, both displays, the stats, rendering left alone, device groups, the refusals, a full-size slab and the JS host."""
 import ctypes as C
 import json
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import np_oracle as NP
 from tests import slice_ref as SR
+from tests.common import F32, LAYOUTS, bits, grid, renderer, small_noise, upload_volume
+from tests.js_host import dump_grid, run_node
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAPI = os.path.join(ROOT, "volxel_amd", "napi")
-F32 = np.float32
-LAYOUTS = {"brickf32": 2, "bricku8": 4, "reference": 0, "cellquad": 1, "auto": 3}
 REDUCE = ("mean", "max", "min")
-
-
-def _grid(vox, sp):
-    from volxel_amd import read_u16_stack_to_grid
-    return read_u16_stack_to_grid(vox, sp)
 
 
 @pytest.fixture(scope="module")
 def noise():
-    from tests.common import small_noise
-    return _grid(*small_noise(64))
+    return grid(*small_noise(64))
 
 
 @pytest.fixture(scope="module")
 def aniso():
     """48 x 40 x 32 voxels of noise with spacing (0.8, 1.0, 2.5): the world box is not a cube"""
-    from tests.common import small_noise
     v, _ = small_noise(64, seed=3)
-    return _grid(np.ascontiguousarray(v[:32, :40, :48]), (0.8, 1.0, 2.5))
-
-
-def _renderer(g, layout=None, devices=None, mode="dvr"):
-    from volxel_amd import BENCHMARK_SETTINGS, Volxel3DRenderer
-    r = Volxel3DRenderer(64, 48, device=None if devices else 0, layout=layout, devices=devices)
-    r.setup_from_grid(g)
-    r.restore_settings(BENCHMARK_SETTINGS)
-    r.settings.render_mode = mode
-    r.settings.dvr_jitter = False
-    return r
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+    return grid(np.ascontiguousarray(v[:32, :40, :48]), (0.8, 1.0, 2.5))
 
 
 def _tilted(r, thickness=0.0, samples=1, size=(80, 72)):
@@ -65,7 +40,7 @@ def _tilted(r, thickness=0.0, samples=1, size=(80, 72)):
 def test_axis_planes_are_the_voxels(noise, layout):
     """closed form: at voxel centres every fraction is 0, so the value is the decoded voxel x density_scale x inv_maj"""
     from volxel_amd import axial, coronal, sagittal
-    r = _renderer(noise, layout=LAYOUTS[layout])
+    r = renderer(noise, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         got = {(f.__name__, i): r.slice(f(r, i)) for f in (axial, coronal, sagittal) for i in (0, 17, 63)}
         p = r._params
@@ -86,7 +61,7 @@ def test_axis_planes_are_the_voxels(noise, layout):
             w = want(a, np.full_like(a, i), b)
         else:
             w = want(np.full_like(a, i), a, b)
-        assert np.array_equal(_bits(v), _bits(w)), (name, i)
+        assert np.array_equal(bits(v), bits(w)), (name, i)
     assert any(float(v.max()) > 0 for v in got.values())
 
 
@@ -95,34 +70,34 @@ def test_axis_planes_are_the_voxels(noise, layout):
 @pytest.mark.parametrize("reduce", REDUCE)
 @pytest.mark.parametrize("thick", [False, True])
 def test_oblique_matches_reference(noise, layout, reduce, thick):
-    r = _renderer(noise, layout=LAYOUTS[layout])
+    r = renderer(noise, layout=LAYOUTS[layout], dvr_jitter=False)
     try:
         sp = _tilted(r, thickness=0.12, samples=9) if thick else _tilted(r)
         got = r.slice(sp, reduce=reduce)
         want = SR.values(sp, noise, r._params, reduce=SR.REDUCE_IDS[reduce])
     finally:
         r.close()
-    assert np.array_equal(_bits(got), _bits(want)), float(np.abs(got - want).max())
+    assert np.array_equal(bits(got), bits(want)), float(np.abs(got - want).max())
     assert (got == 0).any() and float(got.max()) > 0       # part of the plane lies outside the volume
 
 
 @pytest.mark.gpu
 def test_anisotropic_oblique_matches_reference(aniso):
-    r = _renderer(aniso)
+    r = renderer(aniso, dvr_jitter=False)
     try:
         sp = _tilted(r, thickness=0.05, samples=4, size=(33, 47))
         got = r.slice(sp, reduce="max")
         want = SR.values(sp, aniso, r._params, reduce=SR.MAX)
     finally:
         r.close()
-    assert np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(bits(got), bits(want))
     assert float(got.max()) > 0
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("display", ["grey", "tf"])
 def test_display_bytes(noise, display):
-    r = _renderer(noise)
+    r = renderer(noise, dvr_jitter=False)
     try:
         sp = _tilted(r, thickness=0.1, samples=5)
         window = (0.05, 0.6) if display == "grey" else None
@@ -142,7 +117,7 @@ def test_display_bytes(noise, display):
 
 @pytest.mark.gpu
 def test_stats_count_the_samples(noise):
-    r = _renderer(noise)
+    r = renderer(noise, dvr_jitter=False)
     try:
         assert r.slice_stats() == (0, 0.0)
         sp = _tilted(r, thickness=0.1, samples=7, size=(50, 30))
@@ -161,7 +136,7 @@ def test_slicing_leaves_rendering_alone(noise):
     from volxel_amd import axial
 
     def run(with_slice):
-        r = _renderer(noise)
+        r = renderer(noise, dvr_jitter=False)
         try:
             r.reset_counters()
             r.render(frames=4, in_flight=4)
@@ -176,14 +151,14 @@ def test_slicing_leaves_rendering_alone(noise):
 
     a, ca = run(False)
     b, cb = run(True)
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(bits(a), bits(b))
     assert ca == cb and ca[0] > 0
 
 
 @pytest.mark.gpu
 def test_group_gives_the_single_context_bits(noise):
-    one = _renderer(noise)
-    grp = _renderer(noise, devices=[0, 0, 0])
+    one = renderer(noise, dvr_jitter=False)
+    grp = renderer(noise, devices=[0, 0, 0], dvr_jitter=False)
     try:
         sp = _tilted(one, thickness=0.1, samples=6)
         a, ra = one.slice(sp, reduce="max", display="tf")
@@ -192,20 +167,7 @@ def test_group_gives_the_single_context_bits(noise):
     finally:
         one.close()
         grp.close()
-    assert np.array_equal(_bits(a), _bits(b)) and np.array_equal(ra, rb) and sa == sb
-
-
-def _upload(lib, ctx, g):
-    u3 = lambda t: (C.c_uint32 * 3)(*[int(x) for x in t])
-    ind = np.ascontiguousarray(g.indirection, dtype=np.uint32)
-    rng = np.ascontiguousarray(g.range, dtype=np.uint16)
-    atl = np.ascontiguousarray(g.atlas, dtype=np.uint8)
-    mips = [np.ascontiguousarray(m, dtype=np.uint16) for m, _ in g.range_mipmaps]
-    ptrs = (C.c_void_p * len(mips))(*[m.ctypes.data for m in mips])
-    sizes = (C.c_uint32 * (3 * len(mips)))(*[int(x) for _, s in g.range_mipmaps for x in s])
-    return lib.vx_upload_volume(ctx, ind.ctypes.data, u3(g.indirection_size), rng.ctypes.data, u3(g.range_size),
-                                atl.ctypes.data, u3(g.atlas_size), len(mips), ptrs, C.cast(sizes, C.c_void_p),
-                                u3(g.index_extent))
+    assert np.array_equal(bits(a), bits(b)) and np.array_equal(ra, rb) and sa == sb
 
 
 @pytest.mark.gpu
@@ -218,9 +180,9 @@ def test_refusals(noise):
     try:
         assert lib.vx_slice(ctx, C.byref(sp), None, None) == 3                      # VX_ERR_NO_VOLUME
         assert lib.vx_slice_stats(ctx, None, None) == 0
-        assert _upload(lib, ctx, noise) == 0
+        assert upload_volume(lib, ctx, noise) == 0
         assert lib.vx_slice(ctx, C.byref(sp), None, None) == 1 and b"vx_set_params" in lib.vx_last_error(ctx)
-        r = _renderer(noise)
+        r = renderer(noise, dvr_jitter=False)
         try:
             p = r.bind_uniforms()
         finally:
@@ -267,8 +229,8 @@ def test_refusals(noise):
 def test_full_size_mip_slab():
     """a 1024^2 oblique 64-sample MIP slab of the 512^3 config-3 volume, against slice_ref on a 96 x 64 crop"""
     from volxel_amd import synth
-    g = _grid(*synth.value_noise(512))
-    r = _renderer(g)
+    g = grid(*synth.value_noise(512))
+    r = renderer(g, dvr_jitter=False)
     try:
         sp = _tilted(r, thickness=0.06, samples=64, size=(1024, 1024))
         vals, rgba = r.slice(sp, reduce="max", display="tf")
@@ -279,16 +241,15 @@ def test_full_size_mip_slab():
         r.close()
     x0, y0, x1, y1 = win
     assert n == 1024 * 1024 * 64
-    assert np.array_equal(_bits(vals[y0:y1, x0:x1]), _bits(want))
+    assert np.array_equal(bits(vals[y0:y1, x0:x1]), bits(want))
     assert float(want.max()) > 0
 
 
 @pytest.mark.gpu
 @pytest.mark.skipif(shutil.which("node") is None, reason="node not installed")
 def test_js_host_slice_has_the_python_bits(noise, tmp_path):
-    subprocess.check_call(["make", "-C", NAPI, "-s"])
     dims = [int(x) for x in noise.index_extent]
-    r = _renderer(noise)
+    r = renderer(noise, dvr_jitter=False)
     try:
         from volxel_amd import axial
         sp = _tilted(r, thickness=0.1, samples=5)
@@ -299,32 +260,8 @@ def test_js_host_slice_has_the_python_bits(noise, tmp_path):
     spec = {k: [float(x) for x in getattr(sp, k)[:]] for k in ("origin", "du", "dv", "dn")}
     spec.update(size=[int(sp.size[0]), int(sp.size[1])], slabSamples=int(sp.slab_samples))
     (tmp_path / "spec.json").write_text(json.dumps(spec))
-    (tmp_path / "grid.json").write_text(json.dumps({
-        "indirectionSize": list(map(int, noise.indirection_size)), "rangeSize": list(map(int, noise.range_size)),
-        "atlasSize": list(map(int, noise.atlas_size)), "indexExtent": dims, "minMaj": list(map(float, noise.min_maj)),
-        "transform": list(map(float, noise.transform)),
-        "mips": [list(map(int, s)) for _, s in noise.range_mipmaps]}))
-    np.asarray(noise.indirection, dtype=np.uint32).tofile(tmp_path / "ind.bin")
-    np.asarray(noise.range, dtype=np.uint16).tofile(tmp_path / "range.bin")
-    np.asarray(noise.atlas, dtype=np.uint8).tofile(tmp_path / "atlas.bin")
-    for i, (m, _) in enumerate(noise.range_mipmaps):
-        np.asarray(m, dtype=np.uint16).tofile(tmp_path / f"mip{i}.bin")
-    from volxel_amd import BENCHMARK_SETTINGS
-    (tmp_path / "settings.json").write_text(json.dumps(BENCHMARK_SETTINGS))
-    script = r"""
-const fs = require('fs'), path = require('path');
-const [napi, dir] = process.argv.slice(2);
-const v = require(napi);
-const rd = (f, T) => { const b = fs.readFileSync(path.join(dir, f)); return new T(b.buffer.slice(b.byteOffset, b.byteOffset + b.byteLength)); };
-const g = JSON.parse(fs.readFileSync(path.join(dir, 'grid.json')));
-const grid = { type: 'return_dicom', indirectionSize: g.indirectionSize, rangeSize: g.rangeSize, atlasSize: g.atlasSize,
-  indexExtent: g.indexExtent, minMaj: g.minMaj, transform: new Float32Array(g.transform),
-  indirection: rd('ind.bin', Uint32Array), range: rd('range.bin', Uint16Array), atlas: rd('atlas.bin', Uint8Array),
-  rangeMipmaps: g.mips.map((s, i) => ({ mipmap: rd(`mip${i}.bin`, Uint16Array), stride: s })) };
-const r = new v.Volxel3DDicomRenderer({ width: 64, height: 48 });
-r.setupFromGrid(grid);
-r.restoreSettings(JSON.parse(fs.readFileSync(path.join(dir, 'settings.json'))));
-r.settings.renderMode = 'dvr';
+    dump_grid(tmp_path, noise)
+    body = r"""
 const spec = JSON.parse(fs.readFileSync(path.join(dir, 'spec.json')));
 const a = r.slice(Object.assign({}, spec, { reduce: 'min', display: 'grey', window: [0.0, 0.5] }));
 const b = r.slice(r.axial(9));
@@ -334,9 +271,8 @@ fs.writeFileSync(path.join(dir, 'js_ax.bin'), Buffer.from(b.values.buffer));
 console.log(JSON.stringify({ samples: r.sliceStats().samples, axNull: b.rgba8 === null }));
 r.dispose();
 """
-    (tmp_path / "s.js").write_text(script)
-    out = json.loads(subprocess.check_output(["node", str(tmp_path / "s.js"), NAPI, str(tmp_path)], timeout=300))
+    out = run_node(tmp_path, body)
     assert out["axNull"] and out["samples"] == dims[0] * dims[1]
-    assert np.array_equal(np.fromfile(tmp_path / "js_v.bin", dtype=np.uint32), _bits(want_v).reshape(-1))
+    assert np.array_equal(np.fromfile(tmp_path / "js_v.bin", dtype=np.uint32), bits(want_v).reshape(-1))
     assert np.array_equal(np.fromfile(tmp_path / "js_rgba.bin", dtype=np.uint8), want_rgba.reshape(-1))
-    assert np.array_equal(np.fromfile(tmp_path / "js_ax.bin", dtype=np.uint32), _bits(want_ax).reshape(-1))
+    assert np.array_equal(np.fromfile(tmp_path / "js_ax.bin", dtype=np.uint32), bits(want_ax).reshape(-1))
