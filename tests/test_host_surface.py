@@ -201,5 +201,5 @@ def test_merge_launches_is_the_last_counter():
     assert [f[0] for f in fields[-2:]] == ["active_lane_slots", "merge_launches"]
     assert fields[-1][1] is ctypes.c_uint64
     assert _abi.VxCounters.merge_launches.offset + 8 == ctypes.sizeof(_abi.VxCounters)
-    assert 'PUT("mergeLaunches", k.merge_launches)' in open(os.path.join(NAPI, "volxel_napi.c")).read()
+    assert '{"mergeLaunches", (double)k.merge_launches}' in open(os.path.join(NAPI, "volxel_napi.c")).read()
     assert "mergeLaunches: number" in open(os.path.join(NAPI, "index.d.ts")).read()

@@ -72,6 +72,55 @@ def test_node_host_cpu(oracle, tmp_path):
         assert k in keys
 
 
+# every export of volxel_napi.node with the number of arguments it demands; CTX_ARITY: the first one is the context handle
+CTX_ARITY = {
+    "destroy": 1, "uploadVolume": 2, "uploadTransfer": 3, "uploadEnvironment": 4, "setParams": 2, "resize": 3, "setLayout": 2,
+    "renderFrame": 3, "renderFrames": 4, "probeTileCosts": 2, "setTileOrder": 2, "deviceInfo": 1, "finish": 1, "readAccum": 2,
+    "readDisplay": 4, "readDisplayScaled": 6, "getCounters": 1, "resetCounters": 1, "shadowStats": 1, "readShadowGrid": 1,
+    "slice": 4, "sliceStats": 1, "isosurface": 4, "isoStats": 1, "segment": 2, "segmentMask": 2, "sliceMask": 3,
+    "segmentStats": 1, "setSegmentView": 2, "getSegmentView": 1, "segmentEdit": 5, "setSegmentMask": 2, "segmentEditStats": 1,
+    "segmentThreshold": 2, "segmentIslands": 8, "islandsRead": 3, "islandsReadLabels": 2, "islandsStats": 1, "meshExtract": 2,
+    "meshRead": 4, "meshStats": 1}
+NO_CTX = ["create", "createGroup", "buildBrickGrid", "readDicomsToGrid"]
+SIZEOF = {"sizeofParams": "VxParams", "sizeofSliceParams": "VxSliceParams", "sizeofIsoParams": "VxIsoParams",
+          "sizeofSegmentParams": "VxSegmentParams", "sizeofMeshParams": "VxMeshParams"}
+
+
+def test_native_module_boundary(tmp_path):
+    """the addon's exported names, its argument-count and handle guards and the five sizeof* values; no device is touched:
+    every call here is refused before the C ABI is reached"""
+    from volxel_amd import _abi
+    _build()
+    script = r"""
+const native = require(require('path').join(process.argv[2], 'volxel_napi.node'));
+const arity = JSON.parse(process.argv[3]);
+const thrown = (f) => { try { f(); return null; } catch (e) { return { type: e instanceof TypeError, msg: e.message }; } };
+const out = { keys: Object.keys(native).sort(), none: {}, short: {}, handle: {}, sizes: {} };
+for (const k of out.keys) {
+  if (k === 'version' || k.startsWith('sizeof')) continue;
+  out.none[k] = thrown(() => native[k]());
+}
+for (const k of Object.keys(arity)) {
+  out.short[k] = thrown(() => native[k](...new Array(arity[k] - 1).fill({})));   // one argument too few
+  out.handle[k] = thrown(() => native[k]({}, ...new Array(arity[k] - 1).fill(0)));
+}
+for (const k of out.keys.filter((k) => k.startsWith('sizeof'))) out.sizes[k] = native[k]();
+console.log(JSON.stringify(out));
+"""
+    (tmp_path / "b.js").write_text(script)
+    out = json.loads(subprocess.check_output(["node", str(tmp_path / "b.js"), NAPI, json.dumps(CTX_ARITY)], timeout=120))
+    assert out["keys"] == sorted(list(CTX_ARITY) + NO_CTX + list(SIZEOF) + ["version"]) and len(out["keys"]) == 51
+    assert sorted(out["none"]) == sorted(list(CTX_ARITY) + NO_CTX)
+    for k, e in out["none"].items():
+        assert e is not None and e["type"] and "wrong number of arguments" in e["msg"], (k, e)
+    for k in CTX_ARITY:
+        e = out["short"][k]
+        assert e is not None and e["type"] and "wrong number of arguments" in e["msg"], (k, e)
+        e = out["handle"][k]
+        assert e is not None and e["type"] and "expected a context handle" in e["msg"], (k, e)
+    assert out["sizes"] == {k: C.sizeof(getattr(_abi, s)) for k, s in SIZEOF.items()}
+
+
 @pytest.mark.gpu
 def test_node_host_renders_like_the_oracle(oracle, tmp_path):
     import copy

@@ -286,6 +286,20 @@ def test_js_host_segment_view_has_the_python_bits(scenes, tmp_path):
         r.segment_view = "hide"
         r.render(frames=4)
         want = r.read_accum()
+        # the native calls no other JS-host test reaches, on one shadowed frame: setLayout, readShadowGrid, shadowStats,
+        # readDisplayScaled, readDisplay and resetCounters must answer what these answer
+        r.setup_from_grid(g)
+        r.set_layout(2)
+        r.settings.use_env = r.settings.show_environment = False
+        r.settings.dvr_shadow_stride = 2
+        r.restart_rendering()
+        r.render(frames=1)
+        light, (builds, light_samples, _) = r.read_shadow_grid(), r.shadow_stats()
+        scaled, full = r.read_display(), np.empty((H, W, 4), dtype=np.uint8)
+        r._check(r._lib.vx_read_display(r._ctx, full.ctypes.data, float(r.settings.exposure), float(r.settings.gamma)))
+        r.reset_counters()
+        extra = {"dims": list(light.shape[::-1]), "builds": builds, "lightSamples": light_samples,
+                 "samplesAfterReset": r.counters().samples}
     finally:
         r.close()
     dump_grid(tmp_path, g)
@@ -306,6 +320,17 @@ const img = r.readAccum();
 fs.writeFileSync(path.join(dir, 'img.bin'), Buffer.from(img.buffer, img.byteOffset, img.byteLength));
 const view = r.segmentView;
 r.setupFromGrid(grid);
+v.native.setLayout(r.ctx, 2);
+r.settings.useEnv = r.settings.showEnvironment = false;
+r.settings.dvrShadowStride = 2;
+r.restartRendering();
+r.render(1);
+const light = r.readShadowGrid(), ss = r.shadowStats(), full = new Uint8Array(r.width * r.height * 4);
+v.native.readDisplay(r.ctx, full, r.settings.exposure, r.settings.gamma);
+save('light.bin', light.data); save('scaled.bin', r.readDisplay()); save('full.bin', full);
+r.resetCounters();
+const extra = { dims: light.dims, builds: ss.builds, lightSamples: ss.lightSamples, samplesAfterReset: r.counters().samples };
+fs.writeFileSync(path.join(dir, 'extra.json'), JSON.stringify(extra));
 console.log(JSON.stringify({ before, refused, view, after: r.segmentView }));
 r.dispose();
 """
@@ -313,3 +338,7 @@ r.dispose();
     assert out == {"before": "off", "refused": True, "view": "hide", "after": "off"}, out
     got = np.fromfile(tmp_path / "img.bin", dtype=np.float32).reshape(want.shape)
     assert np.array_equal(bits(got), bits(want))
+    assert json.loads((tmp_path / "extra.json").read_text()) == extra and extra["builds"] == 1 and extra["samplesAfterReset"] == 0
+    assert np.array_equal(np.fromfile(tmp_path / "light.bin", dtype=np.float32), light.ravel())
+    assert np.array_equal(np.fromfile(tmp_path / "scaled.bin", dtype=np.uint8), scaled.ravel()) and scaled.any()
+    assert np.array_equal(np.fromfile(tmp_path / "full.bin", dtype=np.uint8), full.ravel())
