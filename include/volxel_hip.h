@@ -704,6 +704,15 @@ int vx_debug_build_skip_mask(const uint32_t* range_packed, const uint32_t brick_
  * nothing is skipped.  bounds_out holds 2 * dims[0] * dims[1] * dims[2] floats, or is NULL to query level / dims. */
 int vx_debug_build_projection_bounds(const uint32_t* range_packed, const uint32_t brick_count[3], const VxParams* params,
                                      float* bounds_out, uint32_t* level_out, uint32_t dims_out[3]);
+/* test hook: which 16x16-pixel blocks of a width x height image no primary DVR ray can hit the clip box from (pure CPU, no
+ * context): flags_out[by * ceil(width / 16) + bx] = 1 for such a block, 0 where a ray may hit; *n_out = how many are 1.  The
+ * proof needs a perspective camera in front of all eight corners of volume_aabb_min .. max and finite matrices; without it, or
+ * with VX_DVR_MISS=0 in the environment, no block is flagged.  A multi-frame launch of plain DVR on the LDS-window kernel hands the
+ * flagged blocks to a light kernel (images and counters do not change).  Either out pointer may be NULL. */
+int vx_debug_classify_miss_blocks(const VxParams* params, uint32_t width, uint32_t height, uint8_t* flags_out, uint32_t* n_out);
+/* test hook: how many 16x16-pixel blocks per frame the last render launch gave its march kernel and the light kernel of the
+ * blocks that cannot hit the clip box (0 when the launch was not split).  group: summed over the members. */
+int vx_debug_last_launch_blocks(VxContext* ctx, uint32_t* heavy_out, uint32_t* miss_out);
 
 #ifdef __cplusplus
 }

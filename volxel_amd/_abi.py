@@ -150,6 +150,8 @@ def load_library():
         "vx_upload_stats": ([vp, P(C.c_double), P(u64), P(i32)], i32),
         "vx_debug_build_skip_mask": ([vp, P(u32), vp, u32, P(VxParams), vp, P(u32), P(u32)], i32),
         "vx_debug_build_projection_bounds": ([vp, P(u32), P(VxParams), vp, P(u32), P(u32)], i32),
+        "vx_debug_classify_miss_blocks": ([P(VxParams), u32, u32, vp, P(u32)], i32),
+        "vx_debug_last_launch_blocks": ([vp, P(u32), P(u32)], i32),
         "vx_shadow_stats": ([vp, P(u64), P(u64), P(C.c_double)], i32),
         "vx_debug_read_shadow_grid": ([vp, vp, P(u32)], i32),
         "vx_slice": ([vp, P(VxSliceParams), vp, vp], i32),

@@ -15,6 +15,7 @@
 #include "../../include/volxel_brick.h"
 #include "vx_dvr.hpp"
 #include "vx_dvr_lds.hpp"
+#include "vx_dvr_miss.hpp"
 #include "vx_kernels.hpp"
 #include "vx_shadow.hpp"
 #include "vx_projection.hpp"
@@ -44,12 +45,31 @@ struct Switches {
   bool ray_shortcuts = true;       // VX_RAY_SHORTCUTS=0: the per-ray divisions themselves (DevVolume::ray_flags = 0)
   std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
   uint32_t seg_check_max = 64;     // VX_SEG_CHECK_MAX (1 .. 4096): the largest batch of flood rounds between read-backs (vx_segment)
+  bool dvr_miss = true;            // VX_DVR_MISS=0: no multi-frame DVR launch is split; every block runs the LDS-window kernel
 };
+// VX_DVR_MISS alone: vx_create reads it with the others, and the classifier's test hook -- which has no context to hold a
+// Switches -- reads this one variable and nothing else
+bool dvr_miss_switch() {
+  const char* v = getenv("VX_DVR_MISS");
+  return !(v && atoi(v) == 0);
+}
+// the only place that reads the other switches from the environment (vx_create)
+Switches read_switches() {
+  Switches sw;
+  if (const char* v = getenv("VX_DVR_KERNEL"); v && !strcmp(v, "generic")) sw.dvr_variant = 0;
+  if (const char* v = getenv("VX_DVR_FUSE")) sw.dvr_fuse = atoi(v) != 0;
+  if (const char* v = getenv("VX_RAY_SHORTCUTS"); v && atoi(v) == 0) sw.ray_shortcuts = false;
+  if (const char* v = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) sw.cellquad_max_bytes = strtoull(v, nullptr, 10);
+  if (const char* v = getenv("VX_SEG_CHECK_MAX")) sw.seg_check_max = (uint32_t)std::min(std::max(atoi(v), 1), 4096);
+  sw.dvr_miss = dvr_miss_switch();
+  return sw;
+}
 
 // ---- the tables a launch derives from the params and the uploads ---------------------------------------------------------
 // The skip mask, the projection bounds, the local majorants and the light grid share one cache rule: a table is rebuilt
 // before a launch that reads it when an upload marked it stale or when its key -- the bits of the params it is built from,
-// listed once in its key function -- differs from the key of the last build.  A camera move rebuilds none of them.
+// listed once in its key function -- differs from the key of the last build.  A camera move rebuilds none of them but the
+// split of a multi-frame DVR launch (miss_key: host arithmetic and one asynchronous copy, no wait on the stream).
 
 // the bits of 4-byte params and param arrays, in order
 template <class... T>
@@ -67,6 +87,13 @@ auto lmaj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volum
 auto shadow_key(const VxParams& p) {
   return key_of(p.light_dir, p.density_transform_inv, p.volume_aabb_min, p.volume_aabb_max, p.volume_maj, p.volume_inv_maj,
                 p.volume_density_scale, p.sample_range, p.dvr_step_voxels, p.dvr_ert_tau, p.dvr_max_steps, p.dvr_shadow_stride);
+}
+// the split of a multi-frame DVR launch (classify_miss_blocks): the matrices the rays use, the clip box, the image, the shard
+// -- a camera move DOES rebuild this one, ahead of the next multi-frame launch (host arithmetic on eight corners and a
+// frame's blocks); the tile map marks it stale itself
+auto miss_key(const VxParams& p) {
+  return key_of(p.camera_view_inv, p.camera_proj_inv, p.camera_ortho, p.volume_aabb_min, p.volume_aabb_max, p.res, p.shard_rank,
+                p.shard_count);
 }
 
 template <auto KEY>
@@ -173,6 +200,38 @@ struct VxContext : VxCore {   // (device, the stream the launches go to, the las
   DevBuf<uchar4> display;
   DevBuf<uint32_t> tile_perm;  // vx_set_tile_order: position -> tile, tile -> position (2 * n_tiles)
   uint32_t tile_perm_n = 0;
+  std::vector<uint32_t> tile_perm_host;   // position -> tile as the device holds it (empty: pos == tile id)
+  // The split of a multi-frame DVR launch of the LDS-window kernel (ensure_miss_split): per logical block of a frame, 1 = it goes to
+  // render_dvr_miss -- no ray of its pixels can hit the clip box (`proved` of them), or it lies outside the shard's tiles or
+  // the image, where either kernel returns at once; the two halves of `order`, split_order's stable partition.
+  struct MissSplit {
+    DerivedTable<miss_key> table;     // stale: never built, or the tile map changed
+    std::vector<uint8_t> flags_host;
+    DevBuf<uint8_t> flags;
+    DevBuf<uint32_t> order_heavy, order_miss;
+    uint32_t blocks = 0;              // frame_blocks of the build
+    uint32_t n_miss = 0, proved = 0;
+    bool split_stale = true;          // `order` or the flags changed since split_order ran
+    uint32_t last_heavy = 0, last_miss = 0;   // blocks per frame slot the last render launch gave each kernel
+    // the flags cross to the device from two pinned buffers used in turn: the copy is asynchronous on the context's stream, and
+    // a buffer is rewritten only behind the event of its last copy (two builds back: complete long since, no stall)
+    struct Stage {
+      uint8_t* p = nullptr;
+      size_t cap = 0;
+      hipEvent_t done = nullptr;
+      bool pending = false;
+    } stage[2];
+    int next_stage = 0;
+    MissSplit() = default;
+    MissSplit(const MissSplit&) = delete;
+    MissSplit& operator=(const MissSplit&) = delete;
+    ~MissSplit() {
+      for (Stage& st : stage) {
+        if (st.p) (void)hipHostFree(st.p);
+        if (st.done) (void)hipEventDestroy(st.done);
+      }
+    }
+  } miss;
 
   // counters / timing
   DevBuf<DevCounters> dc;      // one record per wave of the largest launch grid
@@ -283,6 +342,8 @@ static void update_tilemap(VxContext* c) {
     c->tile_perm.reset();
     c->tile_perm_n = 0;
   }
+  if (!c->tile_perm) c->tile_perm_host.clear();
+  c->miss.table.stale = true;   // blocks map to other pixels
   t.perm = c->tile_perm;
   t.inv = c->tile_perm ? c->tile_perm + t.n_tiles : nullptr;
 }
@@ -293,6 +354,7 @@ static int alloc_framebuffers(VxContext* c) {
     for (size_t i = 0; i < ident.size(); ++i) ident[i] = (uint32_t)i;
     VX_HIP(c, hipMemcpy(c->order, ident.data(), ident.size() * 4, hipMemcpyHostToDevice));
     c->order_builds_left = 2;
+    c->miss.split_stale = true;
   }
   // grow-only: the low-resolution preview (viewer.ts:1167-1188) resizes twice per restart
   update_tilemap(c);
@@ -574,6 +636,7 @@ static int ensure_counters(VxContext* c, size_t waves) {
     if (int rc = c->order.alloc(c, ident.size())) return rc;
     VX_HIP(c, hipMemcpy(c->order, ident.data(), ident.size() * 4, hipMemcpyHostToDevice));
     c->order_builds_left = 2;
+    c->miss.split_stale = true;
   }
   return VX_OK;
 }
@@ -714,6 +777,10 @@ struct LaunchPlan {
   const float* bounds = nullptr;      // PROJ_LDS: the table of range skipping, nullptr without SKIP
   const uint32_t* order = nullptr;    // the tuned kernels' block order, longest first (build_order); nullptr: the probe's
   dim3 grid, block{256};
+  // DVR_LDS, a split launch (VxContext::MissSplit): `grid` and `order` cover the blocks that may hit the clip box, and
+  // render_dvr_miss runs the rest -- miss_grid.x launch slots (0: no split) in the order miss_order; one logical launch
+  dim3 miss_grid{0};
+  const uint32_t* miss_order = nullptr;
   size_t lds = 0;                     // dynamic LDS bytes
   bool fuse = false;                  // the kernel folds the running mean of the launch itself (MultiOut::fuse)
   bool segv = false;                  // DVR_LDS, PROJ_LDS: the segment view's kernel (render_dvr_lds_seg, render_proj_lds_seg)
@@ -806,6 +873,17 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo, bool probe
   lp.grid = dim3(frame_blocks(c) * (lds_window && mo.count == 0u ? 1u : mo.count));
   lp.fuse = c->sw.dvr_fuse && folds(lp.kernel, lp.mode, mo.count);
   lp.lds = lds_bytes(c, lp);
+  // the split: a multi-frame launch of plain DVR on the LDS-window kernel, with a proof for some block and both halves of
+  // the order in place.  Not a single-frame launch: it is bound by the latency of its longest rays, the missing waves ran
+  // beside them for nothing, and split it measured 5 % slower (NOTEBOOK R4.13).
+  const VxContext::MissSplit& ms = c->miss;
+  if (lp.kernel == Kernel::DVR_LDS && !lp.phong && !lp.shadow && !lp.segv && mo.count > 1u && c->sw.dvr_miss && ms.proved > 0u &&
+      ms.table.current(p) && ms.blocks == frame_blocks(c) && !ms.split_stale) {
+    lp.grid = dim3((ms.blocks - ms.n_miss) * mo.count);
+    lp.order = ms.order_heavy;
+    lp.miss_grid = dim3(ms.n_miss * mo.count);
+    lp.miss_order = ms.order_miss;
+  }
   return lp;
 }
 
@@ -858,6 +936,10 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
         });
         break;
       }
+      if (lp.miss_grid.x != 0u)   // the blocks that cannot hit the clip box: the same frame slots, the same fold
+        hipLaunchKernelGGL(render_dvr_miss, lp.miss_grid, lp.block, mo.fuse ? 4u * 320u * sizeof(float) : 0u, s, p, v, tf, n, mo,
+                           weight, tm, lp.miss_order);   // (LDS: fold_frames' scratch, 320 floats per wave, in a launch that folds)
+      if (lp.grid.x == 0u) break;   // (no block of this shard can hit)
       with_bool(lp.skip, [&](auto sk) {
         with_bool(lp.u8, [&](auto u8) {
           constexpr bool SK = decltype(sk)::value, U8 = decltype(u8)::value;
@@ -914,6 +996,11 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
       });
   }
   VX_HIP(c, hipGetLastError());
+  {
+    const uint32_t slots = mo.count == 0u ? 1u : mo.count;
+    c->miss.last_heavy = lp.grid.x / slots;
+    c->miss.last_miss = lp.miss_grid.x / slots;
+  }
   return VX_OK;
 }
 
@@ -1116,13 +1203,7 @@ int vx_create(int device_id, VxContext** out) {
       return VX_ERR_DEVICE;
     }
   }
-  // the diagnostic switches (struct Switches): the only place that reads the environment
-  Switches& sw = c->sw;
-  if (const char* v = getenv("VX_DVR_KERNEL"); v && !strcmp(v, "generic")) sw.dvr_variant = 0;
-  if (const char* v = getenv("VX_DVR_FUSE")) sw.dvr_fuse = atoi(v) != 0;
-  if (const char* v = getenv("VX_RAY_SHORTCUTS"); v && atoi(v) == 0) sw.ray_shortcuts = false;
-  if (const char* v = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) sw.cellquad_max_bytes = strtoull(v, nullptr, 10);
-  if (const char* v = getenv("VX_SEG_CHECK_MAX")) sw.seg_check_max = (uint32_t)std::min(std::max(atoi(v), 1), 4096);
+  c->sw = read_switches();   // the diagnostic switches (struct Switches)
   *out = c;
   return VX_OK;
 }
@@ -1755,7 +1836,77 @@ static int check_segment_view(VxContext* c, const char* fn, bool iso) {
   return VX_OK;
 }
 
-static int prepare_render(VxContext* c) {
+// The split of a plain multi-frame DVR launch of the LDS-window kernel, kept current the way the derived tables are: the
+// classification is rebuilt when the bits of its key change or the tile map did, the two halves of the block order when `order`
+// or the flags did.  Called at the end of prepare_render ahead of a multi-frame launch only (the counters and `order` exist):
+// single-frame launches are never split (NOTEBOOK R4.13) and pay nothing for it.  plan_launch uses what it finds current.
+static int ensure_miss_split(VxContext* c) {
+  VxContext::MissSplit& ms = c->miss;
+  const VxParams& p = c->params;
+  if (!c->sw.dvr_miss || p.render_mode != VX_MODE_DVR || !use_lds_kernel(c)) return VX_OK;
+  const uint32_t nb = frame_blocks(c);
+  if (!ms.table.current(p) || ms.blocks != nb) {
+    ms.table.stale = true;   // until this build is complete: a failure below must not leave the old key over new counts
+    std::vector<uint8_t> img;
+    ms.proved = ms.n_miss = 0;
+    ms.blocks = nb;
+    if (classify_miss_blocks(p, c->W, c->H, img) != 0u) {
+      // image block -> logical block of this shard: block_to_tile, tile_at and wave_pixel on the host
+      const TileMap& tm = c->tm;
+      const uint32_t nbx = (c->W + 15u) / 16u;
+      auto morton_x = [](uint32_t m) { return (m & 1u) | ((m >> 1) & 2u) | ((m >> 2) & 4u); };
+      ms.flags_host.assign(nb, 0);
+      for (uint32_t b = 0; b < nb; ++b) {
+        const uint32_t lt = (b >> 7) * 8u + (b & 7u), wt = ((b >> 3) & 15u) * 4u;
+        const uint32_t pos = lt * tm.shard_count + tm.shard_rank;
+        const uint32_t t = (!c->tile_perm_host.empty() && pos < tm.n_tiles) ? c->tile_perm_host[pos] : pos;
+        const uint32_t x0 = (t % tm.tiles_x) * 64u + morton_x(wt) * 8u, y0 = (t / tm.tiles_x) * 64u + morton_x(wt >> 1) * 8u;
+        if (lt >= tm.tiles_per_shard || t >= tm.n_tiles || x0 >= tm.W || y0 >= tm.H) {
+          ms.flags_host[b] = 1;   // no pixel: either kernel returns at once
+        } else if (img[(size_t)(y0 >> 4) * nbx + (x0 >> 4)]) {
+          ms.flags_host[b] = 1;
+          ms.proved += 1;
+        }
+        ms.n_miss += ms.flags_host[b];
+      }
+    }
+    if (ms.proved > 0u) {
+      if (ms.flags.cap < nb || ms.order_heavy.cap < nb || ms.order_miss.cap < nb) {
+        VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued launch still reads the old halves
+        if (int rc = ms.flags.alloc(c, nb)) return rc;
+        if (int rc = ms.order_heavy.alloc(c, nb)) return rc;
+        if (int rc = ms.order_miss.alloc(c, nb)) return rc;
+      }
+      VxContext::MissSplit::Stage& st = ms.stage[ms.next_stage];
+      ms.next_stage ^= 1;
+      if (st.pending) VX_HIP(c, hipEventSynchronize(st.done));
+      st.pending = false;
+      if (st.cap < nb) {
+        if (st.p) (void)hipHostFree(st.p);
+        st.p = nullptr;
+        st.cap = 0;
+        VX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&st.p), nb, hipHostMallocDefault));
+        st.cap = nb;
+      }
+      if (!st.done) VX_HIP(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+      memcpy(st.p, ms.flags_host.data(), nb);
+      VX_HIP(c, hipMemcpyAsync(ms.flags, st.p, nb, hipMemcpyHostToDevice, c->stream));
+      VX_HIP(c, hipEventRecord(st.done, c->stream));
+      st.pending = true;
+    }
+    ms.table.built(p);
+    ms.split_stale = true;
+  }
+  if (ms.proved > 0u && ms.split_stale) {
+    hipLaunchKernelGGL(split_order, dim3(1), dim3(1024), 0, c->stream, c->order, ms.flags, nb, ms.order_heavy, ms.order_miss);
+    VX_HIP(c, hipGetLastError());
+    ms.split_stale = false;
+  }
+  return VX_OK;
+}
+
+// multi: a multi-frame launch follows (vx_render_frames)
+static int prepare_render(VxContext* c, bool multi = false) {
   if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
   if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
   if (!c->tf) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: no transfer function");
@@ -1851,7 +2002,8 @@ static int prepare_render(VxContext* c) {
     int rc = rebuild_light_grid(c);
     if (rc) return rc;
   }
-  return ensure_counters(c, (size_t)frame_blocks(c) * 4u);  // one record per wave of a frame's blocks
+  if (int rc = ensure_counters(c, (size_t)frame_blocks(c) * 4u)) return rc;  // one record per wave of a frame's blocks
+  return multi ? ensure_miss_split(c) : VX_OK;
 }
 
 static int take_events(VxContext* c, EventPair& ev) {
@@ -1892,6 +2044,7 @@ int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
     c->order_builds_left--;
     hipLaunchKernelGGL(build_order, dim3(1), dim3(1024), 0, c->stream, c->dc, c->order, frame_blocks(c));
     VX_HIP(c, hipGetLastError());
+    c->miss.split_stale = true;
   }
   c->note_launch(1);
   return VX_OK;
@@ -1938,7 +2091,7 @@ int vx_render_frames(VxContext* c, uint32_t first_frame, uint32_t count, const f
     ++done;
   }
   if (done == count) return VX_OK;
-  int rc = prepare_render(c);
+  int rc = prepare_render(c, true);
   if (rc) return rc;
   if ((rc = ensure_pipes(c, (uint32_t)in_flight))) return rc;
   const uint32_t nq = (uint32_t)c->slab_quads;
@@ -2086,6 +2239,7 @@ int vx_set_tile_order(VxContext* c, const uint32_t* perm, uint32_t n) {
     if (int rc = c->tile_perm.alloc(c, both.size())) return rc;
     VX_HIP(c, hipMemcpy(c->tile_perm, both.data(), both.size() * 4, hipMemcpyHostToDevice));
     c->tile_perm_n = n;
+    c->tile_perm_host.assign(both.begin(), both.begin() + n);
   } else {
     c->tile_perm.reset();
     c->tile_perm_n = 0;
@@ -2234,6 +2388,32 @@ int vx_debug_build_projection_bounds(const uint32_t* range_packed, const uint32_
   if (level_out) *level_out = (uint32_t)level;
   if (dims_out) { dims_out[0] = md[0]; dims_out[1] = md[1]; dims_out[2] = md[2]; }
   if (bounds_out) memcpy(bounds_out, lohi.data(), lohi.size() * sizeof(float));
+  return VX_OK;
+}
+
+// test hook: the host's classification of the image's 16x16-pixel blocks (pure CPU, no context), under the VX_DVR_MISS switch
+int vx_debug_classify_miss_blocks(const VxParams* p, uint32_t width, uint32_t height, uint8_t* flags_out, uint32_t* n_out) {
+  if (!p || width == 0 || height == 0 || width > 16384 || height > 16384) return VX_ERR_INVALID;
+  std::vector<uint8_t> flags;
+  uint32_t n = 0;
+  if (dvr_miss_switch()) n = classify_miss_blocks(*p, width, height, flags);
+  else flags.assign((size_t)((width + 15u) / 16u) * ((height + 15u) / 16u), 0);
+  if (flags_out) memcpy(flags_out, flags.data(), flags.size());
+  if (n_out) *n_out = n;
+  return VX_OK;
+}
+
+// test hook: the blocks per frame slot the last render launch gave the LDS-window kernel (or whichever single kernel ran) and
+// render_dvr_miss
+int vx_debug_last_launch_blocks(VxContext* c, uint32_t* heavy, uint32_t* miss) {
+  if (!c) return VX_ERR_INVALID;
+  uint32_t h = 0, m = 0;
+  for (const VxContext* k : is_group(c) ? c->members : std::vector<VxContext*>{c}) {
+    h += k->miss.last_heavy;
+    m += k->miss.last_miss;
+  }
+  if (heavy) *heavy = h;
+  if (miss) *miss = m;
   return VX_OK;
 }
 

@@ -606,6 +606,13 @@ class Volxel3DRenderer:
     def reset_counters(self):
         self._check(self._lib.vx_reset_counters(self._ctx))
 
+    def last_launch_blocks(self):
+        """(march, miss): the 16x16-pixel blocks per frame the last render launch gave its march kernel and the light kernel
+        of the blocks that cannot hit the clip box (vx_debug_last_launch_blocks; miss = 0: the launch was not split)"""
+        a, b = C.c_uint32(), C.c_uint32()
+        self._check(self._lib.vx_debug_last_launch_blocks(self._ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def set_stream(self, hip_stream: int | None):
         self._check(self._lib.vx_set_stream(self._ctx, C.c_void_p(hip_stream or 0)))
 
