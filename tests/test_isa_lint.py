@@ -1,6 +1,7 @@
 """The ISA lint of tools/check_exec_prologue.py (VGPR spill code placed ahead of an exec restore,
 the root cause of the wrong Phong pixels at 8 waves per SIMD): it recognises the fault, leaves correct code alone, and the
 listing of the library as built is clean."""
+import glob
 import os
 import subprocess
 import sys
@@ -74,14 +75,21 @@ def test_lint_accepts_correct_placement(tmp_path):
 
 
 def test_built_library_listing_is_clean(native_lib):
-    """volxel_amd/csrc/Makefile only accepts an object whose listing passes; the listing beside the library says so"""
-    listing = os.path.join(ROOT, "volxel_amd", "csrc", "vx_api.s")
-    if not os.path.exists(listing):   # a library shipped without its build directory
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "volxel_amd", "csrc"), "-s", "-B", "vx_api.o"])
+    """volxel_amd/csrc/Makefile only accepts an object whose listing passes; the listings beside the library say so, one per
+    unit of the host layer (every *.s the Makefile wrote), and the render unit's holds the render_* kernels"""
+    csrc = os.path.join(ROOT, "volxel_amd", "csrc")
+    units = sorted(os.path.basename(p)[:-len(".hip")] for p in glob.glob(os.path.join(csrc, "*.hip")))
+    missing = [u for u in units if not os.path.exists(os.path.join(csrc, u + ".s"))]
+    if missing:   # a library shipped without its build directory
+        subprocess.check_call(["make", "-C", csrc, "-s", "-B"] + [u + ".o" for u in missing])
     import check_exec_prologue as L
-    findings, stats = L.scan(listing)
-    assert findings == []
-    assert sum(1 for k in stats if "render_" in k) >= 20
+    listings = sorted(glob.glob(os.path.join(csrc, "*.s")))
+    assert [os.path.basename(p)[:-len(".s")] for p in listings] == units and "vx_api" in units
+    for listing in listings:
+        findings, stats = L.scan(listing)
+        assert findings == [], listing
+        if os.path.basename(listing) == "vx_api.s":
+            assert sum(1 for k in stats if "render_" in k) >= 20
 
 
 def test_necessary_instruction_model_matches_the_listing(native_lib):

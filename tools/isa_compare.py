@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Function-by-function comparison of two device ISA listings (volxel_amd/csrc/vx_api.s of two builds):
-  python tools/isa_compare.py OLD.s NEW.s
+"""Function-by-function comparison of the device ISA listings of two builds (volxel_amd/csrc/<unit>.s):
+  python tools/isa_compare.py OLD.s NEW.s [NEW.s ...]
+The functions of NEW are looked up in the union of its listings; one found in two of them is reported as "DUPLICATE".
 A function is "identical" when its instructions match after the block labels are renumbered, "args moved" when they match except
 that literals grow by --arg-shift bytes (the kernel-argument offsets behind a grown by-value struct such as VxParams), and
-"DIFFERENT" otherwise.  Exit status 1 when a function of OLD is missing from NEW or differs."""
+"DIFFERENT" otherwise.  Exit status 1 when a function of OLD is missing from NEW or differs, or NEW holds a duplicate."""
 import argparse
 import re
 import sys
@@ -45,11 +46,17 @@ def moved(a, b, shift):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
-    ap.add_argument("new")
+    ap.add_argument("new", nargs="+")
     ap.add_argument("--arg-shift", type=int, default=8)
     a = ap.parse_args()
-    old, new = functions(a.old), functions(a.new)
+    old, new = functions(a.old), {}
     bad = 0
+    for path in a.new:
+        for k, v in functions(path).items():
+            if k in new:
+                print("DUPLICATE", k, path)
+                bad += 1
+            new[k] = v
     for k in sorted(old):
         if k not in new:
             print("MISSING  ", k)
@@ -63,7 +70,7 @@ def main():
             bad += 1
     for k in sorted(set(new) - set(old)):
         print("new      ", k)
-    print(f"{len(old)} functions of OLD: {bad} missing or different", file=sys.stderr)
+    print(f"{len(old)} functions of OLD: {bad} missing, different or duplicate", file=sys.stderr)
     return 1 if bad else 0
 
 

@@ -5,7 +5,12 @@ set -e
 name=$1; shift
 cd "$(dirname "$0")/../volxel_amd/csrc"
 tmp=$(mktemp -d)
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-function "$@" -c vx_api.hip -o $tmp/vx_api.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libvolxel_hip_$name.so $tmp/vx_api.o brick_builder.o dicom_reader.o -lpthread
+objs=""
+for u in vx_api vx_api_view vx_api_segment vx_api_mesh; do   # the host layer's four units
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-function "$@" -c $u.hip -o $tmp/$u.o &
+  objs="$objs $tmp/$u.o"
+done
+wait
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libvolxel_hip_$name.so $objs brick_builder.o dicom_reader.o -lpthread
 rm -rf $tmp
 ls -la ../libvolxel_hip_$name.so

@@ -1,14 +1,14 @@
-// vx_api.hip -- host side of libvolxel_hip.so: the C ABI of include/volxel_hip.h.
+// vx_api.hip -- the render unit of libvolxel_hip.so's host layer (the C ABI of include/volxel_hip.h; units: DESIGN.md section
+// 4.1): contexts and device groups, uploads and layouts, the derived tables, the launch plan, rendering, read-back, counters,
+// probes and test hooks.  Every render_* kernel is instantiated here, so this unit's listing (vx_api.s) holds them all.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <optional>
 #include <string>
 #include <vector>
 
@@ -19,13 +19,7 @@
 #include "vx_kernels.hpp"
 #include "vx_shadow.hpp"
 #include "vx_projection.hpp"
-#include "vx_slice.hpp"
-#include "vx_iso.hpp"
-#include "vx_segment.hpp"
-#include "vx_segedit.hpp"
-#include "vx_islands.hpp"
-#include "vx_mesh.hpp"
-#include "vx_host.hpp"
+#include "vx_context.hpp"
 
 using namespace vx;
 
@@ -33,20 +27,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct EventPair {
-  hipEvent_t a, b;
-  bool merge = false;      // interval of a merge_results launch (reported apart, VxCounters.merge_ms)
-};
-
-// The diagnostic switches of the environment, read once by vx_create (none changes a result bit).
-struct Switches {
-  int dvr_variant = -1;            // VX_DVR_KERNEL=generic: 0, the DVR modes on render_generic; -1: the tuned kernels
-  bool dvr_fuse = true;            // VX_DVR_FUSE=0: no kernel folds the running mean; merge_results blends every multi-frame launch
-  bool ray_shortcuts = true;       // VX_RAY_SHORTCUTS=0: the per-ray divisions themselves (DevVolume::ray_flags = 0)
-  std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
-  uint32_t seg_check_max = 64;     // VX_SEG_CHECK_MAX (1 .. 4096): the largest batch of flood rounds between read-backs (vx_segment)
-  bool dvr_miss = true;            // VX_DVR_MISS=0: no multi-frame DVR launch is split; every block runs the LDS-window kernel
-};
 // VX_DVR_MISS alone: vx_create reads it with the others, and the classifier's test hook -- which has no context to hold a
 // Switches -- reads this one variable and nothing else
 bool dvr_miss_switch() {
@@ -64,244 +44,6 @@ Switches read_switches() {
   sw.dvr_miss = dvr_miss_switch();
   return sw;
 }
-
-// ---- the tables a launch derives from the params and the uploads ---------------------------------------------------------
-// The skip mask, the projection bounds, the local majorants and the light grid share one cache rule: a table is rebuilt
-// before a launch that reads it when an upload marked it stale or when its key -- the bits of the params it is built from,
-// listed once in its key function -- differs from the key of the last build.  A camera move rebuilds none of them but the
-// split of a multi-frame DVR launch (miss_key: host arithmetic and one asynchronous copy, no wait on the stream).
-
-// the bits of 4-byte params and param arrays, in order
-template <class... T>
-std::array<uint32_t, (sizeof(T) + ...) / 4> key_of(const T&... v) {
-  static_assert(((sizeof(T) % 4 == 0) && ...), "key fields are 4-byte values");
-  std::array<uint32_t, (sizeof(T) + ...) / 4> k{};
-  uint32_t* o = k.data();
-  ((memcpy(o, &v, sizeof v), o += sizeof v / 4), ...);
-  return k;
-}
-auto skip_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.sample_range); }
-auto proj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.render_mode); }
-auto iso_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj); }
-auto lmaj_key(const VxParams& p) { return key_of(p.volume_density_scale, p.volume_inv_maj, p.volume_maj, p.sample_range); }
-auto shadow_key(const VxParams& p) {
-  return key_of(p.light_dir, p.density_transform_inv, p.volume_aabb_min, p.volume_aabb_max, p.volume_maj, p.volume_inv_maj,
-                p.volume_density_scale, p.sample_range, p.dvr_step_voxels, p.dvr_ert_tau, p.dvr_max_steps, p.dvr_shadow_stride);
-}
-// the split of a multi-frame DVR launch (classify_miss_blocks): the matrices the rays use, the clip box, the image, the shard
-// -- a camera move DOES rebuild this one, ahead of the next multi-frame launch (host arithmetic on eight corners and a
-// frame's blocks); the tile map marks it stale itself
-auto miss_key(const VxParams& p) {
-  return key_of(p.camera_view_inv, p.camera_proj_inv, p.camera_ortho, p.volume_aabb_min, p.volume_aabb_max, p.res, p.shard_rank,
-                p.shard_count);
-}
-
-template <auto KEY>
-struct DerivedTable {
-  bool stale = true;                      // never built, an upload since the last build, or a rebuild that failed
-  decltype(KEY(VxParams{})) key{};        // KEY of the params of the last build
-  bool current(const VxParams& p) const { return !stale && KEY(p) == key; }
-  void built(const VxParams& p) {
-    key = KEY(p);
-    stale = false;
-  }
-};
-
-}  // namespace
-
-struct VxContext : VxCore {   // (device, the stream the launches go to, the last error: vx_host.hpp)
-  hipStream_t own_stream = nullptr;
-  hipDeviceProp_t prop;
-
-  // Everything that describes the resident volume: vx_upload_volume drops it as a whole (free_volume), so a buffer or a flag
-  // that must not outlive the volume belongs here and needs no line anywhere else.
-  struct Volume {
-    bool has_volume = false;
-    DevVolume dv{};
-    DevBuf<void> cq_alloc, bf_alloc;
-    DevBuf<void> bu_alloc;     // bricku8 codes (+ one zero unit)
-    DevBuf<void> bur_alloc;    // bricku8 per-brick {min, max - min} (+ the {0, 0} entry of the zero unit)
-    // the derived tables (their device arrays below, outside: rebuilt before the next launch that reads them)
-    DerivedTable<skip_key> skip_table;
-    DerivedTable<proj_key> proj_table;
-    DerivedTable<lmaj_key> lmaj_table;
-    DerivedTable<shadow_key> shadow_table;
-    DerivedTable<iso_key> iso_table;
-    DevBuf<float> lmaj_dev;    // default mode: local-majorant table (DevVolume::lmaj)
-    // shadowed DVR: the light grid (vx_shadow.hpp)
-    DevBuf<float> shadow_dev;
-    ShadowGrid shadow{};       // what the last build made (t == nullptr: none since the last upload)
-    // segmentation (vx_segment): one allocation for the masks, flags, stamps, worklists, partial sums and statistics of the
-    // brick grid (ensure_segment); the packed mask of vx_segment_read_mask / vx_segment_write_mask grows on demand
-    DevBuf<void> seg_alloc;
-    SegDev seg{};
-    bool seg_valid = false;        // a segment of the resident volume is current
-    bool seg_pred_valid = false;   // SegDev::pred holds the predicate of a vx_segment / vx_segment_threshold on this volume
-    int seg_view = VX_SEGVIEW_OFF;   // vx_set_segment_view; OFF again after an upload
-    DevBuf<uint8_t> seg_bytes;
-    // segment edits: two scratch masks and the fill's flags, allocated by the first vx_segment_edit (ensure_segedit)
-    DevBuf<void> sed_alloc;
-    uint64_t* sed_mask[2] = {nullptr, nullptr};
-    uint32_t* sed_any = nullptr;
-    // islands (vx_segment_islands): the labels (one u32 per voxel, brick-major), the root counts and their scan in one
-    // allocation made by the first call; the rows and their labels grow to the largest table; the ranked table lives on the
-    // host; the dense label volume is allocated by the first vx_islands_read_labels
-    DevBuf<void> isl_alloc, isl_rows_alloc;
-    IslDev isl{};
-    bool isl_valid = false;    // the table and the labels describe the current segment
-    std::vector<VxIsland> isl_table;
-    DevBuf<uint32_t> isl_dense;
-    // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans
-    // (ensure_mesh); the vertex / cell buffers (3 values per vertex, grown together) and the triangles grow to the largest mesh
-    DevBuf<void> mesh_alloc;
-    MeshDev mesh{};
-    bool mesh_valid = false;   // a mesh of the resident volume is current
-    DevBuf<float> mesh_verts;
-    DevBuf<int32_t> mesh_cells;
-    DevBuf<uint32_t> mesh_tris;
-    uint64_t mesh_nv = 0, mesh_nt = 0;
-  } vol;
-  std::vector<void*> vol_allocs;     // the uploaded arrays DevVolume points to (free_volume)
-  int layout = VX_LAYOUT_AUTO;       // what the host asked for (vx_set_layout); eff_layout() is what a launch samples
-  bool auto_no_cq = false;           // AUTO: no cellquad layout (index range or memory budget): `default` / `no_dda` take primary_layout
-  bool auto_no_bf = false;           // AUTO: too large for brickf32 as well (everything uses REFERENCE)
-
-  // ---- what survives an upload ----
-  // transfer function
-  DevBuf<float4> tf;
-  uint32_t tf_len = 0;
-  std::vector<float> tf_host;
-
-  std::vector<uint32_t> range_host;   // packed (min16<<16)|max16 per brick
-  DevBuf<uint32_t> skip_dev;          // exact empty-space skipping (DVR): macro-cell bitmask
-  DevBuf<float> proj_dev;             // range skipping of the intensity projections: one density bound per macro cell
-
-  DevBuf<unsigned long long> fold_dev;   // the totals of fold_records
-
-  DevBuf<unsigned long long> shadow_count_dev;   // light-march samples of the last light-grid build
-  StageTimer<1> shadow_timer;
-  uint64_t shadow_builds = 0;
-
-  // params
-  VxParams params{};
-  bool has_params = false;
-
-  // framebuffers
-  uint32_t W = 0, H = 0;
-  TileMap tm{};
-  DevBuf<float4> slab;
-  size_t slab_quads = 0;
-  DevBuf<float4> image;
-  DevBuf<float4> env_tex;      // environment map, GL row order
-  DevBuf<float> env_imp;       // importance pyramid
-  DevBuf<float4> env_impq;     // the pyramid as sibling quads (sample_environment)
-  float env_avg_w = 0.0f;
-  uint32_t env_w = 0, env_h = 0;
-  DevBuf<uchar4> display;
-  DevBuf<uint32_t> tile_perm;  // vx_set_tile_order: position -> tile, tile -> position (2 * n_tiles)
-  uint32_t tile_perm_n = 0;
-  std::vector<uint32_t> tile_perm_host;   // position -> tile as the device holds it (empty: pos == tile id)
-  // The split of a multi-frame DVR launch of the LDS-window kernel (ensure_miss_split): per logical block of a frame, 1 = it goes to
-  // render_dvr_miss -- no ray of its pixels can hit the clip box (`proved` of them), or it lies outside the shard's tiles or
-  // the image, where either kernel returns at once; the two halves of `order`, split_order's stable partition.
-  struct MissSplit {
-    DerivedTable<miss_key> table;     // stale: never built, or the tile map changed
-    std::vector<uint8_t> flags_host;
-    DevBuf<uint8_t> flags;
-    DevBuf<uint32_t> order_heavy, order_miss;
-    uint32_t blocks = 0;              // frame_blocks of the build
-    uint32_t n_miss = 0, proved = 0;
-    bool split_stale = true;          // `order` or the flags changed since split_order ran
-    uint32_t last_heavy = 0, last_miss = 0;   // blocks per frame slot the last render launch gave each kernel
-    // the flags cross to the device from two pinned buffers used in turn: the copy is asynchronous on the context's stream, and
-    // a buffer is rewritten only behind the event of its last copy (two builds back: complete long since, no stall)
-    struct Stage {
-      uint8_t* p = nullptr;
-      size_t cap = 0;
-      hipEvent_t done = nullptr;
-      bool pending = false;
-    } stage[2];
-    int next_stage = 0;
-    MissSplit() = default;
-    MissSplit(const MissSplit&) = delete;
-    MissSplit& operator=(const MissSplit&) = delete;
-    ~MissSplit() {
-      for (Stage& st : stage) {
-        if (st.p) (void)hipHostFree(st.p);
-        if (st.done) (void)hipEventDestroy(st.done);
-      }
-    }
-  } miss;
-
-  // counters / timing
-  DevBuf<DevCounters> dc;      // one record per wave of the largest launch grid
-  size_t dc_waves = 0;
-  DevBuf<uint32_t> order;      // launch permutation of the DVR kernel (build_order), dc_waves/4 entries
-  int tex_checked_res[2] = {-1, -1};  // DevVolume::ray_flags: the resolution (pixel + 0.5) / res was last tried against its reciprocal form
-  bool tex_by_reciprocal[2] = {false, false};
-  Switches sw;
-  int order_builds_left = 2;   // rebuild the order after the first frames that follow a change
-  VxCounters base{};           // totals folded in when the record array is reallocated
-  std::vector<EventPair> free_events, pending_events;
-  double kernel_ms = 0.0, last_kernel_ms = 0.0, merge_ms = 0.0;
-  uint64_t launches = 0, frames = 0, merge_launches = 0;
-  uint32_t min_launch_frames = 0, max_launch_frames = 0;   // what the launches since the last reset covered
-  hipStream_t aux_stream = nullptr;   // layout builds of an upload, overlapped with the atlas copy
-  double upload_seconds = 0.0;        // wall time of the last vx_upload_volume (copies + layout build)
-  uint64_t upload_host_bytes = 0;     // host bytes it moved over PCIe
-  int upload_pinned = 0;              // whether the atlas could be pinned in place
-  void note_launch(uint32_t n) {
-    launches += 1;
-    frames += n;
-    min_launch_frames = (min_launch_frames == 0 || n < min_launch_frames) ? n : min_launch_frames;
-    max_launch_frames = n > max_launch_frames ? n : max_launch_frames;
-  }
-  // per-frame result slabs and counter records of multi-frame launches (vx_render_frames), pipe_slots of each in ONE
-  // allocation (slot i at i * pipe_quads / i * pipe_waves)
-  DevBuf<float4> pipe_result_pool;
-  DevBuf<DevCounters> pipe_dc_pool;
-  size_t pipe_quads = 0, pipe_waves = 0;
-  uint32_t pipe_slots = 0;
-  // the slab table the detile kernel reads (one entry per shard, on this device); slab_table_host is what it holds
-  DevBuf<const float4*> slab_table;
-  std::vector<const float4*> slab_table_host;
-  // device group (vx_create_group): member i renders shard i of members.size(); empty for a plain context
-  std::vector<VxContext*> members;
-  hipEvent_t done = nullptr;   // a member's: recorded after its last render, waited on by the display stream
-  // slices (vx_slice): the output buffers, grown to the largest slice, and the facts of the last slice
-  DevBuf<float> slice_values;
-  DevBuf<uchar4> slice_rgba;
-  StageTimer<1> slice_timer;
-  uint64_t slice_samples = 0;
-  // isosurfaces (vx_isosurface): the output buffers, grown to the largest window; the upper density bounds of range skipping
-  // (its own copy of the projections' table, so that MIP's bookkeeping is never disturbed); the counts of the last call
-  DevBuf<float4> iso_rgba, iso_hit;
-  DevBuf<float> iso_bound_dev;
-  IsoBound iso_bound{};
-  DevBuf<unsigned long long> iso_count_dev;   // ISO_NCOUNTS
-  StageTimer<1> iso_timer;
-  uint64_t iso_counts[ISO_NCOUNTS] = {};
-  // the segment chain: the overlay of vx_slice_segment_mask, grown to the largest slice; the last vx_segment's result; the
-  // timers and launch counts the *_stats entry points report.  sed_timer / sed_launches belong to every call that rewrites
-  // the mask outright (vx_segment_edit, vx_segment_write_mask, vx_segment_threshold: vx_segment_edit_stats), not to the
-  // edit scratch.
-  DevBuf<uint8_t> seg_ov;
-  VxSegmentResult seg_res{};
-  StageTimer<3> seg_timer;
-  StageTimer<2> sed_timer;
-  uint32_t sed_launches = 0;
-  StageTimer<7> isl_timer;
-  uint32_t isl_launches = 0;
-  StageTimer<3> mesh_timer;
-  uint32_t mesh_launches = 0;
-};
-
-static bool is_group(const VxContext* c) { return !c->members.empty(); }
-
-// every entry point that touches the device first makes the context's device current for the
-// calling thread (a host with several contexts / devices must not depend on its own hipSetDevice)
-#define VX_DEV(ctx) VX_HIP(ctx, hipSetDevice((ctx)->device))
-
 
 // drop the resident volume and everything derived from it (the caller has made the context's device current)
 static void free_volume(VxContext* c) {
@@ -368,168 +110,6 @@ static int alloc_framebuffers(VxContext* c) {
   return VX_OK;
 }
 
-
-// ---- exact empty-space skipping: host-side construction of the macro-cell bitmask -------------
-// Rule (restated independently by the oracle): TF bin i is dead when its alpha
-// is 0 or it lies wholly outside the sample range (one-bin margin); a brick is transparent when
-// every bin from I(min)-1 to I(max)+1 is dead, I(x) = floor(x*density_scale*inv_maj*L); a macro
-// cell of w = 2^level bricks per axis is empty when the w+1 bricks per axis that can hold a tap of
-// its cells (bricks m*w-1 .. m*w+w-1; value 0 outside the grid) are all transparent.
-static float f16_bits_to_float(uint16_t h) {
-  _Float16 v;
-  memcpy(&v, &h, 2);
-  return (float)v;
-}
-static int skip_level_for(const uint32_t extent[3]) {
-  for (int g = 1; g <= 3; ++g) {
-    uint64_t n = 1;
-    for (int a = 0; a < 3; ++a) n *= (uint64_t)(extent[a] >> (3 + g)) + 1u;
-    if (n <= 65536u) return g;
-  }
-  return 3;
-}
-static void compute_skip_mask(const VxParams& p, const uint32_t* range_packed, const uint32_t bc[3],
-                              const uint32_t extent[3], const float* tf_rgba, uint32_t L,
-                              std::vector<uint32_t>& bits, int& level_out, uint32_t md[3]) {
-  const float lf = (float)L;
-  // prefix count of live bins -> O(1) "any live bin in [a, b]"
-  std::vector<uint32_t> live(L + 1, 0);
-  for (uint32_t i = 0; i < L; ++i) {
-    bool dead = tf_rgba[4 * (size_t)i + 3] == 0.0f || (float)((int)i + 2) / lf < p.sample_range[0] ||
-                (float)((int)i - 1) / lf > p.sample_range[1];
-    live[i + 1] = live[i] + (dead ? 0u : 1u);
-  }
-  auto transparent = [&](float lo, float hi) {
-    float fa = floorf(((lo * p.volume_density_scale) * p.volume_inv_maj) * lf);
-    float fb = floorf(((hi * p.volume_density_scale) * p.volume_inv_maj) * lf);
-    // v_cvt_i32_f32 semantics: NaN -> 0, saturating
-    auto f2i = [](float x) -> int64_t { return x != x ? 0 : (x >= 2147483648.0f ? 2147483647ll : (x <= -2147483648.0f ? -2147483648ll : (int64_t)x)); };
-    int64_t a = f2i(fa) - 1, b = f2i(fb) + 1;
-    if (a < 0) a = 0;
-    if (b > (int64_t)L - 1) b = (int64_t)L - 1;
-    if (b < a) return true;
-    return live[(size_t)b + 1] - live[(size_t)a] == 0u;
-  };
-  const size_t nb = (size_t)bc[0] * bc[1] * bc[2];
-  std::vector<uint8_t> opaque(nb);
-  for (size_t i = 0; i < nb; ++i) {
-    uint32_t pk = range_packed[i];
-    opaque[i] = transparent(f16_bits_to_float((uint16_t)(pk >> 16)), f16_bits_to_float((uint16_t)pk)) ? 0 : 1;
-  }
-  const uint8_t zero_opaque = transparent(0.0f, 0.0f) ? 0 : 1;
-  const int level = skip_level_for(extent);
-  level_out = level;
-  const int w = 1 << level;
-  for (int a = 0; a < 3; ++a) md[a] = (extent[a] >> (3 + level)) + 1u;
-  // separable OR over the window [m*w-1, m*w+w-1] per axis (out-of-grid bricks count as value 0)
-  std::vector<uint8_t> ax((size_t)md[0] * bc[1] * bc[2]), ay((size_t)md[0] * md[1] * bc[2]);
-  for (uint32_t z = 0; z < bc[2]; ++z)
-    for (uint32_t y = 0; y < bc[1]; ++y)
-      for (uint32_t m = 0; m < md[0]; ++m) {
-        uint8_t o = 0;
-        for (int b = (int)m * w - 1; b <= (int)m * w + w - 1; ++b)
-          o |= (b < 0 || (uint32_t)b >= bc[0]) ? zero_opaque : opaque[((size_t)z * bc[1] + y) * bc[0] + b];
-        ax[((size_t)z * bc[1] + y) * md[0] + m] = o;
-      }
-  for (uint32_t z = 0; z < bc[2]; ++z)
-    for (uint32_t m = 0; m < md[1]; ++m)
-      for (uint32_t x = 0; x < md[0]; ++x) {
-        uint8_t o = 0;
-        for (int b = (int)m * w - 1; b <= (int)m * w + w - 1; ++b)
-          o |= (b < 0 || (uint32_t)b >= bc[1]) ? zero_opaque : ax[((size_t)z * bc[1] + b) * md[0] + x];
-        ay[((size_t)z * md[1] + m) * md[0] + x] = o;
-      }
-  const size_t n = (size_t)md[0] * md[1] * md[2];
-  bits.assign((n + 31) / 32, 0u);
-  for (uint32_t m = 0; m < md[2]; ++m)
-    for (uint32_t y = 0; y < md[1]; ++y)
-      for (uint32_t x = 0; x < md[0]; ++x) {
-        uint8_t o = 0;
-        for (int b = (int)m * w - 1; b <= (int)m * w + w - 1; ++b)
-          o |= (b < 0 || (uint32_t)b >= bc[2]) ? zero_opaque : ay[((size_t)b * md[1] + y) * md[0] + x];
-        if (!o) {
-          size_t i = ((size_t)m * md[1] + y) * md[0] + x;
-          bits[i >> 5] |= 1u << (i & 31);
-        }
-      }
-}
-
-// ---- range skipping of the intensity projections: host-side construction of the density bounds ----------------------
-// Per macro cell of the empty-space grid above (level, dims), {lo, hi} with lo <= d <= hi for every density
-// d = (density_scale * mix) * inv_maj the device can compute at a sample of the cell.  Such a sample (mask index
-// floor(q) + 1 in the cell) takes its eight taps from the w + 1 bricks per axis m*w-1 .. m*w+w-1 that compute_skip_mask
-// ORs (a tap outside the grid reads 0), and a tap of brick b is decoded inside b's own range [min, max] (the f16 pair).
-// Rounding, argued against a relative margin of 2^-16 and an absolute one of 2^-100:
-//   * a decoded voxel, fma(c/255, max - min, min), lands at most an ulp or two beyond [min, max] (relative 2^-22);
-//   * a mix fma(b, t, a * (1 - t)): 1 - t and the product round once each, the fma once: with weights t, 1 - t in [0, 1] the
-//     result is within 3 rounding errors (2^-24 each, of the larger operand) of a convex combination, and the trilinear is
-//     three nested mixes -- at most ~10 rounding errors of max(|lo|, |hi|) in all, below 2^-20 relative;
-//   * the products by density_scale and inv_maj add one rounding each, and a device that flushes a denormal moves a value by
-//     less than 2^-126.
-// Bounds widened by 2^-16 of the magnitude and by 2^-100 hold with a margin of more than 16x.  A density_scale or inv_maj
-// that is <= 0 or not finite turns the map around or breaks it: then the bounds are {-inf, +inf} and nothing is skipped.
-static void compute_projection_bounds(const VxParams& p, const uint32_t* range_packed, const uint32_t bc[3],
-                                      const uint32_t extent[3], std::vector<float>& lohi, int& level_out, uint32_t md[3]) {
-  const int level = skip_level_for(extent);
-  level_out = level;
-  const int w = 1 << level;
-  for (int a = 0; a < 3; ++a) md[a] = (extent[a] >> (3 + level)) + 1u;
-  const size_t n = (size_t)md[0] * md[1] * md[2];
-  lohi.assign(2 * n, 0.0f);
-  const float s = p.volume_density_scale, im = p.volume_inv_maj;
-  if (!(s > 0.0f) || !(im > 0.0f) || !std::isfinite(s) || !std::isfinite(im)) {
-    for (size_t i = 0; i < n; ++i) { lohi[2 * i] = -INFINITY; lohi[2 * i + 1] = INFINITY; }
-    return;
-  }
-  // per-brick ranges, then separable min / max over the window [m*w-1, m*w+w-1] per axis (out-of-grid bricks read 0)
-  const size_t nb = (size_t)bc[0] * bc[1] * bc[2];
-  std::vector<float> bmin(nb), bmax(nb);
-  for (size_t i = 0; i < nb; ++i) {
-    const uint32_t pk = range_packed[i];
-    const float a = f16_bits_to_float((uint16_t)(pk >> 16)), b = f16_bits_to_float((uint16_t)pk);
-    bmin[i] = std::min(a, b);
-    bmax[i] = std::max(a, b);
-  }
-  auto reduce = [&](const std::vector<float>& src, uint32_t sx, uint32_t sy, uint32_t sz, int axis, bool hi) {
-    const uint32_t dims_in[3] = {sx, sy, sz};
-    uint32_t d[3] = {sx, sy, sz};
-    d[axis] = md[axis];
-    std::vector<float> out((size_t)d[0] * d[1] * d[2]);
-    for (uint32_t z = 0; z < d[2]; ++z)
-      for (uint32_t y = 0; y < d[1]; ++y)
-        for (uint32_t x = 0; x < d[0]; ++x) {
-          uint32_t at[3] = {x, y, z};
-          const int m = (int)at[axis];
-          float r = 0.0f;
-          bool first = true;
-          for (int b = m * w - 1; b <= m * w + w - 1; ++b) {
-            float v = 0.0f;
-            if (b >= 0 && (uint32_t)b < dims_in[axis]) {
-              at[axis] = (uint32_t)b;
-              v = src[((size_t)at[2] * dims_in[1] + at[1]) * dims_in[0] + at[0]];
-            }
-            r = first ? v : (hi ? std::max(r, v) : std::min(r, v));
-            first = false;
-          }
-          out[((size_t)z * d[1] + y) * d[0] + x] = r;
-        }
-    return out;
-  };
-  for (int hi = 0; hi < 2; ++hi) {
-    const std::vector<float>& b0 = hi ? bmax : bmin;
-    std::vector<float> rx = reduce(b0, bc[0], bc[1], bc[2], 0, hi);
-    std::vector<float> ry = reduce(rx, md[0], bc[1], bc[2], 1, hi);
-    std::vector<float> rz = reduce(ry, md[0], md[1], bc[2], 2, hi);
-    for (size_t i = 0; i < n; ++i) {
-      const double v = rz[i];   // voxel units
-      const double d = v * (double)s * (double)im;
-      const double widened = hi ? d + std::fabs(d) * 0x1p-16 + 0x1p-100 : d - std::fabs(d) * 0x1p-16 - 0x1p-100;
-      float f = (float)widened;   // then one more step outwards against the conversion's rounding
-      f = std::nextafter(f, hi ? INFINITY : -INFINITY);
-      lohi[2 * i + hi] = f;
-    }
-  }
-}
 static bool proj_mode(int m) { return m == VX_MODE_MIP || m == VX_MODE_MINIP; }
 // the device table: the bound the mode tests (hi for MIP, lo for MinIP), one float per macro cell
 static int rebuild_projection_bounds(VxContext* c) {
@@ -588,7 +168,6 @@ static int rebuild_skip_mask(VxContext* c) {
   c->vol.skip_table.built(p);
   return VX_OK;
 }
-
 
 // fold every record array (accumulator slot and the multi-frame slots) into c->base on the device and zero it
 static int fold_counters(VxContext* c) {
@@ -660,15 +239,6 @@ static int eff_layout(const VxContext* c) {
   // 1.4x / 2.0x slower than cellquad and 2.0x / 2.2x faster than the reference textures on the 1024^3 volume at 3840x2160
   // (profiles/r04_layouts_1024.txt) -- and the reference textures only when neither native layout can index the volume
   return c->auto_no_cq ? primary_layout(c) : VX_LAYOUT_CELLQUAD;
-}
-
-// calls f(std::integral_constant<int, LAYOUT_*>) for the device layout `lay` (the path kernels and the tile-cost probe
-// sample brickf32, cellquad, or -- for every other layout -- the reference textures)
-template <class F>
-static void with_layout(int lay, F&& f) {
-  if (lay == VX_LAYOUT_BRICKF32) f(std::integral_constant<int, LAYOUT_BF>{});
-  else if (lay == VX_LAYOUT_CELLQUAD) f(std::integral_constant<int, LAYOUT_CQ>{});
-  else f(std::integral_constant<int, LAYOUT_REF>{});
 }
 
 // ---- shadowed DVR: the light grid (vx_shadow.hpp) ---------------------------------------------------
@@ -887,18 +457,6 @@ static LaunchPlan plan_launch(const VxContext* c, const MultiOut& mo, bool probe
   return lp;
 }
 
-// calls f(std::integral_constant<bool, b>)
-template <class F>
-static void with_bool(bool b, F&& f) {
-  if (b) f(std::true_type{});
-  else f(std::false_type{});
-}
-// calls f(std::integral_constant<int, 6 or 26>) for a checked connectivity (the flood, the edit steps, the islands)
-template <class F>
-static void with_conn(int conn, F&& f) {
-  if (conn == 26) f(std::integral_constant<int, 26>{});
-  else f(std::integral_constant<int, 6>{});
-}
 // calls f(std::integral_constant<int, VX_MODE_*>) for render mode m
 template <class F>
 static void with_mode(int m, F&& f) {
@@ -1004,93 +562,6 @@ static int launch_planned(VxContext* c, const LaunchPlan& lp, const MultiOut& mo
   return VX_OK;
 }
 
-// ---- slices (vx_slice): the kernel a slice runs, chosen apart from plan_launch (a slice is no render launch) ---------------
-// The layout a slice samples: what is resident at the time of the call -- brickf32, else cellquad, else the reference textures
-// (same bits on all three).  Not eff_layout: under AUTO it follows the render mode, and for `default` / `no_dda` it names
-// cellquad before the first render of such a mode has built it; under bricku8 the slice reads the reference textures.
-static int slice_layout(const VxContext* c) {
-  if (c->vol.dv.bf) return VX_LAYOUT_BRICKF32;
-  if (c->vol.dv.cq) return VX_LAYOUT_CELLQUAD;
-  return VX_LAYOUT_REFERENCE;
-}
-// launches slice_reduce<sp.reduce, the layout of slice_layout> for sp on the context's stream
-static void launch_slice(VxContext* c, const VxSliceParams& sp) {
-  const dim3 grid((sp.size[0] + 15u) / 16u, (sp.size[1] + 15u) / 16u);
-  const VxParams& p = c->params;
-  with_layout(slice_layout(c), [&](auto lay) {
-    constexpr int LAY = decltype(lay)::value;
-    auto go = [&](auto red) {
-      hipLaunchKernelGGL((slice_reduce<decltype(red)::value, LAY>), grid, dim3(256), 0, c->stream, sp, c->vol.dv, p.volume_density_scale,
-                         p.volume_inv_maj, c->tf, c->tf_len, p.sample_range[0], p.sample_range[1], c->slice_values, c->slice_rgba);
-    };
-    if (sp.reduce == VX_SLICE_MAX) go(std::integral_constant<int, VX_SLICE_MAX>{});
-    else if (sp.reduce == VX_SLICE_MIN) go(std::integral_constant<int, VX_SLICE_MIN>{});
-    else go(std::integral_constant<int, VX_SLICE_MEAN>{});
-  });
-}
-
-// ---- isosurfaces (vx_isosurface): the upper density bounds of range skipping and the launch --------------------------------
-// The projections' bound table (compute_projection_bounds, its widening argument included), upper bounds only, kept in a buffer
-// of its own: building it never marks, frees or replaces the table MIP / MinIP launches read (proj_table / proj_dev).
-static int rebuild_iso_bounds(VxContext* c) {
-  const VxParams& p = c->params;
-  c->vol.iso_table.stale = true;   // until this build is complete
-  std::vector<float> lohi;
-  int level = 1;
-  uint32_t md[3];
-  compute_projection_bounds(p, c->range_host.data(), c->vol.dv.bc, c->vol.dv.extent, lohi, level, md);
-  const size_t n = lohi.size() / 2;
-  std::vector<float> hi(n);
-  for (size_t i = 0; i < n; ++i) hi[i] = lohi[2 * i + 1];
-  if (int rc = c->iso_bound_dev.alloc(c, n)) return rc;
-  VX_HIP(c, hipMemcpyAsync(c->iso_bound_dev, hi.data(), n * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  IsoBound& b = c->iso_bound;
-  b.hi = c->iso_bound_dev;
-  b.sh = 3u + (uint32_t)level;
-  b.md0 = md[0];
-  b.md1 = md[1];
-  for (int a = 0; a < 3; ++a) b.cmax[a] = c->vol.dv.extent[a] + 7u;
-  c->vol.iso_table.built(p);
-  return VX_OK;
-}
-// launches iso_first_hit<the layout of slice_layout, ip.skip> over the window (x0, y0, ww, wh) on the context's stream
-// (the segment view: iso_first_hit_seg<the layout of slice_layout>, never skipping)
-static void launch_iso(VxContext* c, const VxIsoParams& ip, uint32_t ww, uint32_t wh) {
-  const dim3 grid((ww + 15u) / 16u, (wh + 15u) / 16u);
-  with_layout(slice_layout(c), [&](auto lay) {
-    constexpr int LAY = decltype(lay)::value;
-    if (c->vol.seg_view != VX_SEGVIEW_OFF)
-      hipLaunchKernelGGL((iso_first_hit_seg<LAY>), grid, dim3(256), 0, c->stream, c->params, c->vol.dv, ip, c->iso_rgba, c->iso_hit,
-                         c->iso_count_dev, reinterpret_cast<const uint32_t*>(c->vol.seg.seg), c->vol.seg_view == VX_SEGVIEW_HIDE ? ~0u : 0u);
-    else if (ip.skip)
-      hipLaunchKernelGGL((iso_first_hit<LAY, true>), grid, dim3(256), 0, c->stream, c->params, c->vol.dv, ip, c->iso_bound, c->iso_rgba,
-                         c->iso_hit, c->iso_count_dev);
-    else
-      hipLaunchKernelGGL((iso_first_hit<LAY, false>), grid, dim3(256), 0, c->stream, c->params, c->vol.dv, ip, IsoBound{}, c->iso_rgba,
-                         c->iso_hit, c->iso_count_dev);
-  });
-}
-
-// ---- device groups (vx_create_group): the entry points fan out to the members, read member 0, or gather --------
-// a member's failure, reported on the group handle with the member's index and device
-static int member_fail(VxContext* g, size_t i, int rc) {
-  char head[64];
-  snprintf(head, sizeof head, "member %zu (device %d): ", i, g->members[i]->device);
-  g->err = head + g->members[i]->err;
-  return rc;
-}
-template <class F>
-static int fan_out(VxContext* g, F&& f) {
-  for (size_t i = 0; i < g->members.size(); ++i)
-    if (int rc = f(g->members[i], i)) return member_fail(g, i, rc);
-  return VX_OK;
-}
-static int on_member0(VxContext* g, int rc) { return rc ? member_fail(g, 0, rc) : VX_OK; }
-static int refuse_group(VxContext* g, const char* fn, const char* why) {
-  VX_FAIL(g, VX_ERR_INVALID, "%s: not for a device group (%s)", fn, why);
-}
-
 // point the detile kernel's table at these slabs (entries in stream order: rewritten only when they change)
 static int set_slab_table(VxContext* c, const std::vector<const float4*>& t) {
   if (t == c->slab_table_host) return VX_OK;
@@ -1144,163 +615,6 @@ static int compose_image(VxContext* c, VxContext*& d) {
   VX_HIP(c, hipSetDevice(d->device));
   for (size_t i = 1; i < t.size(); ++i) VX_HIP(c, hipStreamWaitEvent(d->stream, c->members[i]->done, 0));
   return on_member0(c, launch_detile(d, d->image));
-}
-
-extern "C" {
-
-const char* vx_version(void) { return "volxel_hip 0.1 (gfx950)"; }
-
-int vx_create(int device_id, VxContext** out) {
-  if (!out) return VX_ERR_INVALID;
-  *out = nullptr;
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0) {
-    g_create_error = "vx_create: no HIP device visible (libvolxel_hip has no CPU fallback)";
-    return VX_ERR_NO_DEVICE;
-  }
-  if (device_id < 0 || device_id >= n) {
-    g_create_error = "vx_create: device ordinal out of range";
-    return VX_ERR_INVALID;
-  }
-  VxContext* c = new VxContext();
-  c->device = device_id;
-  if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&c->prop, device_id) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
-    g_create_error = "vx_create: device initialisation failed";
-    delete c;
-    return VX_ERR_DEVICE;
-  }
-  c->stream = c->own_stream;
-  {
-    // lanes = pixels x frames (vx_kernels.hpp frame_group) reads per-lane frame slots from the kernel-argument segment
-    // at the offsets of struct KArgs: check once per context that the compiler lays the arguments out that way
-    VxParams tp{};
-    DevVolume tv{};
-    MultiOut tm{};
-    tp.res[0] = 0x1234;
-    tv.extent[0] = 0x5678u;
-    for (uint32_t i = 0; i < (uint32_t)MERGE_MAX; ++i) {
-      tm.out[i] = reinterpret_cast<float4*>((uintptr_t)0x100000000ull * (i + 3u) + 16u * i);
-      tm.frame[i] = 0xabc00000u + 7u * i;
-    }
-    tm.count = MERGE_MAX;
-    uint32_t* bad = nullptr;
-    uint32_t hbad = 1;
-    hipError_t ce = hipMalloc(&bad, 4);
-    if (ce == hipSuccess) {
-      hipLaunchKernelGGL(check_lane_frame_slot, dim3(1), dim3(64), 0, c->stream, tp, tv, (const float4*)nullptr, 0x9abcu, tm, bad);
-      ce = hipGetLastError();
-    }
-    if (ce == hipSuccess) ce = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, c->stream);
-    if (ce == hipSuccess) ce = hipStreamSynchronize(c->stream);
-    if (bad) (void)hipFree(bad);
-    if (ce != hipSuccess || hbad != 0u) {
-      g_create_error = ce != hipSuccess ? "vx_create: device self-check failed to run"
-                                        : "vx_create: kernel-argument layout differs from struct KArgs (lane_frame_slot)";
-      (void)hipStreamDestroy(c->own_stream);
-      delete c;
-      return VX_ERR_DEVICE;
-    }
-  }
-  c->sw = read_switches();   // the diagnostic switches (struct Switches)
-  *out = c;
-  return VX_OK;
-}
-
-int vx_create_group(const int* device_ids, int n, VxContext** out) {
-  if (out) *out = nullptr;
-  if (!device_ids || !out || n < 1 || n > VX_GROUP_MAX) {
-    g_create_error = "vx_create_group: need device_ids, 1 <= n <= 64 and out_ctx";
-    return VX_ERR_INVALID;
-  }
-  VxContext* g = new VxContext();
-  g->device = device_ids[0];
-  auto drop = [g] {   // the members made so far (a group without members is not a context yet)
-    for (VxContext* m : g->members) vx_destroy(m);
-    delete g;
-  };
-  for (int i = 0; i < n; ++i) {
-    VxContext* m = nullptr;
-    int rc = vx_create(device_ids[i], &m);
-    if (rc == VX_OK && hipEventCreateWithFlags(&m->done, hipEventDisableTiming) != hipSuccess) {
-      vx_destroy(m);
-      g_create_error = "event creation failed";
-      rc = VX_ERR_DEVICE;
-    }
-    if (rc) {
-      char head[80];
-      snprintf(head, sizeof head, "vx_create_group: member %d (device %d): ", i, device_ids[i]);
-      g_create_error = head + g_create_error;
-      drop();
-      return rc;
-    }
-    g->members.push_back(m);
-  }
-  // the gather runs on device_ids[0] and reads every other device's slab in place: peer access, no staging copy
-  const int d0 = device_ids[0];
-  for (int i = 1; i < n; ++i) {
-    const int d = device_ids[i];
-    if (d == d0 || std::find(device_ids + 1, device_ids + i, d) != device_ids + i) continue;
-    int can = 0;
-    hipError_t e = hipDeviceCanAccessPeer(&can, d0, d);
-    if (e == hipSuccess && !can) {
-      char buf[160];
-      snprintf(buf, sizeof buf, "vx_create_group: device %d cannot access device %d as a peer", d0, d);
-      g_create_error = buf;
-      drop();
-      return VX_ERR_NO_DEVICE;
-    }
-    if (e == hipSuccess) e = hipSetDevice(d0);
-    if (e == hipSuccess) {
-      e = hipDeviceEnablePeerAccess(d, 0);
-      if (e == hipErrorPeerAccessAlreadyEnabled) {
-        (void)hipGetLastError();
-        e = hipSuccess;
-      }
-    }
-    if (e != hipSuccess) {
-      g_create_error = std::string("vx_create_group: peer access from device ") + std::to_string(d0) + " to " +
-                       std::to_string(d) + ": " + hipGetErrorString(e);
-      drop();
-      return VX_ERR_DEVICE;
-    }
-  }
-  g->prop = g->members[0]->prop;
-  *out = g;
-  return VX_OK;
-}
-
-void vx_destroy(VxContext* c) {
-  if (!c) return;
-  if (is_group(c)) {
-    for (VxContext* m : c->members) vx_destroy(m);
-    delete c;
-    return;
-  }
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  drain_events(c);
-  for (auto& e : c->free_events) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
-  free_volume(c);
-  if (c->done) (void)hipEventDestroy(c->done);
-  if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;   // every buffer and timer the context owns, on the device made current above (vx_host.hpp)
-}
-
-const char* vx_last_error(const VxContext* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
-
-int vx_set_stream(VxContext* c, void* s) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return refuse_group(c, "vx_set_stream", "each member owns its stream");
-  VX_DEV(c);
-  (void)hipStreamSynchronize(c->stream);
-  c->stream = s ? (hipStream_t)s : c->own_stream;
-  return VX_OK;
 }
 
 // Allocate the device layout the trilinear modes sample (cellquad / brickf32); returns its number of z layers
@@ -1477,6 +791,393 @@ struct PinnedRange {
     if (pinned) (void)hipHostUnregister(p);
   }
 };
+
+// The split of a plain multi-frame DVR launch of the LDS-window kernel, kept current the way the derived tables are: the
+// classification is rebuilt when the bits of its key change or the tile map did, the two halves of the block order when `order`
+// or the flags did.  Called at the end of prepare_render ahead of a multi-frame launch only (the counters and `order` exist):
+// single-frame launches are never split (NOTEBOOK R4.13) and pay nothing for it.  plan_launch uses what it finds current.
+static int ensure_miss_split(VxContext* c) {
+  VxContext::MissSplit& ms = c->miss;
+  const VxParams& p = c->params;
+  if (!c->sw.dvr_miss || p.render_mode != VX_MODE_DVR || !use_lds_kernel(c)) return VX_OK;
+  const uint32_t nb = frame_blocks(c);
+  if (!ms.table.current(p) || ms.blocks != nb) {
+    ms.table.stale = true;   // until this build is complete: a failure below must not leave the old key over new counts
+    std::vector<uint8_t> img;
+    ms.proved = ms.n_miss = 0;
+    ms.blocks = nb;
+    if (classify_miss_blocks(p, c->W, c->H, img) != 0u) {
+      // image block -> logical block of this shard: block_to_tile, tile_at and wave_pixel on the host
+      const TileMap& tm = c->tm;
+      const uint32_t nbx = (c->W + 15u) / 16u;
+      auto morton_x = [](uint32_t m) { return (m & 1u) | ((m >> 1) & 2u) | ((m >> 2) & 4u); };
+      ms.flags_host.assign(nb, 0);
+      for (uint32_t b = 0; b < nb; ++b) {
+        const uint32_t lt = (b >> 7) * 8u + (b & 7u), wt = ((b >> 3) & 15u) * 4u;
+        const uint32_t pos = lt * tm.shard_count + tm.shard_rank;
+        const uint32_t t = (!c->tile_perm_host.empty() && pos < tm.n_tiles) ? c->tile_perm_host[pos] : pos;
+        const uint32_t x0 = (t % tm.tiles_x) * 64u + morton_x(wt) * 8u, y0 = (t / tm.tiles_x) * 64u + morton_x(wt >> 1) * 8u;
+        if (lt >= tm.tiles_per_shard || t >= tm.n_tiles || x0 >= tm.W || y0 >= tm.H) {
+          ms.flags_host[b] = 1;   // no pixel: either kernel returns at once
+        } else if (img[(size_t)(y0 >> 4) * nbx + (x0 >> 4)]) {
+          ms.flags_host[b] = 1;
+          ms.proved += 1;
+        }
+        ms.n_miss += ms.flags_host[b];
+      }
+    }
+    if (ms.proved > 0u) {
+      if (ms.flags.cap < nb || ms.order_heavy.cap < nb || ms.order_miss.cap < nb) {
+        VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued launch still reads the old halves
+        if (int rc = ms.flags.alloc(c, nb)) return rc;
+        if (int rc = ms.order_heavy.alloc(c, nb)) return rc;
+        if (int rc = ms.order_miss.alloc(c, nb)) return rc;
+      }
+      VxContext::MissSplit::Stage& st = ms.stage[ms.next_stage];
+      ms.next_stage ^= 1;
+      if (st.pending) VX_HIP(c, hipEventSynchronize(st.done));
+      st.pending = false;
+      if (st.cap < nb) {
+        if (st.p) (void)hipHostFree(st.p);
+        st.p = nullptr;
+        st.cap = 0;
+        VX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&st.p), nb, hipHostMallocDefault));
+        st.cap = nb;
+      }
+      if (!st.done) VX_HIP(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
+      memcpy(st.p, ms.flags_host.data(), nb);
+      VX_HIP(c, hipMemcpyAsync(ms.flags, st.p, nb, hipMemcpyHostToDevice, c->stream));
+      VX_HIP(c, hipEventRecord(st.done, c->stream));
+      st.pending = true;
+    }
+    ms.table.built(p);
+    ms.split_stale = true;
+  }
+  if (ms.proved > 0u && ms.split_stale) {
+    hipLaunchKernelGGL(split_order, dim3(1), dim3(1024), 0, c->stream, c->order, ms.flags, nb, ms.order_heavy, ms.order_miss);
+    VX_HIP(c, hipGetLastError());
+    ms.split_stale = false;
+  }
+  return VX_OK;
+}
+
+// multi: a multi-frame launch follows (vx_render_frames)
+static int prepare_render(VxContext* c, bool multi = false) {
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
+  if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
+  if (!c->tf) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: no transfer function");
+  if (!c->slab) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_resize not called");
+  if ((uint32_t)c->params.res[0] != c->W || (uint32_t)c->params.res[1] != c->H)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: params.res differs from the framebuffer size");
+  if (c->params.use_env > 0 && !c->env_tex)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: use_env = 1 without vx_upload_environment");
+  c->vol.dv.env_tex = c->env_tex;
+  c->vol.dv.env_imp = c->env_imp;
+  c->vol.dv.env_impq = c->env_impq;
+  c->vol.dv.env_avg_w = c->env_avg_w;
+  c->vol.dv.env_w = c->env_w;
+  c->vol.dv.env_h = c->env_h;
+  {
+    // The box the rays are clipped to must lie inside the volume (volume.ts:32-37 clips the volume's own box, so the
+    // viewer cannot ask for anything else): the trilinear look-up of the cellquad layout relies on every sample's cell
+    // lying in the apron lattice (Frame::trilinear, IN_LATTICE), i.e. on index positions within [-1/2, extent + 1/2).
+    // A quarter voxel of that margin is left to the rounding of ray positions near the faces.
+    const VxParams& p = c->params;
+    for (int corner = 0; corner < 8; ++corner) {
+      const float w[3] = {(corner & 1) ? p.volume_aabb_max[0] : p.volume_aabb_min[0],
+                          (corner & 2) ? p.volume_aabb_max[1] : p.volume_aabb_min[1],
+                          (corner & 4) ? p.volume_aabb_max[2] : p.volume_aabb_min[2]};
+      for (int i = 0; i < 3; ++i) {
+        const float* m = p.density_transform_inv;
+        const float q = fmaf(m[12 + i], 1.0f, fmaf(m[8 + i], w[2], fmaf(m[4 + i], w[1], m[i] * w[0])));
+        if (!(q >= -0.25f && q <= (float)c->vol.dv.extent[i] + 0.25f))
+          VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: volume_aabb reaches index %.3f on axis %d, outside the volume [0, %u]: "
+                  "the clip box must lie inside the volume's own box (volume.ts:32-37)", (double)q, i, c->vol.dv.extent[i]);
+      }
+    }
+  }
+  {
+    // the wave-uniform terms of the primary ray (DevVolume::cam_o ...), with the operations of setup_world_ray /
+    // to_index (vx_device.hpp): fma chains in the same order, IEEE divisions -- the same bits as on the device
+    const VxParams& p = c->params;
+    auto mat4 = [](const float* m, float x, float y, float z, float w, float out[4]) {
+      for (int i = 0; i < 4; ++i) out[i] = fmaf(m[12 + i], w, fmaf(m[8 + i], z, fmaf(m[4 + i], y, m[i] * x)));
+    };
+    float cw[4], a[4];
+    mat4(p.camera_view_inv, 0.0f, 0.0f, 0.0f, 1.0f, cw);
+    for (int i = 0; i < 3; ++i) c->vol.dv.cam_o[i] = cw[i] / cw[3];
+    mat4(p.density_transform_inv, c->vol.dv.cam_o[0], c->vol.dv.cam_o[1], c->vol.dv.cam_o[2], 1.0f, a);
+    for (int i = 0; i < 3; ++i) c->vol.dv.cam_ipos[i] = a[i];
+    c->vol.dv.inv_res[0] = 1.0f / (float)p.res[0];
+    c->vol.dv.inv_res[1] = 1.0f / (float)p.res[1];
+    // the per-ray divisions a launch constant decides (DevVolume::ray_flags): both shortcuts are exact or not taken
+    uint32_t flags = 0;
+    const float* vi = p.camera_view_inv;
+    if (vi[3] == 0.0f && vi[7] == 0.0f && vi[11] == 0.0f && vi[15] == 1.0f) flags |= RAY_AFFINE_VIEW;
+    for (int axis = 0; axis < 2; ++axis) {
+      if (c->tex_checked_res[axis] != p.res[axis]) {   // tried once per resolution, not per launch
+        const float res = (float)p.res[axis], y = c->vol.dv.inv_res[axis];
+        bool same = true;
+        for (int px = 0; px < p.res[axis] && same; ++px) {
+          const float a = (float)px + 0.5f, q0 = a * y;
+          same = fmaf(fmaf(-res, q0, a), y, q0) == a / res;
+        }
+        c->tex_checked_res[axis] = p.res[axis];
+        c->tex_by_reciprocal[axis] = same;
+      }
+      if (c->tex_by_reciprocal[axis]) flags |= (axis == 0 ? RAY_TEX_BY_RECIPROCAL_X : RAY_TEX_BY_RECIPROCAL_Y);
+    }
+    if (!c->sw.ray_shortcuts) flags = 0;   // diagnostic: the divisions themselves
+    c->vol.dv.ray_flags = flags;
+  }
+  {
+    const VxParams& p = c->params;
+    const bool dvr = p.render_mode == VX_MODE_DVR || p.render_mode == VX_MODE_DVR_PHONG;
+    int rc = VX_OK;
+    if (dvr && p.dvr_skip_empty && !p.debug_hits && !c->vol.skip_table.current(p)) rc = rebuild_skip_mask(c);
+    if (!rc && proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits && !c->vol.proj_table.current(p))
+      rc = rebuild_projection_bounds(c);
+    if (!rc && p.render_mode == VX_MODE_DEFAULT && !p.debug_hits && !c->vol.lmaj_table.current(p)) rc = rebuild_local_majorants(c);
+    if (rc) return rc;
+  }
+  {
+    // the layouts this launch samples, built on first use beside the one the upload built
+    int lay = eff_layout(c);
+    int rc = VX_OK;
+    if (lay == VX_LAYOUT_CELLQUAD) {
+      rc = ensure_cellquad(c);
+      lay = eff_layout(c);   // AUTO may have stepped down to the resident bricks (memory budget)
+    }
+    if (!rc && (lay == VX_LAYOUT_BRICKF32 ||
+                (c->params.render_mode == VX_MODE_DVR_PHONG && lay == VX_LAYOUT_CELLQUAD && tuned_possible(c))))
+      rc = ensure_brickf32(c);
+    if (rc) return rc;
+  }
+  if (int rc = check_segment_view(c, "vx_render_frame", false)) return rc;
+  if (shadow_on(c) && !c->vol.shadow_table.current(c->params)) {   // after the layouts: the build samples them
+    int rc = rebuild_light_grid(c);
+    if (rc) return rc;
+  }
+  if (int rc = ensure_counters(c, (size_t)frame_blocks(c) * 4u)) return rc;  // one record per wave of a frame's blocks
+  return multi ? ensure_miss_split(c) : VX_OK;
+}
+
+static int take_events(VxContext* c, EventPair& ev) {
+  if (c->free_events.empty()) {
+    if (c->pending_events.size() >= 4096) drain_events(c);
+    if (c->free_events.empty()) {
+      VX_HIP(c, hipEventCreate(&ev.a));
+      VX_HIP(c, hipEventCreate(&ev.b));
+      return VX_OK;
+    }
+  }
+  ev = c->free_events.back();
+  c->free_events.pop_back();
+  return VX_OK;
+}
+
+// at least n slots of per-frame result slabs and counter records for the current framebuffer and grid (grow-only)
+static int ensure_pipes(VxContext* c, uint32_t n) {
+  if (c->pipe_slots >= n && c->pipe_quads == c->slab_quads && c->pipe_waves == c->dc_waves) return VX_OK;
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  {
+    int rc = fold_counters(c);   // keep what the records of the old slots have counted
+    if (rc) return rc;
+  }
+  const size_t ns = std::max(n, c->pipe_slots), waves = c->dc_waves;
+  c->pipe_result_pool.reset();
+  c->pipe_dc_pool.reset();
+  c->pipe_slots = 0;
+  if (int rc = c->pipe_result_pool.alloc(c, ns * c->slab_quads)) return rc;
+  if (int rc = c->pipe_dc_pool.alloc(c, ns * waves)) return rc;
+  VX_HIP(c, hipMemsetAsync(c->pipe_dc_pool, 0, ns * waves * sizeof(DevCounters), c->stream));   // ordered with the launches
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  c->pipe_slots = (uint32_t)ns;
+  c->pipe_quads = c->slab_quads;
+  c->pipe_waves = waves;
+  return VX_OK;
+}
+
+}  // namespace
+
+// The segment view's refusals, in one place: a covered call (`iso`: vx_isosurface; else a render launch, after its layouts are
+// resident) with the view on fails here, before anything is launched, unless a masked instance serves it.
+int vx::check_segment_view(VxContext* c, const char* fn, bool iso) {
+  if (c->vol.seg_view == VX_SEGVIEW_OFF) return VX_OK;
+  const char* view = c->vol.seg_view == VX_SEGVIEW_ONLY ? "only" : "hide";
+  if (is_group(c)) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for a device group (the segment lives on member 0)", fn, view);
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s without a current segment (vx_segment first; an upload drops it)", fn, view);
+  if (iso) return VX_OK;
+  const VxParams& p = c->params;
+  if (p.render_mode <= VX_MODE_RAYMARCH)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for the path-traced render mode %d (default, no_dda, raymarch)", fn, view,
+            p.render_mode);
+  if (p.debug_hits) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not with debug_hits", fn, view);
+  if (p.dvr_shadow_stride != 0)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for shadowed DVR (dvr_shadow_stride = %d)", fn, view, p.dvr_shadow_stride);
+  if (!use_lds_kernel(c))
+    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: this launch has no LDS-window kernel (layout %d, dvr_ert_tau <= 0, a TF of "
+            "more than %u entries or VX_DVR_KERNEL=generic)", fn, view, eff_layout(c), (unsigned)TF_LDS_MAX);
+  return VX_OK;
+}
+
+extern "C" {
+
+const char* vx_version(void) { return "volxel_hip 0.1 (gfx950)"; }
+
+int vx_create(int device_id, VxContext** out) {
+  if (!out) return VX_ERR_INVALID;
+  *out = nullptr;
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess || n <= 0) {
+    g_create_error = "vx_create: no HIP device visible (libvolxel_hip has no CPU fallback)";
+    return VX_ERR_NO_DEVICE;
+  }
+  if (device_id < 0 || device_id >= n) {
+    g_create_error = "vx_create: device ordinal out of range";
+    return VX_ERR_INVALID;
+  }
+  VxContext* c = new VxContext();
+  c->device = device_id;
+  if (hipSetDevice(device_id) != hipSuccess || hipGetDeviceProperties(&c->prop, device_id) != hipSuccess ||
+      hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) {
+    g_create_error = "vx_create: device initialisation failed";
+    delete c;
+    return VX_ERR_DEVICE;
+  }
+  c->stream = c->own_stream;
+  {
+    // lanes = pixels x frames (vx_kernels.hpp frame_group) reads per-lane frame slots from the kernel-argument segment
+    // at the offsets of struct KArgs: check once per context that the compiler lays the arguments out that way
+    VxParams tp{};
+    DevVolume tv{};
+    MultiOut tm{};
+    tp.res[0] = 0x1234;
+    tv.extent[0] = 0x5678u;
+    for (uint32_t i = 0; i < (uint32_t)MERGE_MAX; ++i) {
+      tm.out[i] = reinterpret_cast<float4*>((uintptr_t)0x100000000ull * (i + 3u) + 16u * i);
+      tm.frame[i] = 0xabc00000u + 7u * i;
+    }
+    tm.count = MERGE_MAX;
+    uint32_t* bad = nullptr;
+    uint32_t hbad = 1;
+    hipError_t ce = hipMalloc(&bad, 4);
+    if (ce == hipSuccess) {
+      hipLaunchKernelGGL(check_lane_frame_slot, dim3(1), dim3(64), 0, c->stream, tp, tv, (const float4*)nullptr, 0x9abcu, tm, bad);
+      ce = hipGetLastError();
+    }
+    if (ce == hipSuccess) ce = hipMemcpyAsync(&hbad, bad, 4, hipMemcpyDeviceToHost, c->stream);
+    if (ce == hipSuccess) ce = hipStreamSynchronize(c->stream);
+    if (bad) (void)hipFree(bad);
+    if (ce != hipSuccess || hbad != 0u) {
+      g_create_error = ce != hipSuccess ? "vx_create: device self-check failed to run"
+                                        : "vx_create: kernel-argument layout differs from struct KArgs (lane_frame_slot)";
+      (void)hipStreamDestroy(c->own_stream);
+      delete c;
+      return VX_ERR_DEVICE;
+    }
+  }
+  c->sw = read_switches();   // the diagnostic switches (struct Switches)
+  *out = c;
+  return VX_OK;
+}
+
+int vx_create_group(const int* device_ids, int n, VxContext** out) {
+  if (out) *out = nullptr;
+  if (!device_ids || !out || n < 1 || n > VX_GROUP_MAX) {
+    g_create_error = "vx_create_group: need device_ids, 1 <= n <= 64 and out_ctx";
+    return VX_ERR_INVALID;
+  }
+  VxContext* g = new VxContext();
+  g->device = device_ids[0];
+  auto drop = [g] {   // the members made so far (a group without members is not a context yet)
+    for (VxContext* m : g->members) vx_destroy(m);
+    delete g;
+  };
+  for (int i = 0; i < n; ++i) {
+    VxContext* m = nullptr;
+    int rc = vx_create(device_ids[i], &m);
+    if (rc == VX_OK && hipEventCreateWithFlags(&m->done, hipEventDisableTiming) != hipSuccess) {
+      vx_destroy(m);
+      g_create_error = "event creation failed";
+      rc = VX_ERR_DEVICE;
+    }
+    if (rc) {
+      char head[80];
+      snprintf(head, sizeof head, "vx_create_group: member %d (device %d): ", i, device_ids[i]);
+      g_create_error = head + g_create_error;
+      drop();
+      return rc;
+    }
+    g->members.push_back(m);
+  }
+  // the gather runs on device_ids[0] and reads every other device's slab in place: peer access, no staging copy
+  const int d0 = device_ids[0];
+  for (int i = 1; i < n; ++i) {
+    const int d = device_ids[i];
+    if (d == d0 || std::find(device_ids + 1, device_ids + i, d) != device_ids + i) continue;
+    int can = 0;
+    hipError_t e = hipDeviceCanAccessPeer(&can, d0, d);
+    if (e == hipSuccess && !can) {
+      char buf[160];
+      snprintf(buf, sizeof buf, "vx_create_group: device %d cannot access device %d as a peer", d0, d);
+      g_create_error = buf;
+      drop();
+      return VX_ERR_NO_DEVICE;
+    }
+    if (e == hipSuccess) e = hipSetDevice(d0);
+    if (e == hipSuccess) {
+      e = hipDeviceEnablePeerAccess(d, 0);
+      if (e == hipErrorPeerAccessAlreadyEnabled) {
+        (void)hipGetLastError();
+        e = hipSuccess;
+      }
+    }
+    if (e != hipSuccess) {
+      g_create_error = std::string("vx_create_group: peer access from device ") + std::to_string(d0) + " to " +
+                       std::to_string(d) + ": " + hipGetErrorString(e);
+      drop();
+      return VX_ERR_DEVICE;
+    }
+  }
+  g->prop = g->members[0]->prop;
+  *out = g;
+  return VX_OK;
+}
+
+void vx_destroy(VxContext* c) {
+  if (!c) return;
+  if (is_group(c)) {
+    for (VxContext* m : c->members) vx_destroy(m);
+    delete c;
+    return;
+  }
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  drain_events(c);
+  for (auto& e : c->free_events) {
+    (void)hipEventDestroy(e.a);
+    (void)hipEventDestroy(e.b);
+  }
+  free_volume(c);
+  if (c->done) (void)hipEventDestroy(c->done);
+  if (c->aux_stream) (void)hipStreamDestroy(c->aux_stream);
+  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  delete c;   // every buffer and timer the context owns, on the device made current above (vx_host.hpp)
+}
+
+const char* vx_last_error(const VxContext* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
+
+int vx_set_stream(VxContext* c, void* s) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_set_stream", "each member owns its stream");
+  VX_DEV(c);
+  (void)hipStreamSynchronize(c->stream);
+  c->stream = s ? (hipStream_t)s : c->own_stream;
+  return VX_OK;
+}
 
 int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t ind_size[3],
                      const uint16_t* range, const uint32_t range_size[3], const uint8_t* atlas,
@@ -1814,212 +1515,6 @@ int vx_resize(VxContext* c, uint32_t w, uint32_t h) {
   return alloc_framebuffers(c);
 }
 
-// The segment view's refusals, in one place: a covered call (`iso`: vx_isosurface; else a render launch, after its layouts are
-// resident) with the view on fails here, before anything is launched, unless a masked instance serves it.
-static int check_segment_view(VxContext* c, const char* fn, bool iso) {
-  if (c->vol.seg_view == VX_SEGVIEW_OFF) return VX_OK;
-  const char* view = c->vol.seg_view == VX_SEGVIEW_ONLY ? "only" : "hide";
-  if (is_group(c)) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for a device group (the segment lives on member 0)", fn, view);
-  if (!c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s without a current segment (vx_segment first; an upload drops it)", fn, view);
-  if (iso) return VX_OK;
-  const VxParams& p = c->params;
-  if (p.render_mode <= VX_MODE_RAYMARCH)
-    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for the path-traced render mode %d (default, no_dda, raymarch)", fn, view,
-            p.render_mode);
-  if (p.debug_hits) VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not with debug_hits", fn, view);
-  if (p.dvr_shadow_stride != 0)
-    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: not for shadowed DVR (dvr_shadow_stride = %d)", fn, view, p.dvr_shadow_stride);
-  if (!use_lds_kernel(c))
-    VX_FAIL(c, VX_ERR_INVALID, "%s: segment view %s: this launch has no LDS-window kernel (layout %d, dvr_ert_tau <= 0, a TF of "
-            "more than %u entries or VX_DVR_KERNEL=generic)", fn, view, eff_layout(c), (unsigned)TF_LDS_MAX);
-  return VX_OK;
-}
-
-// The split of a plain multi-frame DVR launch of the LDS-window kernel, kept current the way the derived tables are: the
-// classification is rebuilt when the bits of its key change or the tile map did, the two halves of the block order when `order`
-// or the flags did.  Called at the end of prepare_render ahead of a multi-frame launch only (the counters and `order` exist):
-// single-frame launches are never split (NOTEBOOK R4.13) and pay nothing for it.  plan_launch uses what it finds current.
-static int ensure_miss_split(VxContext* c) {
-  VxContext::MissSplit& ms = c->miss;
-  const VxParams& p = c->params;
-  if (!c->sw.dvr_miss || p.render_mode != VX_MODE_DVR || !use_lds_kernel(c)) return VX_OK;
-  const uint32_t nb = frame_blocks(c);
-  if (!ms.table.current(p) || ms.blocks != nb) {
-    ms.table.stale = true;   // until this build is complete: a failure below must not leave the old key over new counts
-    std::vector<uint8_t> img;
-    ms.proved = ms.n_miss = 0;
-    ms.blocks = nb;
-    if (classify_miss_blocks(p, c->W, c->H, img) != 0u) {
-      // image block -> logical block of this shard: block_to_tile, tile_at and wave_pixel on the host
-      const TileMap& tm = c->tm;
-      const uint32_t nbx = (c->W + 15u) / 16u;
-      auto morton_x = [](uint32_t m) { return (m & 1u) | ((m >> 1) & 2u) | ((m >> 2) & 4u); };
-      ms.flags_host.assign(nb, 0);
-      for (uint32_t b = 0; b < nb; ++b) {
-        const uint32_t lt = (b >> 7) * 8u + (b & 7u), wt = ((b >> 3) & 15u) * 4u;
-        const uint32_t pos = lt * tm.shard_count + tm.shard_rank;
-        const uint32_t t = (!c->tile_perm_host.empty() && pos < tm.n_tiles) ? c->tile_perm_host[pos] : pos;
-        const uint32_t x0 = (t % tm.tiles_x) * 64u + morton_x(wt) * 8u, y0 = (t / tm.tiles_x) * 64u + morton_x(wt >> 1) * 8u;
-        if (lt >= tm.tiles_per_shard || t >= tm.n_tiles || x0 >= tm.W || y0 >= tm.H) {
-          ms.flags_host[b] = 1;   // no pixel: either kernel returns at once
-        } else if (img[(size_t)(y0 >> 4) * nbx + (x0 >> 4)]) {
-          ms.flags_host[b] = 1;
-          ms.proved += 1;
-        }
-        ms.n_miss += ms.flags_host[b];
-      }
-    }
-    if (ms.proved > 0u) {
-      if (ms.flags.cap < nb || ms.order_heavy.cap < nb || ms.order_miss.cap < nb) {
-        VX_HIP(c, hipStreamSynchronize(c->stream));   // no queued launch still reads the old halves
-        if (int rc = ms.flags.alloc(c, nb)) return rc;
-        if (int rc = ms.order_heavy.alloc(c, nb)) return rc;
-        if (int rc = ms.order_miss.alloc(c, nb)) return rc;
-      }
-      VxContext::MissSplit::Stage& st = ms.stage[ms.next_stage];
-      ms.next_stage ^= 1;
-      if (st.pending) VX_HIP(c, hipEventSynchronize(st.done));
-      st.pending = false;
-      if (st.cap < nb) {
-        if (st.p) (void)hipHostFree(st.p);
-        st.p = nullptr;
-        st.cap = 0;
-        VX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&st.p), nb, hipHostMallocDefault));
-        st.cap = nb;
-      }
-      if (!st.done) VX_HIP(c, hipEventCreateWithFlags(&st.done, hipEventDisableTiming));
-      memcpy(st.p, ms.flags_host.data(), nb);
-      VX_HIP(c, hipMemcpyAsync(ms.flags, st.p, nb, hipMemcpyHostToDevice, c->stream));
-      VX_HIP(c, hipEventRecord(st.done, c->stream));
-      st.pending = true;
-    }
-    ms.table.built(p);
-    ms.split_stale = true;
-  }
-  if (ms.proved > 0u && ms.split_stale) {
-    hipLaunchKernelGGL(split_order, dim3(1), dim3(1024), 0, c->stream, c->order, ms.flags, nb, ms.order_heavy, ms.order_miss);
-    VX_HIP(c, hipGetLastError());
-    ms.split_stale = false;
-  }
-  return VX_OK;
-}
-
-// multi: a multi-frame launch follows (vx_render_frames)
-static int prepare_render(VxContext* c, bool multi = false) {
-  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_render_frame: no volume uploaded");
-  if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_set_params not called");
-  if (!c->tf) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: no transfer function");
-  if (!c->slab) VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: vx_resize not called");
-  if ((uint32_t)c->params.res[0] != c->W || (uint32_t)c->params.res[1] != c->H)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: params.res differs from the framebuffer size");
-  if (c->params.use_env > 0 && !c->env_tex)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: use_env = 1 without vx_upload_environment");
-  c->vol.dv.env_tex = c->env_tex;
-  c->vol.dv.env_imp = c->env_imp;
-  c->vol.dv.env_impq = c->env_impq;
-  c->vol.dv.env_avg_w = c->env_avg_w;
-  c->vol.dv.env_w = c->env_w;
-  c->vol.dv.env_h = c->env_h;
-  {
-    // The box the rays are clipped to must lie inside the volume (volume.ts:32-37 clips the volume's own box, so the
-    // viewer cannot ask for anything else): the trilinear look-up of the cellquad layout relies on every sample's cell
-    // lying in the apron lattice (Frame::trilinear, IN_LATTICE), i.e. on index positions within [-1/2, extent + 1/2).
-    // A quarter voxel of that margin is left to the rounding of ray positions near the faces.
-    const VxParams& p = c->params;
-    for (int corner = 0; corner < 8; ++corner) {
-      const float w[3] = {(corner & 1) ? p.volume_aabb_max[0] : p.volume_aabb_min[0],
-                          (corner & 2) ? p.volume_aabb_max[1] : p.volume_aabb_min[1],
-                          (corner & 4) ? p.volume_aabb_max[2] : p.volume_aabb_min[2]};
-      for (int i = 0; i < 3; ++i) {
-        const float* m = p.density_transform_inv;
-        const float q = fmaf(m[12 + i], 1.0f, fmaf(m[8 + i], w[2], fmaf(m[4 + i], w[1], m[i] * w[0])));
-        if (!(q >= -0.25f && q <= (float)c->vol.dv.extent[i] + 0.25f))
-          VX_FAIL(c, VX_ERR_INVALID, "vx_render_frame: volume_aabb reaches index %.3f on axis %d, outside the volume [0, %u]: "
-                  "the clip box must lie inside the volume's own box (volume.ts:32-37)", (double)q, i, c->vol.dv.extent[i]);
-      }
-    }
-  }
-  {
-    // the wave-uniform terms of the primary ray (DevVolume::cam_o ...), with the operations of setup_world_ray /
-    // to_index (vx_device.hpp): fma chains in the same order, IEEE divisions -- the same bits as on the device
-    const VxParams& p = c->params;
-    auto mat4 = [](const float* m, float x, float y, float z, float w, float out[4]) {
-      for (int i = 0; i < 4; ++i) out[i] = fmaf(m[12 + i], w, fmaf(m[8 + i], z, fmaf(m[4 + i], y, m[i] * x)));
-    };
-    float cw[4], a[4];
-    mat4(p.camera_view_inv, 0.0f, 0.0f, 0.0f, 1.0f, cw);
-    for (int i = 0; i < 3; ++i) c->vol.dv.cam_o[i] = cw[i] / cw[3];
-    mat4(p.density_transform_inv, c->vol.dv.cam_o[0], c->vol.dv.cam_o[1], c->vol.dv.cam_o[2], 1.0f, a);
-    for (int i = 0; i < 3; ++i) c->vol.dv.cam_ipos[i] = a[i];
-    c->vol.dv.inv_res[0] = 1.0f / (float)p.res[0];
-    c->vol.dv.inv_res[1] = 1.0f / (float)p.res[1];
-    // the per-ray divisions a launch constant decides (DevVolume::ray_flags): both shortcuts are exact or not taken
-    uint32_t flags = 0;
-    const float* vi = p.camera_view_inv;
-    if (vi[3] == 0.0f && vi[7] == 0.0f && vi[11] == 0.0f && vi[15] == 1.0f) flags |= RAY_AFFINE_VIEW;
-    for (int axis = 0; axis < 2; ++axis) {
-      if (c->tex_checked_res[axis] != p.res[axis]) {   // tried once per resolution, not per launch
-        const float res = (float)p.res[axis], y = c->vol.dv.inv_res[axis];
-        bool same = true;
-        for (int px = 0; px < p.res[axis] && same; ++px) {
-          const float a = (float)px + 0.5f, q0 = a * y;
-          same = fmaf(fmaf(-res, q0, a), y, q0) == a / res;
-        }
-        c->tex_checked_res[axis] = p.res[axis];
-        c->tex_by_reciprocal[axis] = same;
-      }
-      if (c->tex_by_reciprocal[axis]) flags |= (axis == 0 ? RAY_TEX_BY_RECIPROCAL_X : RAY_TEX_BY_RECIPROCAL_Y);
-    }
-    if (!c->sw.ray_shortcuts) flags = 0;   // diagnostic: the divisions themselves
-    c->vol.dv.ray_flags = flags;
-  }
-  {
-    const VxParams& p = c->params;
-    const bool dvr = p.render_mode == VX_MODE_DVR || p.render_mode == VX_MODE_DVR_PHONG;
-    int rc = VX_OK;
-    if (dvr && p.dvr_skip_empty && !p.debug_hits && !c->vol.skip_table.current(p)) rc = rebuild_skip_mask(c);
-    if (!rc && proj_mode(p.render_mode) && p.dvr_skip_empty && !p.debug_hits && !c->vol.proj_table.current(p))
-      rc = rebuild_projection_bounds(c);
-    if (!rc && p.render_mode == VX_MODE_DEFAULT && !p.debug_hits && !c->vol.lmaj_table.current(p)) rc = rebuild_local_majorants(c);
-    if (rc) return rc;
-  }
-  {
-    // the layouts this launch samples, built on first use beside the one the upload built
-    int lay = eff_layout(c);
-    int rc = VX_OK;
-    if (lay == VX_LAYOUT_CELLQUAD) {
-      rc = ensure_cellquad(c);
-      lay = eff_layout(c);   // AUTO may have stepped down to the resident bricks (memory budget)
-    }
-    if (!rc && (lay == VX_LAYOUT_BRICKF32 ||
-                (c->params.render_mode == VX_MODE_DVR_PHONG && lay == VX_LAYOUT_CELLQUAD && tuned_possible(c))))
-      rc = ensure_brickf32(c);
-    if (rc) return rc;
-  }
-  if (int rc = check_segment_view(c, "vx_render_frame", false)) return rc;
-  if (shadow_on(c) && !c->vol.shadow_table.current(c->params)) {   // after the layouts: the build samples them
-    int rc = rebuild_light_grid(c);
-    if (rc) return rc;
-  }
-  if (int rc = ensure_counters(c, (size_t)frame_blocks(c) * 4u)) return rc;  // one record per wave of a frame's blocks
-  return multi ? ensure_miss_split(c) : VX_OK;
-}
-
-static int take_events(VxContext* c, EventPair& ev) {
-  if (c->free_events.empty()) {
-    if (c->pending_events.size() >= 4096) drain_events(c);
-    if (c->free_events.empty()) {
-      VX_HIP(c, hipEventCreate(&ev.a));
-      VX_HIP(c, hipEventCreate(&ev.b));
-      return VX_OK;
-    }
-  }
-  ev = c->free_events.back();
-  c->free_events.pop_back();
-  return VX_OK;
-}
-
 int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
   if (!c) return VX_ERR_INVALID;
   if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_render_frame(m, frame_index, sample_weight); });
@@ -2047,28 +1542,6 @@ int vx_render_frame(VxContext* c, uint32_t frame_index, float sample_weight) {
     c->miss.split_stale = true;
   }
   c->note_launch(1);
-  return VX_OK;
-}
-
-// at least n slots of per-frame result slabs and counter records for the current framebuffer and grid (grow-only)
-static int ensure_pipes(VxContext* c, uint32_t n) {
-  if (c->pipe_slots >= n && c->pipe_quads == c->slab_quads && c->pipe_waves == c->dc_waves) return VX_OK;
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  {
-    int rc = fold_counters(c);   // keep what the records of the old slots have counted
-    if (rc) return rc;
-  }
-  const size_t ns = std::max(n, c->pipe_slots), waves = c->dc_waves;
-  c->pipe_result_pool.reset();
-  c->pipe_dc_pool.reset();
-  c->pipe_slots = 0;
-  if (int rc = c->pipe_result_pool.alloc(c, ns * c->slab_quads)) return rc;
-  if (int rc = c->pipe_dc_pool.alloc(c, ns * waves)) return rc;
-  VX_HIP(c, hipMemsetAsync(c->pipe_dc_pool, 0, ns * waves * sizeof(DevCounters), c->stream));   // ordered with the launches
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  c->pipe_slots = (uint32_t)ns;
-  c->pipe_quads = c->slab_quads;
-  c->pipe_waves = waves;
   return VX_OK;
 }
 
@@ -2542,927 +2015,6 @@ int vx_probe_gather_spread(VxContext* c, uint32_t frame_index, uint64_t out3[3])
     out3[1] += w.rays;           // wave-wide distinct lines, summed over the q0 gathers
     out3[2] += w.pixels;         // look-ups of the 16 lane quads, summed over the q0 gathers
   }
-  return VX_OK;
-}
-
-// ---- the parameter checks the slice and segment entry points share -------------------------------------------------------
-// Each takes the entry point's name: the refusals read "<entry point>: ..." as they always did.
-
-// the preamble: a volume, the params, and the entry point's own argument
-static int check_ready(VxContext* c, const char* fn, const void* arg, const char* arg_name) {
-  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "%s: no volume uploaded", fn);
-  if (!c->has_params)
-    VX_FAIL(c, VX_ERR_INVALID, "%s: vx_set_params first (volume_density_scale and volume_inv_maj come from it)", fn);
-  if (!arg) VX_FAIL(c, VX_ERR_INVALID, "%s: %s is NULL", fn, arg_name);
-  return VX_OK;
-}
-static int check_slice_size(VxContext* c, const char* fn, const VxSliceParams* sp) {
-  for (int i = 0; i < 2; ++i)
-    if (sp->size[i] < 1u || sp->size[i] > 16384u) VX_FAIL(c, VX_ERR_INVALID, "%s: size[%d] = %u outside 1 .. 16384", fn, i, sp->size[i]);
-  if (sp->slab_samples < 1u || sp->slab_samples > 4096u)
-    VX_FAIL(c, VX_ERR_INVALID, "%s: slab_samples = %u outside 1 .. 4096", fn, sp->slab_samples);
-  return VX_OK;
-}
-static int check_slice_frame(VxContext* c, const char* fn, const VxSliceParams* sp) {
-  const struct { const char* name; const float* v; } vecs[4] = {{"origin", sp->origin}, {"du", sp->du}, {"dv", sp->dv}, {"dn", sp->dn}};
-  for (const auto& e : vecs)
-    for (int i = 0; i < 3; ++i)
-      if (!std::isfinite(e.v[i])) VX_FAIL(c, VX_ERR_INVALID, "%s: %s[%d] is not finite", fn, e.name, i);
-  return VX_OK;
-}
-static int check_band(VxContext* c, const char* fn, float lo, float hi) {
-  if (!std::isfinite(lo)) VX_FAIL(c, VX_ERR_INVALID, "%s: lo is not finite", fn);
-  if (!std::isfinite(hi)) VX_FAIL(c, VX_ERR_INVALID, "%s: hi is not finite", fn);
-  if (lo > hi) VX_FAIL(c, VX_ERR_INVALID, "%s: lo = %g > hi = %g", fn, (double)lo, (double)hi);
-  return VX_OK;
-}
-static int check_connectivity(VxContext* c, const char* fn, int conn) {
-  if (conn != 6 && conn != 26) VX_FAIL(c, VX_ERR_INVALID, "%s: connectivity = %d is not 6 or 26", fn, conn);
-  return VX_OK;
-}
-static int check_seed(VxContext* c, const char* fn, const uint32_t seed[3]) {
-  for (int a = 0; a < 3; ++a)
-    if (seed[a] >= c->vol.dv.extent[a])
-      VX_FAIL(c, VX_ERR_INVALID, "%s: seed[%d] = %u outside the index extent %u", fn, a, seed[a], c->vol.dv.extent[a]);
-  return VX_OK;
-}
-// the voxel box [box_lo, box_hi] with VX_SEGMENT_BOX_END resolved, inside the index extent
-struct VoxelBox {
-  uint32_t lo[3], hi[3];
-};
-static int check_box(VxContext* c, const char* fn, const uint32_t box_lo[3], const uint32_t box_hi[3], VoxelBox* b) {
-  const uint32_t* E = c->vol.dv.extent;
-  for (int a = 0; a < 3; ++a) {
-    b->lo[a] = box_lo[a];
-    b->hi[a] = box_hi[a] == VX_SEGMENT_BOX_END ? E[a] - 1u : box_hi[a];
-    if (b->lo[a] > b->hi[a] || b->hi[a] >= E[a])
-      VX_FAIL(c, VX_ERR_INVALID, "%s: box axis %d [%u, %u] is empty or outside the index extent %u", fn, a, box_lo[a], box_hi[a], E[a]);
-  }
-  return VX_OK;
-}
-// bytes of the packed mask (1 bit per voxel) a caller hands over or receives
-static int check_mask_bytes(VxContext* c, const char* fn, uint64_t nbytes, size_t* want) {
-  const uint32_t* E = c->vol.dv.extent;
-  *want = (size_t)E[0] * E[1] * E[2] / 8u;
-  if (nbytes != *want)
-    VX_FAIL(c, VX_ERR_INVALID, "%s: nbytes = %llu, the mask of %u x %u x %u voxels is %zu bytes", fn, (unsigned long long)nbytes, E[0],
-            E[1], E[2], *want);
-  return VX_OK;
-}
-
-int vx_slice(VxContext* c, const VxSliceParams* sp, float* values_out, uint8_t* rgba8_out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_slice(c->members[0], sp, values_out, rgba8_out));
-  VX_DEV(c);
-  if (int rc = check_ready(c, "vx_slice", sp, "sp")) return rc;
-  if (int rc = check_slice_size(c, "vx_slice", sp)) return rc;
-  if (sp->reduce < VX_SLICE_MEAN || sp->reduce > VX_SLICE_MIN) VX_FAIL(c, VX_ERR_INVALID, "vx_slice: unknown reduce %d", sp->reduce);
-  if (sp->display < VX_SLICE_NONE || sp->display > VX_SLICE_TF)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: unknown display %d", sp->display);
-  if (int rc = check_slice_frame(c, "vx_slice", sp)) return rc;
-  if (sp->display == VX_SLICE_GREY &&
-      !(std::isfinite(sp->window[0]) && std::isfinite(sp->window[1]) && sp->window[1] > sp->window[0]))
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: window [%g, %g] with VX_SLICE_GREY: needs finite window[0] < window[1]",
-            (double)sp->window[0], (double)sp->window[1]);
-  if (sp->display == VX_SLICE_TF && !c->tf)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: display VX_SLICE_TF without a transfer function (vx_upload_transfer first)");
-  if (rgba8_out && sp->display == VX_SLICE_NONE)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice: rgba8_out with display VX_SLICE_NONE (no display output)");
-  const size_t px = (size_t)sp->size[0] * sp->size[1];
-  // (every earlier slice has completed: vx_slice synchronises)
-  if (int rc = c->slice_values.ensure(c, px)) return rc;
-  if (int rc = c->slice_rgba.ensure(c, px)) return rc;
-  if (int rc = c->slice_timer.mark(c, 0)) return rc;
-  launch_slice(c, *sp);
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->slice_timer.mark(c, 1)) return rc;
-  if (values_out)
-    VX_HIP(c, hipMemcpyAsync(values_out, c->slice_values, px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  if (rgba8_out) VX_HIP(c, hipMemcpyAsync(rgba8_out, c->slice_rgba, px * sizeof(uchar4), hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  if (int rc = c->slice_timer.read(c)) return rc;
-  c->slice_samples = (uint64_t)px * sp->slab_samples;
-  return VX_OK;
-}
-
-int vx_slice_stats(VxContext* c, uint64_t* samples, double* last_kernel_ms) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_slice_stats(c->members[0], samples, last_kernel_ms));
-  if (samples) *samples = c->slice_samples;
-  if (last_kernel_ms) *last_kernel_ms = c->slice_timer.ms[0];
-  return VX_OK;
-}
-
-int vx_isosurface(VxContext* c, const VxIsoParams* ip, float* rgba_out, float* hit_out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_isosurface(c->members[0], ip, rgba_out, hit_out));
-  VX_DEV(c);
-  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_isosurface: no volume uploaded");
-  if (!c->has_params) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: vx_set_params first (the camera, clip box and march come from it)");
-  if (!ip) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: ip is NULL");
-  // the march of any render mode's params: the checks vx_set_params makes for the marching modes
-  if (!(c->params.dvr_step_voxels > 0.0f)) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: params.dvr_step_voxels must be > 0");
-  if (c->params.dvr_max_steps < 0 || c->params.dvr_max_steps > (1 << 24))
-    VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: params.dvr_max_steps %d outside [0, 2^24]", c->params.dvr_max_steps);
-  const struct { const char* name; float v; } terms[8] = {{"iso", ip->iso}, {"color[0]", ip->color[0]}, {"color[1]", ip->color[1]},
-                                                          {"color[2]", ip->color[2]}, {"ka", ip->ka}, {"kd", ip->kd},
-                                                          {"ks", ip->ks}, {"shininess", ip->shininess}};
-  for (const auto& e : terms)
-    if (!std::isfinite(e.v)) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: %s is not finite", e.name);
-  if (ip->shininess < 0.0f) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: shininess = %g < 0", (double)ip->shininess);
-  if (ip->refine > 16u) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: refine = %u outside 0 .. 16", ip->refine);
-  if (ip->skip != 0 && ip->skip != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: skip = %d is not 0 or 1", ip->skip);
-  const uint32_t W = (uint32_t)c->params.res[0], H = (uint32_t)c->params.res[1];
-  VxIsoParams q = *ip;
-  if (!q.window[0] && !q.window[1] && !q.window[2] && !q.window[3]) {
-    q.window[2] = W;
-    q.window[3] = H;
-  }
-  if (!(q.window[0] < q.window[2] && q.window[1] < q.window[3] && q.window[2] <= W && q.window[3] <= H))
-    VX_FAIL(c, VX_ERR_INVALID, "vx_isosurface: window (%u, %u, %u, %u) is empty or outside the render size %u x %u", q.window[0],
-            q.window[1], q.window[2], q.window[3], W, H);
-  const uint32_t ww = q.window[2] - q.window[0], wh = q.window[3] - q.window[1];
-  const size_t px = (size_t)ww * wh;
-  // (every earlier call has completed: vx_isosurface synchronises)
-  if (int rc = c->iso_rgba.ensure(c, px)) return rc;
-  if (int rc = c->iso_hit.ensure(c, px)) return rc;
-  if (int rc = check_segment_view(c, "vx_isosurface", true)) return rc;
-  if (c->vol.seg_view != VX_SEGVIEW_OFF) q.skip = 0;   // masked: no range skipping
-  if (q.skip && !c->vol.iso_table.current(c->params)) {
-    const int rc = rebuild_iso_bounds(c);
-    if (rc) return rc;
-  }
-  if (int rc = c->iso_count_dev.ensure(c, ISO_NCOUNTS)) return rc;
-  VX_HIP(c, hipMemsetAsync(c->iso_count_dev, 0, ISO_NCOUNTS * sizeof(unsigned long long), c->stream));
-  if (int rc = c->iso_timer.mark(c, 0)) return rc;
-  launch_iso(c, q, ww, wh);
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->iso_timer.mark(c, 1)) return rc;
-  uint64_t counts[ISO_NCOUNTS];
-  VX_HIP(c, hipMemcpyAsync(counts, c->iso_count_dev, sizeof counts, hipMemcpyDeviceToHost, c->stream));
-  if (rgba_out) VX_HIP(c, hipMemcpyAsync(rgba_out, c->iso_rgba, px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  if (hit_out) VX_HIP(c, hipMemcpyAsync(hit_out, c->iso_hit, px * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  if (int rc = c->iso_timer.read(c)) return rc;
-  memcpy(c->iso_counts, counts, sizeof counts);
-  return VX_OK;
-}
-
-int vx_iso_stats(VxContext* c, uint64_t* rays, uint64_t* hits, uint64_t* samples, uint64_t* refine_samples, uint64_t* skipped,
-                 double* last_kernel_ms) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_iso_stats(c->members[0], rays, hits, samples, refine_samples, skipped, last_kernel_ms));
-  if (rays) *rays = c->iso_counts[ISO_RAYS];
-  if (hits) *hits = c->iso_counts[ISO_HITS];
-  if (samples) *samples = c->iso_counts[ISO_SAMPLES];
-  if (refine_samples) *refine_samples = c->iso_counts[ISO_REFINE];
-  if (skipped) *skipped = c->iso_counts[ISO_SKIPPED];
-  if (last_kernel_ms) *last_kernel_ms = c->iso_timer.ms[0];
-  return VX_OK;
-}
-
-// ---- segmentation (vx_segment): seg_predicate, the flood rounds, seg_stats / seg_sum (vx_segment.hpp) ----------------------
-// rounds between host read-backs of the next worklist's length: 1, 2, 4, ... up to Switches::seg_check_max (64; NOTEBOOK
-// "Segmentation" compares caps).  A queued round that finds its worklist empty exits at once (one launch boundary, a few
-// microseconds); a read-back is a host round trip.
-
-// the device buffers of the brick grid, carved from one allocation (sizes in DESIGN.md / INTEGRATION.md's memory bill)
-static int ensure_segment(VxContext* c) {
-  if (c->vol.seg_alloc) return VX_OK;
-  const uint32_t nb = c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2];
-  SegDev& s = c->vol.seg;
-  const int rc = carve(c, c->vol.seg_alloc, [&](Carve& k) {
-    s.pred = k.take<uint64_t>((size_t)nb * 8u);
-    s.seg = k.take<uint64_t>((size_t)nb * 8u);
-    // `partial` stays immediately behind `seg`: the masked LDS-window staging reads the dword right behind the mask for the
-    // zero chunk behind the last brick -- the first of `partial`, inside this allocation -- and drops its bits
-    // (vx_dvr_lds_march.inc)
-    s.partial = k.take<double>(nb);
-    s.st = k.take<SegStats>();
-    s.any = k.take<uint32_t>(nb);
-    s.stamp = k.take<uint32_t>(nb);
-    s.list[0] = k.take<uint32_t>(nb);
-    s.list[1] = k.take<uint32_t>(nb);
-    s.cnt = k.take<uint32_t>(4);
-  });
-  if (rc) return rc;
-  for (int a = 0; a < 3; ++a) s.bc[a] = c->vol.dv.bc[a];
-  s.nb = nb;
-  return VX_OK;
-}
-
-static void launch_seg_predicate(VxContext* c, const SegPredParams& pp) {
-  const VxParams& p = c->params;
-  const uint32_t blocks = std::min<uint32_t>((c->vol.seg.nb + 3u) / 4u, 4096u);
-  with_layout(slice_layout(c), [&](auto lay) {
-    constexpr int LAY = decltype(lay)::value;
-    hipLaunchKernelGGL((seg_predicate<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
-                       pp, c->vol.seg);
-  });
-}
-static SegPredParams seg_pred_params(float lo, float hi, const VoxelBox& b) {
-  return SegPredParams{lo, hi, {b.lo[0], b.lo[1], b.lo[2]}, {b.hi[0], b.hi[1], b.hi[2]}};
-}
-// the brick, the z slice and the bit of a voxel
-static SegSeed seg_seed_of(const SegDev& s, const uint32_t v[3]) {
-  return SegSeed{((v[2] >> 3) * s.bc[1] + (v[1] >> 3)) * s.bc[0] + (v[0] >> 3), v[2] & 7u, 1ull << (((v[1] & 7u) << 3) | (v[0] & 7u))};
-}
-static void launch_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint32_t round) {
-  const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 1024u);
-  with_conn(conn, [&](auto k) {
-    hipLaunchKernelGGL((seg_flood<decltype(k)::value>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
-  });
-}
-// the rounds of a flood on the view s (vx_segment: the segment; vx_segment_edit: the background of fill holes), from a round-0
-// worklist that is already on the device: queued in batches of 1, 2, 4, ... SEG_CHECK_MAX, the next worklist's length read back
-// after each batch.  Ends synchronised; *launched counts the flood launches.
-static int run_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint64_t cap, bool* converged,
-                         uint64_t* launched_out) {
-  uint64_t launched = 0;
-  uint32_t batch = 1, next = 1;
-  *converged = false;
-  while (true) {
-    const uint64_t k = std::min<uint64_t>(batch, cap - launched);
-    for (uint64_t i = 0; i < k; ++i) launch_seg_flood(c, s, conn, seed, (uint32_t)(launched + i));
-    VX_HIP(c, hipGetLastError());
-    launched += k;
-    VX_HIP(c, hipMemcpyAsync(&next, s.cnt + launched % 3u, sizeof next, hipMemcpyDeviceToHost, c->stream));
-    VX_HIP(c, hipStreamSynchronize(c->stream));
-    if (next == 0u) {
-      *converged = true;
-      break;
-    }
-    if (launched >= cap) break;
-    batch = std::min(batch * 2u, c->sw.seg_check_max);
-  }
-  if (launched_out) *launched_out = launched;
-  return VX_OK;
-}
-static void launch_seg_stats(VxContext* c) {
-  const VxParams& p = c->params;
-  const uint32_t blocks = std::min<uint32_t>((c->vol.seg.nb + 3u) / 4u, 4096u);
-  with_layout(slice_layout(c), [&](auto lay) {
-    constexpr int LAY = decltype(lay)::value;
-    hipLaunchKernelGGL((seg_stats<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
-                       c->vol.seg);
-  });
-  hipLaunchKernelGGL(seg_sum, dim3(1), dim3(1024), 0, c->stream, c->vol.seg);
-}
-static float seg_key_float(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  float f;
-  memcpy(&f, &u, sizeof f);
-  return f;
-}
-// the count, bounding box and density statistics of a result; rounds, brick_visits and converged are the caller's
-static VxSegmentResult seg_result(const SegStats& st) {
-  VxSegmentResult r{};
-  r.count = st.count;
-  if (st.count) {
-    for (int a = 0; a < 3; ++a) {
-      r.bbox_lo[a] = st.lo[a];
-      r.bbox_hi[a] = st.hi[a];
-    }
-    r.d_min = seg_key_float(st.dmin);
-    r.d_max = seg_key_float(st.dmax);
-    r.d_sum = st.sum;
-  }
-  return r;
-}
-// The statistics of the mask in SegDev::seg, behind whatever wrote it on the stream: sed_reset, seg_stats / seg_sum (three
-// launches), event `done` of the caller's timer behind them, the read-back.  Ends synchronised.
-extern "C++" {   // (a template, inside the extern "C" block of the entry points)
-template <int N>
-static int seg_mask_stats(VxContext* c, StageTimer<N>& timer, int done, SegStats* st) {
-  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, c->vol.seg, 0u);
-  launch_seg_stats(c);
-  VX_HIP(c, hipGetLastError());
-  if (int rc = timer.mark(c, done)) return rc;
-  VX_HIP(c, hipMemcpyAsync(st, c->vol.seg.st, sizeof *st, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  return VX_OK;
-}
-}
-
-int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment(c->members[0], sp, out));
-  VX_DEV(c);
-  VoxelBox box;
-  if (int rc = check_ready(c, "vx_segment", sp, "sp")) return rc;
-  if (int rc = check_seed(c, "vx_segment", sp->seed)) return rc;
-  if (int rc = check_band(c, "vx_segment", sp->lo, sp->hi)) return rc;
-  if (int rc = check_connectivity(c, "vx_segment", sp->connectivity)) return rc;
-  if (int rc = check_box(c, "vx_segment", sp->box_lo, sp->box_hi, &box)) return rc;
-  c->vol.seg_valid = false;
-  c->vol.seg_pred_valid = false;
-  c->vol.isl_valid = false;
-  if (int rc = ensure_segment(c)) return rc;
-  const SegDev& s = c->vol.seg;
-  const uint32_t* E = c->vol.dv.extent;
-  const SegSeed seed = seg_seed_of(s, sp->seed);
-  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
-  const uint64_t cap = sp->max_rounds ? (uint64_t)sp->max_rounds : std::min<uint64_t>(nvox, 0xfffffffeull);
-  VX_HIP(c, hipMemsetAsync(s.seg, 0, (size_t)s.nb * 64u, c->stream));
-  VX_HIP(c, hipMemsetAsync(s.stamp, 0, (size_t)s.nb * 4u, c->stream));
-  if (int rc = c->seg_timer.mark(c, 0)) return rc;
-  launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->seg_timer.mark(c, 1)) return rc;
-  hipLaunchKernelGGL(seg_seed, dim3(1), dim3(64), 0, c->stream, s, seed);
-  VX_HIP(c, hipGetLastError());
-  bool converged = false;
-  if (int rc = run_seg_flood(c, s, sp->connectivity, seed, cap, &converged, nullptr)) return rc;
-  if (int rc = c->seg_timer.mark(c, 2)) return rc;
-  launch_seg_stats(c);
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->seg_timer.mark(c, 3)) return rc;
-  SegStats st;
-  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  if (int rc = c->seg_timer.read(c)) return rc;
-  VxSegmentResult r = seg_result(st);
-  r.rounds = st.rounds;
-  r.converged = converged ? 1u : 0u;
-  r.brick_visits = st.visits;
-  c->seg_res = r;
-  c->vol.seg_valid = true;
-  c->vol.seg_pred_valid = true;
-  if (out) *out = r;
-  return VX_OK;
-}
-
-int vx_segment_read_mask(VxContext* c, uint8_t* bits, uint64_t nbytes) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_read_mask(c->members[0], bits, nbytes));
-  VX_DEV(c);
-  if (!c->vol.seg_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: no current segment (vx_segment first; an upload drops it)");
-  if (!bits) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: bits is NULL");
-  const uint32_t* E = c->vol.dv.extent;
-  size_t want = 0;
-  if (int rc = check_mask_bytes(c, "vx_segment_read_mask", nbytes, &want)) return rc;
-  if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
-  const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 8192u);
-  hipLaunchKernelGGL(seg_pack, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg, E[0], E[1], want, c->vol.seg_bytes);
-  VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipMemcpyAsync(bits, c->vol.seg_bytes, want, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  return VX_OK;
-}
-
-int vx_slice_segment_mask(VxContext* c, const VxSliceParams* sp, uint8_t* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_slice_segment_mask(c->members[0], sp, out));
-  VX_DEV(c);
-  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice_segment_mask: no volume uploaded");
-  if (!c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: no current segment (vx_segment first; an upload drops it)");
-  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: sp is NULL");
-  if (!out) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: out is NULL");
-  if (int rc = check_slice_size(c, "vx_slice_segment_mask", sp)) return rc;
-  if (int rc = check_slice_frame(c, "vx_slice_segment_mask", sp)) return rc;
-  const size_t px = (size_t)sp->size[0] * sp->size[1];
-  if (int rc = c->seg_ov.ensure(c, px)) return rc;   // (every earlier call has completed: each one synchronises)
-  const dim3 grid((sp->size[0] + 15u) / 16u, (sp->size[1] + 15u) / 16u);
-  hipLaunchKernelGGL(seg_slice_mask, grid, dim3(256), 0, c->stream, *sp, c->vol.seg, c->vol.dv.extent[0], c->vol.dv.extent[1],
-                     c->vol.dv.extent[2], c->seg_ov);
-  VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipMemcpyAsync(out, c->seg_ov, px, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  return VX_OK;
-}
-
-int vx_set_segment_view(VxContext* c, int view) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return refuse_group(c, "vx_set_segment_view", "the segment lives on member 0 only");
-  if (view < VX_SEGVIEW_OFF || view > VX_SEGVIEW_HIDE)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: view = %d is not VX_SEGVIEW_OFF, _ONLY or _HIDE", view);
-  if (view != VX_SEGVIEW_OFF && !c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: %s without a current segment (vx_segment first; an upload drops it)",
-            view == VX_SEGVIEW_ONLY ? "only" : "hide");
-  c->vol.seg_view = view;
-  return VX_OK;
-}
-
-int vx_get_segment_view(VxContext* c, int* view) {
-  if (!c || !view) return VX_ERR_INVALID;
-  *view = c->vol.seg_view;
-  return VX_OK;
-}
-
-int vx_segment_stats(VxContext* c, uint32_t* rounds, uint64_t* brick_visits, double* kernel_ms) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_stats(c->members[0], rounds, brick_visits, kernel_ms));
-  if (rounds) *rounds = c->seg_res.rounds;
-  if (brick_visits) *brick_visits = c->seg_res.brick_visits;
-  if (kernel_ms) std::copy_n(c->seg_timer.ms, 3, kernel_ms);
-  return VX_OK;
-}
-
-// ---- segment edits (vx_segment_edit, vx_segment_write_mask; kernels in vx_segedit.hpp) ---------------------------------------
-// the scratch of the edits: two masks of nb * 8 words (1 bit per voxel each) and the fill's nb "any background" flags
-static int ensure_segedit(VxContext* c) {
-  if (c->vol.sed_alloc) return VX_OK;
-  const size_t nb = c->vol.seg.nb;
-  return carve(c, c->vol.sed_alloc, [&](Carve& k) {
-    c->vol.sed_mask[0] = k.take<uint64_t>(nb * 8u);
-    c->vol.sed_mask[1] = k.take<uint64_t>(nb * 8u);
-    c->vol.sed_any = k.take<uint32_t>(nb);
-  });
-}
-
-// The tail of every call that rewrites the mask outright (behind event 0 of sed_timer and the call's launches): the statistics
-// of the new mask, the two times vx_segment_edit_stats reports, the result.  The flood's rounds and visits are kept when `fill`;
-// `pred`: SegDev::pred now holds this mask's predicate.  Ends synchronised.
-static int finish_mask_edit(VxContext* c, bool fill, bool pred, VxSegmentResult* out) {
-  SegStats st;
-  if (int rc = c->sed_timer.mark(c, 1)) return rc;
-  if (int rc = seg_mask_stats(c, c->sed_timer, 2, &st)) return rc;
-  if (int rc = c->sed_timer.read(c)) return rc;
-  VxSegmentResult r = seg_result(st);
-  r.rounds = fill ? st.rounds : 0u;
-  r.converged = 1u;
-  r.brick_visits = fill ? st.visits : 0u;
-  c->vol.seg_valid = true;
-  if (pred) c->vol.seg_pred_valid = true;
-  if (out) *out = r;
-  return VX_OK;
-}
-
-// `steps` steps of one kind from the mask at *cur.  A step never writes the mask it reads: the chain alternates between the two
-// scratch masks, and the last step of the edit (`last`) writes SegDev::seg itself unless it would read it, so the masked render
-// kernels, seg_pack and the overlay keep the one pointer they read at launch time.
-static void launch_sed_steps(VxContext* c, int conn, bool invert, bool band, uint32_t steps, bool last, uint64_t** cur) {
-  const SegDev& s = c->vol.seg;
-  const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
-  const uint64_t inv = invert ? ~0ull : 0ull;
-  for (uint32_t i = 0; i < steps; ++i) {
-    uint64_t* src = *cur;
-    uint64_t* dst = (last && i + 1u == steps && src != s.seg) ? s.seg : (src == c->vol.sed_mask[0] ? c->vol.sed_mask[1] : c->vol.sed_mask[0]);
-    with_conn(conn, [&](auto conn_c) {
-      with_bool(band, [&](auto band_c) {
-        hipLaunchKernelGGL((sed_step<decltype(conn_c)::value, decltype(band_c)::value>), dim3(blocks), dim3(256), 0, c->stream, src,
-                           dst, s.pred, inv, s.bc[0], s.bc[1], s.bc[2]);
-      });
-    });
-    *cur = dst;
-    ++c->sed_launches;
-  }
-}
-
-int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_edit(c->members[0], ep, out));
-  VX_DEV(c);
-  if (int rc = check_ready(c, "vx_segment_edit", ep, "params")) return rc;
-  if (ep->op < VX_SEGEDIT_DILATE || ep->op > VX_SEGEDIT_FILL_HOLES)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: op = %d is not a VxSegmentEditOp (0 .. 4)", ep->op);
-  if (int rc = check_connectivity(c, "vx_segment_edit", ep->connectivity)) return rc;
-  const bool fill = ep->op == VX_SEGEDIT_FILL_HOLES;
-  if (fill ? ep->steps > 1u : (ep->steps < 1u || ep->steps > VX_SEGEDIT_MAX_STEPS))
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: steps = %u outside %s", ep->steps, fill ? "0 .. 1 (fill holes)" : "1 .. 1024");
-  if (ep->band != 0 && ep->band != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = %d is not 0 or 1", ep->band);
-  if (ep->band && ep->op != VX_SEGEDIT_DILATE)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 is for VX_SEGEDIT_DILATE only (op = %d)", ep->op);
-  if (!c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: no current segment (vx_segment or vx_segment_write_mask first; an upload drops it)");
-  if (ep->band && !c->vol.seg_pred_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
-  if (int rc = ensure_segedit(c)) return rc;
-  c->vol.isl_valid = false;
-  const SegDev& s = c->vol.seg;
-  const int conn = ep->connectivity;
-  const uint32_t n = ep->steps;
-  c->sed_launches = 0;
-  if (int rc = c->sed_timer.mark(c, 0)) return rc;
-  uint64_t* cur = s.seg;
-  switch (ep->op) {
-    case VX_SEGEDIT_DILATE: launch_sed_steps(c, conn, false, ep->band != 0, n, true, &cur); break;
-    case VX_SEGEDIT_ERODE: launch_sed_steps(c, conn, true, false, n, true, &cur); break;
-    case VX_SEGEDIT_OPEN:
-      launch_sed_steps(c, conn, true, false, n, false, &cur);
-      launch_sed_steps(c, conn, false, false, n, true, &cur);
-      break;
-    case VX_SEGEDIT_CLOSE:
-      launch_sed_steps(c, conn, false, false, n, false, &cur);
-      launch_sed_steps(c, conn, true, false, n, true, &cur);
-      break;
-    default: {
-      // the background flood on a second view: predicate ~M and the reached set in the scratch masks, the bookkeeping shared
-      // with vx_segment (its predicate WORDS stay: band dilation after a fill is legal)
-      SegDev f = s;
-      f.pred = c->vol.sed_mask[0];
-      f.seg = c->vol.sed_mask[1];
-      f.any = c->vol.sed_any;
-      const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
-      hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 1u);
-      hipLaunchKernelGGL(sed_fill_seed, dim3(blocks), dim3(256), 0, c->stream, s.seg, f);
-      VX_HIP(c, hipGetLastError());
-      bool converged = false;
-      uint64_t launched = 0;
-      const uint64_t nvox = (uint64_t)c->vol.dv.extent[0] * c->vol.dv.extent[1] * c->vol.dv.extent[2];
-      if (int rc = run_seg_flood(c, f, conn, SegSeed{0u, 0u, 0ull}, std::min<uint64_t>(nvox, 0xfffffffeull), &converged, &launched))
-        return rc;
-      const size_t words = (size_t)s.nb * 8u;
-      hipLaunchKernelGGL(sed_fill_finish, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream,
-                         f.seg, s.seg, words);
-      c->sed_launches = (uint32_t)std::min<uint64_t>(launched + 3u, 0xffffffffull);
-      cur = s.seg;
-    }
-  }
-  VX_HIP(c, hipGetLastError());
-  // a single step read SegDev::seg and so wrote a scratch mask: copy it home on the stream
-  if (cur != s.seg) VX_HIP(c, hipMemcpyAsync(s.seg, cur, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
-  return finish_mask_edit(c, fill, false, out);
-}
-
-int vx_segment_write_mask(VxContext* c, const uint8_t* bits, uint64_t nbytes, VxSegmentResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_write_mask(c->members[0], bits, nbytes, out));
-  VX_DEV(c);
-  if (int rc = check_ready(c, "vx_segment_write_mask", bits, "bits")) return rc;
-  size_t want = 0;
-  if (int rc = check_mask_bytes(c, "vx_segment_write_mask", nbytes, &want)) return rc;
-  if (int rc = ensure_segment(c)) return rc;
-  if (int rc = ensure_segedit(c)) return rc;
-  if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
-  c->vol.isl_valid = false;
-  const SegDev& s = c->vol.seg;
-  VX_HIP(c, hipMemcpyAsync(c->vol.seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
-  if (int rc = c->sed_timer.mark(c, 0)) return rc;
-  const size_t words = (size_t)s.nb * 8u;
-  hipLaunchKernelGGL(sed_unpack, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream, s,
-                     c->vol.dv.extent[1], c->vol.seg_bytes);
-  VX_HIP(c, hipGetLastError());
-  c->sed_launches = 1;
-  return finish_mask_edit(c, false, false, out);
-}
-
-int vx_segment_edit_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_edit_stats(c->members[0], launches, kernel_ms));
-  if (launches) *launches = c->sed_launches;
-  if (kernel_ms) std::copy_n(c->sed_timer.ms, 2, kernel_ms);
-  return VX_OK;
-}
-
-// ---- islands (vx_segment_threshold, vx_segment_islands, vx_islands_read*; kernels in vx_islands.hpp) ---------------------------
-// (the mask is rewritten outright: timed and counted like vx_segment_write_mask, reported by vx_segment_edit_stats)
-int vx_segment_threshold(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_threshold(c->members[0], sp, out));
-  VX_DEV(c);
-  VoxelBox box;
-  if (int rc = check_ready(c, "vx_segment_threshold", sp, "sp")) return rc;
-  if (int rc = check_band(c, "vx_segment_threshold", sp->lo, sp->hi)) return rc;
-  if (int rc = check_box(c, "vx_segment_threshold", sp->box_lo, sp->box_hi, &box)) return rc;
-  if (int rc = ensure_segment(c)) return rc;
-  c->vol.seg_valid = false;
-  c->vol.seg_pred_valid = false;
-  c->vol.isl_valid = false;
-  const SegDev& s = c->vol.seg;
-  if (int rc = c->sed_timer.mark(c, 0)) return rc;
-  launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
-  VX_HIP(c, hipGetLastError());
-  // the mask = the predicate words.  SegDev::seg keeps its address: the masked render kernels read it at launch time
-  VX_HIP(c, hipMemcpyAsync(s.seg, s.pred, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
-  c->sed_launches = 1;
-  return finish_mask_edit(c, false, true, out);
-}
-
-static int ensure_islands(VxContext* c) {
-  if (c->vol.isl_alloc) return VX_OK;
-  const size_t nb = c->vol.seg.nb;
-  IslDev& d = c->vol.isl;
-  return carve(c, c->vol.isl_alloc, [&](Carve& k) {
-    d.lab = k.take<uint32_t>(nb * 512u);
-    d.nroots = k.take<uint32_t>(nb);
-    d.off = k.take<uint32_t>(nb);
-    d.hdr = k.take<IslHdr>();
-  });
-}
-
-// room for n rows and their labels, 1024 at least (every earlier call has completed: each one synchronises)
-static int ensure_island_rows(VxContext* c, uint32_t n) {
-  IslDev& d = c->vol.isl;
-  n = std::max(n, 1u);
-  if (n <= d.cap) return VX_OK;
-  d.cap = 0;
-  const size_t cap = std::max<size_t>(n, 1024u);
-  const int rc = carve(c, c->vol.isl_rows_alloc, [&](Carve& k) {
-    d.rows = k.take<IslRow>(cap);
-    d.newlab = k.take<uint32_t>(cap);
-  });
-  if (rc) return rc;
-  d.cap = (uint32_t)cap;
-  return VX_OK;
-}
-
-int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_segment_islands(c->members[0], ip, out));
-  VX_DEV(c);
-  if (int rc = check_ready(c, "vx_segment_islands", ip, "params")) return rc;
-  if (ip->op < VX_ISLANDS_LABEL || ip->op > VX_ISLANDS_KEEP_AT)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: op = %d is not a VxIslandsOp (0 .. 3)", ip->op);
-  if (int rc = check_connectivity(c, "vx_segment_islands", ip->connectivity)) return rc;
-  if (ip->op == VX_ISLANDS_KEEP_LARGEST && ip->keep == 0)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: keep = 0 (KEEP_LARGEST keeps at least one island)");
-  if (ip->op == VX_ISLANDS_REMOVE_SMALL && ip->min_voxels == 0)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: min_voxels = 0 (REMOVE_SMALL needs a size of at least 1)");
-  const uint32_t* E = c->vol.dv.extent;
-  if (ip->op == VX_ISLANDS_KEEP_AT)
-    if (int rc = check_seed(c, "vx_segment_islands", ip->seed)) return rc;
-  if (!c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: no current segment (vx_segment, vx_segment_threshold or vx_segment_write_mask "
-                               "first; an upload drops it)");
-  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
-  if (nvox >= 0x80000000ull)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: %llu voxels are beyond the 31-bit voxel index of the labels",
-            (unsigned long long)nvox);
-  if (int rc = ensure_islands(c)) return rc;
-  if (int rc = ensure_island_rows(c, 1u)) return rc;
-  c->vol.isl_valid = false;
-  const SegDev& s = c->vol.seg;
-  const bool modify = ip->op != VX_ISLANDS_LABEL;
-  const dim3 grid(std::min<uint32_t>((s.nb + 3u) / 4u, 16384u)), block(256);
-  uint32_t launches = 0;
-  VX_HIP(c, hipMemsetAsync(c->vol.isl.hdr, 0, sizeof(IslHdr), c->stream));
-  StageTimer<7>& timer = c->isl_timer;
-  if (int rc = timer.mark(c, 0)) return rc;
-  with_conn(ip->connectivity, [&](auto k) { hipLaunchKernelGGL(isl_local<decltype(k)::value>, grid, block, 0, c->stream, s, c->vol.isl); });
-  if (int rc = timer.mark(c, 1)) return rc;
-  with_conn(ip->connectivity, [&](auto k) { hipLaunchKernelGGL(isl_merge<decltype(k)::value>, grid, block, 0, c->stream, s, c->vol.isl); });
-  if (int rc = timer.mark(c, 2)) return rc;
-  hipLaunchKernelGGL(isl_flatten, grid, block, 0, c->stream, s, c->vol.isl);
-  hipLaunchKernelGGL(isl_scan, dim3(1), dim3(1024), 0, c->stream, s, c->vol.isl);
-  VX_HIP(c, hipGetLastError());
-  launches += 4;
-  if (int rc = timer.mark(c, 3)) return rc;
-  // the one read-back that sizes the table: the number of islands
-  IslHdr hdr{};
-  VX_HIP(c, hipMemcpyAsync(&hdr, c->vol.isl.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  const uint32_t R = hdr.roots;
-  if (int rc = ensure_island_rows(c, R)) return rc;
-  const IslDev& d = c->vol.isl;
-  const SegSeed seed = ip->op == VX_ISLANDS_KEEP_AT ? seg_seed_of(s, ip->seed) : SegSeed{0u, 0u, 1ull};
-  hipLaunchKernelGGL(isl_rootid, grid, block, 0, c->stream, s, d);
-  hipLaunchKernelGGL(isl_table, grid, block, 0, c->stream, s, d);
-  hipLaunchKernelGGL(isl_seed_row, dim3(1), dim3(64), 0, c->stream, s, d, seed);
-  VX_HIP(c, hipGetLastError());
-  launches += 3;
-  if (int rc = timer.mark(c, 4)) return rc;
-  VX_HIP(c, hipEventSynchronize(timer.ev[4]));
-  // the host's share: the rows come back once, are ranked by (count descending, anchor ascending), and every row's label
-  // (0: dropped by the op) goes back up.  O(islands), not O(voxels).
-  const auto t0 = std::chrono::steady_clock::now();
-  std::vector<IslRow> rows(R);
-  VX_HIP(c, hipMemcpyAsync(&hdr, d.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
-  if (R) VX_HIP(c, hipMemcpyAsync(rows.data(), d.rows, (size_t)R * sizeof(IslRow), hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  std::vector<uint32_t> order(R);
-  for (uint32_t i = 0; i < R; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    return rows[a].count != rows[b].count ? rows[a].count > rows[b].count : rows[a].anchor < rows[b].anchor;
-  });
-  std::vector<uint32_t> newlab(std::max(R, 1u), 0u);
-  std::vector<VxIsland> table;
-  table.reserve(R);
-  for (uint32_t k = 0; k < R; ++k) {
-    const uint32_t i = order[k];
-    const IslRow& r = rows[i];
-    bool keep = true;
-    switch (ip->op) {
-      case VX_ISLANDS_KEEP_LARGEST: keep = (uint64_t)k < ip->keep; break;
-      case VX_ISLANDS_REMOVE_SMALL: keep = r.count >= ip->min_voxels; break;
-      case VX_ISLANDS_KEEP_AT: keep = i == hdr.seed_row; break;
-      default: break;
-    }
-    if (!keep) continue;
-    VxIsland v{};
-    v.count = r.count;
-    v.anchor[0] = r.anchor % E[0];
-    v.anchor[1] = (r.anchor / E[0]) % E[1];
-    v.anchor[2] = r.anchor / (E[0] * E[1]);
-    for (int a = 0; a < 3; ++a) {
-      v.bbox_lo[a] = r.lo[a];
-      v.bbox_hi[a] = r.hi[a];
-    }
-    table.push_back(v);
-    table.back().label = (uint32_t)table.size();
-    newlab[i] = (uint32_t)table.size();
-  }
-  VX_HIP(c, hipMemcpyAsync(d.newlab, newlab.data(), newlab.size() * 4u, hipMemcpyHostToDevice, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));   // (newlab is pageable host memory of this frame)
-  const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (int rc = timer.mark(c, 5)) return rc;
-  if (modify) {
-    hipLaunchKernelGGL(isl_apply, grid, block, 0, c->stream, s, d);
-    ++launches;
-  }
-  if (int rc = timer.mark(c, 6)) return rc;
-  SegStats st;
-  if (int rc = seg_mask_stats(c, timer, 7, &st)) return rc;
-  launches += 3;
-  if (int rc = timer.read(c)) return rc;
-  timer.ms[4] = host_ms;             // stage 4 is the host's share: wall time, not the events around it
-  if (!modify) timer.ms[5] = 0.0;    // (two events back to back still measure a few microseconds)
-  c->isl_launches = launches;
-  VxIslandsResult r{};
-  r.islands = R;
-  r.kept = table.size();
-  r.largest = R ? rows[order[0]].count : 0u;
-  r.seg = seg_result(st);
-  r.seg.converged = 1u;
-  c->vol.isl_table.swap(table);
-  c->vol.isl_valid = true;
-  if (out) *out = r;
-  return VX_OK;
-}
-
-int vx_islands_read(VxContext* c, uint64_t first, uint64_t n, VxIsland* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_islands_read(c->members[0], first, n, out));
-  if (!c->vol.isl_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: no current table (vx_segment_islands first; an upload and every call that "
-                               "changes the segment drop it)");
-  const uint64_t have = c->vol.isl_table.size();
-  if (first > have || n > have - first)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: rows %llu .. %llu are beyond the %llu islands of the table",
-            (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)have);
-  if (n && !out) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: out is NULL");
-  if (n) memcpy(out, c->vol.isl_table.data() + first, (size_t)n * sizeof(VxIsland));
-  return VX_OK;
-}
-
-int vx_islands_read_labels(VxContext* c, uint32_t* labels, uint64_t nvoxels) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_islands_read_labels(c->members[0], labels, nvoxels));
-  VX_DEV(c);
-  if (!c->vol.isl_valid || !c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: no current table (vx_segment_islands first; an upload and every call "
-                               "that changes the segment drop it)");
-  if (!labels) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: labels is NULL");
-  const uint32_t* E = c->vol.dv.extent;
-  const size_t want = (size_t)E[0] * E[1] * E[2];
-  if (nvoxels != want)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: nvoxels = %llu, the volume has %u x %u x %u = %zu voxels",
-            (unsigned long long)nvoxels, E[0], E[1], E[2], want);
-  if (int rc = c->vol.isl_dense.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
-  const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 16384u);
-  hipLaunchKernelGGL(isl_labels_out, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg, c->vol.isl, E[0], E[1], want, c->vol.isl_dense);
-  VX_HIP(c, hipGetLastError());
-  VX_HIP(c, hipMemcpyAsync(labels, c->vol.isl_dense, want * 4u, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  return VX_OK;
-}
-
-int vx_islands_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_islands_stats(c->members[0], launches, kernel_ms));
-  if (launches) *launches = c->isl_launches;
-  if (kernel_ms) std::copy_n(c->isl_timer.ms, 7, kernel_ms);
-  return VX_OK;
-}
-
-// ---- meshes (vx_mesh_extract, vx_mesh_read; kernels in vx_mesh.hpp) -----------------------------------------------------------
-// Five launches whatever the mesh: the inside words, the active cells with their counts, the two launches that finish the
-// exclusive scan, the emission.  The totals are read back once, between the scan and the emission, to size the outputs.
-static int ensure_mesh(VxContext* c) {
-  if (c->vol.mesh_alloc) return VX_OK;
-  MeshDev& m = c->vol.mesh;
-  for (int a = 0; a < 3; ++a) {
-    m.bc[a] = c->vol.dv.bc[a];
-    m.cb[a] = c->vol.dv.bc[a] + 1u;
-  }
-  const size_t nb = (size_t)m.bc[0] * m.bc[1] * m.bc[2], ncb = (size_t)m.cb[0] * m.cb[1] * m.cb[2];
-  if (ncb > 0xffffff00ull) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: %zu cell blocks are beyond the 32-bit block index", ncb);
-  const size_t np = (ncb + 255u) / 256u;
-  const int rc = carve(c, c->vol.mesh_alloc, [&](Carve& k) {
-    m.inside = k.take<uint64_t>(nb * 8u);
-    m.act = k.take<uint64_t>(ncb * 8u);
-    m.vq = k.take<uint2>(ncb);
-    m.off = k.take<uint2>(ncb);
-    m.part = k.take<uint2>(np);
-    m.poff = k.take<uint2>(np);
-    m.st = k.take<MeshStats>();
-  });
-  if (rc) return rc;
-  m.nb = (uint32_t)nb;
-  m.ncb = (uint32_t)ncb;
-  m.np = (uint32_t)np;
-  return VX_OK;
-}
-
-int vx_mesh_extract(VxContext* c, const VxMeshParams* mp, VxMeshResult* out) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_mesh_extract(c->members[0], mp, out));
-  VX_DEV(c);
-  if (int rc = check_ready(c, "vx_mesh_extract", mp, "params")) return rc;
-  if (mp->source != VX_MESH_DENSITY && mp->source != VX_MESH_SEGMENT)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: source = %d is not VX_MESH_DENSITY or VX_MESH_SEGMENT", mp->source);
-  const bool segment = mp->source == VX_MESH_SEGMENT;
-  if (!segment && !(std::isfinite(mp->iso) && mp->iso > 0.0f))
-    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: iso = %g is not finite and > 0", (double)mp->iso);
-  VoxelBox vb;
-  if (int rc = check_box(c, "vx_mesh_extract", mp->box_lo, mp->box_hi, &vb)) return rc;
-  const MeshBox box{{vb.lo[0], vb.lo[1], vb.lo[2]}, {vb.hi[0], vb.hi[1], vb.hi[2]}};
-  if (segment && !c->vol.seg_valid)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: source = VX_MESH_SEGMENT with no current segment (vx_segment or vx_segment_write_mask "
-            "first; an upload drops it)");
-  if (int rc = ensure_mesh(c)) return rc;
-  c->vol.mesh_valid = false;
-  c->vol.mesh_nv = c->vol.mesh_nt = 0;
-  const MeshDev& m = c->vol.mesh;
-  const VxParams& p = c->params;
-  const float iso = segment ? 0.5f : mp->iso;
-  if (int rc = c->mesh_timer.mark(c, 0)) return rc;
-  if (segment) {
-    const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)m.nb * 8u + 255u) / 256u, 8192u);
-    hipLaunchKernelGGL(mesh_inside_segment, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg.seg, box, m);
-  } else {
-    const uint32_t blocks = std::min<uint32_t>((m.nb + 3u) / 4u, 4096u);
-    with_layout(slice_layout(c), [&](auto lay) {
-      constexpr int LAY = decltype(lay)::value;
-      hipLaunchKernelGGL((mesh_inside_density<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale,
-                         p.volume_inv_maj, iso, box, m);
-    });
-  }
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->mesh_timer.mark(c, 1)) return rc;
-  hipLaunchKernelGGL(mesh_active, dim3(m.np), dim3(256), 0, c->stream, m);
-  hipLaunchKernelGGL(mesh_scan_partials, dim3(1), dim3(1024), 0, c->stream, m);
-  hipLaunchKernelGGL(mesh_offsets, dim3(m.np), dim3(256), 0, c->stream, m);
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->mesh_timer.mark(c, 2)) return rc;
-  MeshStats st;
-  VX_HIP(c, hipMemcpyAsync(&st, m.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  const uint64_t nv = st.verts, nt = 2u * (uint64_t)st.quads;
-  const uint64_t maxv = mp->max_vertices ? mp->max_vertices : 0xfffffffeull, maxt = mp->max_triangles ? mp->max_triangles : 0xfffffffeull;
-  if (nv > maxv || nt > maxt)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_extract: the mesh has %llu vertices and %llu triangles, more than max_vertices = %llu or "
-            "max_triangles = %llu", (unsigned long long)nv, (unsigned long long)nt, (unsigned long long)maxv, (unsigned long long)maxt);
-  // three values per vertex and per triangle (every earlier call has completed: each one synchronises)
-  if (int rc = c->vol.mesh_verts.ensure(c, (size_t)nv * 3u)) return rc;
-  if (int rc = c->vol.mesh_cells.ensure(c, (size_t)nv * 3u)) return rc;
-  if (int rc = c->vol.mesh_tris.ensure(c, (size_t)nt * 3u)) return rc;
-  {
-    const uint32_t blocks = std::min<uint32_t>((m.ncb + 3u) / 4u, 4096u);
-    if (segment)   // no voxel is read: one instance serves every layout
-      hipLaunchKernelGGL((mesh_emit<LAYOUT_REF, true>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
-                         iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->vol.mesh_verts, c->vol.mesh_cells, c->vol.mesh_tris);
-    else
-      with_layout(slice_layout(c), [&](auto lay) {
-        constexpr int LAY = decltype(lay)::value;
-        hipLaunchKernelGGL((mesh_emit<LAY, false>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
-                           iso, box, m, (unsigned long long)nv, (unsigned long long)st.quads, c->vol.mesh_verts, c->vol.mesh_cells, c->vol.mesh_tris);
-      });
-  }
-  VX_HIP(c, hipGetLastError());
-  if (int rc = c->mesh_timer.mark(c, 3)) return rc;
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  if (int rc = c->mesh_timer.read(c)) return rc;
-  c->mesh_launches = 5u;
-  c->vol.mesh_nv = nv;
-  c->vol.mesh_nt = nt;
-  c->vol.mesh_valid = true;
-  if (out) {
-    VxMeshResult r{};
-    r.vertices = nv;
-    r.triangles = nt;
-    r.active_blocks = st.active_blocks;
-    r.blocks = m.ncb;
-    if (nv)
-      for (int a = 0; a < 3; ++a) {
-        r.bbox_lo[a] = st.lo[a] - 1u;   // the statistics hold cell + 1; cell -1 wraps to its two's complement
-        r.bbox_hi[a] = st.hi[a] - 1u;
-      }
-    *out = r;
-  }
-  return VX_OK;
-}
-
-int vx_mesh_read(VxContext* c, float* verts_xyz, int32_t* cells_xyz, uint32_t* tris) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_mesh_read(c->members[0], verts_xyz, cells_xyz, tris));
-  VX_DEV(c);
-  if (!c->vol.mesh_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_mesh_read: no current mesh (vx_mesh_extract first; an upload drops it)");
-  if (verts_xyz && c->vol.mesh_nv)
-    VX_HIP(c, hipMemcpyAsync(verts_xyz, c->vol.mesh_verts, (size_t)c->vol.mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
-  if (cells_xyz && c->vol.mesh_nv)
-    VX_HIP(c, hipMemcpyAsync(cells_xyz, c->vol.mesh_cells, (size_t)c->vol.mesh_nv * 12u, hipMemcpyDeviceToHost, c->stream));
-  if (tris && c->vol.mesh_nt) VX_HIP(c, hipMemcpyAsync(tris, c->vol.mesh_tris, (size_t)c->vol.mesh_nt * 12u, hipMemcpyDeviceToHost, c->stream));
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  return VX_OK;
-}
-
-int vx_mesh_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_mesh_stats(c->members[0], launches, kernel_ms));
-  if (launches) *launches = c->mesh_launches;
-  if (kernel_ms) std::copy_n(c->mesh_timer.ms, 3, kernel_ms);
   return VX_OK;
 }
 

@@ -1,0 +1,635 @@
+// vx_api_segment.hip -- the segment unit of the host layer (units: DESIGN.md section 4.1): the segment chain -- seeded region
+// growing, the mask's read-back, slice overlay and view, the edits, the threshold and the islands.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "vx_segment.hpp"
+#include "vx_segedit.hpp"
+#include "vx_islands.hpp"
+#include "vx_context.hpp"
+
+using namespace vx;
+
+namespace {
+
+// ---- segmentation (vx_segment): seg_predicate, the flood rounds, seg_stats / seg_sum (vx_segment.hpp) ----------------------
+// rounds between host read-backs of the next worklist's length: 1, 2, 4, ... up to Switches::seg_check_max (64; NOTEBOOK
+// "Segmentation" compares caps).  A queued round that finds its worklist empty exits at once (one launch boundary, a few
+// microseconds); a read-back is a host round trip.
+
+// the device buffers of the brick grid, carved from one allocation (sizes in DESIGN.md / INTEGRATION.md's memory bill)
+static int ensure_segment(VxContext* c) {
+  if (c->vol.seg_alloc) return VX_OK;
+  const uint32_t nb = c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2];
+  SegDev& s = c->vol.seg;
+  const int rc = carve(c, c->vol.seg_alloc, [&](Carve& k) {
+    s.pred = k.take<uint64_t>((size_t)nb * 8u);
+    s.seg = k.take<uint64_t>((size_t)nb * 8u);
+    // `partial` stays immediately behind `seg`: the masked LDS-window staging reads the dword right behind the mask for the
+    // zero chunk behind the last brick -- the first of `partial`, inside this allocation -- and drops its bits
+    // (vx_dvr_lds_march.inc)
+    s.partial = k.take<double>(nb);
+    s.st = k.take<SegStats>();
+    s.any = k.take<uint32_t>(nb);
+    s.stamp = k.take<uint32_t>(nb);
+    s.list[0] = k.take<uint32_t>(nb);
+    s.list[1] = k.take<uint32_t>(nb);
+    s.cnt = k.take<uint32_t>(4);
+  });
+  if (rc) return rc;
+  for (int a = 0; a < 3; ++a) s.bc[a] = c->vol.dv.bc[a];
+  s.nb = nb;
+  return VX_OK;
+}
+
+static void launch_seg_predicate(VxContext* c, const SegPredParams& pp) {
+  const VxParams& p = c->params;
+  const uint32_t blocks = std::min<uint32_t>((c->vol.seg.nb + 3u) / 4u, 4096u);
+  with_layout(slice_layout(c), [&](auto lay) {
+    constexpr int LAY = decltype(lay)::value;
+    hipLaunchKernelGGL((seg_predicate<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
+                       pp, c->vol.seg);
+  });
+}
+
+static SegPredParams seg_pred_params(float lo, float hi, const VoxelBox& b) {
+  return SegPredParams{lo, hi, {b.lo[0], b.lo[1], b.lo[2]}, {b.hi[0], b.hi[1], b.hi[2]}};
+}
+
+// the brick, the z slice and the bit of a voxel
+static SegSeed seg_seed_of(const SegDev& s, const uint32_t v[3]) {
+  return SegSeed{((v[2] >> 3) * s.bc[1] + (v[1] >> 3)) * s.bc[0] + (v[0] >> 3), v[2] & 7u, 1ull << (((v[1] & 7u) << 3) | (v[0] & 7u))};
+}
+
+static void launch_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint32_t round) {
+  const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 1024u);
+  with_conn(conn, [&](auto k) {
+    hipLaunchKernelGGL((seg_flood<decltype(k)::value>), dim3(blocks), dim3(256), 0, c->stream, s, seed, round);
+  });
+}
+
+// the rounds of a flood on the view s (vx_segment: the segment; vx_segment_edit: the background of fill holes), from a round-0
+// worklist that is already on the device: queued in batches of 1, 2, 4, ... SEG_CHECK_MAX, the next worklist's length read back
+// after each batch.  Ends synchronised; *launched counts the flood launches.
+static int run_seg_flood(VxContext* c, const SegDev& s, int conn, const SegSeed& seed, uint64_t cap, bool* converged,
+                         uint64_t* launched_out) {
+  uint64_t launched = 0;
+  uint32_t batch = 1, next = 1;
+  *converged = false;
+  while (true) {
+    const uint64_t k = std::min<uint64_t>(batch, cap - launched);
+    for (uint64_t i = 0; i < k; ++i) launch_seg_flood(c, s, conn, seed, (uint32_t)(launched + i));
+    VX_HIP(c, hipGetLastError());
+    launched += k;
+    VX_HIP(c, hipMemcpyAsync(&next, s.cnt + launched % 3u, sizeof next, hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipStreamSynchronize(c->stream));
+    if (next == 0u) {
+      *converged = true;
+      break;
+    }
+    if (launched >= cap) break;
+    batch = std::min(batch * 2u, c->sw.seg_check_max);
+  }
+  if (launched_out) *launched_out = launched;
+  return VX_OK;
+}
+
+static void launch_seg_stats(VxContext* c) {
+  const VxParams& p = c->params;
+  const uint32_t blocks = std::min<uint32_t>((c->vol.seg.nb + 3u) / 4u, 4096u);
+  with_layout(slice_layout(c), [&](auto lay) {
+    constexpr int LAY = decltype(lay)::value;
+    hipLaunchKernelGGL((seg_stats<LAY>), dim3(blocks), dim3(256), 0, c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj,
+                       c->vol.seg);
+  });
+  hipLaunchKernelGGL(seg_sum, dim3(1), dim3(1024), 0, c->stream, c->vol.seg);
+}
+
+static float seg_key_float(uint32_t k) {
+  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  float f;
+  memcpy(&f, &u, sizeof f);
+  return f;
+}
+
+// the count, bounding box and density statistics of a result; rounds, brick_visits and converged are the caller's
+static VxSegmentResult seg_result(const SegStats& st) {
+  VxSegmentResult r{};
+  r.count = st.count;
+  if (st.count) {
+    for (int a = 0; a < 3; ++a) {
+      r.bbox_lo[a] = st.lo[a];
+      r.bbox_hi[a] = st.hi[a];
+    }
+    r.d_min = seg_key_float(st.dmin);
+    r.d_max = seg_key_float(st.dmax);
+    r.d_sum = st.sum;
+  }
+  return r;
+}
+
+// The statistics of the mask in SegDev::seg, behind whatever wrote it on the stream: sed_reset, seg_stats / seg_sum (three
+// launches), event `done` of the caller's timer behind them, the read-back.  Ends synchronised.
+template <int N>
+static int seg_mask_stats(VxContext* c, StageTimer<N>& timer, int done, SegStats* st) {
+  hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, c->vol.seg, 0u);
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  if (int rc = timer.mark(c, done)) return rc;
+  VX_HIP(c, hipMemcpyAsync(st, c->vol.seg.st, sizeof *st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+// ---- segment edits (vx_segment_edit, vx_segment_write_mask; kernels in vx_segedit.hpp) ---------------------------------------
+// the scratch of the edits: two masks of nb * 8 words (1 bit per voxel each) and the fill's nb "any background" flags
+static int ensure_segedit(VxContext* c) {
+  if (c->vol.sed_alloc) return VX_OK;
+  const size_t nb = c->vol.seg.nb;
+  return carve(c, c->vol.sed_alloc, [&](Carve& k) {
+    c->vol.sed_mask[0] = k.take<uint64_t>(nb * 8u);
+    c->vol.sed_mask[1] = k.take<uint64_t>(nb * 8u);
+    c->vol.sed_any = k.take<uint32_t>(nb);
+  });
+}
+
+// The tail of every call that rewrites the mask outright (behind event 0 of sed_timer and the call's launches): the statistics
+// of the new mask, the two times vx_segment_edit_stats reports, the result.  The flood's rounds and visits are kept when `fill`;
+// `pred`: SegDev::pred now holds this mask's predicate.  Ends synchronised.
+static int finish_mask_edit(VxContext* c, bool fill, bool pred, VxSegmentResult* out) {
+  SegStats st;
+  if (int rc = c->sed_timer.mark(c, 1)) return rc;
+  if (int rc = seg_mask_stats(c, c->sed_timer, 2, &st)) return rc;
+  if (int rc = c->sed_timer.read(c)) return rc;
+  VxSegmentResult r = seg_result(st);
+  r.rounds = fill ? st.rounds : 0u;
+  r.converged = 1u;
+  r.brick_visits = fill ? st.visits : 0u;
+  c->vol.seg_valid = true;
+  if (pred) c->vol.seg_pred_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+// `steps` steps of one kind from the mask at *cur.  A step never writes the mask it reads: the chain alternates between the two
+// scratch masks, and the last step of the edit (`last`) writes SegDev::seg itself unless it would read it, so the masked render
+// kernels, seg_pack and the overlay keep the one pointer they read at launch time.
+static void launch_sed_steps(VxContext* c, int conn, bool invert, bool band, uint32_t steps, bool last, uint64_t** cur) {
+  const SegDev& s = c->vol.seg;
+  const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
+  const uint64_t inv = invert ? ~0ull : 0ull;
+  for (uint32_t i = 0; i < steps; ++i) {
+    uint64_t* src = *cur;
+    uint64_t* dst = (last && i + 1u == steps && src != s.seg) ? s.seg : (src == c->vol.sed_mask[0] ? c->vol.sed_mask[1] : c->vol.sed_mask[0]);
+    with_conn(conn, [&](auto conn_c) {
+      with_bool(band, [&](auto band_c) {
+        hipLaunchKernelGGL((sed_step<decltype(conn_c)::value, decltype(band_c)::value>), dim3(blocks), dim3(256), 0, c->stream, src,
+                           dst, s.pred, inv, s.bc[0], s.bc[1], s.bc[2]);
+      });
+    });
+    *cur = dst;
+    ++c->sed_launches;
+  }
+}
+
+static int ensure_islands(VxContext* c) {
+  if (c->vol.isl_alloc) return VX_OK;
+  const size_t nb = c->vol.seg.nb;
+  IslDev& d = c->vol.isl;
+  return carve(c, c->vol.isl_alloc, [&](Carve& k) {
+    d.lab = k.take<uint32_t>(nb * 512u);
+    d.nroots = k.take<uint32_t>(nb);
+    d.off = k.take<uint32_t>(nb);
+    d.hdr = k.take<IslHdr>();
+  });
+}
+
+// room for n rows and their labels, 1024 at least (every earlier call has completed: each one synchronises)
+static int ensure_island_rows(VxContext* c, uint32_t n) {
+  IslDev& d = c->vol.isl;
+  n = std::max(n, 1u);
+  if (n <= d.cap) return VX_OK;
+  d.cap = 0;
+  const size_t cap = std::max<size_t>(n, 1024u);
+  const int rc = carve(c, c->vol.isl_rows_alloc, [&](Carve& k) {
+    d.rows = k.take<IslRow>(cap);
+    d.newlab = k.take<uint32_t>(cap);
+  });
+  if (rc) return rc;
+  d.cap = (uint32_t)cap;
+  return VX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment(c->members[0], sp, out));
+  VX_DEV(c);
+  VoxelBox box;
+  if (int rc = check_ready(c, "vx_segment", sp, "sp")) return rc;
+  if (int rc = check_seed(c, "vx_segment", sp->seed)) return rc;
+  if (int rc = check_band(c, "vx_segment", sp->lo, sp->hi)) return rc;
+  if (int rc = check_connectivity(c, "vx_segment", sp->connectivity)) return rc;
+  if (int rc = check_box(c, "vx_segment", sp->box_lo, sp->box_hi, &box)) return rc;
+  c->vol.seg_valid = false;
+  c->vol.seg_pred_valid = false;
+  c->vol.isl_valid = false;
+  if (int rc = ensure_segment(c)) return rc;
+  const SegDev& s = c->vol.seg;
+  const uint32_t* E = c->vol.dv.extent;
+  const SegSeed seed = seg_seed_of(s, sp->seed);
+  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
+  const uint64_t cap = sp->max_rounds ? (uint64_t)sp->max_rounds : std::min<uint64_t>(nvox, 0xfffffffeull);
+  VX_HIP(c, hipMemsetAsync(s.seg, 0, (size_t)s.nb * 64u, c->stream));
+  VX_HIP(c, hipMemsetAsync(s.stamp, 0, (size_t)s.nb * 4u, c->stream));
+  if (int rc = c->seg_timer.mark(c, 0)) return rc;
+  launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
+  VX_HIP(c, hipGetLastError());
+  if (int rc = c->seg_timer.mark(c, 1)) return rc;
+  hipLaunchKernelGGL(seg_seed, dim3(1), dim3(64), 0, c->stream, s, seed);
+  VX_HIP(c, hipGetLastError());
+  bool converged = false;
+  if (int rc = run_seg_flood(c, s, sp->connectivity, seed, cap, &converged, nullptr)) return rc;
+  if (int rc = c->seg_timer.mark(c, 2)) return rc;
+  launch_seg_stats(c);
+  VX_HIP(c, hipGetLastError());
+  if (int rc = c->seg_timer.mark(c, 3)) return rc;
+  SegStats st;
+  VX_HIP(c, hipMemcpyAsync(&st, s.st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  if (int rc = c->seg_timer.read(c)) return rc;
+  VxSegmentResult r = seg_result(st);
+  r.rounds = st.rounds;
+  r.converged = converged ? 1u : 0u;
+  r.brick_visits = st.visits;
+  c->seg_res = r;
+  c->vol.seg_valid = true;
+  c->vol.seg_pred_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_segment_read_mask(VxContext* c, uint8_t* bits, uint64_t nbytes) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_read_mask(c->members[0], bits, nbytes));
+  VX_DEV(c);
+  if (!c->vol.seg_valid) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: no current segment (vx_segment first; an upload drops it)");
+  if (!bits) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_read_mask: bits is NULL");
+  const uint32_t* E = c->vol.dv.extent;
+  size_t want = 0;
+  if (int rc = check_mask_bytes(c, "vx_segment_read_mask", nbytes, &want)) return rc;
+  if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
+  const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 8192u);
+  hipLaunchKernelGGL(seg_pack, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg, E[0], E[1], want, c->vol.seg_bytes);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipMemcpyAsync(bits, c->vol.seg_bytes, want, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_slice_segment_mask(VxContext* c, const VxSliceParams* sp, uint8_t* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_slice_segment_mask(c->members[0], sp, out));
+  VX_DEV(c);
+  if (!c->vol.has_volume) VX_FAIL(c, VX_ERR_NO_VOLUME, "vx_slice_segment_mask: no volume uploaded");
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: no current segment (vx_segment first; an upload drops it)");
+  if (!sp) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: sp is NULL");
+  if (!out) VX_FAIL(c, VX_ERR_INVALID, "vx_slice_segment_mask: out is NULL");
+  if (int rc = check_slice_size(c, "vx_slice_segment_mask", sp)) return rc;
+  if (int rc = check_slice_frame(c, "vx_slice_segment_mask", sp)) return rc;
+  const size_t px = (size_t)sp->size[0] * sp->size[1];
+  if (int rc = c->seg_ov.ensure(c, px)) return rc;   // (every earlier call has completed: each one synchronises)
+  const dim3 grid((sp->size[0] + 15u) / 16u, (sp->size[1] + 15u) / 16u);
+  hipLaunchKernelGGL(seg_slice_mask, grid, dim3(256), 0, c->stream, *sp, c->vol.seg, c->vol.dv.extent[0], c->vol.dv.extent[1],
+                     c->vol.dv.extent[2], c->seg_ov);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipMemcpyAsync(out, c->seg_ov, px, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_set_segment_view(VxContext* c, int view) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return refuse_group(c, "vx_set_segment_view", "the segment lives on member 0 only");
+  if (view < VX_SEGVIEW_OFF || view > VX_SEGVIEW_HIDE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: view = %d is not VX_SEGVIEW_OFF, _ONLY or _HIDE", view);
+  if (view != VX_SEGVIEW_OFF && !c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_set_segment_view: %s without a current segment (vx_segment first; an upload drops it)",
+            view == VX_SEGVIEW_ONLY ? "only" : "hide");
+  c->vol.seg_view = view;
+  return VX_OK;
+}
+
+int vx_get_segment_view(VxContext* c, int* view) {
+  if (!c || !view) return VX_ERR_INVALID;
+  *view = c->vol.seg_view;
+  return VX_OK;
+}
+
+int vx_segment_stats(VxContext* c, uint32_t* rounds, uint64_t* brick_visits, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_stats(c->members[0], rounds, brick_visits, kernel_ms));
+  if (rounds) *rounds = c->seg_res.rounds;
+  if (brick_visits) *brick_visits = c->seg_res.brick_visits;
+  if (kernel_ms) std::copy_n(c->seg_timer.ms, 3, kernel_ms);
+  return VX_OK;
+}
+
+int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_edit(c->members[0], ep, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_edit", ep, "params")) return rc;
+  if (ep->op < VX_SEGEDIT_DILATE || ep->op > VX_SEGEDIT_FILL_HOLES)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: op = %d is not a VxSegmentEditOp (0 .. 4)", ep->op);
+  if (int rc = check_connectivity(c, "vx_segment_edit", ep->connectivity)) return rc;
+  const bool fill = ep->op == VX_SEGEDIT_FILL_HOLES;
+  if (fill ? ep->steps > 1u : (ep->steps < 1u || ep->steps > VX_SEGEDIT_MAX_STEPS))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: steps = %u outside %s", ep->steps, fill ? "0 .. 1 (fill holes)" : "1 .. 1024");
+  if (ep->band != 0 && ep->band != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = %d is not 0 or 1", ep->band);
+  if (ep->band && ep->op != VX_SEGEDIT_DILATE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 is for VX_SEGEDIT_DILATE only (op = %d)", ep->op);
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: no current segment (vx_segment or vx_segment_write_mask first; an upload drops it)");
+  if (ep->band && !c->vol.seg_pred_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
+  if (int rc = ensure_segedit(c)) return rc;
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
+  const int conn = ep->connectivity;
+  const uint32_t n = ep->steps;
+  c->sed_launches = 0;
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
+  uint64_t* cur = s.seg;
+  switch (ep->op) {
+    case VX_SEGEDIT_DILATE: launch_sed_steps(c, conn, false, ep->band != 0, n, true, &cur); break;
+    case VX_SEGEDIT_ERODE: launch_sed_steps(c, conn, true, false, n, true, &cur); break;
+    case VX_SEGEDIT_OPEN:
+      launch_sed_steps(c, conn, true, false, n, false, &cur);
+      launch_sed_steps(c, conn, false, false, n, true, &cur);
+      break;
+    case VX_SEGEDIT_CLOSE:
+      launch_sed_steps(c, conn, false, false, n, false, &cur);
+      launch_sed_steps(c, conn, true, false, n, true, &cur);
+      break;
+    default: {
+      // the background flood on a second view: predicate ~M and the reached set in the scratch masks, the bookkeeping shared
+      // with vx_segment (its predicate WORDS stay: band dilation after a fill is legal)
+      SegDev f = s;
+      f.pred = c->vol.sed_mask[0];
+      f.seg = c->vol.sed_mask[1];
+      f.any = c->vol.sed_any;
+      const uint32_t blocks = std::min<uint32_t>((s.nb + 255u) / 256u, 4096u);
+      hipLaunchKernelGGL(sed_reset, dim3(1), dim3(64), 0, c->stream, s, 1u);
+      hipLaunchKernelGGL(sed_fill_seed, dim3(blocks), dim3(256), 0, c->stream, s.seg, f);
+      VX_HIP(c, hipGetLastError());
+      bool converged = false;
+      uint64_t launched = 0;
+      const uint64_t nvox = (uint64_t)c->vol.dv.extent[0] * c->vol.dv.extent[1] * c->vol.dv.extent[2];
+      if (int rc = run_seg_flood(c, f, conn, SegSeed{0u, 0u, 0ull}, std::min<uint64_t>(nvox, 0xfffffffeull), &converged, &launched))
+        return rc;
+      const size_t words = (size_t)s.nb * 8u;
+      hipLaunchKernelGGL(sed_fill_finish, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream,
+                         f.seg, s.seg, words);
+      c->sed_launches = (uint32_t)std::min<uint64_t>(launched + 3u, 0xffffffffull);
+      cur = s.seg;
+    }
+  }
+  VX_HIP(c, hipGetLastError());
+  // a single step read SegDev::seg and so wrote a scratch mask: copy it home on the stream
+  if (cur != s.seg) VX_HIP(c, hipMemcpyAsync(s.seg, cur, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
+  return finish_mask_edit(c, fill, false, out);
+}
+
+int vx_segment_write_mask(VxContext* c, const uint8_t* bits, uint64_t nbytes, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_write_mask(c->members[0], bits, nbytes, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_write_mask", bits, "bits")) return rc;
+  size_t want = 0;
+  if (int rc = check_mask_bytes(c, "vx_segment_write_mask", nbytes, &want)) return rc;
+  if (int rc = ensure_segment(c)) return rc;
+  if (int rc = ensure_segedit(c)) return rc;
+  if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
+  VX_HIP(c, hipMemcpyAsync(c->vol.seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
+  const size_t words = (size_t)s.nb * 8u;
+  hipLaunchKernelGGL(sed_unpack, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 8192u)), dim3(256), 0, c->stream, s,
+                     c->vol.dv.extent[1], c->vol.seg_bytes);
+  VX_HIP(c, hipGetLastError());
+  c->sed_launches = 1;
+  return finish_mask_edit(c, false, false, out);
+}
+
+int vx_segment_edit_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_edit_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->sed_launches;
+  if (kernel_ms) std::copy_n(c->sed_timer.ms, 2, kernel_ms);
+  return VX_OK;
+}
+
+// ---- islands (vx_segment_threshold, vx_segment_islands, vx_islands_read*; kernels in vx_islands.hpp) ---------------------------
+// (the mask is rewritten outright: timed and counted like vx_segment_write_mask, reported by vx_segment_edit_stats)
+int vx_segment_threshold(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_threshold(c->members[0], sp, out));
+  VX_DEV(c);
+  VoxelBox box;
+  if (int rc = check_ready(c, "vx_segment_threshold", sp, "sp")) return rc;
+  if (int rc = check_band(c, "vx_segment_threshold", sp->lo, sp->hi)) return rc;
+  if (int rc = check_box(c, "vx_segment_threshold", sp->box_lo, sp->box_hi, &box)) return rc;
+  if (int rc = ensure_segment(c)) return rc;
+  c->vol.seg_valid = false;
+  c->vol.seg_pred_valid = false;
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
+  launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
+  VX_HIP(c, hipGetLastError());
+  // the mask = the predicate words.  SegDev::seg keeps its address: the masked render kernels read it at launch time
+  VX_HIP(c, hipMemcpyAsync(s.seg, s.pred, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
+  c->sed_launches = 1;
+  return finish_mask_edit(c, false, true, out);
+}
+
+int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_islands(c->members[0], ip, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_islands", ip, "params")) return rc;
+  if (ip->op < VX_ISLANDS_LABEL || ip->op > VX_ISLANDS_KEEP_AT)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: op = %d is not a VxIslandsOp (0 .. 3)", ip->op);
+  if (int rc = check_connectivity(c, "vx_segment_islands", ip->connectivity)) return rc;
+  if (ip->op == VX_ISLANDS_KEEP_LARGEST && ip->keep == 0)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: keep = 0 (KEEP_LARGEST keeps at least one island)");
+  if (ip->op == VX_ISLANDS_REMOVE_SMALL && ip->min_voxels == 0)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: min_voxels = 0 (REMOVE_SMALL needs a size of at least 1)");
+  const uint32_t* E = c->vol.dv.extent;
+  if (ip->op == VX_ISLANDS_KEEP_AT)
+    if (int rc = check_seed(c, "vx_segment_islands", ip->seed)) return rc;
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: no current segment (vx_segment, vx_segment_threshold or vx_segment_write_mask "
+                               "first; an upload drops it)");
+  const uint64_t nvox = (uint64_t)E[0] * E[1] * E[2];
+  if (nvox >= 0x80000000ull)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_islands: %llu voxels are beyond the 31-bit voxel index of the labels",
+            (unsigned long long)nvox);
+  if (int rc = ensure_islands(c)) return rc;
+  if (int rc = ensure_island_rows(c, 1u)) return rc;
+  c->vol.isl_valid = false;
+  const SegDev& s = c->vol.seg;
+  const bool modify = ip->op != VX_ISLANDS_LABEL;
+  const dim3 grid(std::min<uint32_t>((s.nb + 3u) / 4u, 16384u)), block(256);
+  uint32_t launches = 0;
+  VX_HIP(c, hipMemsetAsync(c->vol.isl.hdr, 0, sizeof(IslHdr), c->stream));
+  StageTimer<7>& timer = c->isl_timer;
+  if (int rc = timer.mark(c, 0)) return rc;
+  with_conn(ip->connectivity, [&](auto k) { hipLaunchKernelGGL(isl_local<decltype(k)::value>, grid, block, 0, c->stream, s, c->vol.isl); });
+  if (int rc = timer.mark(c, 1)) return rc;
+  with_conn(ip->connectivity, [&](auto k) { hipLaunchKernelGGL(isl_merge<decltype(k)::value>, grid, block, 0, c->stream, s, c->vol.isl); });
+  if (int rc = timer.mark(c, 2)) return rc;
+  hipLaunchKernelGGL(isl_flatten, grid, block, 0, c->stream, s, c->vol.isl);
+  hipLaunchKernelGGL(isl_scan, dim3(1), dim3(1024), 0, c->stream, s, c->vol.isl);
+  VX_HIP(c, hipGetLastError());
+  launches += 4;
+  if (int rc = timer.mark(c, 3)) return rc;
+  // the one read-back that sizes the table: the number of islands
+  IslHdr hdr{};
+  VX_HIP(c, hipMemcpyAsync(&hdr, c->vol.isl.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  const uint32_t R = hdr.roots;
+  if (int rc = ensure_island_rows(c, R)) return rc;
+  const IslDev& d = c->vol.isl;
+  const SegSeed seed = ip->op == VX_ISLANDS_KEEP_AT ? seg_seed_of(s, ip->seed) : SegSeed{0u, 0u, 1ull};
+  hipLaunchKernelGGL(isl_rootid, grid, block, 0, c->stream, s, d);
+  hipLaunchKernelGGL(isl_table, grid, block, 0, c->stream, s, d);
+  hipLaunchKernelGGL(isl_seed_row, dim3(1), dim3(64), 0, c->stream, s, d, seed);
+  VX_HIP(c, hipGetLastError());
+  launches += 3;
+  if (int rc = timer.mark(c, 4)) return rc;
+  VX_HIP(c, hipEventSynchronize(timer.ev[4]));
+  // the host's share: the rows come back once, are ranked by (count descending, anchor ascending), and every row's label
+  // (0: dropped by the op) goes back up.  O(islands), not O(voxels).
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<IslRow> rows(R);
+  VX_HIP(c, hipMemcpyAsync(&hdr, d.hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+  if (R) VX_HIP(c, hipMemcpyAsync(rows.data(), d.rows, (size_t)R * sizeof(IslRow), hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<uint32_t> order(R);
+  for (uint32_t i = 0; i < R; ++i) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    return rows[a].count != rows[b].count ? rows[a].count > rows[b].count : rows[a].anchor < rows[b].anchor;
+  });
+  std::vector<uint32_t> newlab(std::max(R, 1u), 0u);
+  std::vector<VxIsland> table;
+  table.reserve(R);
+  for (uint32_t k = 0; k < R; ++k) {
+    const uint32_t i = order[k];
+    const IslRow& r = rows[i];
+    bool keep = true;
+    switch (ip->op) {
+      case VX_ISLANDS_KEEP_LARGEST: keep = (uint64_t)k < ip->keep; break;
+      case VX_ISLANDS_REMOVE_SMALL: keep = r.count >= ip->min_voxels; break;
+      case VX_ISLANDS_KEEP_AT: keep = i == hdr.seed_row; break;
+      default: break;
+    }
+    if (!keep) continue;
+    VxIsland v{};
+    v.count = r.count;
+    v.anchor[0] = r.anchor % E[0];
+    v.anchor[1] = (r.anchor / E[0]) % E[1];
+    v.anchor[2] = r.anchor / (E[0] * E[1]);
+    for (int a = 0; a < 3; ++a) {
+      v.bbox_lo[a] = r.lo[a];
+      v.bbox_hi[a] = r.hi[a];
+    }
+    table.push_back(v);
+    table.back().label = (uint32_t)table.size();
+    newlab[i] = (uint32_t)table.size();
+  }
+  VX_HIP(c, hipMemcpyAsync(d.newlab, newlab.data(), newlab.size() * 4u, hipMemcpyHostToDevice, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));   // (newlab is pageable host memory of this frame)
+  const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (int rc = timer.mark(c, 5)) return rc;
+  if (modify) {
+    hipLaunchKernelGGL(isl_apply, grid, block, 0, c->stream, s, d);
+    ++launches;
+  }
+  if (int rc = timer.mark(c, 6)) return rc;
+  SegStats st;
+  if (int rc = seg_mask_stats(c, timer, 7, &st)) return rc;
+  launches += 3;
+  if (int rc = timer.read(c)) return rc;
+  timer.ms[4] = host_ms;             // stage 4 is the host's share: wall time, not the events around it
+  if (!modify) timer.ms[5] = 0.0;    // (two events back to back still measure a few microseconds)
+  c->isl_launches = launches;
+  VxIslandsResult r{};
+  r.islands = R;
+  r.kept = table.size();
+  r.largest = R ? rows[order[0]].count : 0u;
+  r.seg = seg_result(st);
+  r.seg.converged = 1u;
+  c->vol.isl_table.swap(table);
+  c->vol.isl_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_islands_read(VxContext* c, uint64_t first, uint64_t n, VxIsland* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_islands_read(c->members[0], first, n, out));
+  if (!c->vol.isl_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: no current table (vx_segment_islands first; an upload and every call that "
+                               "changes the segment drop it)");
+  const uint64_t have = c->vol.isl_table.size();
+  if (first > have || n > have - first)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: rows %llu .. %llu are beyond the %llu islands of the table",
+            (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)have);
+  if (n && !out) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read: out is NULL");
+  if (n) memcpy(out, c->vol.isl_table.data() + first, (size_t)n * sizeof(VxIsland));
+  return VX_OK;
+}
+
+int vx_islands_read_labels(VxContext* c, uint32_t* labels, uint64_t nvoxels) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_islands_read_labels(c->members[0], labels, nvoxels));
+  VX_DEV(c);
+  if (!c->vol.isl_valid || !c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: no current table (vx_segment_islands first; an upload and every call "
+                               "that changes the segment drop it)");
+  if (!labels) VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: labels is NULL");
+  const uint32_t* E = c->vol.dv.extent;
+  const size_t want = (size_t)E[0] * E[1] * E[2];
+  if (nvoxels != want)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_islands_read_labels: nvoxels = %llu, the volume has %u x %u x %u = %zu voxels",
+            (unsigned long long)nvoxels, E[0], E[1], E[2], want);
+  if (int rc = c->vol.isl_dense.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
+  const uint32_t blocks = (uint32_t)std::min<size_t>((want + 255u) / 256u, 16384u);
+  hipLaunchKernelGGL(isl_labels_out, dim3(blocks), dim3(256), 0, c->stream, c->vol.seg, c->vol.isl, E[0], E[1], want, c->vol.isl_dense);
+  VX_HIP(c, hipGetLastError());
+  VX_HIP(c, hipMemcpyAsync(labels, c->vol.isl_dense, want * 4u, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_islands_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_islands_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->isl_launches;
+  if (kernel_ms) std::copy_n(c->isl_timer.ms, 7, kernel_ms);
+  return VX_OK;
+}
+
+}  // extern "C"

@@ -12,67 +12,11 @@
 #include <stdint.h>
 
 #include "../../include/volxel_hip.h"
+#include "vx_types.hpp"
 
 #define VXD __device__ __forceinline__
 
 namespace vx {
-
-// ---------------------------------------------------------------------------------------
-// device view of an uploaded volume
-struct DevVolume {
-  // reference layout: the three textures of viewer.ts:1106-1142 as linear buffers
-  const uint32_t* indirection;  // 10-10-10 pointers            (brick.rs:30-35)
-  const uint32_t* range;        // (f16 min << 16) | f16 max    (brick.rs:19-23)
-  const uint8_t* atlas;         // u8 voxels, x fastest         (buf3d.rs:26-28)
-  const uint32_t* mips[3];      // range mips, GL levels 1..3   (brick.rs:153-190)
-  uint32_t bc[3];               // bricks per axis (= indirection = range dims)
-  uint32_t atlas_size[3];
-  uint32_t extent[3];           // padded index extent = bc*8   (brick.rs:236-238)
-  uint32_t mip_size[3][3];
-  // MI355X layout "cellquad": apron bricks of pre-decoded fp32 xy-quads
-  const float4* cq;             // [(bc+1)^3][9 slices][8][8] float4
-  uint32_t cq_bc[3];            // bc + 1
-  // MI355X layout "brickf32": every 8^3 brick decoded to fp32, 2 KiB contiguous, brick-major
-  const float* bf;              // [bc.z][bc.y][bc.x][8][8][8], one all-zero 16-byte chunk behind the last brick
-  uint32_t bf_zero;             // index (in floats) of that chunk, or 0 when the layout needs more than 32 index bits
-  // MI355X layout "bricku8" (opt-in): the same bricks as the atlas' 8-bit codes, 4 per dword, dword index = the
-  // 16-byte-unit index of brickf32 (brick * 128 + z * 16 + y * 2 + (x >> 2)); one zero dword behind the last brick.
-  // bu_range[b] = {min, max - min} of brick b (range texture, decoded from f16); the entry behind the last brick is
-  // {0, 0}: it serves the zero dword, so rows and chunks outside the volume decode to 0 (A4).
-  const uint32_t* bu;
-  const float2* bu_range;
-  uint32_t bu_active;           // unused: vx_api.hip plan_launch decides U8; kept so the offsets behind it stay
-  // exact empty-space skipping (DVR): one bit per macro cell of 8 << skip_level voxels
-  const uint32_t* skip_bits;    // nullptr: none
-  uint32_t skip_level;
-  uint32_t skip_dims[3];        // (extent >> (3 + level)) + 1
-  uint32_t skip_words;
-  // default mode (A13): the local majorant maj * TF(scale * range max).a of every cell of range-texture levels 0..3
-  // (dda.glsl:36,78), levels back to back, each at the strides of level 0; entry lmaj_cells = the value outside
-  const float* lmaj;            // built by vx_api before a `default` launch (build_local_majorants)
-  uint32_t lmaj_cells;          // 4 * bricks
-  // environment map (environment.ts): RGBA32F texels in GL row order + importance mip pyramid
-  const float4* env_tex;        // nullptr: none (directional light only)
-  uint32_t env_w, env_h;
-  const float* env_imp;         // levels 0..9 of the 512^2 map back to back (imp_offset)
-  const float4* env_impq;       // the same levels 0..8 as 2x2 sibling quads, one 16-byte load per level
-  float env_avg_w;              // level 9 (the mean importance)
-  // wave-uniform terms of the primary ray, evaluated once per launch on the host with the device's own operations
-  // (IEEE fma chains and divisions: vx_api.hip derive_camera) instead of once per wave on the vector ALUs -- the
-  // reference hoists its matrix inverses the same way (quirk Q11).  Perspective camera only (an orthographic ray's
-  // origin is per pixel); read by the tuned DVR kernels through dvr_setup.
-  float cam_o[3];               // inverse(view) * (0,0,0,1), divided by w          (utils.glsl:25-27)
-  float cam_ipos[3];            // density_transform_inv * (cam_o, 1)               (to_index of the origin)
-  float inv_res[2];             // 1 / u_res
-  // Round 4: two more per-ray divisions decided per launch on the host (vx_api.hip prepare_render), both exact:
-  //  * RAY_AFFINE_VIEW: inverse(view) has the bottom row (0,0,0,1), so the w of inverse(view) * (v, 1) is fma(1, 1, 0 * ...)
-  //    = 1.0 and the three divisions by it (utils.glsl:35-37) return their numerators;
-  //  * RAY_TEX_BY_RECIPROCAL: (pixel + 0.5) / res over the whole image equals the quotient corrected once with the rounded
-  //    reciprocal -- q0 = a * y, q = fma(fma(-res, q0, a), y, q0) -- for EVERY pixel coordinate of this resolution (the host
-  //    tries all of them against the IEEE division; a resolution for which one differs keeps the division).
-  uint32_t ray_flags;
-};
-constexpr uint32_t RAY_AFFINE_VIEW = 1u, RAY_TEX_BY_RECIPROCAL_X = 2u, RAY_TEX_BY_RECIPROCAL_Y = 4u;
 
 constexpr uint32_t IMP_DIM = 512, IMP_LEVELS = 10, IMP_FLOATS = 349525;
 // quads of level k (children of the texels of level k+1): (IMP_DIM >> (k+1))^2 float4, row major
@@ -301,8 +245,6 @@ VXD float4 decode_codes4(uint32_t code4, float2 rg) {
 
 VXD float gl_mix(float x, float y, float a) { return fma_(y, a, x * (1.0f - a)); }
 
-enum { LAYOUT_REF = 0, LAYOUT_CQ = 1, LAYOUT_BF = 2 };
-
 // decoded voxel from the brickf32 layout; out-of-range taps are 0; straight-line as above
 VXD float bf_voxel(const DevVolume& v, int x, int y, int z) {
   const bool in = (uint32_t)x < v.extent[0] && (uint32_t)y < v.extent[1] && (uint32_t)z < v.extent[2];
@@ -389,16 +331,6 @@ VXD float trilinear_cell(const DevVolume& v, float density_scale, int ix, int iy
   return density_scale * gl_mix(gl_mix(lx0, lx1, fy), gl_mix(hx0, hx1, fy), fz);
 }
 
-// [build] the light grid of shadowed DVR: transmittance toward the directional light at the nodes of a
-// lattice of stride s voxels, node (i, j, k) at cell-frame position s * (i, j, k), x fastest
-struct ShadowGrid {
-  const float* t;   // n[0] * n[1] * n[2] node values
-  uint32_t n[3];    // nodes per axis: ceil((extent - 1) / s) + 1
-  float inv_s;      // 1 / s (s = 1, 2 or 4: q * inv_s is q / s exactly)
-  float glo[3];     // the first and last node per axis whose position lies inside the clip box (vx_api.hip light_march)
-  float ghi[3];
-  float gmax[3];    // n - 1
-};
 // T_L at cell-frame position q: g = q / s clamped to [glo, ghi] per axis -- a sample within a node spacing of a clip-box face
 // takes the outermost node inside the box, never one outside it (whose march misses the box) -- cell i = min(floor(g), n - 2)
 // (n >= 2: extents are multiples of 8), fractions g - i, the eight nodes mixed x -> y -> z in common.glsl:62-68's order.
@@ -707,5 +639,39 @@ struct Counts {
   // calls).  The wave's march lane slots follow at the kernel's end: 64 x (max over the lanes of each), exact at bounces 1
   uint32_t it_p, it_s;
 };
+
+// ---- wave-wide reductions ------------------------------------------------------------
+// sum over the 64 lanes of the wave, in every lane: a DPP scan inside the rows of 16 lanes, two row broadcasts, one
+// v_readlane (6 vector instructions; the __shfl_down form went through ds_bpermute: ~30 instructions and six LDS round
+// trips per sum).  Every launch of this library runs whole waves (256-thread workgroups, no lane returns early).
+VXD uint32_t wave_sum(uint32_t x) {
+  int v = (int)x;
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8  -> lane 15 of each row = row sum
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
+  return (uint32_t)__builtin_amdgcn_readlane(v, 63);
+}
+
+// max over the 64 lanes of the wave, in every lane (whole waves, like wave_sum)
+VXD uint32_t wave_max_u32(uint32_t x) {
+  int v = (int)x;   // trip counts: far below 2^31
+  auto mx = [](int a, int b) { return a > b ? a : b; };
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
+  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));
+  return (uint32_t)__builtin_amdgcn_readlane(v, 63);
+}
+
+// d(i) = (volume_density_scale * v(i)) * volume_inv_maj: trilinear_q at q = i, where every mix weight is 0
+template <int LAYOUT>
+VXD float seg_density(const DevVolume& v, float scale, float inv_maj, uint32_t x, uint32_t y, uint32_t z) {
+  return (scale * lookup_density_nearest<LAYOUT>(v, (int)x, (int)y, (int)z)) * inv_maj;
+}
 
 }  // namespace vx

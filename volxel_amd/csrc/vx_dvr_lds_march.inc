@@ -257,7 +257,7 @@
                                ((((uint32_t)gz & 7u) << 4) | (((uint32_t)gy & 7u) << 1));
       // SEGV: the chunk's four segment bits.  A 16-byte unit `at` (brick * 128 + z * 16 + y * 2 + x / 4) is nibble `at` of
       // the brick-major mask (8 x u64 per brick, word z, bit y * 8 + x): dword at >> 3, bits (at & 7) * 4 .. + 3, x = 0 .. 3 of
-      // the chunk.  The zero chunk behind the last brick reads the dword behind the mask (vx_api.hip ensure_segment keeps one
+      // the chunk.  The zero chunk behind the last brick reads the dword behind the mask (vx_api_segment.hip ensure_segment keeps one
       // there); its value is +0 whatever the bits say.
       [[maybe_unused]] uint32_t sbits[NC];
       if (U8) {

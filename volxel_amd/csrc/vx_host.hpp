@@ -1,4 +1,4 @@
-// vx_host.hpp -- host-only helpers of vx_api.hip: the error macros and the three owners of device resources (a device
+// vx_host.hpp -- host-only helpers of the host units (vx_api*.hip): the error macros and the three owners of device resources (a device
 // buffer, the carve of one allocation into typed arrays, a stage timer), and the proof of the image blocks that cannot hit the
 // clip box (classify_miss_blocks).  No device code.
 //
@@ -13,12 +13,15 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "../../include/volxel_hip.h"
+
+// (namespace vx is hidden in the host headers: the library exports its C ABI and nothing of its own helpers)
 
 // what the owners need of a context (VxContext derives from it)
 struct VxCore {
@@ -41,7 +44,7 @@ struct VxCore {
     if (e_ != hipSuccess) VX_FAIL(ctx, VX_ERR_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-namespace vx {
+namespace vx __attribute__((visibility("hidden"))) {
 
 // A device buffer that owns its memory; cap counts elements (bytes for DevBuf<void>).  Reads as its pointer.
 template <class T>
@@ -223,6 +226,168 @@ inline uint32_t classify_miss_blocks(const VxParams& p, uint32_t W, uint32_t H, 
       }
     }
   return n;
+}
+
+// ---- exact empty-space skipping: host-side construction of the macro-cell bitmask -------------
+// Rule (restated independently by the oracle): TF bin i is dead when its alpha
+// is 0 or it lies wholly outside the sample range (one-bin margin); a brick is transparent when
+// every bin from I(min)-1 to I(max)+1 is dead, I(x) = floor(x*density_scale*inv_maj*L); a macro
+// cell of w = 2^level bricks per axis is empty when the w+1 bricks per axis that can hold a tap of
+// its cells (bricks m*w-1 .. m*w+w-1; value 0 outside the grid) are all transparent.
+inline float f16_bits_to_float(uint16_t h) {
+  _Float16 v;
+  memcpy(&v, &h, 2);
+  return (float)v;
+}
+inline int skip_level_for(const uint32_t extent[3]) {
+  for (int g = 1; g <= 3; ++g) {
+    uint64_t n = 1;
+    for (int a = 0; a < 3; ++a) n *= (uint64_t)(extent[a] >> (3 + g)) + 1u;
+    if (n <= 65536u) return g;
+  }
+  return 3;
+}
+inline void compute_skip_mask(const VxParams& p, const uint32_t* range_packed, const uint32_t bc[3],
+                              const uint32_t extent[3], const float* tf_rgba, uint32_t L,
+                              std::vector<uint32_t>& bits, int& level_out, uint32_t md[3]) {
+  const float lf = (float)L;
+  // prefix count of live bins -> O(1) "any live bin in [a, b]"
+  std::vector<uint32_t> live(L + 1, 0);
+  for (uint32_t i = 0; i < L; ++i) {
+    bool dead = tf_rgba[4 * (size_t)i + 3] == 0.0f || (float)((int)i + 2) / lf < p.sample_range[0] ||
+                (float)((int)i - 1) / lf > p.sample_range[1];
+    live[i + 1] = live[i] + (dead ? 0u : 1u);
+  }
+  auto transparent = [&](float lo, float hi) {
+    float fa = floorf(((lo * p.volume_density_scale) * p.volume_inv_maj) * lf);
+    float fb = floorf(((hi * p.volume_density_scale) * p.volume_inv_maj) * lf);
+    // v_cvt_i32_f32 semantics: NaN -> 0, saturating
+    auto f2i = [](float x) -> int64_t { return x != x ? 0 : (x >= 2147483648.0f ? 2147483647ll : (x <= -2147483648.0f ? -2147483648ll : (int64_t)x)); };
+    int64_t a = f2i(fa) - 1, b = f2i(fb) + 1;
+    if (a < 0) a = 0;
+    if (b > (int64_t)L - 1) b = (int64_t)L - 1;
+    if (b < a) return true;
+    return live[(size_t)b + 1] - live[(size_t)a] == 0u;
+  };
+  const size_t nb = (size_t)bc[0] * bc[1] * bc[2];
+  std::vector<uint8_t> opaque(nb);
+  for (size_t i = 0; i < nb; ++i) {
+    uint32_t pk = range_packed[i];
+    opaque[i] = transparent(f16_bits_to_float((uint16_t)(pk >> 16)), f16_bits_to_float((uint16_t)pk)) ? 0 : 1;
+  }
+  const uint8_t zero_opaque = transparent(0.0f, 0.0f) ? 0 : 1;
+  const int level = skip_level_for(extent);
+  level_out = level;
+  const int w = 1 << level;
+  for (int a = 0; a < 3; ++a) md[a] = (extent[a] >> (3 + level)) + 1u;
+  // separable OR over the window [m*w-1, m*w+w-1] per axis (out-of-grid bricks count as value 0)
+  std::vector<uint8_t> ax((size_t)md[0] * bc[1] * bc[2]), ay((size_t)md[0] * md[1] * bc[2]);
+  for (uint32_t z = 0; z < bc[2]; ++z)
+    for (uint32_t y = 0; y < bc[1]; ++y)
+      for (uint32_t m = 0; m < md[0]; ++m) {
+        uint8_t o = 0;
+        for (int b = (int)m * w - 1; b <= (int)m * w + w - 1; ++b)
+          o |= (b < 0 || (uint32_t)b >= bc[0]) ? zero_opaque : opaque[((size_t)z * bc[1] + y) * bc[0] + b];
+        ax[((size_t)z * bc[1] + y) * md[0] + m] = o;
+      }
+  for (uint32_t z = 0; z < bc[2]; ++z)
+    for (uint32_t m = 0; m < md[1]; ++m)
+      for (uint32_t x = 0; x < md[0]; ++x) {
+        uint8_t o = 0;
+        for (int b = (int)m * w - 1; b <= (int)m * w + w - 1; ++b)
+          o |= (b < 0 || (uint32_t)b >= bc[1]) ? zero_opaque : ax[((size_t)z * bc[1] + b) * md[0] + x];
+        ay[((size_t)z * md[1] + m) * md[0] + x] = o;
+      }
+  const size_t n = (size_t)md[0] * md[1] * md[2];
+  bits.assign((n + 31) / 32, 0u);
+  for (uint32_t m = 0; m < md[2]; ++m)
+    for (uint32_t y = 0; y < md[1]; ++y)
+      for (uint32_t x = 0; x < md[0]; ++x) {
+        uint8_t o = 0;
+        for (int b = (int)m * w - 1; b <= (int)m * w + w - 1; ++b)
+          o |= (b < 0 || (uint32_t)b >= bc[2]) ? zero_opaque : ay[((size_t)b * md[1] + y) * md[0] + x];
+        if (!o) {
+          size_t i = ((size_t)m * md[1] + y) * md[0] + x;
+          bits[i >> 5] |= 1u << (i & 31);
+        }
+      }
+}
+
+// ---- range skipping of the intensity projections: host-side construction of the density bounds ----------------------
+// Per macro cell of the empty-space grid above (level, dims), {lo, hi} with lo <= d <= hi for every density
+// d = (density_scale * mix) * inv_maj the device can compute at a sample of the cell.  Such a sample (mask index
+// floor(q) + 1 in the cell) takes its eight taps from the w + 1 bricks per axis m*w-1 .. m*w+w-1 that compute_skip_mask
+// ORs (a tap outside the grid reads 0), and a tap of brick b is decoded inside b's own range [min, max] (the f16 pair).
+// Rounding, argued against a relative margin of 2^-16 and an absolute one of 2^-100:
+//   * a decoded voxel, fma(c/255, max - min, min), lands at most an ulp or two beyond [min, max] (relative 2^-22);
+//   * a mix fma(b, t, a * (1 - t)): 1 - t and the product round once each, the fma once: with weights t, 1 - t in [0, 1] the
+//     result is within 3 rounding errors (2^-24 each, of the larger operand) of a convex combination, and the trilinear is
+//     three nested mixes -- at most ~10 rounding errors of max(|lo|, |hi|) in all, below 2^-20 relative;
+//   * the products by density_scale and inv_maj add one rounding each, and a device that flushes a denormal moves a value by
+//     less than 2^-126.
+// Bounds widened by 2^-16 of the magnitude and by 2^-100 hold with a margin of more than 16x.  A density_scale or inv_maj
+// that is <= 0 or not finite turns the map around or breaks it: then the bounds are {-inf, +inf} and nothing is skipped.
+inline void compute_projection_bounds(const VxParams& p, const uint32_t* range_packed, const uint32_t bc[3],
+                                      const uint32_t extent[3], std::vector<float>& lohi, int& level_out, uint32_t md[3]) {
+  const int level = skip_level_for(extent);
+  level_out = level;
+  const int w = 1 << level;
+  for (int a = 0; a < 3; ++a) md[a] = (extent[a] >> (3 + level)) + 1u;
+  const size_t n = (size_t)md[0] * md[1] * md[2];
+  lohi.assign(2 * n, 0.0f);
+  const float s = p.volume_density_scale, im = p.volume_inv_maj;
+  if (!(s > 0.0f) || !(im > 0.0f) || !std::isfinite(s) || !std::isfinite(im)) {
+    for (size_t i = 0; i < n; ++i) { lohi[2 * i] = -INFINITY; lohi[2 * i + 1] = INFINITY; }
+    return;
+  }
+  // per-brick ranges, then separable min / max over the window [m*w-1, m*w+w-1] per axis (out-of-grid bricks read 0)
+  const size_t nb = (size_t)bc[0] * bc[1] * bc[2];
+  std::vector<float> bmin(nb), bmax(nb);
+  for (size_t i = 0; i < nb; ++i) {
+    const uint32_t pk = range_packed[i];
+    const float a = f16_bits_to_float((uint16_t)(pk >> 16)), b = f16_bits_to_float((uint16_t)pk);
+    bmin[i] = std::min(a, b);
+    bmax[i] = std::max(a, b);
+  }
+  auto reduce = [&](const std::vector<float>& src, uint32_t sx, uint32_t sy, uint32_t sz, int axis, bool hi) {
+    const uint32_t dims_in[3] = {sx, sy, sz};
+    uint32_t d[3] = {sx, sy, sz};
+    d[axis] = md[axis];
+    std::vector<float> out((size_t)d[0] * d[1] * d[2]);
+    for (uint32_t z = 0; z < d[2]; ++z)
+      for (uint32_t y = 0; y < d[1]; ++y)
+        for (uint32_t x = 0; x < d[0]; ++x) {
+          uint32_t at[3] = {x, y, z};
+          const int m = (int)at[axis];
+          float r = 0.0f;
+          bool first = true;
+          for (int b = m * w - 1; b <= m * w + w - 1; ++b) {
+            float v = 0.0f;
+            if (b >= 0 && (uint32_t)b < dims_in[axis]) {
+              at[axis] = (uint32_t)b;
+              v = src[((size_t)at[2] * dims_in[1] + at[1]) * dims_in[0] + at[0]];
+            }
+            r = first ? v : (hi ? std::max(r, v) : std::min(r, v));
+            first = false;
+          }
+          out[((size_t)z * d[1] + y) * d[0] + x] = r;
+        }
+    return out;
+  };
+  for (int hi = 0; hi < 2; ++hi) {
+    const std::vector<float>& b0 = hi ? bmax : bmin;
+    std::vector<float> rx = reduce(b0, bc[0], bc[1], bc[2], 0, hi);
+    std::vector<float> ry = reduce(rx, md[0], bc[1], bc[2], 1, hi);
+    std::vector<float> rz = reduce(ry, md[0], md[1], bc[2], 2, hi);
+    for (size_t i = 0; i < n; ++i) {
+      const double v = rz[i];   // voxel units
+      const double d = v * (double)s * (double)im;
+      const double widened = hi ? d + std::fabs(d) * 0x1p-16 + 0x1p-100 : d - std::fabs(d) * 0x1p-16 - 0x1p-100;
+      float f = (float)widened;   // then one more step outwards against the conversion's rounding
+      f = std::nextafter(f, hi ? INFINITY : -INFINITY);
+      lohi[2 * i + hi] = f;
+    }
+  }
 }
 
 // The timer of N stages of a call: N + 1 events, created by the first mark.  mark(c, i) records event i on the context's

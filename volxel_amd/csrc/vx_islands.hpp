@@ -36,31 +36,6 @@ namespace vx {
 constexpr uint32_t ISL_NONE = 0xffffffffu;   // the entry of an unset voxel (never followed: the mask bit is tested first)
 constexpr uint32_t ISL_ID = 0x80000000u;     // an entry that holds a table row; voxel indices and rows stay below 2^31
 
-// one island while the table is built (device side; the host ranks the rows)
-struct IslRow {
-  unsigned long long count;
-  uint32_t anchor;            // C-order index over (z, y, x) of the island's first voxel
-  uint32_t lo[3], hi[3];      // bbox, inclusive
-  uint32_t pad;
-};
-
-struct IslHdr {
-  uint32_t roots;      // isl_scan: the number of islands
-  uint32_t seed_row;   // isl_seed_row: the row of the seed voxel, ISL_NONE when it is not set
-  uint32_t retries;    // isl_merge: failed compare-exchanges (a probe figure; not part of any result)
-  uint32_t pad;
-};
-
-struct IslDev {
-  uint32_t* lab;       // nb * 512
-  uint32_t* nroots;    // nb
-  uint32_t* off;       // nb
-  IslHdr* hdr;
-  IslRow* rows;        // cap
-  uint32_t* newlab;    // cap: the label (rank + 1) of a row, 0 when the op dropped it
-  uint32_t cap;
-};
-
 #define ISL_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // the root of x; the start node is moved up to it (a min: parents only decrease, and the root is an ancestor)

@@ -11,19 +11,6 @@
 
 namespace vx {
 
-// counts of one launch (unsigned long long each, zeroed by the host before it)
-enum IsoCount { ISO_RAYS = 0, ISO_HITS, ISO_SAMPLES, ISO_REFINE, ISO_SKIPPED, ISO_NCOUNTS };
-
-// The range-skipping table: `bound` holds the upper density bound of every macro cell of the empty-space grid (the intensity
-// projections' table, vx_api.hip compute_projection_bounds); a sample's macro cell is that of its mask cell floor(q) + 1,
-// clamped as the projection kernel clamps it (a clamped cell is outside the volume, where every tap reads 0, and the clamped
-// macro cell's window holds out-of-grid bricks: its bound is >= 0).
-struct IsoBound {
-  const float* __restrict__ hi;   // nullptr unless SKIP
-  uint32_t sh, md0, md1;          // 3 + level, macro cells per axis x / y
-  uint32_t cmax[3];               // extent + 7 per axis
-};
-
 // The segment view (DESIGN.md section 2 "Segment views"): the decoded voxel (x, y, z) of the masked volume -- +0 where its bit of
 // the brick-major segment mask (8 x u64 per brick, word z, bit y * 8 + x; read as 16 dwords, dword z * 2 + y / 4, bit
 // (y & 3) * 8 + x) XOR `inv` (0: ONLY, ~0u: HIDE) is 0.  A voxel outside the volume reads 0 anyway; its mask index is clamped.

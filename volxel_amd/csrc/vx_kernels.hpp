@@ -5,18 +5,6 @@
 
 namespace vx {
 
-// image <-> slab mapping: 64x64-pixel sharding tiles dealt
-// round-robin to shards; inside a tile 64 wave-tiles of 8x8 pixels in Morton order; the
-// accumulator ("slab") is tile-major so that one wave owns 1 KiB of contiguous pixels.
-struct TileMap {
-  uint32_t W, H;
-  uint32_t tiles_x, tiles_y, n_tiles;
-  uint32_t shard_rank, shard_count, tiles_per_shard;
-  // optional dealing order of the tiles (vx_set_tile_order): position pos = lt * shard_count + rank holds
-  // tile perm[pos]; inv is the inverse.  nullptr: pos == tile id (tiles dealt round-robin in row-major order).
-  const uint32_t* perm;
-  const uint32_t* inv;
-};
 VXD uint32_t tile_at(const TileMap& tm, uint32_t lt) {  // tile id of local tile lt, >= n_tiles: padding
   uint32_t pos = lt * tm.shard_count + tm.shard_rank;
   return (tm.perm && pos < tm.n_tiles) ? tm.perm[pos] : pos;
@@ -50,35 +38,6 @@ VXD bool wave_pixel(const TileMap& tm, uint32_t lt, uint32_t wt, uint32_t lane, 
   py = (int)(ty * 64u + morton_x(wt >> 1) * 8u + ly);
   return (uint32_t)px < tm.W && (uint32_t)py < tm.H;
 }
-
-// sum over the 64 lanes of the wave, in every lane: a DPP scan inside the rows of 16 lanes, two row broadcasts, one
-// v_readlane (6 vector instructions; the __shfl_down form went through ds_bpermute: ~30 instructions and six LDS round
-// trips per sum).  Every launch of this library runs whole waves (256-thread workgroups, no lane returns early).
-VXD uint32_t wave_sum(uint32_t x) {
-  int v = (int)x;
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8  -> lane 15 of each row = row sum
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
-  return (uint32_t)__builtin_amdgcn_readlane(v, 63);
-}
-
-// Work counters: one record per wave of the launch grid, owned by that wave and updated with a
-// plain read-modify-write (launches on a stream are ordered, so no atomics are needed).
-// Atomics on shared words were measured to cost ~1.1 ms per 1080p frame (32768 waves x 4
-// same-line atomics at ~88 per microsecond) -- three times the march itself.
-struct DevCounters {
-  unsigned long long samples, slots;
-  uint32_t rays, pixels, skips, grads;
-  uint32_t last_slots;  // lane slots of the most recent launch: the cost fed back to build_order
-  uint32_t gathers;     // 16-byte-per-lane gather wave instructions issued (tuned DVR kernels)
-  uint32_t lds_reads;   // LDS tap-read wave instructions (LDS-tile kernels)
-  uint32_t tf;          // samples inside the sample range (LUT fetched)
-  uint32_t active;      // lane slots that did work (path-traced modes, flush_counts)
-  uint32_t pad;
-};
 
 __global__ void zero_totals(unsigned long long* sums) { sums[threadIdx.x] = 0ull; }   // 10 totals (fold_records)
 
@@ -122,19 +81,6 @@ VXD void add_counts(DevCounters* dc, uint32_t samples, uint32_t rays, uint32_t p
     c.grads += grads;
     *w = c;
   }
-}
-
-// max over the 64 lanes of the wave, in every lane (whole waves, like wave_sum)
-VXD uint32_t wave_max_u32(uint32_t x) {
-  int v = (int)x;   // trip counts: far below 2^31
-  auto mx = [](int a, int b) { return a > b ? a : b; };
-  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
-  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
-  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));
-  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));
-  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
-  v = mx(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));
-  return (uint32_t)__builtin_amdgcn_readlane(v, 63);
 }
 
 // The path-traced modes also report their march lane slots (VxCounters.lane_slots / active_lane_slots): a wave runs each of its

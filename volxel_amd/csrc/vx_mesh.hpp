@@ -24,26 +24,9 @@
 // every output word has one writer, and every write is guarded by the totals the host sized the outputs with.
 #pragma once
 
-#include "vx_segment.hpp"
+#include "vx_device.hpp"
 
 namespace vx {
-
-struct MeshStats {
-  unsigned long long verts, quads, active_blocks;
-  uint32_t lo[3], hi[3];   // bbox of the active cells as cell + 1 (cells start at -1)
-};
-
-struct MeshDev {
-  uint64_t* inside;   // nb * 8 words
-  uint64_t* act;      // ncb * 8 words: the active cells of every cell block
-  uint2* vq;          // ncb: {vertices, quads} of the block
-  uint2* off;         // ncb: their exclusive prefix sums
-  uint2* part;        // np: the sums of each workgroup of mesh_active (256 blocks)
-  uint2* poff;        // np: their exclusive prefix sums
-  MeshStats* st;
-  uint32_t bc[3], cb[3];   // bricks, cell blocks (= bricks + 1) per axis
-  uint32_t nb, ncb, np;
-};
 
 struct MeshBox {
   uint32_t lo[3], hi[3];

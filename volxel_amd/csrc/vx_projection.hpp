@@ -9,7 +9,7 @@
 namespace vx {
 
 // Range skipping (SKIP): `pbound` holds ONE float per macro cell of the empty-space grid (v.skip_level / v.skip_dims), the upper
-// density bound for MIP and the lower one for MinIP (vx_api.hip compute_projection_bounds).  It stays in global memory and is
+// density bound for MIP and the lower one for MinIP (vx_host.hpp compute_projection_bounds).  It stays in global memory and is
 // read through the caches: 65 536 cells x 4 B does not fit beside the TF and the tiles in a CU's 160 KB of LDS, a table rounded
 // to 8 or 16 bits would skip less, and the bound is only read in free flight -- once per lane and flight round before a window
 // is placed, not per march step -- where one cached load per lane is small against the window it saves.

@@ -21,33 +21,7 @@
 
 namespace vx {
 
-constexpr uint64_t SEG_COL0 = 0x0101010101010101ull, SEG_COL7 = 0x8080808080808080ull;   // x = 0 / x = 7 of every row
-constexpr uint64_t SEG_ROW0 = 0x00000000000000ffull, SEG_ROW7 = 0xff00000000000000ull;   // y = 0 / y = 7
 constexpr uint32_t SEG_FIXPOINT_MAX = 512u;   // in-brick dilation steps: each one that changes adds a voxel
-
-// the statistics and round bookkeeping of one segment (device side; vx_api.hip reads it back whole)
-struct SegStats {
-  unsigned long long count;
-  uint32_t lo[3], hi[3];      // bbox, inclusive
-  uint32_t dmin, dmax;        // seg_order_key of the extreme densities
-  double sum;                 // written by seg_sum
-  uint32_t rounds;            // flood launches with a non-empty worklist
-  uint32_t pad;
-  unsigned long long visits;  // worklist entries processed
-};
-
-struct SegDev {
-  uint64_t* pred;        // nb * 8 words
-  uint64_t* seg;         // nb * 8 words
-  double* partial;       // nb: each brick's float64 sum
-  uint32_t* any;         // nb: the predicate has a bit in the brick
-  uint32_t* stamp;       // nb: the round + 1 whose worklist the brick was last appended to
-  uint32_t* list[2];     // nb each: the worklists of even and odd rounds
-  uint32_t* cnt;         // 3: the worklist lengths of rounds r, r + 1, r + 2 (mod 3)
-  SegStats* st;
-  uint32_t bc[3];
-  uint32_t nb;
-};
 
 // the seed of the flood: its brick, word and bit
 struct SegSeed {
@@ -59,12 +33,6 @@ struct SegSeed {
 VXD uint32_t seg_order_key(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// d(i) = (volume_density_scale * v(i)) * volume_inv_maj: trilinear_q at q = i, where every mix weight is 0
-template <int LAYOUT>
-VXD float seg_density(const DevVolume& v, float scale, float inv_maj, uint32_t x, uint32_t y, uint32_t z) {
-  return (scale * lookup_density_nearest<LAYOUT>(v, (int)x, (int)y, (int)z)) * inv_maj;
 }
 
 struct SegPredParams {
