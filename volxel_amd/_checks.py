@@ -1,0 +1,74 @@
+"""The argument checks that several renderer methods share, as pure functions: each returns the value in the form the C
+structs take, or raises the ValueError of the method that asked.  Nothing here touches the device."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import _abi
+
+
+def integer(x, lo: int, hi: int, message: str, whole_floats: bool = True) -> int:
+    """x as an int in lo .. hi, or ValueError(message).  A bool never passes; a float with a whole value (2.0) passes unless
+    whole_floats is False, which asks for an int or a NumPy integer."""
+    whole = int(x) == x if whole_floats else isinstance(x, (int, np.integer))
+    if isinstance(x, bool) or not whole or not lo <= int(x) <= hi:
+        raise ValueError(message)
+    return int(x)
+
+
+def voxel(name: str, v, ext) -> tuple:
+    """the voxel v = (x, y, z) inside the index extent; `name` is what the caller's argument is called"""
+    t = tuple(v)
+    if len(t) != 3 or any(isinstance(a, bool) or int(a) != a for a in t):
+        raise ValueError(f"{name} must be three integer voxel indices (x, y, z), not {v!r}")
+    if not all(0 <= int(a) < e for a, e in zip(t, ext)):
+        raise ValueError(f"{name} {v!r} is outside the index extent {tuple(ext)}")
+    return tuple(int(a) for a in t)
+
+
+def band(lo, hi):
+    """(lo, hi) as float32 with lo <= hi; hi = inf stands for the largest float32"""
+    lo32 = np.float32(lo)
+    hi32 = np.float32(np.finfo(np.float32).max) if hi == math.inf else np.float32(hi)
+    if not (np.isfinite(lo32) and np.isfinite(hi32)):
+        raise ValueError(f"lo and hi must be finite (hi may be inf), not {lo!r}, {hi!r}")
+    if lo32 > hi32:
+        raise ValueError(f"lo = {lo!r} > hi = {hi!r}")
+    return lo32, hi32
+
+
+def connectivity(c) -> int:
+    if c not in (6, 26) or isinstance(c, bool):
+        raise ValueError(f"connectivity must be 6 or 26, not {c!r}")
+    return int(c)
+
+
+def box(b, ext):
+    """(lo, hi) of box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices inside the index extent; None: all of it"""
+    if b is None:
+        return (0, 0, 0), tuple(e - 1 for e in ext)
+    try:
+        blo, bhi = (tuple(v) for v in b)
+    except (TypeError, ValueError):
+        raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)), not {b!r}") from None
+    if len(blo) != 3 or len(bhi) != 3 or any(isinstance(a, bool) or int(a) != a for a in blo + bhi):
+        raise ValueError(f"box must be ((x0, y0, z0), (x1, y1, z1)) of integers, not {b!r}")
+    blo, bhi = tuple(int(a) for a in blo), tuple(int(a) for a in bhi)
+    if not all(0 <= a <= b1 < e for a, b1, e in zip(blo, bhi, ext)):
+        raise ValueError(f"box {b!r} is empty or outside the index extent {tuple(ext)}")
+    return blo, bhi
+
+
+def slice_spec(sp):
+    """(W, H, slab samples) of a VxSliceParams whose size, slab_samples and vectors the device will accept"""
+    W, H, N = int(sp.size[0]), int(sp.size[1]), int(sp.slab_samples)
+    if not (1 <= W <= _abi.SLICE_MAX_SIZE and 1 <= H <= _abi.SLICE_MAX_SIZE):
+        raise ValueError(f"slice size must be 1 .. {_abi.SLICE_MAX_SIZE} per side, not {W} x {H}")
+    if not 1 <= N <= _abi.SLICE_MAX_SAMPLES:
+        raise ValueError(f"slab_samples must be 1 .. {_abi.SLICE_MAX_SAMPLES}, not {N}")
+    for name in ("origin", "du", "dv", "dn"):
+        if not np.isfinite(np.asarray(getattr(sp, name)[:], dtype=np.float32)).all():
+            raise ValueError(f"slice {name} must be finite")
+    return W, H, N

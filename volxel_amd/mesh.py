@@ -7,6 +7,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import _checks
+
 MESH_SPACES = ("voxel", "grid", "world")
 
 
@@ -90,8 +92,7 @@ def check_extract_args(iso, segment, space, max_vertices, max_triangles):
     if space not in MESH_SPACES:
         raise ValueError(f"space must be one of {MESH_SPACES}, not {space!r}")
     for name, v in (("max_vertices", max_vertices), ("max_triangles", max_triangles)):
-        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 2 ** 32:
-            raise ValueError(f"{name} must be an integer 0 .. 2^32 - 1, not {v!r}")
+        _checks.integer(v, 0, 2 ** 32 - 1, f"{name} must be an integer 0 .. 2^32 - 1, not {v!r}")
     if segment:
         return None
     with np.errstate(over="ignore"):

@@ -241,7 +241,6 @@ function readZipSlices(buf) {
 }
 /** worker.ts:115-126 fetch(url) + exportResponseBytes: a path or a file:// URL (this Node has no fetch, the machines no network) */
 function fetchBytes(url) {
-  const fs = require('fs');
   if (/^file:\/\//.test(url)) return fs.readFileSync(new (require('url').URL)(url));
   if (/^[a-z][a-z0-9+.-]*:\/\//i.test(url)) throw new Error(`fetch is not available in this host: ${url} (read the bytes and call the *Bytes / loadEnv method)`);
   return fs.readFileSync(url);
@@ -277,6 +276,35 @@ function decodeEnvironment(b) {
     floats[4 * i] = Math.fround(px[4 * i] * s); floats[4 * i + 1] = Math.fround(px[4 * i + 1] * s); floats[4 * i + 2] = Math.fround(px[4 * i + 2] * s); floats[4 * i + 3] = 1;
   }
   return { floats, width: w, height: h };
+}
+
+// ---- the argument checks several methods share; `who` is the calling method, the prefix of its messages ------------------
+const F32_MAX = 3.4028234663852886e38;
+const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
+/** [lo, hi] as float32 with lo <= hi; hi = Infinity stands for the largest float32 */
+function checkBand(who, lo, hi) {
+  const l32 = Math.fround(lo), h32 = hi === Infinity ? F32_MAX : Math.fround(hi);
+  if (!Number.isFinite(l32) || !Number.isFinite(h32)) throw new Error(`${who}: lo and hi must be finite (hi may be Infinity)`);
+  if (l32 > h32) throw new Error(`${who}: lo = ${lo} > hi = ${hi}`);
+  return [l32, h32];
+}
+/** [lo, hi] of box = [[x0, y0, z0], [x1, y1, z1]], inclusive voxel indices inside the index extent e; null: all of it */
+function checkBox(who, box, e) {
+  const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
+  if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
+    throw new Error(`${who}: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+  return [blo, bhi];
+}
+/** the voxel v = [x, y, z] inside the index extent e; `name` is what the method calls it */
+const checkVoxel = (who, name, v, e) => { if (!ints(v) || !v.every((x, a) => x >= 0 && x < e[a])) throw new Error(`${who}: ${name} ${v} is outside the index extent ${e}`); };
+const checkConnectivity = (who, c) => { if (c !== 6 && c !== 26) throw new Error(`${who}: connectivity must be 6 or 26, not ${c}`); };
+/** the VxSliceParams block of a slice spec with reduce = mean, no display and the window [0, 1] */
+function sliceParams(who, origin, du, dv, dn, [W, H], slabSamples) {
+  if (!(W >= 1 && W <= 16384 && H >= 1 && H <= 16384)) throw new Error(`${who}: size must be 1 .. 16384 per side, not ${W} x ${H}`);
+  const p = new ParamsBlock(SLICE_LAYOUT);
+  p.set('origin', origin); p.set('du', du); p.set('dv', dv); p.set('dn', dn);
+  p.set('size', [W, H]); p.set('slab_samples', slabSamples); p.set('reduce', 0); p.set('display', 0); p.set('window', [0, 1]);
+  return p;
 }
 
 let workerFactory = null;
@@ -336,12 +364,10 @@ class Volxel3DDicomRenderer {
 
   /** restartFromFiles (viewer.ts:963-975): DICOM slice paths (or Uint8Arrays) in stacking order */
   restartFromFiles(files, threads = 0) {
-    const fs = require('fs');
     this.restartFromBytes(files.map(f => (typeof f === 'string' ? new Uint8Array(fs.readFileSync(f)) : f)), threads);
   }
   /** restartFromZip (viewer.ts:977-989): a ZIP of DICOM slices (Buffer / Uint8Array / path), folder rule of zip.rs:54-70 */
   restartFromZip(zip, threads = 0) {
-    const fs = require('fs');
     this.restartFromBytes(readZipSlices(typeof zip === 'string' ? fs.readFileSync(zip) : Buffer.from(zip.buffer || zip, zip.byteOffset || 0, zip.byteLength)), threads);
   }
   /** restartFromZipUrl (viewer.ts:991-1003, worker.ts:115-118) */
@@ -573,13 +599,9 @@ class Volxel3DDicomRenderer {
     if (display === 'grey' && !(window && window.length === 2 && Math.fround(window[1]) > Math.fround(window[0])))
       throw new Error('slice: display grey needs window = [black, white] with black < white');
     if (display !== 'grey' && window !== null) throw new Error('slice: window applies to display grey only');
-    const [W, H] = size;
-    if (!(W >= 1 && W <= 16384 && H >= 1 && H <= 16384)) throw new Error(`slice: size must be 1 .. 16384 per side, not ${W} x ${H}`);
-    const p = new ParamsBlock(SLICE_LAYOUT);
-    p.set('origin', origin); p.set('du', du); p.set('dv', dv); p.set('dn', dn);
-    p.set('size', [W, H]); p.set('slab_samples', slabSamples);
+    const p = sliceParams('slice', origin, du, dv, dn, size, slabSamples), [W, H] = size;
     p.set('reduce', SliceReduce[reduce]); p.set('display', display === null ? 0 : SliceDisplay[display]);
-    p.set('window', display === 'grey' ? window : [0, 1]);
+    if (display === 'grey') p.set('window', window);
     this.bindUniforms();
     const values = new Float32Array(W * H), rgba8 = display === null ? null : new Uint8Array(W * H * 4);
     native.slice(this.ctx, p.buffer, values, rgba8);
@@ -628,16 +650,10 @@ class Volxel3DDicomRenderer {
    *  dMax, dSum, mean, rounds, converged, brickVisits }.  Binds the current uniforms first. */
   segment(seed, lo, { hi = Infinity, connectivity = 6, box = null, maxRounds = 0 } = {}) {
     const e = this.sliceExtent();
-    const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
-    if (!ints(seed) || !seed.every((x, a) => x >= 0 && x < e[a])) throw new Error(`segment: seed ${seed} is outside the index extent ${e}`);
-    const F32_MAX = 3.4028234663852886e38;
-    const l32 = Math.fround(lo), h32 = hi === Infinity ? F32_MAX : Math.fround(hi);
-    if (!Number.isFinite(l32) || !Number.isFinite(h32)) throw new Error('segment: lo and hi must be finite (hi may be Infinity)');
-    if (l32 > h32) throw new Error(`segment: lo = ${lo} > hi = ${hi}`);
-    if (connectivity !== 6 && connectivity !== 26) throw new Error(`segment: connectivity must be 6 or 26, not ${connectivity}`);
-    const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
-    if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
-      throw new Error(`segment: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+    checkVoxel('segment', 'seed', seed, e);
+    const [l32, h32] = checkBand('segment', lo, hi);
+    checkConnectivity('segment', connectivity);
+    const [blo, bhi] = checkBox('segment', box, e);
     if (!Number.isInteger(maxRounds) || maxRounds < 0 || maxRounds > 4294967295) throw new Error(`segment: maxRounds must be an integer >= 0`);
     const p = new ParamsBlock(SEGMENT_LAYOUT);
     p.set('seed', seed); p.set('lo', l32); p.set('hi', h32); p.set('connectivity', connectivity);
@@ -652,7 +668,7 @@ class Volxel3DDicomRenderer {
   segmentEdit(op, { steps = 1, connectivity = 6, band = false } = {}) {
     const i = SEGMENT_EDIT_OPS.indexOf(op);
     if (i < 0) throw new Error(`segmentEdit: op must be one of ${SEGMENT_EDIT_OPS.join(', ')}, not ${op}`);
-    if (connectivity !== 6 && connectivity !== 26) throw new Error(`segmentEdit: connectivity must be 6 or 26, not ${connectivity}`);
+    checkConnectivity('segmentEdit', connectivity);
     const fill = op === 'fill_holes';
     if (!Number.isInteger(steps) || steps < (fill ? 0 : 1) || steps > (fill ? 1 : 1024))
       throw new Error(`segmentEdit: steps must be an integer ${fill ? '0 .. 1' : '1 .. 1024'} for ${op}, not ${steps}`);
@@ -681,14 +697,7 @@ class Volxel3DDicomRenderer {
    *  Infinity, box = null } -> what segment() returns (rounds = brickVisits = 0).  Binds the current uniforms first. */
   threshold(lo, { hi = Infinity, box = null } = {}) {
     const e = this.sliceExtent();
-    const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
-    const F32_MAX = 3.4028234663852886e38;
-    const l32 = Math.fround(lo), h32 = hi === Infinity ? F32_MAX : Math.fround(hi);
-    if (!Number.isFinite(l32) || !Number.isFinite(h32)) throw new Error('threshold: lo and hi must be finite (hi may be Infinity)');
-    if (l32 > h32) throw new Error(`threshold: lo = ${lo} > hi = ${hi}`);
-    const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
-    if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
-      throw new Error(`threshold: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+    const [l32, h32] = checkBand('threshold', lo, hi), [blo, bhi] = checkBox('threshold', box, e);
     const p = new ParamsBlock(SEGMENT_LAYOUT);
     p.set('seed', [0, 0, 0]); p.set('lo', l32); p.set('hi', h32); p.set('connectivity', 6);
     p.set('box_lo', blo); p.set('box_hi', bhi); p.set('max_rounds', 0);
@@ -696,7 +705,7 @@ class Volxel3DDicomRenderer {
     return this._segmentResult(native.segmentThreshold(this.ctx, p.buffer));
   }
   _islandsCall(name, op, connectivity, keep = 0, minVoxels = 0, seed = [0, 0, 0]) {
-    if (connectivity !== 6 && connectivity !== 26) throw new Error(`${name}: connectivity must be 6 or 26, not ${connectivity}`);
+    checkConnectivity(name, connectivity);
     this.bindUniforms();
     const r = native.segmentIslands(this.ctx, op, connectivity, keep, minVoxels, seed[0], seed[1], seed[2]);
     this._islandRows = r.kept;
@@ -734,9 +743,7 @@ class Volxel3DDicomRenderer {
   }
   /** keeps the island of the current segment that holds voxel = [x, y, z] (the empty set when the voxel is not in it) */
   keepIslandAt(voxel, { connectivity = 6 } = {}) {
-    const e = this.sliceExtent();
-    if (!Array.isArray(voxel) || voxel.length !== 3 || !voxel.every((x, a) => Number.isInteger(x) && x >= 0 && x < e[a]))
-      throw new Error(`keepIslandAt: voxel ${voxel} is outside the index extent ${e}`);
+    checkVoxel('keepIslandAt', 'voxel', voxel, this.sliceExtent());
     return this._islandSegment(this._islandsCall('keepIslandAt', 3, connectivity, 0, 0, voxel));
   }
   /** the last islands call: kernels launched and the times of its passes; hostRankMs is the host's ranking of the rows */
@@ -755,11 +762,7 @@ class Volxel3DDicomRenderer {
       if (!Number.isInteger(v) || v < 0 || v > 4294967295) throw new Error(`extractMesh: ${k} must be an integer 0 .. 2^32 - 1, not ${v}`);
     const i32 = segment ? 0 : Math.fround(iso);
     if (!segment && !(Number.isFinite(i32) && i32 > 0)) throw new Error(`extractMesh: iso must be finite and > 0, not ${iso}`);
-    const e = this.sliceExtent();
-    const ints = (v) => Array.isArray(v) && v.length === 3 && v.every(Number.isInteger);
-    const [blo, bhi] = box === null ? [[0, 0, 0], e.map(x => x - 1)] : box;
-    if (!ints(blo) || !ints(bhi) || ![0, 1, 2].every(a => blo[a] >= 0 && blo[a] <= bhi[a] && bhi[a] < e[a]))
-      throw new Error(`extractMesh: box ${JSON.stringify(box)} is empty or outside the index extent ${e}`);
+    const [blo, bhi] = checkBox('extractMesh', box, this.sliceExtent());
     const p = new ParamsBlock(MESH_LAYOUT);
     p.set('source', segment ? 1 : 0); p.set('iso', i32); p.set('box_lo', blo); p.set('box_hi', bhi);
     p.set('max_vertices', maxVertices); p.set('max_triangles', maxTriangles);
@@ -823,11 +826,7 @@ class Volxel3DDicomRenderer {
   /** the current segment on a slice spec (axial / coronal / sagittal or { origin, du, dv, dn, size, slabSamples }):
    *  { mask: Uint8Array (W*H, 0 / 1, row 0 = y = 0), width, height } */
   sliceMask({ origin, du, dv, dn, size, slabSamples = 1 }) {
-    const [W, H] = size;
-    if (!(W >= 1 && W <= 16384 && H >= 1 && H <= 16384)) throw new Error(`sliceMask: size must be 1 .. 16384 per side, not ${W} x ${H}`);
-    const p = new ParamsBlock(SLICE_LAYOUT);
-    p.set('origin', origin); p.set('du', du); p.set('dv', dv); p.set('dn', dn);
-    p.set('size', [W, H]); p.set('slab_samples', slabSamples); p.set('reduce', 0); p.set('display', 0); p.set('window', [0, 1]);
+    const p = sliceParams('sliceMask', origin, du, dv, dn, size, slabSamples), [W, H] = size;
     const mask = new Uint8Array(W * H);
     native.sliceMask(this.ctx, p.buffer, mask);
     return { mask, width: W, height: H };

@@ -1,0 +1,280 @@
+"""The segment chain of `Volxel3DRenderer` (vx_api_segment.hip): seeded region growing and thresholds, edits, islands, the
+masked views, the masks and voxel_index.  A mixin: the renderer supplies _lib, _ctx, _check, _out, _index_extent,
+bind_uniforms and restart_rendering."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _abi, _checks
+from ._errors import VolxelError
+
+
+@dataclass(frozen=True)
+class Segment:
+    """What Volxel3DRenderer.segment returns (VxSegmentResult): the voxel count, the inclusive bbox (x, y, z), min / max / sum
+    (float64) / mean of the density over the segment (0, 0, 0 and nan when empty), the flood's rounds and brick visits (which may
+    vary from run to run), whether it converged, and its volume: volume_grid = count * |det(grid.transform[:3, :3])| in the
+    grid's own units (the voxel spacing: mm^3 for DICOM), volume_world = count * |det(density_transform[:3, :3])| in the
+    scene's, where the volume is normalised to a unit box."""
+    count: int
+    bbox_lo: tuple
+    bbox_hi: tuple
+    d_min: float
+    d_max: float
+    d_sum: float
+    mean: float
+    rounds: int
+    converged: bool
+    brick_visits: int
+    volume_grid: float
+    volume_world: float
+
+
+@dataclass(frozen=True)
+class IslandSegment(Segment):
+    """The `Segment` of the mask after keep_largest_islands / remove_small_islands / keep_island_at, with the op's own
+    figures (VxIslandsResult): `islands` of the mask before the op, `kept` after it, `largest` = the voxel count of the
+    largest island before the op (0 for an empty mask)."""
+    islands: int = 0
+    kept: int = 0
+    largest: int = 0
+
+
+class Islands:
+    """What Volxel3DRenderer.islands returns: the islands of the current segment in canonical order (count descending, ties by
+    the C-order index of the anchor ascending; island k has label k + 1).  count: how many; sizes: their voxel counts (uint64);
+    table: one dict per island (label, count, anchor, bbox_lo, bbox_hi, each (x, y, z)); largest; segment: the `Segment` of the
+    labelled mask; labels(): the dense (Z, Y, X) uint32 label volume, read from the device when asked (refused once the
+    segment has changed)."""
+
+    def __init__(self, renderer, res, rows, segment):
+        self._renderer = renderer
+        self.count = int(res.islands)
+        self.largest = int(res.largest)
+        self.segment = segment
+        self.sizes = np.array([r.count for r in rows], dtype=np.uint64)
+        self.table = [dict(label=int(r.label), count=int(r.count), anchor=tuple(r.anchor[:]), bbox_lo=tuple(r.bbox_lo[:]),
+                           bbox_hi=tuple(r.bbox_hi[:])) for r in rows]
+
+    def labels(self) -> np.ndarray:
+        return self._renderer.island_labels()
+
+    def __len__(self):
+        return self.count
+
+
+class SegmentMixin:
+    def segment(self, seed, lo: float, hi: float = math.inf, connectivity: int = 6, box=None, max_rounds: int = 0):
+        """Seeded region growing (vx_segment, DESIGN.md section 2 "Segmentation"): the connected component of
+        lo <= d(i) <= hi (both inclusive; d(i) = (volume_density_scale * v(i)) * volume_inv_maj, the isosurfaces' density at
+        q = i) inside `box` that holds the voxel `seed` = (x, y, z).  connectivity: 6 (faces) or 26 (faces, edges, corners).
+        box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices, or None for the whole volume.  hi = inf stands for the
+        largest float32.  max_rounds: a cap on the flood's rounds (0: no practical cap); a capped flood returns
+        converged = False and a connected part of the segment.  Binds the current uniforms first.  Returns a `Segment`; the
+        mask stays on the device (segment_mask, slice_mask) until the next segment or upload."""
+        ext = self._index_extent("segment")
+        q = _abi.VxSegmentParams()
+        q.seed[:] = _checks.voxel("seed", seed, ext)
+        q.lo, q.hi = (float(a) for a in _checks.band(lo, hi))
+        q.connectivity = _checks.connectivity(connectivity)
+        q.box_lo[:], q.box_hi[:] = _checks.box(box, ext)
+        q.max_rounds = _checks.integer(max_rounds, 0, 2 ** 32 - 1,
+                                       f"max_rounds must be an integer 0 .. 2^32 - 1, not {max_rounds!r}")
+        return self._segment_call("vx_segment", C.byref(q))
+
+    def _segment_call(self, fn: str, *args) -> Segment:
+        """binds the current uniforms, runs the entry point fn(ctx, *args, &result) and returns the result's `Segment`"""
+        p = self.bind_uniforms()
+        res = _abi.VxSegmentResult()
+        self._check(getattr(self._lib, fn)(self._ctx, *args, C.byref(res)))
+        return self._segment_result(res, p)
+
+    def _segment_result(self, res, p, restart: bool = True) -> Segment:
+        """the `Segment` of a VxSegmentResult under the uniforms p just bound (segment, segment_edit, set_segment_mask); the
+        masked views show the new mask, so accumulation restarts when one is on"""
+        if restart and self.segment_view != "off":
+            self.restart_rendering()
+        g3 = np.asarray(self.volume.grid.transform, dtype=np.float64)[:3, :3]
+        d3 = np.asarray(p.density_transform[:], dtype=np.float32).astype(np.float64).reshape(4, 4).T[:3, :3]
+        n = int(res.count)
+        return Segment(count=n, bbox_lo=tuple(res.bbox_lo[:]), bbox_hi=tuple(res.bbox_hi[:]), d_min=float(res.d_min),
+                       d_max=float(res.d_max), d_sum=float(res.d_sum), mean=float(res.d_sum) / n if n else math.nan,
+                       rounds=int(res.rounds), converged=bool(res.converged), brick_visits=int(res.brick_visits),
+                       volume_grid=n * abs(float(np.linalg.det(g3))), volume_world=n * abs(float(np.linalg.det(d3))))
+
+    SEGMENT_EDIT_OPS = ("dilate", "erode", "open", "close", "fill_holes")   # VxSegmentEditOp, in order
+
+    def segment_edit(self, op: str, steps: int = 1, connectivity: int = 6, band: bool = False) -> Segment:
+        """Edits the current segment on the GPU (vx_segment_edit, DESIGN.md section 2 "Segment edits"): "dilate" / "erode" by
+        `steps` voxels of the 6- or 26-neighbourhood (outside the volume counts as not set for dilate and as set for erode),
+        "open" (erode then dilate), "close" (dilate then erode), or "fill_holes" (the background components, under
+        `connectivity`, that touch no face of the volume; steps is ignored).  band=True (dilate only) grows only into voxels
+        that pass the predicate of the last segment().  Binds the current uniforms first; returns the `Segment` of the edited
+        mask (rounds and brick_visits: the fill's background flood)."""
+        self._index_extent("segment_edit")
+        if op not in self.SEGMENT_EDIT_OPS:
+            raise ValueError(f"op must be one of {self.SEGMENT_EDIT_OPS}, not {op!r}")
+        q = _abi.VxSegmentEditParams()
+        q.op, q.connectivity = _abi.SEGEDIT_OPS[op], _checks.connectivity(connectivity)
+        lo, hi = (0, 1) if op == "fill_holes" else (1, _abi.SEGEDIT_MAX_STEPS)
+        q.steps = _checks.integer(steps, lo, hi, f"steps must be an integer {lo} .. {hi} for {op}, not {steps!r}",
+                                  whole_floats=False)
+        if not isinstance(band, (bool, np.bool_)):
+            raise ValueError(f"band must be a bool, not {band!r}")
+        if band and op != "dilate":
+            raise ValueError(f"band is for dilate only, not {op}")
+        q.band = int(bool(band))
+        return self._segment_call("vx_segment_edit", C.byref(q))
+
+    def set_segment_mask(self, mask) -> Segment:
+        """Installs a (Z, Y, X) bool array over the index extent as the current segment (vx_segment_write_mask, the inverse of
+        segment_mask): a saved segmentation, a host-side combination of masks, or an undo.  The predicate of the last
+        segment() and the segment view stay.  Binds the current uniforms first; returns the mask's `Segment`."""
+        X, Y, Z = self._index_extent("set_segment_mask")
+        m = np.asarray(mask)
+        if m.dtype != np.bool_:
+            raise ValueError(f"mask must be a bool array, not {m.dtype}")
+        if m.shape != (Z, Y, X):
+            raise ValueError(f"mask shape must be (Z, Y, X) = {(Z, Y, X)} of the index extent, not {m.shape}")
+        bits = np.packbits(np.ascontiguousarray(m).ravel(), bitorder="little")
+        return self._segment_call("vx_segment_write_mask", bits.ctypes.data, bits.size)
+
+    def segment_edit_stats(self):
+        """(launches, edit_ms, stats_ms) of the last segment_edit or set_segment_mask (vx_segment_edit_stats)"""
+        return self._out("vx_segment_edit_stats", C.c_uint32, C.c_double * 2)
+
+    def threshold(self, lo: float, hi: float = math.inf, box=None) -> Segment:
+        """The whole band as the current segment, without a seed (vx_segment_threshold): every voxel with lo <= d(i) <= hi
+        inside `box`; arguments as for segment().  It also becomes the predicate of band dilation.  Returns its `Segment`
+        (rounds = brick_visits = 0)."""
+        ext = self._index_extent("threshold")
+        q = _abi.VxSegmentParams()
+        q.lo, q.hi = (float(a) for a in _checks.band(lo, hi))
+        q.connectivity = 6
+        q.box_lo[:], q.box_hi[:] = _checks.box(box, ext)
+        return self._segment_call("vx_segment_threshold", C.byref(q))
+
+    def _islands_call(self, name, op, connectivity, keep=0, min_voxels=0, seed=(0, 0, 0)):
+        self._index_extent(name)
+        q = _abi.VxIslandsParams()
+        q.op, q.connectivity, q.keep, q.min_voxels = _abi.ISLANDS_OPS[op], _checks.connectivity(connectivity), keep, min_voxels
+        q.seed[:] = seed
+        p = self.bind_uniforms()
+        res = _abi.VxIslandsResult()
+        self._check(self._lib.vx_segment_islands(self._ctx, C.byref(q), C.byref(res)))
+        self._island_rows = int(res.kept)
+        # (labelling leaves the mask as it was: a masked view does not restart)
+        return res, self._segment_result(res.seg, p, restart=op != "label")
+
+    def _island_segment(self, res, seg) -> IslandSegment:
+        return IslandSegment(**{f: getattr(seg, f) for f in Segment.__dataclass_fields__}, islands=int(res.islands),
+                             kept=int(res.kept), largest=int(res.largest))
+
+    def islands(self, connectivity: int = 6) -> Islands:
+        """Labels the islands of the current segment on the GPU (vx_segment_islands, DESIGN.md section 2 "Islands"): its 6- or
+        26-connected components, ordered by voxel count descending, ties by the first voxel in C order.  The segment is not
+        changed.  Returns an `Islands` (count, sizes, table, labels())."""
+        res, seg = self._islands_call("islands", "label", connectivity)
+        return Islands(self, res, self.island_table(), seg)
+
+    def island_table(self, first: int = 0, n: int | None = None):
+        """rows first .. first + n - 1 (default: all the rest) of the current island table as VxIsland structs (vx_islands_read)"""
+        if n is None:
+            n = max(getattr(self, "_island_rows", 0) - int(first), 0)
+        rows = (_abi.VxIsland * max(int(n), 1))()
+        self._check(self._lib.vx_islands_read(self._ctx, int(first), int(n), rows))
+        return list(rows[:int(n)])
+
+    def island_labels(self) -> np.ndarray:
+        """the dense (Z, Y, X) uint32 label volume of the current island table: 0 outside the segment, k + 1 for island k
+        (vx_islands_read_labels)"""
+        X, Y, Z = self._index_extent("island_labels", hint="")
+        out = np.empty((Z, Y, X), dtype=np.uint32)
+        self._check(self._lib.vx_islands_read_labels(self._ctx, out.ctypes.data, out.size))
+        return out
+
+    def keep_largest_islands(self, n: int = 1, connectivity: int = 6) -> IslandSegment:
+        """Keeps the n largest islands of the current segment (canonical order; n >= the number of islands keeps all).  Returns
+        the `Segment` of the new mask with .islands (before), .kept (after) and .largest."""
+        n = _checks.integer(n, 1, 2 ** 64 - 1, f"n must be an integer >= 1, not {n!r}", whole_floats=False)
+        return self._island_segment(*self._islands_call("keep_largest_islands", "keep_largest", connectivity, keep=n))
+
+    def remove_small_islands(self, min_voxels: int, connectivity: int = 6) -> IslandSegment:
+        """Removes the islands of fewer than min_voxels voxels from the current segment (none left is legal)."""
+        min_voxels = _checks.integer(min_voxels, 1, 2 ** 64 - 1, f"min_voxels must be an integer >= 1, not {min_voxels!r}",
+                                     whole_floats=False)
+        return self._island_segment(*self._islands_call("remove_small_islands", "remove_small", connectivity,
+                                                        min_voxels=min_voxels))
+
+    def keep_island_at(self, voxel, connectivity: int = 6) -> IslandSegment:
+        """Keeps the island of the current segment that holds `voxel` = (x, y, z); the empty set when the voxel is not in it."""
+        sd = _checks.voxel("voxel", voxel, self._index_extent("keep_island_at"))
+        return self._island_segment(*self._islands_call("keep_island_at", "keep_at", connectivity, seed=sd))
+
+    def islands_stats(self):
+        """(launches, local_ms, merge_ms, flatten_ms, table_ms, host_rank_ms, apply_ms, stats_ms) of the last islands call
+        (vx_islands_stats); host_rank_ms is the host's wall clock for reading back, ranking and re-uploading the rows"""
+        return self._out("vx_islands_stats", C.c_uint32, C.c_double * 7)
+
+    SEGMENT_VIEWS = ("off", "only", "hide")   # VX_SEGVIEW_OFF, _ONLY, _HIDE
+
+    @property
+    def segment_view(self) -> str:
+        """"off" (the default, and again after setup_from_grid), "only" (the current segment alone) or "hide" (everything but
+        it): DVR, Phong, MIP / MinIP renders and the isosurfaces (hence pick) sample a volume whose hidden voxels read 0
+        (vx_set_segment_view, DESIGN.md section 2 "Segment views"); slices and segment() keep the unmasked data"""
+        return self.SEGMENT_VIEWS[self._out("vx_get_segment_view", C.c_int32)[0]]
+
+    @segment_view.setter
+    def segment_view(self, view: str):
+        if view not in self.SEGMENT_VIEWS:
+            raise VolxelError(f"segment_view must be one of {self.SEGMENT_VIEWS}, not {view!r}")
+        self._check(self._lib.vx_set_segment_view(self._ctx, self.SEGMENT_VIEWS.index(view)))
+        self.restart_rendering()
+
+    def segment_mask(self) -> np.ndarray:
+        """the current segment as a (Z, Y, X) bool array over the index extent (vx_segment_read_mask)"""
+        X, Y, Z = self._index_extent("segment_mask", hint="")
+        bits = np.empty(X * Y * Z // 8, dtype=np.uint8)
+        self._check(self._lib.vx_segment_read_mask(self._ctx, bits.ctypes.data, bits.size))
+        return np.unpackbits(bits, bitorder="little").astype(bool).reshape(Z, Y, X)
+
+    def slice_mask(self, sp) -> np.ndarray:
+        """the current segment on the slice or slab sp (volxel_amd.mpr; reduce, display and window are ignored): an (H, W)
+        bool array, True where the nearest voxel of any slab sample is in the segment (vx_slice_segment_mask)"""
+        if not isinstance(sp, _abi.VxSliceParams):
+            raise TypeError("sp must be a VxSliceParams (volxel_amd.mpr builds them)")
+        W, H, _ = _checks.slice_spec(sp)
+        out = np.empty((H, W), dtype=np.uint8)
+        self._check(self._lib.vx_slice_segment_mask(self._ctx, C.byref(sp), out.ctypes.data))
+        return out.astype(bool)
+
+    def segment_stats(self):
+        """(rounds, brick_visits, predicate_ms, flood_ms, stats_ms) of the last segment; flood_ms runs from the first round to
+        the last, the host's read-backs of the worklist length included"""
+        return self._out("vx_segment_stats", C.c_uint32, C.c_uint64, C.c_double * 3)
+
+    def voxel_index(self, world_point):
+        """the voxel (x, y, z) nearest a world point, or None outside the volume: q = density_transform_inv * w - 1/2 in float64
+        (the current params, as mpr.oblique maps planes), then floor(q + 1/2) per axis.  A point from pick() lies on the
+        interpolated surface, so its nearest voxel can fall just below the threshold: seed a segment with it where the
+        structure is thicker than a voxel, or lower lo a little."""
+        ext = self._index_extent("voxel_index", hint="")
+        w = np.asarray(world_point, dtype=np.float64).reshape(-1)
+        if w.size != 3 or not np.isfinite(w).all():
+            raise ValueError(f"world_point must be three finite numbers, not {world_point!r}")
+        # the float32 matrix the uniforms carry now (compute_params, as bind_uniforms sends it), not a copy from an earlier bind
+        from .renderer import compute_params
+        p = compute_params(self.settings, self.camera, self.volume, self.density_scale, self.width, self.height,
+                           self.env_strength, self.shard_rank, self.shard_count, has_environment=self.environment is not None)
+        m = [float(v) for v in np.asarray(p.density_transform_inv[:], dtype=np.float32)]   # column major
+        # q = m * w - 1/2 in float64, each row summed x, y, z, translation in that order (the JS host's voxelIndex sums alike)
+        qv = [m[r] * w[0] + m[4 + r] * w[1] + m[8 + r] * w[2] + m[12 + r] - 0.5 for r in range(3)]
+        i = [math.floor(a + 0.5) for a in qv]
+        if not all(0 <= a < e for a, e in zip(i, ext)):
+            return None
+        return tuple(int(a) for a in i)
