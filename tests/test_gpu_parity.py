@@ -1292,7 +1292,7 @@ def test_config5_reference_modes_crop_matches_live_oracle(huge_scene, oracle, mo
 
 def test_volume_beyond_the_cellquad_index_range_is_refused(oracle):
     """more than 2^32 quads (about 1550^3 voxels) cannot be indexed by the march's 32-bit quad offsets:
-    vx_upload_volume says so and names the layouts that work (vx_api.hip alloc_layout); brick.rs:77-81 allows
+    vx_upload_volume says so and names the layouts that work (vx_api_volume.hip alloc_one_layout); brick.rs:77-81 allows
     up to 1016 bricks per axis"""
     from types import SimpleNamespace
     from volxel_amd import Volxel3DRenderer, VolxelError

@@ -6,7 +6,7 @@ name=$1; shift
 cd "$(dirname "$0")/../volxel_amd/csrc"
 tmp=$(mktemp -d)
 objs=""
-for u in vx_api vx_api_view vx_api_segment vx_api_mesh; do   # the host layer's four units
+for u in vx_api vx_api_volume vx_api_view vx_api_segment vx_api_mesh; do   # the host layer's five units
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -Wall -Wno-unused-function "$@" -c $u.hip -o $tmp/$u.o &
   objs="$objs $tmp/$u.o"
 done

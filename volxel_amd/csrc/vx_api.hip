@@ -1,10 +1,9 @@
 // vx_api.hip -- the render unit of libvolxel_hip.so's host layer (the C ABI of include/volxel_hip.h; units: DESIGN.md section
-// 4.1): contexts and device groups, uploads and layouts, the derived tables, the launch plan, rendering, read-back, counters,
-// probes and test hooks.  Every render_* kernel is instantiated here, so this unit's listing (vx_api.s) holds them all.
+// 4.1): contexts and device groups, the transfer-function and environment uploads, the derived tables, the launch plan,
+// rendering, read-back, counters, probes and test hooks.  Every render_* kernel is instantiated here, so this unit's listing (vx_api.s) holds them all.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -12,7 +11,6 @@
 #include <string>
 #include <vector>
 
-#include "../../include/volxel_brick.h"
 #include "vx_dvr.hpp"
 #include "vx_dvr_lds.hpp"
 #include "vx_dvr_miss.hpp"
@@ -43,13 +41,6 @@ Switches read_switches() {
   if (const char* v = getenv("VX_SEG_CHECK_MAX")) sw.seg_check_max = (uint32_t)std::min(std::max(atoi(v), 1), 4096);
   sw.dvr_miss = dvr_miss_switch();
   return sw;
-}
-
-// drop the resident volume and everything derived from it (the caller has made the context's device current)
-static void free_volume(VxContext* c) {
-  for (void* p : c->vol_allocs) (void)hipFree(p);
-  c->vol_allocs.clear();
-  c->vol = VxContext::Volume{};
 }
 
 static void drain_events(VxContext* c) {
@@ -110,7 +101,6 @@ static int alloc_framebuffers(VxContext* c) {
   return VX_OK;
 }
 
-static bool proj_mode(int m) { return m == VX_MODE_MIP || m == VX_MODE_MINIP; }
 // the device table: the bound the mode tests (hi for MIP, lo for MinIP), one float per macro cell
 static int rebuild_projection_bounds(VxContext* c) {
   const VxParams& p = c->params;
@@ -218,27 +208,6 @@ static int ensure_counters(VxContext* c, size_t waves) {
     c->miss.split_stale = true;
   }
   return VX_OK;
-}
-
-// The device layout the kernels of the current render mode sample.  VX_LAYOUT_AUTO (default): the DVR modes march
-// the brickf32 layout through LDS windows (vx_dvr_lds.hpp: fastest, 4 bytes per voxel), `default` and `no_dda`
-// gather from cellquad (two 16-byte loads per trilinear look-up instead of eight bounds-checked taps), `raymarch`
-// reads its single nearest tap from brickf32.
-static int primary_layout(const VxContext* c) {
-  if (c->layout != VX_LAYOUT_AUTO) return c->layout;
-  return c->auto_no_bf ? VX_LAYOUT_REFERENCE : VX_LAYOUT_BRICKF32;
-}
-static int eff_layout(const VxContext* c) {
-  if (c->layout != VX_LAYOUT_AUTO) return c->layout;
-  const int m = c->has_params ? c->params.render_mode : VX_MODE_DVR;
-  // raymarch takes ONE nearest tap per sample (common.glsl:72-76): the 4-byte-per-voxel bricks serve it better than
-  // the 18-byte-per-voxel quads, and the layout is resident already
-  if (m == VX_MODE_DVR || m == VX_MODE_DVR_PHONG || m == VX_MODE_RAYMARCH || proj_mode(m)) return primary_layout(c);
-  // `default` / `no_dda`: cellquad (18 B / voxel) while the volume is inside its index range and the build fits the device
-  // memory budget (ensure_cellquad); beyond that the fp32 bricks that are resident anyway -- eight taps per look-up, measured
-  // 1.4x / 2.0x slower than cellquad and 2.0x / 2.2x faster than the reference textures on the 1024^3 volume at 3840x2160
-  // (profiles/r04_layouts_1024.txt) -- and the reference textures only when neither native layout can index the volume
-  return c->auto_no_cq ? primary_layout(c) : VX_LAYOUT_CELLQUAD;
 }
 
 // ---- shadowed DVR: the light grid (vx_shadow.hpp) ---------------------------------------------------
@@ -617,181 +586,6 @@ static int compose_image(VxContext* c, VxContext*& d) {
   return on_member0(c, launch_detile(d, d->image));
 }
 
-// Allocate the device layout the trilinear modes sample (cellquad / brickf32); returns its number of z layers
-// (apron-brick layers / brick layers) through n_layers.  The contents are filled by build_layout_layers.
-static int alloc_layout(VxContext* c, uint32_t& n_layers) {
-  if (c->vol.cq_alloc) c->vol.dv.cq = nullptr;
-  if (c->vol.bf_alloc) {
-    c->vol.dv.bf = nullptr;
-    c->vol.dv.bf_zero = 0;
-  }
-  for (DevBuf<void>* b : {&c->vol.cq_alloc, &c->vol.bf_alloc, &c->vol.bu_alloc, &c->vol.bur_alloc}) b->reset();
-  c->vol.dv.bu = nullptr;
-  c->vol.dv.bu_range = nullptr;
-  n_layers = 0;
-  c->auto_no_cq = c->auto_no_bf = false;
-  if (c->layout == VX_LAYOUT_AUTO) {   // what the volume's size allows
-    const uint64_t nv = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] * 512u;
-    const uint64_t nq = (uint64_t)(c->vol.dv.bc[0] + 1) * (c->vol.dv.bc[1] + 1) * (c->vol.dv.bc[2] + 1) * CQ_BRICK_QUADS;
-    c->auto_no_bf = nv / 4u > 0xffffffffull;
-    c->auto_no_cq = nq > 0xffffffffull;
-  }
-  if (primary_layout(c) == VX_LAYOUT_BRICKF32) {
-    uint64_t n_vox = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] * 512u;
-    // the staging loads index the layout in 16-byte units with 32 bits: 64 GiB, about 2500^3 voxels
-    if (n_vox / 4u > 0xffffffffull)
-      VX_FAIL(c, VX_ERR_INVALID, "volume too large for the brickf32 layout (%llu voxels): select VX_LAYOUT_REFERENCE "
-              "with vx_set_layout", (unsigned long long)n_vox);
-    // + one zero 16-byte chunk behind the last brick: the window staging of the LDS kernel reads it for rows and
-    // chunks outside the volume (one select per load instead of a branch and a zero fill)
-    if (int rc = c->vol.bf_alloc.alloc(c, n_vox * sizeof(float) + 16)) return rc;
-    VX_HIP(c, hipMemsetAsync((char*)c->vol.bf_alloc.p + n_vox * sizeof(float), 0, 16, c->stream));
-    c->vol.dv.bf = (const float*)c->vol.bf_alloc.p;
-    c->vol.dv.bf_zero = n_vox <= 0xfffffff0ull ? (uint32_t)n_vox : 0u;
-    n_layers = c->vol.dv.bc[2];
-    return VX_OK;
-  }
-  if (primary_layout(c) == VX_LAYOUT_BRICKU8) {
-    const uint64_t n_bricks = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2];
-    const uint64_t n_units = n_bricks * 128u;   // dwords of four codes; the staging indexes them with 32 bits
-    if (n_units > 0xfffffff0ull)
-      VX_FAIL(c, VX_ERR_INVALID, "volume too large for the bricku8 layout (%llu bricks): select VX_LAYOUT_REFERENCE "
-              "with vx_set_layout", (unsigned long long)n_bricks);
-    // + one zero unit behind the last brick and its {0, 0} range: rows and chunks outside the volume decode to +0
-    if (int rc = c->vol.bu_alloc.alloc(c, (n_units + 4u) * sizeof(uint32_t))) return rc;
-    if (int rc = c->vol.bur_alloc.alloc(c, (n_bricks + 1u) * sizeof(float2))) return rc;
-    VX_HIP(c, hipMemsetAsync((char*)c->vol.bu_alloc.p + n_units * sizeof(uint32_t), 0, 4u * sizeof(uint32_t), c->stream));
-    VX_HIP(c, hipMemsetAsync((char*)c->vol.bur_alloc.p + n_bricks * sizeof(float2), 0, sizeof(float2), c->stream));
-    c->vol.dv.bu = (const uint32_t*)c->vol.bu_alloc.p;
-    c->vol.dv.bu_range = (const float2*)c->vol.bur_alloc.p;
-    n_layers = c->vol.dv.bc[2];
-    return VX_OK;
-  }
-  if (primary_layout(c) != VX_LAYOUT_CELLQUAD) return VX_OK;
-  for (int i = 0; i < 3; ++i) c->vol.dv.cq_bc[i] = c->vol.dv.bc[i] + 1;
-  uint64_t n_quads = (uint64_t)c->vol.dv.cq_bc[0] * c->vol.dv.cq_bc[1] * c->vol.dv.cq_bc[2] * CQ_BRICK_QUADS;
-  // the march indexes quads with 32 bits (and bricks with 24-bit multiplies): 64 GiB, about 1550^3 voxels
-  if (n_quads > 0xffffffffull)
-    VX_FAIL(c, VX_ERR_INVALID,
-            "volume too large for the cellquad layout (%llu quads > 2^32): select VX_LAYOUT_BRICKF32 or "
-            "VX_LAYOUT_REFERENCE with vx_set_layout", (unsigned long long)n_quads);
-  if (int rc = c->vol.cq_alloc.alloc(c, n_quads * sizeof(float4))) return rc;
-  c->vol.dv.cq = (const float4*)c->vol.cq_alloc.p;
-  n_layers = c->vol.dv.cq_bc[2];
-  return VX_OK;
-}
-
-// fill z layers [z0, z1) of the layout on `st` (one thread per quad / voxel; layers are contiguous in both layouts)
-static int build_layout_layers(VxContext* c, uint32_t z0, uint32_t z1, hipStream_t st) {
-  if (z1 <= z0) return VX_OK;
-  if (primary_layout(c) == VX_LAYOUT_BRICKF32) {
-    const uint64_t per = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * 512u;
-    const uint64_t first = per * z0, end = per * z1;
-    for (uint64_t at = first; at < end;) {   // <= 2^31 threads per launch
-      uint64_t n = end - at < (1ull << 31) ? end - at : (1ull << 31);
-      hipLaunchKernelGGL(build_brickf32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c->vol.dv,
-                         (float*)c->vol.bf_alloc.p, at, at + n);
-      at += n;
-    }
-  } else if (primary_layout(c) == VX_LAYOUT_BRICKU8) {
-    const uint64_t bricks_per = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1];
-    const uint64_t first = bricks_per * 128u * z0, end = bricks_per * 128u * z1;   // dword units, < 2^32 (alloc_layout)
-    hipLaunchKernelGGL(build_bricku8, dim3((uint32_t)((end - first + 255) / 256)), dim3(256), 0, st, c->vol.dv,
-                       (uint32_t*)c->vol.bu_alloc.p, first, end);
-    const uint32_t b0 = (uint32_t)(bricks_per * z0), b1 = (uint32_t)(bricks_per * z1);
-    hipLaunchKernelGGL(build_bricku8_range, dim3((b1 - b0 + 255) / 256), dim3(256), 0, st, c->vol.dv, (float2*)c->vol.bur_alloc.p,
-                       b0, b1);
-  } else if (primary_layout(c) == VX_LAYOUT_CELLQUAD) {
-    const uint64_t per = (uint64_t)c->vol.dv.cq_bc[0] * c->vol.dv.cq_bc[1] * CQ_BRICK_QUADS;
-    const uint64_t first = per * z0, end = per * z1;
-    for (uint64_t at = first; at < end;) {
-      uint64_t n = end - at < (1ull << 31) ? end - at : (1ull << 31);
-      hipLaunchKernelGGL(build_cellquad, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, c->vol.dv,
-                         (float4*)c->vol.cq_alloc.p, at, at + n);
-      at += n;
-    }
-  }
-  VX_HIP(c, hipGetLastError());
-  return VX_OK;
-}
-
-// dvr_phong runs on the LDS-window kernel, which samples the brickf32 layout: a context whose primary layout is
-// cellquad gets the 4-byte-per-voxel brick layout built beside it the first time Phong is rendered
-static int ensure_brickf32(VxContext* c) {
-  if (c->vol.dv.bf) return VX_OK;
-  const uint64_t n_vox = (uint64_t)c->vol.dv.bc[0] * c->vol.dv.bc[1] * c->vol.dv.bc[2] * 512u;
-  if (n_vox / 4u > 0xffffffffull) return VX_OK;   // too large: the generic kernel serves Phong
-  if (int rc = c->vol.bf_alloc.alloc(c, n_vox * sizeof(float) + 16)) return rc;   // + the zero chunk (alloc_layout)
-  VX_HIP(c, hipMemsetAsync((char*)c->vol.bf_alloc.p + n_vox * sizeof(float), 0, 16, c->stream));
-  c->vol.dv.bf = (const float*)c->vol.bf_alloc.p;
-  c->vol.dv.bf_zero = n_vox <= 0xfffffff0ull ? (uint32_t)n_vox : 0u;
-  for (uint64_t at = 0; at < n_vox;) {
-    uint64_t n = n_vox - at < (1ull << 31) ? n_vox - at : (1ull << 31);
-    hipLaunchKernelGGL(build_brickf32, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->vol.dv,
-                       (float*)c->vol.bf_alloc.p, at, at + n);
-    at += n;
-  }
-  VX_HIP(c, hipGetLastError());
-  return VX_OK;
-}
-
-// the cellquad layout built beside the primary one the first time a mode that gathers from it is rendered
-// (VX_LAYOUT_AUTO: the path-traced reference modes)
-static int ensure_cellquad(VxContext* c) {
-  if (c->vol.dv.cq) return VX_OK;
-  for (int i = 0; i < 3; ++i) c->vol.dv.cq_bc[i] = c->vol.dv.bc[i] + 1;
-  const uint64_t n_quads = (uint64_t)c->vol.dv.cq_bc[0] * c->vol.dv.cq_bc[1] * c->vol.dv.cq_bc[2] * CQ_BRICK_QUADS;
-  if (c->layout == VX_LAYOUT_AUTO) {
-    // AUTO builds this layout on demand, beside what is resident: only when it leaves half of the free device memory to
-    // the rest of the process (19.8 GB for 1024^3 on a 288 GB MI355X: always; a volume near the layout's 64 GiB index limit
-    // on a device that other contexts share: not necessarily).  Otherwise `default` / `no_dda` take the resident bricks.
-    // VX_AUTO_CELLQUAD_MAX_BYTES (Switches) overrides the budget -- 0 keeps AUTO off this layout.
-    size_t free_b = 0, total_b = 0;
-    VX_HIP(c, hipMemGetInfo(&free_b, &total_b));
-    const uint64_t budget = c->sw.cellquad_max_bytes.value_or((uint64_t)free_b / 2u);
-    if (n_quads * sizeof(float4) > budget) {
-      c->auto_no_cq = true;
-      return VX_OK;
-    }
-  }
-  if (int rc = c->vol.cq_alloc.alloc(c, n_quads * sizeof(float4))) return rc;
-  c->vol.dv.cq = (const float4*)c->vol.cq_alloc.p;
-  for (uint64_t at = 0; at < n_quads;) {
-    uint64_t n = n_quads - at < (1ull << 31) ? n_quads - at : (1ull << 31);
-    hipLaunchKernelGGL(build_cellquad, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, c->vol.dv,
-                       (float4*)c->vol.cq_alloc.p, at, at + n);
-    at += n;
-  }
-  VX_HIP(c, hipGetLastError());
-  return VX_OK;
-}
-
-static int build_layout(VxContext* c) {   // whole layout on the context's stream (vx_set_layout)
-  uint32_t n = 0;
-  int rc = alloc_layout(c, n);
-  if (rc) return rc;
-  return build_layout_layers(c, 0, n, c->stream);
-}
-
-// Pin a caller-owned host range for the duration of an upload so that the copy engine reads it directly at
-// PCIe rate ("pin/upload volumes to HBM", BASELINE north star).  Pageable memory would be staged through the
-// runtime's bounce buffers at a fraction of that.  Failing to pin (already registered, locked-memory limit)
-// is not an error: the copies then go the pageable way.
-struct PinnedRange {
-  void* p = nullptr;
-  bool pinned = false;
-  PinnedRange(const void* ptr, size_t bytes) {
-    if (!ptr || bytes < (1u << 20)) return;
-    p = const_cast<void*>(ptr);
-    hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
-    pinned = (e == hipSuccess);
-    if (!pinned) (void)hipGetLastError();   // clear the sticky error
-  }
-  ~PinnedRange() {
-    if (pinned) (void)hipHostUnregister(p);
-  }
-};
-
 // The split of a plain multi-frame DVR launch of the LDS-window kernel, kept current the way the derived tables are: the
 // classification is rebuilt when the bits of its key change or the tile map did, the two halves of the block order when `order`
 // or the flags did.  Called at the end of prepare_render ahead of a multi-frame launch only (the counters and `order` exist):
@@ -941,16 +735,17 @@ static int prepare_render(VxContext* c, bool multi = false) {
     if (rc) return rc;
   }
   {
-    // the layouts this launch samples, built on first use beside the one the upload built
+    // the layouts this launch samples, made resident on first use beside the one the upload built; dvr_phong runs on the
+    // LDS-window kernel, which samples brickf32: a context on cellquad gets the bricks beside it the first time Phong is rendered
     int lay = eff_layout(c);
     int rc = VX_OK;
     if (lay == VX_LAYOUT_CELLQUAD) {
-      rc = ensure_cellquad(c);
+      rc = ensure_layout(c, VX_LAYOUT_CELLQUAD);
       lay = eff_layout(c);   // AUTO may have stepped down to the resident bricks (memory budget)
     }
     if (!rc && (lay == VX_LAYOUT_BRICKF32 ||
                 (c->params.render_mode == VX_MODE_DVR_PHONG && lay == VX_LAYOUT_CELLQUAD && tuned_possible(c))))
-      rc = ensure_brickf32(c);
+      rc = ensure_layout(c, VX_LAYOUT_BRICKF32);
     if (rc) return rc;
   }
   if (int rc = check_segment_view(c, "vx_render_frame", false)) return rc;
@@ -1176,207 +971,6 @@ int vx_set_stream(VxContext* c, void* s) {
   VX_DEV(c);
   (void)hipStreamSynchronize(c->stream);
   c->stream = s ? (hipStream_t)s : c->own_stream;
-  return VX_OK;
-}
-
-int vx_upload_volume(VxContext* c, const uint32_t* indirection, const uint32_t ind_size[3],
-                     const uint16_t* range, const uint32_t range_size[3], const uint8_t* atlas,
-                     const uint32_t atlas_size[3], int n_mips, const uint16_t* const* mip_data,
-                     const uint32_t (*mip_size)[3], const uint32_t index_extent[3]) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c))
-    return fan_out(c, [&](VxContext* m, size_t) {
-      return vx_upload_volume(m, indirection, ind_size, range, range_size, atlas, atlas_size, n_mips, mip_data, mip_size,
-                              index_extent);
-    });
-  VX_DEV(c);
-  if (!indirection || !range || !ind_size || !range_size || !atlas_size || !index_extent)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: null argument");
-  if (n_mips != 3 || !mip_data || !mip_size)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: expected 3 range mipmaps (brick.rs:13)");
-  for (int i = 0; i < 3; ++i) {
-    if (ind_size[i] != range_size[i] || ind_size[i] == 0 || ind_size[i] >= 1024u)
-      VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: bad brick grid dimensions");
-    if (index_extent[i] != ind_size[i] * 8u)
-      VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: index_extent must be brick_count*8 (brick.rs:236-238)");
-    if (i < 2 && atlas_size[i] != ind_size[i] * 8u)
-      VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: atlas x/y dims must be brick_count*8 (brick.rs:85)");
-  }
-  if (atlas_size[2] % 8u != 0 || atlas_size[2] > ind_size[2] * 8u)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: bad atlas depth");
-  size_t atlas_bytes = (size_t)atlas_size[0] * atlas_size[1] * atlas_size[2];
-  if (atlas_bytes && !atlas) VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: null atlas");
-  for (int k = 0; k < 3; ++k) {
-    if (!mip_data[k] && (size_t)mip_size[k][0] * mip_size[k][1] * mip_size[k][2])
-      VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: null mip %d", k);
-    if (mip_size[k][0] != (ind_size[0] >> (k + 1)) || mip_size[k][1] != (ind_size[1] >> (k + 1)) ||
-        mip_size[k][2] != (ind_size[2] >> (k + 1)))
-      VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: mip %d has wrong dimensions (brick.rs:156)", k);
-  }
-  const auto t_begin = std::chrono::steady_clock::now();
-  VX_HIP(c, hipStreamSynchronize(c->stream));
-  free_volume(c);
-  const size_t nb = (size_t)ind_size[0] * ind_size[1] * ind_size[2];
-  const size_t per_layer = (size_t)ind_size[0] * ind_size[1];
-  // every pointer must address an allocated atlas brick; while scanning, note how many 8-slice atlas layers
-  // the bricks of each brick z layer reach into (the builder allocates slots in scan order, brick.rs:127-129,
-  // so this grows with z and the layout of early layers can be built while the rest of the atlas still copies)
-  std::vector<uint32_t> reach(ind_size[2], 0u);
-  {
-    const uint32_t max_slot = atlas_size[2] / 8u;
-    for (size_t i = 0; i < nb; ++i) {
-      uint32_t p = indirection[i];
-      uint32_t az = (p >> 20) & 1023u;
-      if ((p & 1023u) >= ind_size[0] || ((p >> 10) & 1023u) >= ind_size[1] || (az >= max_slot && p != 0))
-        VX_FAIL(c, VX_ERR_INVALID, "vx_upload_volume: indirection pointer outside the atlas");
-      uint32_t& r = reach[i / per_layer];
-      if (max_slot && az + 1u > r) r = az + 1u;   // constant bricks alias slot 0 (quirk Q6): also fine
-    }
-    for (uint32_t z = 1; z < ind_size[2]; ++z) reach[z] = reach[z] > reach[z - 1] ? reach[z] : reach[z - 1];
-  }
-  auto alloc = [&](size_t bytes, void** dst) -> int {
-    *dst = nullptr;
-    if (bytes == 0) return VX_OK;
-    VX_HIP(c, hipMalloc(dst, bytes));
-    c->vol_allocs.push_back(*dst);
-    return VX_OK;
-  };
-  void *d_ind = nullptr, *d_range = nullptr, *d_atlas = nullptr, *d_mip[3] = {nullptr, nullptr, nullptr};
-  int rc;
-  // the atlas allocation is never empty: a tap that points outside the pruned atlas reads byte 0 and selects 0
-  // (lookup_density_brick is straight-line code)
-  if ((rc = alloc(nb * 4, &d_ind)) || (rc = alloc(nb * 4, &d_range)) || (rc = alloc(atlas_bytes ? atlas_bytes : 16, &d_atlas))) { free_volume(c); return rc; }
-  if (!atlas_bytes) VX_HIP(c, hipMemsetAsync(d_atlas, 0, 16, c->stream));
-  size_t mip_n[3];
-  for (int k = 0; k < 3; ++k) {
-    mip_n[k] = (size_t)mip_size[k][0] * mip_size[k][1] * mip_size[k][2];
-    if ((rc = alloc(mip_n[k] * 4, &d_mip[k]))) { free_volume(c); return rc; }
-    c->vol.dv.mips[k] = (const uint32_t*)d_mip[k];
-    for (int i = 0; i < 3; ++i) c->vol.dv.mip_size[k][i] = mip_size[k][i];
-  }
-  c->vol.dv.indirection = (const uint32_t*)d_ind;
-  c->vol.dv.range = (const uint32_t*)d_range;   // u16 stream [max,min] == LE u32 (min<<16)|max
-  c->vol.dv.atlas = (const uint8_t*)d_atlas;
-  for (int i = 0; i < 3; ++i) {
-    c->vol.dv.bc[i] = ind_size[i];
-    c->vol.dv.atlas_size[i] = atlas_size[i];
-    c->vol.dv.extent[i] = index_extent[i];
-  }
-  c->range_host.assign((const uint32_t*)range, (const uint32_t*)range + nb);
-  c->vol.skip_table.stale = c->vol.proj_table.stale = c->vol.iso_table.stale = true;
-  c->order_builds_left = 2;
-  uint32_t n_layers = 0;
-  if ((rc = alloc_layout(c, n_layers))) { free_volume(c); return rc; }
-  if (!c->aux_stream) VX_HIP(c, hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-
-  // ---- copies: metadata first, then the atlas in chunks of whole 8-slice layers from pinned memory;
-  //      the layout layers whose bricks are complete are built on the aux stream behind each chunk
-  // Every failure from here on goes through ONE exit (below): both streams are synchronised before the pinned
-  // ranges are unregistered and the partial volume is freed -- an early return would unpin pages an earlier
-  // asynchronous copy may still be reading.
-  PinnedRange pin_atlas(atlas, atlas_bytes), pin_ind(indirection, nb * 4), pin_range(range, nb * 4);
-  hipError_t le = hipMemcpyAsync(d_ind, indirection, nb * 4, hipMemcpyHostToDevice, c->stream);
-  if (le == hipSuccess) le = hipMemcpyAsync(d_range, range, nb * 4, hipMemcpyHostToDevice, c->stream);
-  for (int k = 0; k < 3 && le == hipSuccess; ++k)
-    if (mip_n[k]) le = hipMemcpyAsync(d_mip[k], mip_data[k], mip_n[k] * 4, hipMemcpyHostToDevice, c->stream);
-  const uint32_t atlas_layers = atlas_size[2] / 8u;
-  const size_t layer_bytes = (size_t)atlas_size[0] * atlas_size[1] * 8u;
-  const uint32_t chunk_layers = layer_bytes ? (uint32_t)std::max<size_t>(1, (16u << 20) / layer_bytes) : 1u;
-  std::vector<hipEvent_t> evs;
-  uint32_t built = 0;     // layout layers launched so far
-  auto buildable = [&](uint32_t copied) {   // layout layers whose source bricks lie in the copied atlas prefix
-    uint32_t z = built;
-    while (z < n_layers) {
-      // cellquad apron layer z reads brick layers z-1 and z; brickf32 layer z reads brick layer z
-      uint32_t top = z < ind_size[2] ? z : ind_size[2] - 1u;
-      if (reach[top] > copied) break;
-      ++z;
-    }
-    return z;
-  };
-  for (uint32_t l0 = 0; l0 < atlas_layers && le == hipSuccess; l0 += chunk_layers) {
-    uint32_t l1 = l0 + chunk_layers < atlas_layers ? l0 + chunk_layers : atlas_layers;
-    le = hipMemcpyAsync((char*)d_atlas + l0 * layer_bytes, atlas + l0 * layer_bytes, (l1 - l0) * layer_bytes,
-                        hipMemcpyHostToDevice, c->stream);
-    if (le != hipSuccess) break;
-    uint32_t z1 = buildable(l1);
-    if (z1 > built && l1 < atlas_layers) {   // the last chunk's layers go with the final build below
-      hipEvent_t e;
-      if ((le = hipEventCreateWithFlags(&e, hipEventDisableTiming)) != hipSuccess) break;
-      evs.push_back(e);
-      if ((le = hipEventRecord(e, c->stream)) != hipSuccess) break;
-      if ((le = hipStreamWaitEvent(c->aux_stream, e, 0)) != hipSuccess) break;
-      if ((rc = build_layout_layers(c, built, z1, c->aux_stream))) { le = hipErrorUnknown; break; }
-      built = z1;
-    }
-  }
-  if (le == hipSuccess && built < n_layers) {
-    hipEvent_t e;
-    if ((le = hipEventCreateWithFlags(&e, hipEventDisableTiming)) == hipSuccess) {
-      evs.push_back(e);
-      le = hipEventRecord(e, c->stream);
-      if (le == hipSuccess) le = hipStreamWaitEvent(c->aux_stream, e, 0);
-      if (le == hipSuccess && (rc = build_layout_layers(c, built, n_layers, c->aux_stream))) le = hipErrorUnknown;
-    }
-  }
-  hipError_t s1 = hipStreamSynchronize(c->stream);    // host buffers may be dropped on return
-  hipError_t s2 = hipStreamSynchronize(c->aux_stream);
-  for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-  if (le != hipSuccess || s1 != hipSuccess || s2 != hipSuccess) {
-    hipError_t bad = le != hipSuccess ? le : (s1 != hipSuccess ? s1 : s2);
-    free_volume(c);
-    VX_FAIL(c, VX_ERR_DEVICE, "vx_upload_volume: %s", hipGetErrorString(bad));
-  }
-  c->vol.has_volume = true;
-  c->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-  c->upload_host_bytes = (uint64_t)atlas_bytes + (uint64_t)nb * 8u + (uint64_t)(mip_n[0] + mip_n[1] + mip_n[2]) * 4u;
-  c->upload_pinned = pin_atlas.pinned ? 1 : 0;
-  return VX_OK;
-}
-
-int vx_upload_stats(VxContext* c, double* seconds, uint64_t* host_bytes, int* pinned) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return on_member0(c, vx_upload_stats(c->members[0], seconds, host_bytes, pinned));
-  if (seconds) *seconds = c->upload_seconds;
-  if (host_bytes) *host_bytes = c->upload_host_bytes;
-  if (pinned) *pinned = c->upload_pinned;
-  return VX_OK;
-}
-
-int vx_upload_brick_grid(VxContext* c, const VxBrickGrid* g) {
-  if (!c) return VX_ERR_INVALID;
-  if (!g) VX_FAIL(c, VX_ERR_INVALID, "vx_upload_brick_grid: null grid");
-  uint32_t is[3], rs[3], as[3], ext[3], ms[3][3];
-  vxb_indirection_size(g, is);
-  vxb_range_size(g, rs);
-  vxb_atlas_size(g, as);
-  vxb_index_extent(g, ext);
-  const uint32_t n = vxb_range_mipmaps(g);
-  if (n != 3) VX_FAIL(c, VX_ERR_INVALID, "vx_upload_brick_grid: grid has %u range mips, expected 3", n);
-  const uint16_t* mips[3];
-  for (uint32_t i = 0; i < 3; ++i) {
-    mips[i] = vxb_range_mipmap(g, i);
-    vxb_range_mipmap_stride(g, i, ms[i]);
-  }
-  return vx_upload_volume(c, vxb_indirection_data(g), is, vxb_range_data(g), rs, vxb_atlas_data(g), as, 3, mips,
-                          ms, ext);
-}
-
-int vx_set_layout(VxContext* c, int layout) {
-  if (!c) return VX_ERR_INVALID;
-  if (is_group(c)) return fan_out(c, [&](VxContext* m, size_t) { return vx_set_layout(m, layout); });
-  VX_DEV(c);
-  if (layout != VX_LAYOUT_REFERENCE && layout != VX_LAYOUT_CELLQUAD && layout != VX_LAYOUT_BRICKF32 &&
-      layout != VX_LAYOUT_AUTO && layout != VX_LAYOUT_BRICKU8)
-    VX_FAIL(c, VX_ERR_INVALID, "vx_set_layout: unknown layout %d", layout);
-  if (layout == c->layout) return VX_OK;
-  c->layout = layout;
-  if (c->vol.has_volume) {
-    VX_HIP(c, hipStreamSynchronize(c->stream));
-    int rc = build_layout(c);
-    if (rc) return rc;
-    VX_HIP(c, hipStreamSynchronize(c->stream));
-  }
   return VX_OK;
 }
 

@@ -1,5 +1,5 @@
 // vx_context.hpp -- the context behind the C ABI of include/volxel_hip.h, once, for every unit of the host layer
-// (vx_api.hip, vx_api_view.hip, vx_api_segment.hip, vx_api_mesh.hip): VxContext and what it is made
+// (vx_api.hip, vx_api_volume.hip, vx_api_view.hip, vx_api_segment.hip, vx_api_mesh.hip): VxContext and what it is made
 // of, the helpers of device groups, the dispatch helpers from a run-time value to a template argument, and the parameter
 // checks the entry points of several units share.  Host only: no kernel and no device code, and no kernel header is
 // included -- the plain structs the context holds by value come from vx_types.hpp.
@@ -30,7 +30,7 @@ struct Switches {
   int dvr_variant = -1;            // VX_DVR_KERNEL=generic: 0, the DVR modes on render_generic; -1: the tuned kernels
   bool dvr_fuse = true;            // VX_DVR_FUSE=0: no kernel folds the running mean; merge_results blends every multi-frame launch
   bool ray_shortcuts = true;       // VX_RAY_SHORTCUTS=0: the per-ray divisions themselves (DevVolume::ray_flags = 0)
-  std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_cellquad)
+  std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_layout)
   uint32_t seg_check_max = 64;     // VX_SEG_CHECK_MAX (1 .. 4096): the largest batch of flood rounds between read-backs (vx_segment)
   bool dvr_miss = true;            // VX_DVR_MISS=0: no multi-frame DVR launch is split; every block runs the LDS-window kernel
 };
@@ -298,6 +298,29 @@ inline void with_conn(int conn, F&& f) {
   else f(std::integral_constant<int, 6>{});
 }
 
+inline bool proj_mode(int m) { return m == VX_MODE_MIP || m == VX_MODE_MINIP; }
+
+// The device layout the kernels of the current render mode sample.  VX_LAYOUT_AUTO (default): the DVR modes march
+// the brickf32 layout through LDS windows (vx_dvr_lds.hpp: fastest, 4 bytes per voxel), `default` and `no_dda`
+// gather from cellquad (two 16-byte loads per trilinear look-up instead of eight bounds-checked taps), `raymarch`
+// reads its single nearest tap from brickf32.
+inline int primary_layout(const VxContext* c) {
+  if (c->layout != VX_LAYOUT_AUTO) return c->layout;
+  return c->auto_no_bf ? VX_LAYOUT_REFERENCE : VX_LAYOUT_BRICKF32;
+}
+inline int eff_layout(const VxContext* c) {
+  if (c->layout != VX_LAYOUT_AUTO) return c->layout;
+  const int m = c->has_params ? c->params.render_mode : VX_MODE_DVR;
+  // raymarch takes ONE nearest tap per sample (common.glsl:72-76): the 4-byte-per-voxel bricks serve it better than
+  // the 18-byte-per-voxel quads, and the layout is resident already
+  if (m == VX_MODE_DVR || m == VX_MODE_DVR_PHONG || m == VX_MODE_RAYMARCH || proj_mode(m)) return primary_layout(c);
+  // `default` / `no_dda`: cellquad (18 B / voxel) while the volume is inside its index range and the build fits the device
+  // memory budget (ensure_layout); beyond that the fp32 bricks that are resident anyway -- eight taps per look-up, measured
+  // 1.4x / 2.0x slower than cellquad and 2.0x / 2.2x faster than the reference textures on the 1024^3 volume at 3840x2160
+  // (profiles/r04_layouts_1024.txt) -- and the reference textures only when neither native layout can index the volume
+  return c->auto_no_cq ? primary_layout(c) : VX_LAYOUT_CELLQUAD;
+}
+
 // The layout a slice samples: what is resident at the time of the call -- brickf32, else cellquad, else the reference textures
 // (same bits on all three).  Not eff_layout: under AUTO it follows the render mode, and for `default` / `no_dda` it names
 // cellquad before the first render of such a mode has built it; under bricku8 the slice reads the reference textures.
@@ -394,5 +417,11 @@ inline int check_mask_bytes(VxContext* c, const char* fn, uint64_t nbytes, size_
 // ---- the functions one unit defines and another calls (hidden like the rest of this namespace: the library exports none) -----
 // defined in vx_api.hip, which knows whether a launch has an LDS-window kernel; also called by vx_isosurface (vx_api_view.hip)
 int check_segment_view(VxContext* c, const char* fn, bool iso);
+// defined in vx_api_volume.hip.  free_volume drops the resident volume and everything derived from it (the caller has made the
+// context's device current).  ensure_layout makes `layout` (brickf32 or cellquad) resident beside what is there, for a launch
+// prepare_render found to sample it; VX_OK without it where the launch has another way: a volume beyond the layout's index range, or
+// AUTO's cellquad beyond its memory budget (then auto_no_cq is set and eff_layout steps down).
+void free_volume(VxContext* c);
+int ensure_layout(VxContext* c, int layout);
 
 }  // namespace vx

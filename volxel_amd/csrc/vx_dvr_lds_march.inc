@@ -72,7 +72,7 @@
   const float4* __restrict__ bf4 = reinterpret_cast<const float4*>(v.bf);   // 16-byte units: 64 GiB of layout in 32 bits
   const uint32_t* __restrict__ bu = v.bu;                                   // U8: one dword of four codes per unit
   const float2* __restrict__ bur = v.bu_range;
-  const uint32_t zero_chunk = bcx * bcy * v.bc[2] * 128u;   // the all-zero chunk behind the last brick (vx_api alloc_layout)
+  const uint32_t zero_chunk = bcx * bcy * v.bc[2] * 128u;   // the all-zero chunk behind the last brick (vx_api_volume.hip alloc_one_layout)
   const uint32_t sh = 3u + v.skip_level, md0 = v.skip_dims[0], md1 = v.skip_dims[1];
   const uint32_t cmaxx = ex + 7u, cmaxy = ey + 7u, cmaxz = ez + 7u;
   // Phong terms (vx_modes.hpp Frame::dvr<true>)
