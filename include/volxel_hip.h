@@ -622,6 +622,80 @@ int vx_islands_read_labels(VxContext* ctx, uint32_t* labels, uint64_t nvoxels);
  * the first call.  Any pointer may be NULL.  group: member 0. */
 int vx_islands_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
 
+/* ---- distances and margins (DESIGN.md section 2 "Distances and margins"): the squared Euclidean distance transform of the
+ * current segment M under an anisotropic voxel spacing s = (s_x, s_y, s_z), and the margins in physical units built on it.
+ * Voxels are those of index_extent, padding included.  The source set S is M (side OUTSIDE) or the complement of M inside the
+ * volume (side INSIDE); voxels outside the volume are never candidates -- the border rules of DILATE and ERODE.
+ *   term     t_a(n) = fl32(p * p), p = fl32(fl32(n) * s_a), for an offset of n voxels on axis a: fp32, no contraction
+ *   D2(i)    min over j in S of fl32(fl32(t_x(|dx|) + t_y(|dy|)) + t_z(|dz|)); +inf when S is empty.  Rounding is monotone, so
+ *            the minimum separates exactly into an x, a y and a z pass, each a plain minimum over the candidates of a line.
+ *   cap      R2 = fl32(r * r) of max_distance / radius r; every voxel with D2 > R2 reports +inf.
+ *   GROW     { i : D2_M(i) <= R2 };  band = 1: M | (GROW(M) & P), P the predicate words of the last vx_segment / _threshold
+ *   SHRINK   { i in M : D2_complement(i) > R2 }: the whole volume shrinks to itself, the empty set grows to itself
+ *   CLOSE    SHRINK(GROW(M));  OPEN  GROW(SHRINK(M))
+ * The device holds D2 and never takes a square root: a host takes it of what it reads.  Every result is a unique function of
+ * M, s and r: it does not depend on layout, launch shape or scheduling, and two calls give the same bytes. */
+typedef enum VxDistanceSide {
+  VX_DISTANCE_OUTSIDE = 0,   /* S = M: how far every voxel is from the segment (0 inside it)                          */
+  VX_DISTANCE_INSIDE = 1     /* S = the complement: how far every voxel of the segment is from leaving it (0 outside) */
+} VxDistanceSide;
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxDistanceParams {
+  float spacing[3];        /* s_x, s_y, s_z: finite, > 0 (mm for DICOM: the column norms of grid.transform)             */
+  float max_distance;      /* the cap r, > 0, in the units of spacing; +inf: none                                      */
+  int32_t side;            /* VxDistanceSide                                                                           */
+} VxDistanceParams;
+/* finite: the voxels with D2 <= R2 (those of S included).  max_d2: the largest D2 <= R2 over the voxels NOT in S, and argmax
+ * (x, y, z) the first voxel in C order over (z, y, x) that attains it; 0 and (0, 0, 0) when there is none.  With side INSIDE
+ * sqrt(max_d2) is the radius of the largest ball of voxel centres that fits inside the segment, centred at argmax.
+ * every member is 4 or 8 bytes wide, no padding */
+typedef struct VxDistanceResult {
+  uint64_t finite;
+  float max_d2;
+  uint32_t argmax[3];
+} VxDistanceResult;
+/* Computes the field of the current segment on the context's stream behind every queued render and synchronises.  out may be
+ * NULL.  The segment, its predicate, the island table, the mesh, the accumulator, the frame state, VxCounters, the light grid,
+ * the bound tables, VxParams, the segment view and what the other *_stats calls report are not touched.  The field (4 B per
+ * voxel, one field: the y and z passes run in place) and 24 KiB of partial statistics are allocated by the first call and freed
+ * with the volume.  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the field and changing nothing, before
+ * vx_set_params, for NULL params, no current segment, a spacing component that is not finite or <= 0, a max_distance that is
+ * NaN or <= 0, an unknown side, and a volume with more than 16384 voxels along y or z (a line the passes cannot hold in LDS).
+ * group: member 0. */
+int vx_segment_distance(VxContext* ctx, const VxDistanceParams* params, VxDistanceResult* out);
+/* the field of the last vx_segment_distance: D2 per voxel, dense (Z, Y, X) in C order, +inf beyond the cap; nvoxels must be
+ * X * Y * Z of index_extent.  VX_ERR_INVALID with no current field (none yet; an upload and every call that changes or replaces
+ * the segment -- vx_segment, _threshold, _edit, _write_mask, _margin and a modifying vx_segment_islands -- drop it), for NULL d2
+ * and a wrong nvoxels. */
+int vx_distance_read(VxContext* ctx, float* d2, uint64_t nvoxels);
+typedef enum VxMarginOp {
+  VX_MARGIN_GROW = 0,
+  VX_MARGIN_SHRINK = 1,
+  VX_MARGIN_OPEN = 2,
+  VX_MARGIN_CLOSE = 3
+} VxMarginOp;
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxMarginParams {
+  int32_t op;              /* VxMarginOp                                                                               */
+  float radius;            /* r: finite, > 0, in the units of spacing                                                  */
+  float spacing[3];        /* as VxDistanceParams                                                                      */
+  int32_t band;            /* 0, or 1 with GROW: only into the predicate of the last vx_segment / vx_segment_threshold  */
+} VxMarginParams;
+/* Edits the current segment in place by a margin in physical units, on the context's stream behind every queued render, and
+ * synchronises: one transform for GROW and SHRINK, two for OPEN and CLOSE, whatever the radius.  out (may be NULL) holds the
+ * statistics of the new mask as vx_segment_edit reports them (rounds = brick_visits = 0, converged = 1).  It drops the island
+ * table and the distance field; the accumulator, the frame state, VxCounters, the light grid, the bound tables, the mesh,
+ * VxParams, the segment view and what vx_segment_stats and vx_segment_edit_stats report are not touched; with a view on, the
+ * next covered call reads the new mask.  Buffers as vx_segment_distance.  VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID,
+ * naming the field and changing nothing, before vx_set_params, for NULL params, no current segment, a spacing component that is
+ * not finite or <= 0, a radius that is not finite or <= 0, an op outside the enum, band not 0 or 1, band = 1 with another op or
+ * with no predicate on this volume, and a volume with more than 16384 voxels along y or z.  group: member 0. */
+int vx_segment_margin(VxContext* ctx, const VxMarginParams* params, VxSegmentResult* out);
+/* the last vx_segment_distance or vx_segment_margin: kernels launched by the call itself (the mask's statistics apart), and
+ * kernel_ms[0 .. 3] = the HIP-event times of the x pass, the y pass, the z pass and the compare-and-pack / the reduction, each
+ * summed over the two transforms of OPEN and CLOSE; all 0 before the first call.  Any pointer may be NULL.  group: member 0. */
+int vx_distance_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
+
 /* ---- segment views (DESIGN.md section 2 "Segment views"): show only, or hide, the current segment.  With a view other than
  * OFF the covered calls -- vx_render_frame / vx_render_frames in VX_MODE_DVR, _DVR_PHONG, _MIP and _MINIP, and vx_isosurface
  * (hence picking) -- sample the masked volume: every decoded voxel v(i) reads +0.0f where it is hidden (ONLY: i is not in the

@@ -17,4 +17,5 @@ from .mpr import axial, coronal, sagittal, oblique, overlay  # noqa: F401,E402
 from ._abi import VxSliceParams, VxIsoParams, VxSegmentParams, VxSegmentResult, VxSegmentEditParams  # noqa: F401,E402
 from ._abi import VxMeshParams, VxMeshResult  # noqa: F401,E402
 from .mesh import Mesh  # noqa: F401,E402
-from .renderer import Segment  # noqa: F401,E402
+from .renderer import Segment, SegmentDistance  # noqa: F401,E402
+from ._abi import VxDistanceParams, VxDistanceResult, VxMarginParams  # noqa: F401,E402

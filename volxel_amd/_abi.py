@@ -57,6 +57,9 @@ VxSegmentEditParams = struct_from_header("volxel_hip.h", "VxSegmentEditParams")
 VxIslandsParams = struct_from_header("volxel_hip.h", "VxIslandsParams")
 VxIslandsResult = struct_from_header("volxel_hip.h", "VxIslandsResult")
 VxIsland = struct_from_header("volxel_hip.h", "VxIsland")
+VxDistanceParams = struct_from_header("volxel_hip.h", "VxDistanceParams")
+VxDistanceResult = struct_from_header("volxel_hip.h", "VxDistanceResult")
+VxMarginParams = struct_from_header("volxel_hip.h", "VxMarginParams")
 VxMeshParams = struct_from_header("volxel_hip.h", "VxMeshParams")
 VxMeshResult = struct_from_header("volxel_hip.h", "VxMeshResult")
 
@@ -74,6 +77,8 @@ ISO_MAX_REFINE = 16
 SEGEDIT_OPS = {"dilate": 0, "erode": 1, "open": 2, "close": 3, "fill_holes": 4}   # enum VxSegmentEditOp
 SEGEDIT_MAX_STEPS = 1024
 ISLANDS_OPS = {"label": 0, "keep_largest": 1, "remove_small": 2, "keep_at": 3}   # enum VxIslandsOp
+DISTANCE_SIDES = {"outside": 0, "inside": 1}            # enum VxDistanceSide
+MARGIN_OPS = {"grow": 0, "shrink": 1, "open": 2, "close": 3}   # enum VxMarginOp
 MESH_DENSITY, MESH_SEGMENT = range(2)                  # enum VxMeshSource
 
 
@@ -172,6 +177,10 @@ def load_library():
         "vx_islands_read": ([vp, u64, u64, P(VxIsland)], i32),
         "vx_islands_read_labels": ([vp, vp, u64], i32),
         "vx_islands_stats": ([vp, P(u32), P(C.c_double)], i32),
+        "vx_segment_distance": ([vp, P(VxDistanceParams), P(VxDistanceResult)], i32),
+        "vx_distance_read": ([vp, vp, u64], i32),
+        "vx_segment_margin": ([vp, P(VxMarginParams), P(VxSegmentResult)], i32),
+        "vx_distance_stats": ([vp, P(u32), P(C.c_double)], i32),
         "vx_mesh_extract": ([vp, P(VxMeshParams), P(VxMeshResult)], i32),
         "vx_mesh_read": ([vp, vp, vp, vp], i32),
         "vx_mesh_stats": ([vp, P(u32), P(C.c_double)], i32),

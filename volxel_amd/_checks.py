@@ -45,6 +45,30 @@ def connectivity(c) -> int:
     return int(c)
 
 
+def spacing(sp, transform) -> tuple:
+    """the voxel spacing (s_x, s_y, s_z) as three finite float32 > 0; None: the norms of the columns of transform[:3, :3]
+    (the grid's own units: mm for DICOM), cast to float32"""
+    if sp is None:
+        sp = np.linalg.norm(np.asarray(transform, dtype=np.float64)[:3, :3], axis=0)
+    try:
+        t = tuple(np.float32(a) for a in sp)
+    except (TypeError, ValueError):
+        t = ()
+    if len(t) != 3 or not all(np.isfinite(a) and a > 0 for a in t):
+        raise ValueError(f"spacing must be three finite numbers > 0 (x, y, z), not {sp!r}")
+    return tuple(float(a) for a in t)
+
+
+def distance(name: str, r, allow_inf: bool) -> float:
+    """a radius or a cap r > 0 as float32; finite unless allow_inf (max_distance = inf: no cap)"""
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be a number > 0, not {r!r}")
+    r32 = np.float32(r)
+    if not r32 > 0 or (np.isinf(r32) and not (allow_inf and r == math.inf)):
+        raise ValueError(f"{name} must be {'> 0 (inf: no cap)' if allow_inf else 'finite and > 0'}, not {r!r}")
+    return float(r32)
+
+
 def box(b, ext):
     """(lo, hi) of box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices inside the index extent; None: all of it"""
     if b is None:

@@ -39,6 +39,7 @@ Switches read_switches() {
   if (const char* v = getenv("VX_RAY_SHORTCUTS"); v && atoi(v) == 0) sw.ray_shortcuts = false;
   if (const char* v = getenv("VX_AUTO_CELLQUAD_MAX_BYTES")) sw.cellquad_max_bytes = strtoull(v, nullptr, 10);
   if (const char* v = getenv("VX_SEG_CHECK_MAX")) sw.seg_check_max = (uint32_t)std::min(std::max(atoi(v), 1), 4096);
+  if (const char* v = getenv("VX_DIST_LDS_BYTES")) sw.dist_lds_bytes = (uint32_t)std::min(std::max(atoi(v), 256), 65536);
   sw.dvr_miss = dvr_miss_switch();
   return sw;
 }

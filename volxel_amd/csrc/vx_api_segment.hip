@@ -1,5 +1,6 @@
 // vx_api_segment.hip -- the segment unit of the host layer (units: DESIGN.md section 4.1): the segment chain -- seeded region
-// growing, the mask's read-back, slice overlay and view, the edits, the threshold and the islands.
+// growing, the mask's read-back, slice overlay and view, the edits, the threshold, the islands, and the distance field with the
+// millimetre margins.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include "vx_segment.hpp"
 #include "vx_segedit.hpp"
 #include "vx_islands.hpp"
+#include "vx_distance.hpp"
 #include "vx_context.hpp"
 
 using namespace vx;
@@ -197,6 +199,111 @@ static void launch_sed_steps(VxContext* c, int conn, bool invert, bool band, uin
   }
 }
 
+// ---- distances and margins (vx_segment_distance, vx_distance_read, vx_segment_margin; kernels in vx_distance.hpp) ------------
+constexpr uint32_t DST_MAX_PARTIALS = 1024;
+
+// the field (4 B per voxel) and the partials of its statistics
+static int ensure_distance(VxContext* c) {
+  const uint32_t* E = c->vol.dv.extent;
+  if (int rc = c->vol.dist_field.ensure(c, (size_t)E[0] * E[1] * E[2])) return rc;
+  return c->vol.dist_partials.ensure(c, DST_MAX_PARTIALS);
+}
+
+// the longest line the y / z passes hold in LDS (one column of it at the least)
+static uint32_t dst_max_line(const VxContext* c) { return c->sw.dist_lds_bytes / 4u; }
+
+static int check_spacing(VxContext* c, const char* fn, const float sp[3]) {
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(sp[a]) || !(sp[a] > 0.0f))
+      VX_FAIL(c, VX_ERR_INVALID, "%s: spacing[%d] = %g is not finite and > 0", fn, a, (double)sp[a]);
+  return VX_OK;
+}
+// the y and z lines of the volume fit the LDS of a line pass
+static int check_line_extent(VxContext* c, const char* fn) {
+  const uint32_t* E = c->vol.dv.extent;
+  for (int a = 1; a < 3; ++a)
+    if (E[a] > dst_max_line(c))
+      VX_FAIL(c, VX_ERR_INVALID, "%s: index extent %u on axis %d is beyond the %u voxels of a line the distance passes hold in LDS", fn,
+              E[a], a, dst_max_line(c));
+  return VX_OK;
+}
+
+// the host's copy of dst_term (the same two fp32 products; this unit is built without contraction) and the window it gives a
+// cap: the largest n <= L - 1 with term(n) <= r2.  Terms grow with n, so the first one above the cap ends the search.
+static float dst_term_host(uint32_t n, float s) {
+  const float p = (float)n * s;
+  return p * p;
+}
+static uint32_t dst_window(float s, float r2, uint32_t L) {
+  uint32_t w = 0;
+  while (w + 1u < L && dst_term_host(w + 1u, s) <= r2) ++w;
+  return w;
+}
+
+// One transform on the stream: the field = D2 of the mask `src` (complemented by inv) under the cap r2, events ev0 .. ev0 + 3 of
+// dst_timer ahead of the x, y and z pass and behind the last.  The tile of a line pass is the widest of 32, 16, ... 1 columns
+// whose whole lines fit the LDS budget (DESIGN.md section 2 "Distances and margins").
+static int run_distance(VxContext* c, const uint64_t* src, uint64_t inv, const float sp[3], float r2, int ev0) {
+  const SegDev& s = c->vol.seg;
+  const uint32_t* E = c->vol.dv.extent;
+  float* field = c->vol.dist_field;
+  const size_t rows = (size_t)E[1] * E[2] * s.bc[0];
+  if (int rc = c->dst_timer.mark(c, ev0)) return rc;
+  hipLaunchKernelGGL(dst_xpass, dim3((uint32_t)std::min<size_t>((rows + 255u) / 256u, 65536u)), dim3(256), 0, c->stream, src, inv, field,
+                     s.bc[0], s.bc[1], s.bc[2], sp[0], dst_window(sp[0], r2, E[0]));
+  VX_HIP(c, hipGetLastError());
+  for (int axis = 1; axis < 3; ++axis) {
+    if (int rc = c->dst_timer.mark(c, ev0 + axis)) return rc;
+    const uint32_t L = E[axis];
+    uint32_t tx = 32;
+    while (tx > 1u && (size_t)L * tx * 4u > c->sw.dist_lds_bytes) tx >>= 1;
+    const uint32_t ntx = (E[0] + tx - 1u) / tx, nouter = axis == 1 ? E[2] : E[1];
+    const size_t plane = (size_t)E[0] * E[1];
+    const size_t lstride = axis == 1 ? E[0] : plane, ostride = axis == 1 ? plane : E[0];
+    const uint32_t w = dst_window(sp[axis], r2, L);
+    auto launch = [&](auto k) {
+      hipLaunchKernelGGL((dst_linepass<decltype(k)::value>), dim3(ntx * nouter), dim3(256), (size_t)L * tx * 4u, c->stream, field, E[0], L,
+                         lstride, ostride, ntx, sp[axis], w, r2);
+    };
+    switch (tx) {
+      case 32: launch(std::integral_constant<int, 32>{}); break;
+      case 16: launch(std::integral_constant<int, 16>{}); break;
+      case 8: launch(std::integral_constant<int, 8>{}); break;
+      case 4: launch(std::integral_constant<int, 4>{}); break;
+      case 2: launch(std::integral_constant<int, 2>{}); break;
+      default: launch(std::integral_constant<int, 1>{}); break;
+    }
+    VX_HIP(c, hipGetLastError());
+  }
+  c->dst_launches += 3;
+  return c->dst_timer.mark(c, ev0 + 3);
+}
+
+// compare and pack behind a transform: the mask in SegDev::seg from the field (dst_pack), event ev of dst_timer behind it
+static int pack_distance(VxContext* c, bool shrink, bool band, float r2, int ev) {
+  const SegDev& s = c->vol.seg;
+  const size_t words = (size_t)s.nb * 8u;
+  hipLaunchKernelGGL(dst_pack, dim3((uint32_t)std::min<size_t>((words + 255u) / 256u, 16384u)), dim3(256), 0, c->stream,
+                     (const float*)c->vol.dist_field, s.seg, band ? (const uint64_t*)s.pred : nullptr, shrink ? 1u : 0u, s.bc[0], s.bc[1],
+                     s.bc[2], r2);
+  VX_HIP(c, hipGetLastError());
+  ++c->dst_launches;
+  return c->dst_timer.mark(c, ev);
+}
+
+// the unused events of dst_timer from `from` to `to`, back to back (read() takes every pair)
+static int mark_rest(VxContext* c, int from, int to) {
+  for (int i = from; i <= to; ++i)
+    if (int rc = c->dst_timer.mark(c, i)) return rc;
+  return VX_OK;
+}
+// the times of `rounds` transforms (4 stages each from event 0), summed per pass; every event is recorded and complete
+static int read_distance_times(VxContext* c, int rounds) {
+  if (int rc = c->dst_timer.read(c)) return rc;
+  for (int k = 0; k < 4; ++k) c->dst_ms[k] = c->dst_timer.ms[k] + (rounds > 1 ? c->dst_timer.ms[4 + k] : 0.0);
+  return VX_OK;
+}
+
 static int ensure_islands(VxContext* c) {
   if (c->vol.isl_alloc) return VX_OK;
   const size_t nb = c->vol.seg.nb;
@@ -242,6 +349,7 @@ int vx_segment(VxContext* c, const VxSegmentParams* sp, VxSegmentResult* out) {
   c->vol.seg_valid = false;
   c->vol.seg_pred_valid = false;
   c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
   if (int rc = ensure_segment(c)) return rc;
   const SegDev& s = c->vol.seg;
   const uint32_t* E = c->vol.dv.extent;
@@ -364,6 +472,7 @@ int vx_segment_edit(VxContext* c, const VxSegmentEditParams* ep, VxSegmentResult
     VX_FAIL(c, VX_ERR_INVALID, "vx_segment_edit: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
   if (int rc = ensure_segedit(c)) return rc;
   c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
   const SegDev& s = c->vol.seg;
   const int conn = ep->connectivity;
   const uint32_t n = ep->steps;
@@ -421,6 +530,7 @@ int vx_segment_write_mask(VxContext* c, const uint8_t* bits, uint64_t nbytes, Vx
   if (int rc = ensure_segedit(c)) return rc;
   if (int rc = c->vol.seg_bytes.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
   c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
   const SegDev& s = c->vol.seg;
   VX_HIP(c, hipMemcpyAsync(c->vol.seg_bytes, bits, want, hipMemcpyHostToDevice, c->stream));
   if (int rc = c->sed_timer.mark(c, 0)) return rc;
@@ -454,6 +564,7 @@ int vx_segment_threshold(VxContext* c, const VxSegmentParams* sp, VxSegmentResul
   c->vol.seg_valid = false;
   c->vol.seg_pred_valid = false;
   c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
   const SegDev& s = c->vol.seg;
   if (int rc = c->sed_timer.mark(c, 0)) return rc;
   launch_seg_predicate(c, seg_pred_params(sp->lo, sp->hi, box));
@@ -491,6 +602,7 @@ int vx_segment_islands(VxContext* c, const VxIslandsParams* ip, VxIslandsResult*
   c->vol.isl_valid = false;
   const SegDev& s = c->vol.seg;
   const bool modify = ip->op != VX_ISLANDS_LABEL;
+  if (modify) c->vol.dist_valid = false;
   const dim3 grid(std::min<uint32_t>((s.nb + 3u) / 4u, 16384u)), block(256);
   uint32_t launches = 0;
   VX_HIP(c, hipMemsetAsync(c->vol.isl.hdr, 0, sizeof(IslHdr), c->stream));
@@ -629,6 +741,126 @@ int vx_islands_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (is_group(c)) return on_member0(c, vx_islands_stats(c->members[0], launches, kernel_ms));
   if (launches) *launches = c->isl_launches;
   if (kernel_ms) std::copy_n(c->isl_timer.ms, 7, kernel_ms);
+  return VX_OK;
+}
+
+// ---- distances and margins -------------------------------------------------------------------------------------------------------
+int vx_segment_distance(VxContext* c, const VxDistanceParams* dp, VxDistanceResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_distance(c->members[0], dp, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_distance", dp, "params")) return rc;
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_distance: no current segment (vx_segment, vx_segment_threshold or vx_segment_write_mask "
+                               "first; an upload drops it)");
+  if (int rc = check_spacing(c, "vx_segment_distance", dp->spacing)) return rc;
+  if (int rc = check_line_extent(c, "vx_segment_distance")) return rc;
+  if (!(dp->max_distance > 0.0f))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_distance: max_distance = %g is not > 0 (+inf: no cap)", (double)dp->max_distance);
+  if (dp->side != VX_DISTANCE_OUTSIDE && dp->side != VX_DISTANCE_INSIDE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_distance: side = %d is not VX_DISTANCE_OUTSIDE or _INSIDE", dp->side);
+  if (int rc = ensure_distance(c)) return rc;
+  c->vol.dist_valid = false;
+  const SegDev& s = c->vol.seg;
+  const uint32_t* E = c->vol.dv.extent;
+  const float r2 = dp->max_distance * dp->max_distance;
+  const uint64_t inv = dp->side == VX_DISTANCE_INSIDE ? ~0ull : 0ull;
+  c->dst_launches = 0;
+  if (int rc = run_distance(c, s.seg, inv, dp->spacing, r2, 0)) return rc;
+  const size_t words = (size_t)s.nb * 8u;
+  const uint32_t blocks = (uint32_t)std::min<size_t>((words + 255u) / 256u, DST_MAX_PARTIALS);
+  DstPartial* partials = c->vol.dist_partials;
+  hipLaunchKernelGGL(dst_reduce, dim3(blocks), dim3(256), 0, c->stream, (const float*)c->vol.dist_field, (const uint64_t*)s.seg, inv,
+                     s.bc[0], s.bc[1], s.bc[2], r2, partials);
+  hipLaunchKernelGGL(dst_reduce_final, dim3(1), dim3(256), 0, c->stream, partials, blocks);
+  VX_HIP(c, hipGetLastError());
+  c->dst_launches += 2;
+  if (int rc = mark_rest(c, 4, 9)) return rc;
+  DstPartial top{};
+  VX_HIP(c, hipMemcpyAsync(&top, partials, sizeof top, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  if (int rc = read_distance_times(c, 1)) return rc;
+  VxDistanceResult r{};
+  r.finite = top.finite;
+  if (top.idx != DST_NONE) {
+    r.max_d2 = top.d2;
+    r.argmax[0] = (uint32_t)(top.idx % E[0]);
+    r.argmax[1] = (uint32_t)((top.idx / E[0]) % E[1]);
+    r.argmax[2] = (uint32_t)(top.idx / ((uint64_t)E[0] * E[1]));
+  }
+  c->vol.dist_valid = true;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_distance_read(VxContext* c, float* d2, uint64_t nvoxels) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_distance_read(c->members[0], d2, nvoxels));
+  VX_DEV(c);
+  if (!c->vol.dist_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_distance_read: no current field (vx_segment_distance first; an upload and every call that changes "
+                               "or replaces the segment drop it)");
+  if (!d2) VX_FAIL(c, VX_ERR_INVALID, "vx_distance_read: d2 is NULL");
+  const uint32_t* E = c->vol.dv.extent;
+  const size_t want = (size_t)E[0] * E[1] * E[2];
+  if (nvoxels != want)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_distance_read: nvoxels = %llu, the volume has %u x %u x %u = %zu voxels", (unsigned long long)nvoxels,
+            E[0], E[1], E[2], want);
+  VX_HIP(c, hipMemcpyAsync(d2, c->vol.dist_field, want * 4u, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+int vx_segment_margin(VxContext* c, const VxMarginParams* mp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_margin(c->members[0], mp, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_margin", mp, "params")) return rc;
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_margin: no current segment (vx_segment, vx_segment_threshold or vx_segment_write_mask "
+                               "first; an upload drops it)");
+  if (int rc = check_spacing(c, "vx_segment_margin", mp->spacing)) return rc;
+  if (int rc = check_line_extent(c, "vx_segment_margin")) return rc;
+  if (!std::isfinite(mp->radius) || !(mp->radius > 0.0f))
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_margin: radius = %g is not finite and > 0", (double)mp->radius);
+  if (mp->op < VX_MARGIN_GROW || mp->op > VX_MARGIN_CLOSE)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_margin: op = %d is not a VxMarginOp (0 .. 3)", mp->op);
+  if (mp->band != 0 && mp->band != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_segment_margin: band = %d is not 0 or 1", mp->band);
+  if (mp->band && mp->op != VX_MARGIN_GROW)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_margin: band = 1 is for VX_MARGIN_GROW only (op = %d)", mp->op);
+  if (mp->band && !c->vol.seg_pred_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_margin: band = 1 without a predicate on this volume (vx_segment first; an upload drops it)");
+  if (int rc = ensure_distance(c)) return rc;
+  c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
+  const SegDev& s = c->vol.seg;
+  const float r2 = mp->radius * mp->radius;
+  // the halves of the op in order: grow measures from the segment, shrink from its complement; each packs SegDev::seg in place
+  const bool first_shrinks = mp->op == VX_MARGIN_SHRINK || mp->op == VX_MARGIN_OPEN;
+  const int rounds = mp->op == VX_MARGIN_OPEN || mp->op == VX_MARGIN_CLOSE ? 2 : 1;
+  c->dst_launches = 0;
+  // (event 4 is recorded twice with two rounds, behind the first pack and again ahead of the second x pass: adjacent on the
+  // stream, and the later record is the one both neighbouring stages are read against)
+  for (int k = 0; k < rounds; ++k) {
+    const bool shrink = first_shrinks == (k == 0);
+    if (int rc = run_distance(c, s.seg, shrink ? ~0ull : 0ull, mp->spacing, r2, 4 * k)) return rc;
+    if (int rc = pack_distance(c, shrink, mp->band != 0, r2, 4 * k + 4)) return rc;
+  }
+  if (int rc = mark_rest(c, 4 * rounds + 1, 8)) return rc;
+  SegStats st;
+  if (int rc = seg_mask_stats(c, c->dst_timer, 9, &st)) return rc;
+  if (int rc = read_distance_times(c, rounds)) return rc;
+  VxSegmentResult r = seg_result(st);
+  r.converged = 1u;
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_distance_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_distance_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->dst_launches;
+  if (kernel_ms) std::copy_n(c->dst_ms, 4, kernel_ms);
   return VX_OK;
 }
 

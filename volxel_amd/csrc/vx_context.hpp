@@ -33,6 +33,7 @@ struct Switches {
   std::optional<uint64_t> cellquad_max_bytes;   // VX_AUTO_CELLQUAD_MAX_BYTES: AUTO's budget for the cellquad layout (ensure_layout)
   uint32_t seg_check_max = 64;     // VX_SEG_CHECK_MAX (1 .. 4096): the largest batch of flood rounds between read-backs (vx_segment)
   bool dvr_miss = true;            // VX_DVR_MISS=0: no multi-frame DVR launch is split; every block runs the LDS-window kernel
+  uint32_t dist_lds_bytes = 65536; // VX_DIST_LDS_BYTES (256 .. 65536): the LDS a tile of the distance line passes may take (its width follows)
 };
 
 // ---- the tables a launch derives from the params and the uploads ---------------------------------------------------------
@@ -123,6 +124,11 @@ struct VxContext : VxCore {   // (device, the stream the launches go to, the las
     bool isl_valid = false;    // the table and the labels describe the current segment
     std::vector<VxIsland> isl_table;
     DevBuf<uint32_t> isl_dense;
+    // distances (vx_segment_distance, vx_segment_margin): the D2 field, one fp32 per voxel, and the partials of its statistics,
+    // allocated by the first call (ensure_distance)
+    DevBuf<float> dist_field;
+    DevBuf<DstPartial> dist_partials;
+    bool dist_valid = false;   // the field is the last vx_segment_distance's and the mask has not changed since
     // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans
     // (ensure_mesh); the vertex / cell buffers (3 values per vertex, grown together) and the triangles grow to the largest mesh
     DevBuf<void> mesh_alloc;
@@ -266,6 +272,10 @@ struct VxContext : VxCore {   // (device, the stream the launches go to, the las
   uint32_t isl_launches = 0;
   StageTimer<3> mesh_timer;
   uint32_t mesh_launches = 0;
+  // distances: two rounds of (x, y, z, compare / reduce) and the statistics of a margin's mask; dst_ms sums the rounds per pass
+  StageTimer<9> dst_timer;
+  double dst_ms[4] = {};
+  uint32_t dst_launches = 0;
 };
 
 namespace vx __attribute__((visibility("hidden"))) {

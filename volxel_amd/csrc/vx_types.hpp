@@ -152,6 +152,17 @@ struct SegDev {
   uint32_t nb;
 };
 
+// ---- the distance field (vx_distance.hpp)
+// a partial of the field's statistics: the voxels with D2 <= R2, and the largest such D2 over voxels outside the source set with
+// idx = the C-order index of the first voxel that attains it, DST_NONE when there is no such voxel
+constexpr unsigned long long DST_NONE = ~0ull;
+struct DstPartial {
+  unsigned long long finite;
+  unsigned long long idx;
+  float d2;
+  uint32_t pad;
+};
+
 // ---- the islands (vx_islands.hpp)
 // one island while the table is built (device side; the host ranks the rows)
 struct IslRow {

@@ -108,6 +108,20 @@ export declare class Volxel3DDicomRenderer {
   segmentEdit(op: 'dilate' | 'erode' | 'open' | 'close' | 'fill_holes', opts?: { steps?: number; connectivity?: 6 | 26; band?: boolean }):
     { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
       mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** grow, shrink, open or close the current segment by a radius in physical units (include/volxel_hip.h vx_segment_margin) */
+  segmentMargin(op: 'grow' | 'shrink' | 'open' | 'close', radius: number,
+    opts?: { spacing?: [number, number, number] | null; band?: boolean }):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** the exact Euclidean distance field of the current segment under the voxel spacing (vx_segment_distance); squared() and
+   *  distance() read the field over (z, y, x), Infinity beyond maxDistance */
+  segmentDistance(opts?: { side?: 'outside' | 'inside'; maxDistance?: number; spacing?: [number, number, number] | null }):
+    { finite: number; maxD2: number; maxDistance: number; argmax: [number, number, number]; squared(): Float32Array;
+      distance(): Float32Array };
+  /** the squared distances of the last segmentDistance over (z, y, x) (vx_distance_read) */
+  distanceField(): Float32Array;
+  /** the last segmentDistance or segmentMargin: kernels launched and the times of its passes */
+  distanceStats(): { launches: number; xMs: number; yMs: number; zMs: number; compareMs: number };
   /** install a packed mask (the layout of segmentMask()) as the current segment (vx_segment_write_mask) */
   setSegmentMask(bits: Uint8Array):
     { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;

@@ -12,6 +12,7 @@
 const fs = require('fs');
 const path = require('path');
 const native = require('./volxel_napi.node');
+const nativeDistance = require('./volxel_napi_distance.node');   // the addon of the distance calls, on native's handles
 
 const RenderMode = Object.freeze({ default: 0, no_dda: 1, raymarch: 2, dvr: 3, dvr_phong: 4, mip: 5, minip: 6 });
 const LOW_RES_DURATION = 5; // viewer.ts:132
@@ -44,6 +45,8 @@ const MESH_LAYOUT = parseParamsLayout('VxMeshParams', native.sizeofMeshParams())
 const MESH_SPACES = ['voxel', 'grid', 'world'];
 const SEGMENT_VIEWS = ['off', 'only', 'hide'];   // VX_SEGVIEW_OFF, _ONLY, _HIDE
 const SEGMENT_EDIT_OPS = ['dilate', 'erode', 'open', 'close', 'fill_holes'];   // VxSegmentEditOp, in order
+const MARGIN_OPS = ['grow', 'shrink', 'open', 'close'];   // VxMarginOp, in order
+const DISTANCE_SIDES = ['outside', 'inside'];             // VxDistanceSide, in order
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
 const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
@@ -298,6 +301,21 @@ function checkBox(who, box, e) {
 /** the voxel v = [x, y, z] inside the index extent e; `name` is what the method calls it */
 const checkVoxel = (who, name, v, e) => { if (!ints(v) || !v.every((x, a) => x >= 0 && x < e[a])) throw new Error(`${who}: ${name} ${v} is outside the index extent ${e}`); };
 const checkConnectivity = (who, c) => { if (c !== 6 && c !== 26) throw new Error(`${who}: connectivity must be 6 or 26, not ${c}`); };
+/** the voxel spacing [sx, sy, sz] as three finite float32 > 0; null: the norms of the columns of the grid transform (column
+ *  major), the grid's own units (mm for DICOM) */
+function checkSpacing(who, sp, transform) {
+  if (sp === null) sp = [0, 1, 2].map(a => Math.sqrt(transform[4 * a] ** 2 + transform[4 * a + 1] ** 2 + transform[4 * a + 2] ** 2));
+  const t = Array.isArray(sp) || ArrayBuffer.isView(sp) ? Array.from(sp, x => (typeof x === 'number' ? Math.fround(x) : NaN)) : [];
+  if (t.length !== 3 || !t.every(x => Number.isFinite(x) && x > 0)) throw new Error(`${who}: spacing must be three finite numbers > 0 (x, y, z), not ${sp}`);
+  return t;
+}
+/** a radius or a cap r > 0 as float32; finite unless allowInf (maxDistance = Infinity: no cap) */
+function checkDistance(who, name, r, allowInf) {
+  const r32 = typeof r === 'number' ? Math.fround(r) : NaN;
+  if (!(r32 > 0) || (!Number.isFinite(r32) && !(allowInf && r === Infinity)))
+    throw new Error(`${who}: ${name} must be ${allowInf ? '> 0 (Infinity: no cap)' : 'finite and > 0'}, not ${r}`);
+  return r32;
+}
 /** the VxSliceParams block of a slice spec with reduce = mean, no display and the window [0, 1] */
 function sliceParams(who, origin, du, dv, dn, [W, H], slabSamples) {
   if (!(W >= 1 && W <= 16384 && H >= 1 && H <= 16384)) throw new Error(`${who}: size must be 1 .. 16384 per side, not ${W} x ${H}`);
@@ -677,6 +695,49 @@ class Volxel3DDicomRenderer {
     this.bindUniforms();
     return this._segmentResult(native.segmentEdit(this.ctx, i, connectivity, steps, band ? 1 : 0));
   }
+  /** vx_segment_margin (DESIGN.md section 2 "Distances and margins"): op 'grow' | 'shrink' | 'open' | 'close' on the current
+   *  segment by `radius` in physical units, one exact Euclidean transform per half whatever the radius; opts: { spacing = null
+   *  ([sx, sy, sz] in the units of radius; null: the column norms of grid.transform, mm for DICOM), band = false (grow only:
+   *  only into voxels that pass the predicate of the last segment() / threshold()) } -> what segment() returns, for the new
+   *  mask.  Binds the current uniforms first. */
+  segmentMargin(op, radius, { spacing = null, band = false } = {}) {
+    this.sliceExtent();
+    const i = MARGIN_OPS.indexOf(op);
+    if (i < 0) throw new Error(`segmentMargin: op must be one of ${MARGIN_OPS.join(', ')}, not ${op}`);
+    const r = checkDistance('segmentMargin', 'radius', radius, false);
+    const sp = checkSpacing('segmentMargin', spacing, this.volume.grid.transform);
+    if (typeof band !== 'boolean') throw new Error(`segmentMargin: band must be a boolean, not ${band}`);
+    if (band && op !== 'grow') throw new Error(`segmentMargin: band is for grow only, not ${op}`);
+    this.bindUniforms();
+    return this._segmentResult(nativeDistance.segmentMargin(this.ctx, i, r, sp[0], sp[1], sp[2], band ? 1 : 0));
+  }
+  /** vx_segment_distance: the exact Euclidean distance field of the current segment; opts: { side = 'outside' (how far every
+   *  voxel is from the segment) | 'inside' (how far every voxel of the segment is from leaving it), maxDistance = Infinity
+   *  (distances above it read Infinity), spacing = null (as segmentMargin) } -> { finite, maxD2, maxDistance, argmax: [x, y, z],
+   *  squared(): Float32Array over (z, y, x), distance(): its square roots }.  The segment is not changed. */
+  segmentDistance({ side = 'outside', maxDistance = Infinity, spacing = null } = {}) {
+    this.sliceExtent();
+    const i = DISTANCE_SIDES.indexOf(side);
+    if (i < 0) throw new Error(`segmentDistance: side must be one of ${DISTANCE_SIDES.join(', ')}, not ${side}`);
+    const cap = checkDistance('segmentDistance', 'maxDistance', maxDistance, true);
+    const sp = checkSpacing('segmentDistance', spacing, this.volume.grid.transform);
+    this.bindUniforms();
+    const r = nativeDistance.segmentDistance(this.ctx, sp[0], sp[1], sp[2], cap, i);
+    r.maxDistance = Math.fround(Math.sqrt(r.maxD2));
+    r.squared = () => this.distanceField();
+    r.distance = () => this.distanceField().map(v => Math.fround(Math.sqrt(v)));
+    return r;
+  }
+  /** the squared distances of the last segmentDistance over (z, y, x), Infinity beyond the cap (vx_distance_read) */
+  distanceField() {
+    const e = this.sliceExtent();
+    const out = new Float32Array(e[0] * e[1] * e[2]);
+    nativeDistance.distanceRead(this.ctx, out);
+    return out;
+  }
+  /** the last segmentDistance or segmentMargin: kernels launched and the times of the x, y and z pass and of the compare /
+   *  reduction (open and close: summed over their two transforms) */
+  distanceStats() { return nativeDistance.distanceStats(this.ctx); }
   /** vx_segment_write_mask, the inverse of segmentMask(): installs a Uint8Array of X*Y*Z/8 bytes (one bit per voxel of
    *  (z, y, x) in C order, LSB first) as the current segment -> what segment() returns, for that mask */
   setSegmentMask(bits) {

@@ -1,5 +1,5 @@
 """The segment chain of `Volxel3DRenderer` (vx_api_segment.hip): seeded region growing and thresholds, edits, islands, the
-masked views, the masks and voxel_index.  A mixin: the renderer supplies _lib, _ctx, _check, _out, _index_extent,
+distance field and the margins, the masked views, the masks and voxel_index.  A mixin: the renderer supplies _lib, _ctx, _check, _out, _index_extent,
 bind_uniforms and restart_rendering."""
 from __future__ import annotations
 
@@ -67,6 +67,28 @@ class Islands:
         return self.count
 
 
+class SegmentDistance:
+    """What Volxel3DRenderer.segment_distance returns (VxDistanceResult): `finite` = the voxels within the cap, `max_distance` =
+    the largest distance within the cap over the voxels outside the source set (side "inside": the radius of the largest ball of
+    voxel centres inside the segment) and `argmax` = (x, y, z), the first voxel in C order that attains it ((0, 0, 0) and 0.0
+    when there is none); squared() and distance(): the (Z, Y, X) float32 field of squared distances and its square root, inf
+    beyond the cap, read from the device when asked (refused once the segment has changed)."""
+
+    def __init__(self, renderer, res, side, spacing, cap):
+        self._renderer = renderer
+        self.side, self.spacing, self.cap = side, spacing, cap
+        self.finite = int(res.finite)
+        self.max_d2 = float(res.max_d2)
+        self.max_distance = float(np.sqrt(np.float32(res.max_d2)))
+        self.argmax = tuple(res.argmax[:])
+
+    def squared(self) -> np.ndarray:
+        return self._renderer.distance_field()
+
+    def distance(self) -> np.ndarray:
+        return np.sqrt(self.squared())
+
+
 class SegmentMixin:
     def segment(self, seed, lo: float, hi: float = math.inf, connectivity: int = 6, box=None, max_rounds: int = 0):
         """Seeded region growing (vx_segment, DESIGN.md section 2 "Segmentation"): the connected component of
@@ -129,6 +151,62 @@ class SegmentMixin:
             raise ValueError(f"band is for dilate only, not {op}")
         q.band = int(bool(band))
         return self._segment_call("vx_segment_edit", C.byref(q))
+
+    MARGIN_OPS = ("grow", "shrink", "open", "close")   # VxMarginOp, in order
+
+    def segment_margin(self, op: str, radius: float, spacing=None, band: bool = False) -> Segment:
+        """Edits the current segment by a margin in physical units (vx_segment_margin, DESIGN.md section 2 "Distances and
+        margins"): "grow" adds every voxel whose centre lies within `radius` of a voxel centre of the segment, "shrink" removes
+        every voxel within `radius` of one outside it (outside the volume counts as inside: a structure cut by the edge of
+        the scan does not shrink from there), "close" = grow then shrink, "open" = shrink then grow.  spacing = (s_x, s_y,
+        s_z) in the units of radius; None: the column norms of grid.transform (mm for DICOM, the units of volume_grid).
+        band=True (grow only) adds only voxels that pass the predicate of the last segment() / threshold().  One exact
+        Euclidean transform per half, whatever the radius.  Binds the current uniforms first; returns the `Segment` of the new
+        mask."""
+        self._index_extent("segment_margin")
+        if op not in self.MARGIN_OPS:
+            raise ValueError(f"op must be one of {self.MARGIN_OPS}, not {op!r}")
+        q = _abi.VxMarginParams()
+        q.op, q.radius = _abi.MARGIN_OPS[op], _checks.distance("radius", radius, allow_inf=False)
+        q.spacing[:] = _checks.spacing(spacing, self.volume.grid.transform)
+        if not isinstance(band, (bool, np.bool_)):
+            raise ValueError(f"band must be a bool, not {band!r}")
+        if band and op != "grow":
+            raise ValueError(f"band is for grow only, not {op}")
+        q.band = int(bool(band))
+        return self._segment_call("vx_segment_margin", C.byref(q))
+
+    DISTANCE_SIDES = ("outside", "inside")   # VxDistanceSide, in order
+
+    def segment_distance(self, side: str = "outside", max_distance: float = math.inf, spacing=None) -> SegmentDistance:
+        """The exact Euclidean distance field of the current segment (vx_segment_distance): side "outside" = how far every
+        voxel centre is from the nearest voxel centre of the segment (0 inside it), "inside" = how far every voxel of the segment
+        is from the nearest voxel outside it (0 outside; voxels beyond the volume are never candidates).  Distances above
+        max_distance read inf.  spacing as for segment_margin.  The segment is not changed.  Returns a `SegmentDistance`."""
+        self._index_extent("segment_distance")
+        if side not in self.DISTANCE_SIDES:
+            raise ValueError(f"side must be one of {self.DISTANCE_SIDES}, not {side!r}")
+        q = _abi.VxDistanceParams()
+        q.max_distance = _checks.distance("max_distance", max_distance, allow_inf=True)
+        q.spacing[:] = _checks.spacing(spacing, self.volume.grid.transform)
+        q.side = _abi.DISTANCE_SIDES[side]
+        self.bind_uniforms()
+        res = _abi.VxDistanceResult()
+        self._check(self._lib.vx_segment_distance(self._ctx, C.byref(q), C.byref(res)))
+        return SegmentDistance(self, res, side, tuple(q.spacing[:]), float(q.max_distance))
+
+    def distance_field(self) -> np.ndarray:
+        """the squared distances of the last segment_distance as a (Z, Y, X) float32 array, inf beyond the cap
+        (vx_distance_read); refused once the segment has changed"""
+        X, Y, Z = self._index_extent("distance_field", hint="")
+        out = np.empty((Z, Y, X), dtype=np.float32)
+        self._check(self._lib.vx_distance_read(self._ctx, out.ctypes.data, out.size))
+        return out
+
+    def distance_stats(self):
+        """(launches, x_ms, y_ms, z_ms, compare_ms) of the last segment_distance or segment_margin (vx_distance_stats); the
+        passes of open / close are summed over their two transforms"""
+        return self._out("vx_distance_stats", C.c_uint32, C.c_double * 4)
 
     def set_segment_mask(self, mask) -> Segment:
         """Installs a (Z, Y, X) bool array over the index extent as the current segment (vx_segment_write_mask, the inverse of
