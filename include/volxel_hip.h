@@ -696,6 +696,80 @@ int vx_segment_margin(VxContext* ctx, const VxMarginParams* params, VxSegmentRes
  * summed over the two transforms of OPEN and CLOSE; all 0 before the first call.  Any pointer may be NULL.  group: member 0. */
 int vx_distance_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
 
+/* ---- the segment store (DESIGN.md section 2 "Segment store"): VX_SEGMENT_SLOTS masks kept on the device beside the current
+ * segment, and the calls that need two masks present at once -- the set operations, the comparison of two segmentations and
+ * the label map of several.  A slot holds a mask only: one bit per voxel of index_extent (padding included), an allocation
+ * of its own of X * Y * Z / 8 bytes made when the slot is first stored to, freed by vx_segment_drop and with the volume (an
+ * upload empties the store).  A = the current segment, B = the mask of a slot.  All calls run on the context's stream behind
+ * every queued render and synchronise; none touches the accumulator, the frame state, VxCounters, the light grid, the bound
+ * tables, the mesh, VxParams, the segment view, the predicate words of the last vx_segment / vx_segment_threshold or what
+ * vx_segment_stats reports.  Every call: VX_ERR_INVALID for a NULL ctx, VX_ERR_NO_VOLUME before an upload, VX_ERR_INVALID
+ * before vx_set_params, and a refused call changes nothing.  group: member 0. */
+#define VX_SEGMENT_SLOTS 32u
+/* Copies the current segment into `slot`, replacing what it held; the current segment stays.  VX_ERR_INVALID for
+ * slot >= VX_SEGMENT_SLOTS and with no current segment. */
+int vx_segment_store(VxContext* ctx, uint32_t slot);
+/* Makes the mask of `slot` the current segment (creating one where there was none); the slot keeps its copy.  out (may be
+ * NULL) holds the statistics of the mask as vx_segment_write_mask reports them, and vx_segment_edit_stats reports the call
+ * (launches = 1).  Drops the island table and the distance field, nothing else.  VX_ERR_INVALID for slot >=
+ * VX_SEGMENT_SLOTS and for an empty slot. */
+int vx_segment_load(VxContext* ctx, uint32_t slot, VxSegmentResult* out);
+/* Frees `slot`; VX_OK for a slot that is empty already.  VX_ERR_INVALID for slot >= VX_SEGMENT_SLOTS. */
+int vx_segment_drop(VxContext* ctx, uint32_t slot);
+/* occupied: bit k is set when slot k holds a mask.  VX_ERR_INVALID for NULL occupied. */
+int vx_segment_slots(VxContext* ctx, uint32_t* occupied);
+typedef enum VxCombineOp {
+  VX_COMBINE_UNION = 0,       /* A | B                                            */
+  VX_COMBINE_INTERSECT = 1,   /* A & B                                            */
+  VX_COMBINE_SUBTRACT = 2,    /* A & ~B                                           */
+  VX_COMBINE_XOR = 3,         /* A ^ B                                            */
+  VX_COMBINE_INVERT = 4       /* ~A over index_extent; slot is ignored            */
+} VxCombineOp;
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxCombineParams {
+  int32_t op;              /* VxCombineOp                                                                          */
+  uint32_t slot;           /* B; ignored by INVERT                                                                 */
+} VxCombineParams;
+/* Rewrites the current segment in place as op(A, B) with one word-wise kernel.  out (may be NULL) holds the statistics of the
+ * new mask as vx_segment_write_mask reports them (rounds = brick_visits = 0, converged = 1); vx_segment_edit_stats reports
+ * the call (launches = 1).  Drops the island table and the distance field, nothing else; the slot is not changed; with a view
+ * on, the next covered call reads the new mask.  VX_ERR_INVALID for NULL params, an op outside the enum, no current segment
+ * (INVERT included), and -- for every op but INVERT -- slot >= VX_SEGMENT_SLOTS or an empty slot. */
+int vx_segment_combine(VxContext* ctx, const VxCombineParams* params, VxSegmentResult* out);
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxCompareParams {
+  uint32_t slot;           /* B                                                                                    */
+  int32_t hausdorff;       /* 0: the overlap counts only; 1: the two directed Hausdorff distances as well          */
+  float spacing[3];        /* as VxDistanceParams; read with hausdorff = 1 only                                    */
+} VxCompareParams;
+/* count_a, count_b, count_and: |A|, |B|, |A & B|, exact (Dice = 2 and / (a + b), Jaccard = and / (a + b - and): the hosts
+ * derive them).  With hausdorff = 1, d2_ab = the largest D2_B(i) over i in A and d2_ba = the largest D2_A(i) over i in B, D2_S
+ * the uncapped squared distance transform of S with the bits vx_segment_distance gives, and argmax_ab / argmax_ba (x, y, z)
+ * the first voxel in C order over (z, y, x) that attains it.  A direction whose own set is empty reports 0 and (0, 0, 0); one
+ * whose own set is not empty while the other set is reports +inf and the first voxel of its own set.  The Hausdorff distance is
+ * sqrt(max(d2_ab, d2_ba)); the device takes no square root.  With hausdorff = 0 the five are 0.
+ * every member is 4 or 8 bytes wide, no padding */
+typedef struct VxCompareResult {
+  uint64_t count_a, count_b, count_and;
+  float d2_ab, d2_ba;
+  uint32_t argmax_ab[3], argmax_ba[3];
+} VxCompareResult;
+/* Compares the current segment with the mask of a slot; neither, nor the island table, is changed.  hausdorff = 0 counts the
+ * overlap (a popcount kernel and its reduction), has no limit on the extent and leaves the distance field alone.
+ * hausdorff = 1 adds two uncapped transforms (of B, then of A) in the buffers of vx_segment_distance, each followed by a
+ * reduction over the voxels of the other set: it overwrites the field, so vx_distance_read is refused afterwards, and
+ * vx_distance_stats reports the call's two transforms summed per pass (launches = 10).  out may be NULL.  VX_ERR_INVALID for
+ * NULL params, slot >= VX_SEGMENT_SLOTS, an empty slot, no current segment, hausdorff not 0 or 1 and, with hausdorff = 1, a
+ * spacing component that is not finite or <= 0 and a volume with more than 16384 voxels along y or z. */
+int vx_segment_compare(VxContext* ctx, const VxCompareParams* params, VxCompareResult* out);
+/* The label map of n = 1 .. VX_SEGMENT_SLOTS slots, dense (Z, Y, X) uint8 in C order: labels[i] = k + 1 for the first k with
+ * voxel i in slots[k], 0 when no listed slot holds it; nvoxels must be X * Y * Z of index_extent.  overlaps (may be NULL): the
+ * number of voxels that more than one listed slot holds.  The current segment is not read (none is needed) or changed.  The
+ * device buffer, 1 B per voxel, is allocated by the first call and freed with the volume.  VX_ERR_INVALID for NULL slots or
+ * labels, n outside 1 .. VX_SEGMENT_SLOTS, a listed slot >= VX_SEGMENT_SLOTS, an empty one, a slot listed twice (duplicate)
+ * and a wrong nvoxels. */
+int vx_segments_labelmap(VxContext* ctx, const uint32_t* slots, uint32_t n, uint8_t* labels, uint64_t nvoxels, uint64_t* overlaps);
+
 /* ---- segment views (DESIGN.md section 2 "Segment views"): show only, or hide, the current segment.  With a view other than
  * OFF the covered calls -- vx_render_frame / vx_render_frames in VX_MODE_DVR, _DVR_PHONG, _MIP and _MINIP, and vx_isosurface
  * (hence picking) -- sample the masked volume: every decoded voxel v(i) reads +0.0f where it is hidden (ONLY: i is not in the

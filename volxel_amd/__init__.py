@@ -17,5 +17,6 @@ from .mpr import axial, coronal, sagittal, oblique, overlay  # noqa: F401,E402
 from ._abi import VxSliceParams, VxIsoParams, VxSegmentParams, VxSegmentResult, VxSegmentEditParams  # noqa: F401,E402
 from ._abi import VxMeshParams, VxMeshResult  # noqa: F401,E402
 from .mesh import Mesh  # noqa: F401,E402
-from .renderer import Segment, SegmentDistance  # noqa: F401,E402
+from .renderer import Segment, SegmentComparison, SegmentDistance  # noqa: F401,E402
 from ._abi import VxDistanceParams, VxDistanceResult, VxMarginParams  # noqa: F401,E402
+from ._abi import VxCombineParams, VxCompareParams, VxCompareResult  # noqa: F401,E402

@@ -60,6 +60,9 @@ VxIsland = struct_from_header("volxel_hip.h", "VxIsland")
 VxDistanceParams = struct_from_header("volxel_hip.h", "VxDistanceParams")
 VxDistanceResult = struct_from_header("volxel_hip.h", "VxDistanceResult")
 VxMarginParams = struct_from_header("volxel_hip.h", "VxMarginParams")
+VxCombineParams = struct_from_header("volxel_hip.h", "VxCombineParams")
+VxCompareParams = struct_from_header("volxel_hip.h", "VxCompareParams")
+VxCompareResult = struct_from_header("volxel_hip.h", "VxCompareResult")
 VxMeshParams = struct_from_header("volxel_hip.h", "VxMeshParams")
 VxMeshResult = struct_from_header("volxel_hip.h", "VxMeshResult")
 
@@ -79,6 +82,8 @@ SEGEDIT_MAX_STEPS = 1024
 ISLANDS_OPS = {"label": 0, "keep_largest": 1, "remove_small": 2, "keep_at": 3}   # enum VxIslandsOp
 DISTANCE_SIDES = {"outside": 0, "inside": 1}            # enum VxDistanceSide
 MARGIN_OPS = {"grow": 0, "shrink": 1, "open": 2, "close": 3}   # enum VxMarginOp
+SEGMENT_SLOTS = 32                                     # VX_SEGMENT_SLOTS
+COMBINE_OPS = {"union": 0, "intersect": 1, "subtract": 2, "xor": 3, "invert": 4}   # enum VxCombineOp
 MESH_DENSITY, MESH_SEGMENT = range(2)                  # enum VxMeshSource
 
 
@@ -181,6 +186,13 @@ def load_library():
         "vx_distance_read": ([vp, vp, u64], i32),
         "vx_segment_margin": ([vp, P(VxMarginParams), P(VxSegmentResult)], i32),
         "vx_distance_stats": ([vp, P(u32), P(C.c_double)], i32),
+        "vx_segment_store": ([vp, u32], i32),
+        "vx_segment_load": ([vp, u32, P(VxSegmentResult)], i32),
+        "vx_segment_drop": ([vp, u32], i32),
+        "vx_segment_slots": ([vp, P(u32)], i32),
+        "vx_segment_combine": ([vp, P(VxCombineParams), P(VxSegmentResult)], i32),
+        "vx_segment_compare": ([vp, P(VxCompareParams), P(VxCompareResult)], i32),
+        "vx_segments_labelmap": ([vp, P(u32), u32, vp, u64, P(u64)], i32),
         "vx_mesh_extract": ([vp, P(VxMeshParams), P(VxMeshResult)], i32),
         "vx_mesh_read": ([vp, vp, vp, vp], i32),
         "vx_mesh_stats": ([vp, P(u32), P(C.c_double)], i32),

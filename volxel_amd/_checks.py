@@ -69,6 +69,26 @@ def distance(name: str, r, allow_inf: bool) -> float:
     return float(r32)
 
 
+def slot(s, name: str = "slot") -> int:
+    """a slot of the segment store: an int 0 .. SEGMENT_SLOTS - 1 (no bool, no float, no string)"""
+    return integer(s, 0, _abi.SEGMENT_SLOTS - 1,
+                   f"{name} must be an integer 0 .. {_abi.SEGMENT_SLOTS - 1}, not {s!r}", whole_floats=False)
+
+
+def slots(ss) -> tuple:
+    """the slot list of a label map: 1 .. SEGMENT_SLOTS different slots, in the order given"""
+    try:
+        t = tuple(ss)
+    except TypeError:
+        raise ValueError(f"slots must be a sequence of slots, not {ss!r}") from None
+    if not 1 <= len(t) <= _abi.SEGMENT_SLOTS:
+        raise ValueError(f"slots must list 1 .. {_abi.SEGMENT_SLOTS} slots, not {len(t)}")
+    t = tuple(slot(s, "slots: every entry") for s in t)
+    if len(set(t)) != len(t):
+        raise ValueError(f"slots must not list a slot twice, as {list(t)!r} does")
+    return t
+
+
 def box(b, ext):
     """(lo, hi) of box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices inside the index extent; None: all of it"""
     if b is None:

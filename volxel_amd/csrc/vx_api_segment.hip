@@ -1,6 +1,6 @@
 // vx_api_segment.hip -- the segment unit of the host layer (units: DESIGN.md section 4.1): the segment chain -- seeded region
-// growing, the mask's read-back, slice overlay and view, the edits, the threshold, the islands, and the distance field with the
-// millimetre margins.
+// growing, the mask's read-back, slice overlay and view, the edits, the threshold, the islands, the distance field with the
+// millimetre margins, and the segment store with its set operations, comparison and label map.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "vx_segedit.hpp"
 #include "vx_islands.hpp"
 #include "vx_distance.hpp"
+#include "vx_segstore.hpp"
 #include "vx_context.hpp"
 
 using namespace vx;
@@ -301,6 +302,36 @@ static int mark_rest(VxContext* c, int from, int to) {
 static int read_distance_times(VxContext* c, int rounds) {
   if (int rc = c->dst_timer.read(c)) return rc;
   for (int k = 0; k < 4; ++k) c->dst_ms[k] = c->dst_timer.ms[k] + (rounds > 1 ? c->dst_timer.ms[4 + k] : 0.0);
+  return VX_OK;
+}
+
+// ---- the segment store (vx_segment_store .. vx_segments_labelmap; kernels in vx_segstore.hpp) ----------------------------------
+constexpr uint32_t SST_MAX_PARTIALS = 1024;
+
+// `slot` names a slot; with `occupied`, one that holds a mask
+static int check_slot(VxContext* c, const char* fn, uint32_t slot, bool occupied) {
+  if (slot >= VX_SEGMENT_SLOTS) VX_FAIL(c, VX_ERR_INVALID, "%s: slot = %u outside 0 .. %u", fn, slot, VX_SEGMENT_SLOTS - 1u);
+  if (occupied && !c->vol.slots[slot].p)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: slot %u is empty (vx_segment_store first; vx_segment_drop and an upload empty it)", fn, slot);
+  return VX_OK;
+}
+static int check_current(VxContext* c, const char* fn) {
+  if (!c->vol.seg_valid)
+    VX_FAIL(c, VX_ERR_INVALID, "%s: no current segment (vx_segment, vx_segment_threshold, vx_segment_write_mask or vx_segment_load "
+                               "first; an upload drops it)", fn);
+  return VX_OK;
+}
+
+// behind an uncapped transform: the largest D2 over the voxels of `over` into partials[0] (sst_max_over, dst_reduce_final)
+static int launch_max_over(VxContext* c, const uint64_t* over, DstPartial* partials) {
+  const SegDev& s = c->vol.seg;
+  const size_t words = (size_t)s.nb * 8u;
+  const uint32_t blocks = (uint32_t)std::min<size_t>((words + 255u) / 256u, DST_MAX_PARTIALS / 2u);
+  hipLaunchKernelGGL(sst_max_over, dim3(blocks), dim3(256), 0, c->stream, (const float*)c->vol.dist_field, over, s.bc[0], s.bc[1], s.bc[2],
+                     partials);
+  hipLaunchKernelGGL(dst_reduce_final, dim3(1), dim3(256), 0, c->stream, partials, blocks);
+  VX_HIP(c, hipGetLastError());
+  c->dst_launches += 2;
   return VX_OK;
 }
 
@@ -861,6 +892,192 @@ int vx_distance_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
   if (is_group(c)) return on_member0(c, vx_distance_stats(c->members[0], launches, kernel_ms));
   if (launches) *launches = c->dst_launches;
   if (kernel_ms) std::copy_n(c->dst_ms, 4, kernel_ms);
+  return VX_OK;
+}
+
+// ---- the segment store -----------------------------------------------------------------------------------------------------------
+// (a slot is freed or first allocated between calls: every earlier call has completed, each one synchronises)
+int vx_segment_store(VxContext* c, uint32_t slot) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_store(c->members[0], slot));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_store", c, "ctx")) return rc;
+  if (int rc = check_slot(c, "vx_segment_store", slot, false)) return rc;
+  if (int rc = check_current(c, "vx_segment_store")) return rc;
+  const SegDev& s = c->vol.seg;
+  DevBuf<uint64_t>& dst = c->vol.slots[slot];
+  if (!dst.p)
+    if (int rc = dst.alloc(c, (size_t)s.nb * 8u)) return rc;
+  VX_HIP(c, hipMemcpyAsync(dst.p, s.seg, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  return VX_OK;
+}
+
+// (the mask is rewritten outright: timed and counted like vx_segment_write_mask, the copy as its one launch)
+int vx_segment_load(VxContext* c, uint32_t slot, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_load(c->members[0], slot, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_load", c, "ctx")) return rc;
+  if (int rc = check_slot(c, "vx_segment_load", slot, true)) return rc;
+  if (int rc = ensure_segment(c)) return rc;   // (there already: a slot was stored from it)
+  c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
+  const SegDev& s = c->vol.seg;
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
+  // SegDev::seg keeps its address: the masked render kernels read it at launch time
+  VX_HIP(c, hipMemcpyAsync(s.seg, c->vol.slots[slot].p, (size_t)s.nb * 64u, hipMemcpyDeviceToDevice, c->stream));
+  c->sed_launches = 1;
+  return finish_mask_edit(c, false, false, out);
+}
+
+int vx_segment_drop(VxContext* c, uint32_t slot) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_drop(c->members[0], slot));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_drop", c, "ctx")) return rc;
+  if (int rc = check_slot(c, "vx_segment_drop", slot, false)) return rc;
+  c->vol.slots[slot].reset();
+  return VX_OK;
+}
+
+int vx_segment_slots(VxContext* c, uint32_t* occupied) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_slots(c->members[0], occupied));
+  if (int rc = check_ready(c, "vx_segment_slots", occupied, "occupied")) return rc;
+  uint32_t bits = 0;
+  for (uint32_t k = 0; k < VX_SEGMENT_SLOTS; ++k)
+    if (c->vol.slots[k].p) bits |= 1u << k;
+  *occupied = bits;
+  return VX_OK;
+}
+
+int vx_segment_combine(VxContext* c, const VxCombineParams* cp, VxSegmentResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_combine(c->members[0], cp, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_combine", cp, "params")) return rc;
+  if (cp->op < VX_COMBINE_UNION || cp->op > VX_COMBINE_INVERT)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_combine: op = %d is not a VxCombineOp (0 .. 4)", cp->op);
+  const bool invert = cp->op == VX_COMBINE_INVERT;
+  if (!invert)
+    if (int rc = check_slot(c, "vx_segment_combine", cp->slot, false)) return rc;
+  if (int rc = check_current(c, "vx_segment_combine")) return rc;
+  if (!invert)
+    if (int rc = check_slot(c, "vx_segment_combine", cp->slot, true)) return rc;
+  c->vol.isl_valid = false;
+  c->vol.dist_valid = false;
+  const SegDev& s = c->vol.seg;
+  if (int rc = c->sed_timer.mark(c, 0)) return rc;
+  const size_t pairs = (size_t)s.nb * 4u;
+  hipLaunchKernelGGL(sst_combine, dim3((uint32_t)std::min<size_t>((pairs + 255u) / 256u, 8192u)), dim3(256), 0, c->stream, s.seg,
+                     invert ? (const uint64_t*)nullptr : (const uint64_t*)c->vol.slots[cp->slot].p, cp->op, pairs);
+  VX_HIP(c, hipGetLastError());
+  c->sed_launches = 1;
+  return finish_mask_edit(c, false, false, out);
+}
+
+int vx_segment_compare(VxContext* c, const VxCompareParams* cp, VxCompareResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segment_compare(c->members[0], cp, out));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segment_compare", cp, "params")) return rc;
+  if (int rc = check_slot(c, "vx_segment_compare", cp->slot, false)) return rc;
+  if (int rc = check_current(c, "vx_segment_compare")) return rc;
+  if (int rc = check_slot(c, "vx_segment_compare", cp->slot, true)) return rc;
+  if (cp->hausdorff != 0 && cp->hausdorff != 1)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segment_compare: hausdorff = %d is not 0 or 1", cp->hausdorff);
+  if (cp->hausdorff) {
+    if (int rc = check_spacing(c, "vx_segment_compare", cp->spacing)) return rc;
+    if (int rc = check_line_extent(c, "vx_segment_compare")) return rc;
+    if (int rc = ensure_distance(c)) return rc;
+  }
+  if (int rc = c->vol.sst_partials.ensure(c, SST_MAX_PARTIALS)) return rc;
+  const SegDev& s = c->vol.seg;
+  const uint32_t* E = c->vol.dv.extent;
+  const uint64_t* A = s.seg;
+  const uint64_t* B = c->vol.slots[cp->slot].p;
+  const size_t pairs = (size_t)s.nb * 4u;
+  const uint32_t blocks = (uint32_t)std::min<size_t>((pairs + 255u) / 256u, SST_MAX_PARTIALS);
+  SstCount* counts = c->vol.sst_partials;
+  hipLaunchKernelGGL(sst_count, dim3(blocks), dim3(256), 0, c->stream, A, B, pairs, counts);
+  hipLaunchKernelGGL(sst_count_final, dim3(1), dim3(256), 0, c->stream, counts, blocks);
+  VX_HIP(c, hipGetLastError());
+  DstPartial* tops = c->vol.dist_partials;   // with hausdorff: A over D2_B at [0], B over D2_A at [DST_MAX_PARTIALS / 2]
+  if (cp->hausdorff) {
+    // the field buffer is overwritten: whatever vx_segment_distance left there is gone
+    c->vol.dist_valid = false;
+    c->dst_launches = 0;
+    // (event 4 is recorded twice, behind the first reduction and again ahead of the second x pass, as a two-round margin does)
+    if (int rc = run_distance(c, B, 0ull, cp->spacing, DST_INF, 0)) return rc;
+    if (int rc = launch_max_over(c, A, tops)) return rc;
+    if (int rc = c->dst_timer.mark(c, 4)) return rc;
+    if (int rc = run_distance(c, A, 0ull, cp->spacing, DST_INF, 4)) return rc;
+    if (int rc = launch_max_over(c, B, tops + DST_MAX_PARTIALS / 2u)) return rc;
+    if (int rc = mark_rest(c, 8, 9)) return rc;
+  }
+  SstCount n{};
+  DstPartial top[2] = {{0ull, DST_NONE, 0.0f, 0u}, {0ull, DST_NONE, 0.0f, 0u}};
+  VX_HIP(c, hipMemcpyAsync(&n, counts, sizeof n, hipMemcpyDeviceToHost, c->stream));
+  if (cp->hausdorff) {
+    VX_HIP(c, hipMemcpyAsync(&top[0], tops, sizeof top[0], hipMemcpyDeviceToHost, c->stream));
+    VX_HIP(c, hipMemcpyAsync(&top[1], tops + DST_MAX_PARTIALS / 2u, sizeof top[1], hipMemcpyDeviceToHost, c->stream));
+  }
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  if (cp->hausdorff)
+    if (int rc = read_distance_times(c, 2)) return rc;
+  VxCompareResult r{};
+  r.count_a = n.a;
+  r.count_b = n.b;
+  r.count_and = n.ab;
+  float* d2[2] = {&r.d2_ab, &r.d2_ba};
+  uint32_t* arg[2] = {r.argmax_ab, r.argmax_ba};
+  for (int k = 0; k < 2; ++k) {
+    if (top[k].idx == DST_NONE) continue;   // its own set is empty (or hausdorff = 0): 0 and (0, 0, 0)
+    *d2[k] = top[k].d2;
+    arg[k][0] = (uint32_t)(top[k].idx % E[0]);
+    arg[k][1] = (uint32_t)((top[k].idx / E[0]) % E[1]);
+    arg[k][2] = (uint32_t)(top[k].idx / ((uint64_t)E[0] * E[1]));
+  }
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_segments_labelmap(VxContext* c, const uint32_t* slots, uint32_t n, uint8_t* labels, uint64_t nvoxels, uint64_t* overlaps) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_segments_labelmap(c->members[0], slots, n, labels, nvoxels, overlaps));
+  VX_DEV(c);
+  if (int rc = check_ready(c, "vx_segments_labelmap", slots, "slots")) return rc;
+  if (!labels) VX_FAIL(c, VX_ERR_INVALID, "vx_segments_labelmap: labels is NULL");
+  if (n < 1u || n > VX_SEGMENT_SLOTS)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segments_labelmap: n = %u outside 1 .. %u (an empty or over-long list)", n, VX_SEGMENT_SLOTS);
+  SstSlots list{};
+  uint32_t listed = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    if (int rc = check_slot(c, "vx_segments_labelmap", slots[k], true)) return rc;
+    if (listed & (1u << slots[k])) VX_FAIL(c, VX_ERR_INVALID, "vx_segments_labelmap: slot %u is listed twice (duplicate)", slots[k]);
+    listed |= 1u << slots[k];
+    list.w[k] = c->vol.slots[slots[k]].p;
+  }
+  list.n = n;
+  const uint32_t* E = c->vol.dv.extent;
+  const uint32_t* bc = c->vol.dv.bc;
+  const size_t want = (size_t)E[0] * E[1] * E[2];
+  if (nvoxels != want)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_segments_labelmap: nvoxels = %llu, the volume has %u x %u x %u = %zu voxels",
+            (unsigned long long)nvoxels, E[0], E[1], E[2], want);
+  if (int rc = c->vol.sst_labels.ensure(c, want)) return rc;   // (every earlier call has completed: each one synchronises)
+  if (int rc = c->vol.sst_overlaps.ensure(c, 1)) return rc;
+  unsigned long long* multi = c->vol.sst_overlaps;
+  VX_HIP(c, hipMemsetAsync(multi, 0, sizeof *multi, c->stream));
+  const uint32_t blocks = (uint32_t)std::min<size_t>((want / 8u + 255u) / 256u, 16384u);
+  hipLaunchKernelGGL(sst_labelmap, dim3(blocks), dim3(256), 0, c->stream, list, bc[0], bc[1], bc[2], (uint8_t*)c->vol.sst_labels, multi);
+  VX_HIP(c, hipGetLastError());
+  unsigned long long over = 0;
+  VX_HIP(c, hipMemcpyAsync(labels, c->vol.sst_labels, want, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipMemcpyAsync(&over, multi, sizeof over, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  if (overlaps) *overlaps = over;
   return VX_OK;
 }
 

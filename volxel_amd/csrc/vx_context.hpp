@@ -129,6 +129,13 @@ struct VxContext : VxCore {   // (device, the stream the launches go to, the las
     DevBuf<float> dist_field;
     DevBuf<DstPartial> dist_partials;
     bool dist_valid = false;   // the field is the last vx_segment_distance's and the mask has not changed since
+    // the segment store (vx_segment_store .. vx_segments_labelmap): a slot is an allocation of its own of nb * 8 words, made by
+    // the first store to it (p != nullptr: occupied); the partials of the overlap counts and the dense label map (1 B per voxel,
+    // with the count of overlapping voxels behind it) are allocated by the first call that needs them
+    DevBuf<uint64_t> slots[VX_SEGMENT_SLOTS];
+    DevBuf<SstCount> sst_partials;
+    DevBuf<uint8_t> sst_labels;
+    DevBuf<unsigned long long> sst_overlaps;
     // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans
     // (ensure_mesh); the vertex / cell buffers (3 values per vertex, grown together) and the triangles grow to the largest mesh
     DevBuf<void> mesh_alloc;

@@ -163,6 +163,17 @@ struct DstPartial {
   uint32_t pad;
 };
 
+// ---- the segment store (vx_segstore.hpp)
+// a partial of the overlap counts: |A|, |B| and |A & B| over the words a workgroup read
+struct SstCount {
+  unsigned long long a, b, ab;
+};
+// the masks of a label map in list order, by value: w[k] = the nb * 8 words of the k-th listed slot, k < n
+struct SstSlots {
+  const uint64_t* w[VX_SEGMENT_SLOTS];
+  uint32_t n;
+};
+
 // ---- the islands (vx_islands.hpp)
 // one island while the table is built (device side; the host ranks the rows)
 struct IslRow {

@@ -122,6 +122,29 @@ export declare class Volxel3DDicomRenderer {
   distanceField(): Float32Array;
   /** the last segmentDistance or segmentMargin: kernels launched and the times of its passes */
   distanceStats(): { launches: number; xMs: number; yMs: number; zMs: number; compareMs: number };
+  /** copy the current segment into a slot (0 .. 31) of the device's segment store (include/volxel_hip.h vx_segment_store) */
+  storeSegment(slot: number): void;
+  /** the mask of a slot becomes the current segment; the slot keeps its copy (vx_segment_load) */
+  loadSegment(slot: number):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** free a slot; an empty one is fine (vx_segment_drop) */
+  dropSegment(slot: number): void;
+  /** the occupied slots, ascending (vx_segment_slots) */
+  storedSegments(): number[];
+  /** a set operation on the current segment A and the mask B of a slot, in place; 'invert' takes no slot (vx_segment_combine) */
+  segmentCombine(op: 'union' | 'intersect' | 'subtract' | 'xor' | 'invert', slot?: number | null):
+    { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;
+      mean: number; rounds: number; converged: boolean; brickVisits: number };
+  /** overlap counts, Dice, Jaccard and (hausdorff, the default) the directed Hausdorff distances of the current segment A and
+   *  the mask B of a slot; the distance fields are null without hausdorff (vx_segment_compare) */
+  segmentCompare(slot: number, opts?: { hausdorff?: boolean; spacing?: [number, number, number] | null }):
+    { countA: number; countB: number; countAnd: number; dice: number; jaccard: number; d2Ab: number | null; d2Ba: number | null;
+      hausdorffAb: number | null; hausdorffBa: number | null; hausdorff: number | null;
+      argmaxAb: [number, number, number] | null; argmaxBa: [number, number, number] | null };
+  /** the uint8 label map over (z, y, x) of the listed slots, first listed first, and the number of voxels more than one of
+   *  them holds (vx_segments_labelmap) */
+  segmentsLabelmap(slots: number[] | Uint32Array): { labels: Uint8Array; overlaps: number };
   /** install a packed mask (the layout of segmentMask()) as the current segment (vx_segment_write_mask) */
   setSegmentMask(bits: Uint8Array):
     { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;

@@ -13,6 +13,7 @@ const fs = require('fs');
 const path = require('path');
 const native = require('./volxel_napi.node');
 const nativeDistance = require('./volxel_napi_distance.node');   // the addon of the distance calls, on native's handles
+const nativeSegments = require('./volxel_napi_segments.node');   // the addon of the segment store, on native's handles
 
 const RenderMode = Object.freeze({ default: 0, no_dda: 1, raymarch: 2, dvr: 3, dvr_phong: 4, mip: 5, minip: 6 });
 const LOW_RES_DURATION = 5; // viewer.ts:132
@@ -47,6 +48,8 @@ const SEGMENT_VIEWS = ['off', 'only', 'hide'];   // VX_SEGVIEW_OFF, _ONLY, _HIDE
 const SEGMENT_EDIT_OPS = ['dilate', 'erode', 'open', 'close', 'fill_holes'];   // VxSegmentEditOp, in order
 const MARGIN_OPS = ['grow', 'shrink', 'open', 'close'];   // VxMarginOp, in order
 const DISTANCE_SIDES = ['outside', 'inside'];             // VxDistanceSide, in order
+const COMBINE_OPS = ['union', 'intersect', 'subtract', 'xor', 'invert'];   // VxCombineOp, in order
+const SEGMENT_SLOTS = 32;                                 // VX_SEGMENT_SLOTS
 const SliceReduce = Object.freeze({ mean: 0, max: 1, min: 2 });         // enum VxSliceReduce
 const SliceDisplay = Object.freeze({ grey: 1, tf: 2 });                  // enum VxSliceDisplay (null: VX_SLICE_NONE)
 
@@ -315,6 +318,19 @@ function checkDistance(who, name, r, allowInf) {
   if (!(r32 > 0) || (!Number.isFinite(r32) && !(allowInf && r === Infinity)))
     throw new Error(`${who}: ${name} must be ${allowInf ? '> 0 (Infinity: no cap)' : 'finite and > 0'}, not ${r}`);
   return r32;
+}
+/** a slot of the segment store: an integer 0 .. SEGMENT_SLOTS - 1; `name` is what the method calls it */
+function checkSlot(who, s, name = 'slot') {
+  if (!Number.isInteger(s) || s < 0 || s >= SEGMENT_SLOTS) throw new Error(`${who}: ${name} must be an integer 0 .. ${SEGMENT_SLOTS - 1}, not ${s}`);
+  return s;
+}
+/** the slot list of a label map: 1 .. SEGMENT_SLOTS different slots, in the order given */
+function checkSlots(who, ss) {
+  const t = Array.isArray(ss) || ArrayBuffer.isView(ss) ? Array.from(ss) : null;
+  if (t === null || t.length < 1 || t.length > SEGMENT_SLOTS) throw new Error(`${who}: slots must list 1 .. ${SEGMENT_SLOTS} slots, not ${t === null ? ss : t.length}`);
+  t.forEach(s => checkSlot(who, s, 'slots: every entry'));
+  if (new Set(t).size !== t.length) throw new Error(`${who}: slots must not list a slot twice, as ${t} does`);
+  return Uint32Array.from(t);
 }
 /** the VxSliceParams block of a slice spec with reduce = mean, no display and the window [0, 1] */
 function sliceParams(who, origin, du, dv, dn, [W, H], slabSamples) {
@@ -738,6 +754,80 @@ class Volxel3DDicomRenderer {
   /** the last segmentDistance or segmentMargin: kernels launched and the times of the x, y and z pass and of the compare /
    *  reduction (open and close: summed over their two transforms) */
   distanceStats() { return nativeDistance.distanceStats(this.ctx); }
+  /** vx_segment_store (DESIGN.md section 2 "Segment store"): copies the current segment into `slot` (0 .. 31) of the device's
+   *  segment store, replacing what it held; the current segment stays */
+  storeSegment(slot) {
+    this.sliceExtent();
+    checkSlot('storeSegment', slot);
+    this.bindUniforms();
+    nativeSegments.storeSegment(this.ctx, slot);
+  }
+  /** vx_segment_load: the mask of `slot` becomes the current segment (the slot keeps its copy) -> what segment() returns */
+  loadSegment(slot) {
+    this.sliceExtent();
+    checkSlot('loadSegment', slot);
+    this.bindUniforms();
+    return this._segmentResult(nativeSegments.loadSegment(this.ctx, slot));
+  }
+  /** vx_segment_drop: frees `slot`; an empty slot is fine */
+  dropSegment(slot) {
+    this.sliceExtent();
+    checkSlot('dropSegment', slot);
+    this.bindUniforms();
+    nativeSegments.dropSegment(this.ctx, slot);
+  }
+  /** the occupied slots, ascending (vx_segment_slots) */
+  storedSegments() {
+    this.sliceExtent();
+    this.bindUniforms();
+    const bits = nativeSegments.storedSegments(this.ctx);
+    return Array.from({ length: SEGMENT_SLOTS }, (_, k) => k).filter(k => (bits >>> k) & 1);
+  }
+  /** vx_segment_combine: op 'union' | 'intersect' | 'subtract' | 'xor' on the current segment A and the mask B of `slot`
+   *  (A | B, A & B, A & ~B, A ^ B), or 'invert' (~A over the index extent; no slot), in place on the GPU -> what segment()
+   *  returns, for the new mask.  Binds the current uniforms first. */
+  segmentCombine(op, slot = null) {
+    this.sliceExtent();
+    const i = COMBINE_OPS.indexOf(op);
+    if (i < 0) throw new Error(`segmentCombine: op must be one of ${COMBINE_OPS.join(', ')}, not ${op}`);
+    if ((op === 'invert') !== (slot === null)) throw new Error(op === 'invert' ? 'segmentCombine: slot must be null for invert' : `segmentCombine: slot is required for ${op}`);
+    if (slot !== null) checkSlot('segmentCombine', slot);
+    this.bindUniforms();
+    return this._segmentResult(nativeSegments.segmentCombine(this.ctx, i, slot === null ? 0 : slot));
+  }
+  /** vx_segment_compare: the current segment A against the mask B of `slot`; opts: { hausdorff = true, spacing = null (as
+   *  segmentMargin) } -> { countA, countB, countAnd, dice, jaccard (NaN when both sets are empty), and with hausdorff: d2Ab, d2Ba,
+   *  hausdorffAb, hausdorffBa (their float32 square roots), hausdorff (the larger), argmaxAb, argmaxBa: [x, y, z]; null
+   *  without }.  Neither mask is changed. */
+  segmentCompare(slot, { hausdorff = true, spacing = null } = {}) {
+    this.sliceExtent();
+    checkSlot('segmentCompare', slot);
+    if (typeof hausdorff !== 'boolean') throw new Error(`segmentCompare: hausdorff must be a boolean, not ${hausdorff}`);
+    const sp = checkSpacing('segmentCompare', spacing, this.volume.grid.transform);
+    this.bindUniforms();
+    const r = nativeSegments.segmentCompare(this.ctx, slot, hausdorff ? 1 : 0, sp[0], sp[1], sp[2]);
+    const sum = r.countA + r.countB;
+    r.dice = sum ? 2 * r.countAnd / sum : NaN;
+    r.jaccard = sum ? r.countAnd / (sum - r.countAnd) : NaN;
+    if (hausdorff) {
+      r.hausdorffAb = Math.fround(Math.sqrt(r.d2Ab));
+      r.hausdorffBa = Math.fround(Math.sqrt(r.d2Ba));
+      r.hausdorff = Math.max(r.hausdorffAb, r.hausdorffBa);
+    } else {
+      for (const k of ['d2Ab', 'd2Ba', 'argmaxAb', 'argmaxBa', 'hausdorffAb', 'hausdorffBa', 'hausdorff']) r[k] = null;
+    }
+    return r;
+  }
+  /** vx_segments_labelmap: the label map of the listed slots -> { labels: Uint8Array over (z, y, x), k + 1 where slots[k] is the
+   *  first listed slot that holds the voxel and 0 where none does; overlaps: the voxels more than one listed slot holds } */
+  segmentsLabelmap(slots) {
+    const e = this.sliceExtent();
+    const list = checkSlots('segmentsLabelmap', slots);
+    this.bindUniforms();
+    const labels = new Uint8Array(e[0] * e[1] * e[2]);
+    const overlaps = nativeSegments.segmentsLabelmap(this.ctx, list, labels);
+    return { labels, overlaps };
+  }
   /** vx_segment_write_mask, the inverse of segmentMask(): installs a Uint8Array of X*Y*Z/8 bytes (one bit per voxel of
    *  (z, y, x) in C order, LSB first) as the current segment -> what segment() returns, for that mask */
   setSegmentMask(bits) {

@@ -6,7 +6,7 @@
  * Plain C against <node_api.h> (N-API v3+, Node >= 10).
  *
  * The helpers come first: arguments in (the context handle among them) and results out in volxel_napi_helpers.h, shared with
- * the addon of the distance calls (volxel_napi_distance.c); grids out and the making of context handles below.  A wrapper
+ * the addons of the distance calls and of the segment store (volxel_napi_distance.c, volxel_napi_segments.c); grids out and the making of context handles below.  A wrapper
  * states only what is particular to its entry point: it opens with CTX_ARGS (or get_args where there is no context), reads a
  * params struct with struct_arg and a typed array with typed / typed_or_null / typed_required, and answers with status,
  * num_object or the set_* calls.  A new wrapper is written from these, not from a neighbour.

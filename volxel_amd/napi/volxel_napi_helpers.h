@@ -1,6 +1,7 @@
 /*
  * volxel_napi_helpers.h -- the helpers every N-API wrapper of this directory is written from (volxel_napi.c, and
- * volxel_napi_distance.c, the addon of the distance calls): arguments in, results out.  A context handle made by
+ * volxel_napi_distance.c and volxel_napi_segments.c, the addons of the distance calls and of the segment store): arguments in,
+ * results out.  A context handle made by
  * volxel_napi.node is read by any of them: it is an external around a Handle.
  */
 #ifndef VOLXEL_NAPI_HELPERS_H

@@ -1,5 +1,5 @@
 """The segment chain of `Volxel3DRenderer` (vx_api_segment.hip): seeded region growing and thresholds, edits, islands, the
-distance field and the margins, the masked views, the masks and voxel_index.  A mixin: the renderer supplies _lib, _ctx, _check, _out, _index_extent,
+distance field and the margins, the segment store with its set operations, comparison and label map, the masked views, the masks and voxel_index.  A mixin: the renderer supplies _lib, _ctx, _check, _out, _index_extent,
 bind_uniforms and restart_rendering."""
 from __future__ import annotations
 
@@ -87,6 +87,28 @@ class SegmentDistance:
 
     def distance(self) -> np.ndarray:
         return np.sqrt(self.squared())
+
+
+@dataclass(frozen=True)
+class SegmentComparison:
+    """What Volxel3DRenderer.segment_compare returns (VxCompareResult), A the current segment and B the slot: count_a, count_b,
+    count_and = |A|, |B|, |A & B|; dice = 2 and / (a + b) and jaccard = and / (a + b - and), nan when both sets are empty.  With
+    hausdorff: d2_ab / d2_ba = the largest squared distance from a voxel of A to B / of B to A, hausdorff_ab / hausdorff_ba their
+    float32 square roots, hausdorff the larger of the two, argmax_ab / argmax_ba = (x, y, z), the first voxel in C order that
+    attains each; a direction whose own set is empty gives 0 and (0, 0, 0), one whose other set alone is empty inf and the first
+    voxel of its own.  All of these are None when hausdorff was not asked for."""
+    count_a: int
+    count_b: int
+    count_and: int
+    dice: float
+    jaccard: float
+    d2_ab: float | None = None
+    d2_ba: float | None = None
+    hausdorff_ab: float | None = None
+    hausdorff_ba: float | None = None
+    hausdorff: float | None = None
+    argmax_ab: tuple | None = None
+    argmax_ba: tuple | None = None
 
 
 class SegmentMixin:
@@ -210,7 +232,8 @@ class SegmentMixin:
 
     def set_segment_mask(self, mask) -> Segment:
         """Installs a (Z, Y, X) bool array over the index extent as the current segment (vx_segment_write_mask, the inverse of
-        segment_mask): a saved segmentation, a host-side combination of masks, or an undo.  The predicate of the last
+        segment_mask): a saved segmentation or a mask made on the host (combinations and undo have a GPU path: store_segment,
+        segment_combine).  The predicate of the last
         segment() and the segment view stay.  Binds the current uniforms first; returns the mask's `Segment`."""
         X, Y, Z = self._index_extent("set_segment_mask")
         m = np.asarray(mask)
@@ -297,6 +320,88 @@ class SegmentMixin:
         """(launches, local_ms, merge_ms, flatten_ms, table_ms, host_rank_ms, apply_ms, stats_ms) of the last islands call
         (vx_islands_stats); host_rank_ms is the host's wall clock for reading back, ranking and re-uploading the rows"""
         return self._out("vx_islands_stats", C.c_uint32, C.c_double * 7)
+
+    # ---- the segment store (DESIGN.md section 2 "Segment store") ----------------------------------------------------------------
+    COMBINE_OPS = ("union", "intersect", "subtract", "xor", "invert")   # VxCombineOp, in order
+
+    def store_segment(self, slot: int) -> None:
+        """Copies the current segment into `slot` (0 .. 31) of the device's segment store, replacing what it held
+        (vx_segment_store); the current segment stays.  A slot costs 1 bit per voxel and lasts until drop_segment or the next
+        setup_from_grid."""
+        self._index_extent("store_segment")
+        slot = _checks.slot(slot)
+        self.bind_uniforms()
+        self._check(self._lib.vx_segment_store(self._ctx, slot))
+
+    def load_segment(self, slot: int) -> Segment:
+        """Makes the mask of `slot` the current segment (vx_segment_load): an undo, or the start of the next edit.  The slot
+        keeps its copy; the predicate of the last segment() / threshold() stays.  Returns the mask's `Segment`."""
+        self._index_extent("load_segment")
+        return self._segment_call("vx_segment_load", _checks.slot(slot))
+
+    def drop_segment(self, slot: int) -> None:
+        """frees `slot` (vx_segment_drop); an empty slot is fine"""
+        self._index_extent("drop_segment")
+        slot = _checks.slot(slot)
+        self.bind_uniforms()
+        self._check(self._lib.vx_segment_drop(self._ctx, slot))
+
+    def stored_segments(self) -> tuple:
+        """the occupied slots, ascending (vx_segment_slots)"""
+        self._index_extent("stored_segments")
+        self.bind_uniforms()
+        bits = self._out("vx_segment_slots", C.c_uint32)[0]
+        return tuple(k for k in range(_abi.SEGMENT_SLOTS) if bits >> k & 1)
+
+    def segment_combine(self, op: str, slot: int | None = None) -> Segment:
+        """A set operation on the current segment A and the mask B of `slot`, in place on the GPU (vx_segment_combine): "union"
+        A | B, "intersect" A & B, "subtract" A & ~B, "xor" A ^ B, or "invert" ~A over the index extent (padding included), which
+        takes no slot.  The slot is not changed.  Binds the current uniforms first; returns the `Segment` of the new mask."""
+        self._index_extent("segment_combine")
+        if op not in self.COMBINE_OPS:
+            raise ValueError(f"op must be one of {self.COMBINE_OPS}, not {op!r}")
+        if (op == "invert") != (slot is None):
+            raise ValueError("slot must be None for invert" if op == "invert" else f"slot is required for {op}")
+        q = _abi.VxCombineParams()
+        q.op, q.slot = _abi.COMBINE_OPS[op], 0 if slot is None else _checks.slot(slot)
+        return self._segment_call("vx_segment_combine", C.byref(q))
+
+    def segment_compare(self, slot: int, hausdorff: bool = True, spacing=None) -> SegmentComparison:
+        """Compares the current segment A with the mask B of `slot` (vx_segment_compare): the exact overlap counts with Dice and
+        Jaccard, and with hausdorff=True the two directed Hausdorff distances from two exact Euclidean transforms (spacing as
+        for segment_margin).  Neither mask is changed; with hausdorff=True the field of the last segment_distance is
+        overwritten.  Returns a `SegmentComparison`."""
+        self._index_extent("segment_compare")
+        q = _abi.VxCompareParams()
+        q.slot = _checks.slot(slot)
+        if not isinstance(hausdorff, (bool, np.bool_)):
+            raise ValueError(f"hausdorff must be a bool, not {hausdorff!r}")
+        q.hausdorff = int(bool(hausdorff))
+        q.spacing[:] = _checks.spacing(spacing, self.volume.grid.transform)
+        self.bind_uniforms()
+        res = _abi.VxCompareResult()
+        self._check(self._lib.vx_segment_compare(self._ctx, C.byref(q), C.byref(res)))
+        a, b, n = int(res.count_a), int(res.count_b), int(res.count_and)
+        kw = dict(count_a=a, count_b=b, count_and=n, dice=2 * n / (a + b) if a + b else math.nan,
+                  jaccard=n / (a + b - n) if a + b else math.nan)
+        if hausdorff:
+            ab, ba = (float(np.sqrt(np.float32(v))) for v in (res.d2_ab, res.d2_ba))
+            kw.update(d2_ab=float(res.d2_ab), d2_ba=float(res.d2_ba), hausdorff_ab=ab, hausdorff_ba=ba, hausdorff=max(ab, ba),
+                      argmax_ab=tuple(res.argmax_ab[:]), argmax_ba=tuple(res.argmax_ba[:]))
+        return SegmentComparison(**kw)
+
+    def segments_labelmap(self, slots):
+        """The label map of the listed slots (vx_segments_labelmap): a (Z, Y, X) uint8 array with k + 1 where slots[k] is the
+        first listed slot that holds the voxel and 0 where none does, and the number of voxels more than one listed slot
+        holds.  Returns (labels, overlaps): how a multi-segment segmentation is saved."""
+        X, Y, Z = self._index_extent("segments_labelmap")
+        t = _checks.slots(slots)
+        self.bind_uniforms()
+        out = np.empty((Z, Y, X), dtype=np.uint8)
+        over = C.c_uint64()
+        self._check(self._lib.vx_segments_labelmap(self._ctx, (C.c_uint32 * len(t))(*t), len(t), out.ctypes.data, out.size,
+                                                   C.byref(over)))
+        return out, int(over.value)
 
     SEGMENT_VIEWS = ("off", "only", "hide")   # VX_SEGVIEW_OFF, _ONLY, _HIDE
 
