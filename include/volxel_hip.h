@@ -770,6 +770,82 @@ int vx_segment_compare(VxContext* ctx, const VxCompareParams* params, VxCompareR
  * and a wrong nvoxels. */
 int vx_segments_labelmap(VxContext* ctx, const uint32_t* slots, uint32_t n, uint8_t* labels, uint64_t nvoxels, uint64_t* overlaps);
 
+/* ---- histograms (DESIGN.md section 2 "Histograms"): the density histogram, the moments and the exact order statistics of a
+ * region, on the device.  Read-only: the call changes nothing but its own buffers.
+ *
+ * Region.  R = the voxels i of index_extent (padding included, as everywhere in the segment chain) inside the inclusive voxel
+ * box [box_lo, box_hi] (VxSegmentParams' meaning, VX_SEGMENT_BOX_END included; the renderer's clip box does not apply) that
+ * `source` selects: VX_HIST_VOLUME every voxel of the box (no segment is needed), VX_HIST_SEGMENT the voxels of the current
+ * segment, VX_HIST_SLOT those of slot `slot` of the segment store.  d(i) is the density vx_segment thresholds:
+ * (volume_density_scale * v(i)) * volume_inv_maj of the last vx_set_params, the same bits on every layout.
+ *
+ * Two bin rules, one kernel.
+ * VX_HIST_LINEAR, lo < hi finite and bins = B in 1 .. VX_HIST_MAX_BINS: the library computes inv = fl32(fl32(B) / fl32(hi - lo))
+ * once on the host.  A voxel with d < lo counts in `below`, one with d > hi in `above`; otherwise
+ *   bin = min(B - 1, (uint32_t)fl32(fl32(d - lo) * inv)),
+ * two fp32 operations rounded to nearest, never contracted.  d == hi lands in the last bin (np.histogram's convention).  Both
+ * operations are monotone in d (a rounded subtraction of a constant and a rounded product with a positive constant never
+ * reverse an order), so the bins are monotone in d and cumulative counts mean what they say.  A range so narrow that inv is
+ * not finite is refused.
+ * VX_HIST_KEY, prefix_bits = p in 0 .. 31, key_bits = b in 1 .. VX_HIST_MAX_KEY_BITS, p + b <= 32, prefix < 2^p (0 when p = 0):
+ * key(d) = the bits of d as an unsigned integer with the order of the floats (negative: all bits flipped; otherwise: the sign
+ * bit set; -0 below +0).  With top = p ? key >> (32 - p) : 0, a voxel with top < prefix counts in `below`, one with top > prefix
+ * in `above`, otherwise bin = (key >> (32 - p - b)) & (2^b - 1); there are 2^b bins.  Three calls (11, 11 and 10 bits, each
+ * with the prefix the last one found) are a radix select: the hosts derive the exact k-th smallest density of R from them.
+ *
+ * Result.  counts[ncounts] receives the bins; ncounts must equal the number of bins.  Always
+ * below + above + sum(counts) == count == |R|.  With moments = 1, d_sum and d_sum2 are the float64 sums of (double)d and
+ * (double)d * (double)d over ALL of R (not only the voxels in range), added in a fixed order -- per brick in the order of
+ * vx_segment's sum, then a fixed tree over the per-brick partials -- and d_min / d_max run over R: two calls return the same
+ * bytes, and d_sum of a segment equals VxSegmentResult::d_sum bit for bit.  With moments = 0 the four fields are 0 and their
+ * kernels do not run (the radix passes).  An empty R is legal: everything is 0. */
+typedef enum VxHistSource {
+  VX_HIST_VOLUME = 0,    /* every voxel of the box                             */
+  VX_HIST_SEGMENT = 1,   /* the current segment                                */
+  VX_HIST_SLOT = 2       /* slot `slot` of the segment store                   */
+} VxHistSource;
+typedef enum VxHistRule {
+  VX_HIST_LINEAR = 0,    /* bins of equal width over [lo, hi]                  */
+  VX_HIST_KEY = 1        /* key_bits bits of the order key under a prefix      */
+} VxHistRule;
+#define VX_HIST_MAX_BINS 4096u
+#define VX_HIST_MAX_KEY_BITS 12u
+/* every member is 4 bytes wide, no padding (parsed like VxParams by the hosts) */
+typedef struct VxHistogramParams {
+  int32_t source;          /* VxHistSource                                                                         */
+  uint32_t slot;           /* VX_HIST_SLOT only                                                                    */
+  uint32_t box_lo[3];      /* inclusive voxel box, as VxSegmentParams                                              */
+  uint32_t box_hi[3];      /* or VX_SEGMENT_BOX_END per axis: to the far face                                      */
+  int32_t rule;            /* VxHistRule                                                                           */
+  uint32_t bins;           /* LINEAR: B, 1 .. VX_HIST_MAX_BINS                                                     */
+  float lo, hi;            /* LINEAR: the range, lo < hi, finite                                                   */
+  uint32_t prefix;         /* KEY: the top prefix_bits bits a counted key must have                                */
+  uint32_t prefix_bits;    /* KEY: p, 0 .. 31                                                                      */
+  uint32_t key_bits;       /* KEY: b, 1 .. VX_HIST_MAX_KEY_BITS; 2^b bins                                          */
+  int32_t moments;         /* 1: d_sum, d_sum2, d_min, d_max as well; 0: they read 0                               */
+} VxHistogramParams;
+/* every member is 4 or 8 bytes wide, no padding */
+typedef struct VxHistogramResult {
+  uint64_t count, below, above;
+  double d_sum, d_sum2;
+  float d_min, d_max;
+} VxHistogramResult;
+/* The histogram of R.  Runs on the context's stream behind every queued render and synchronises.  It changes nothing: not
+ * the segment, its predicate, the slots, the island table, the distance field, the mesh, the segment view, the accumulator,
+ * the frame state, VxCounters, VxParams, or what any other *_stats call reports.  Its buffers -- the 64-bit bin array and
+ * 24 B of partial moments per brick -- are allocated by the first call and freed with the volume.  out may be NULL.
+ * VX_ERR_INVALID for a NULL ctx; VX_ERR_NO_VOLUME before an upload; VX_ERR_INVALID, naming the field and changing nothing,
+ * before vx_set_params, for NULL params, a source or rule outside its enum, SEGMENT with no current segment, SLOT with
+ * slot >= VX_SEGMENT_SLOTS or an empty slot, a box that is empty or outside the volume, LINEAR with bins outside
+ * 1 .. VX_HIST_MAX_BINS, lo or hi not finite, lo >= hi or a range too narrow for a finite inv, KEY with key_bits outside
+ * 1 .. VX_HIST_MAX_KEY_BITS, prefix_bits > 31, prefix_bits + key_bits > 32 or prefix >= 2^prefix_bits, ncounts that is not
+ * the number of bins, NULL counts, and moments that is not 0 or 1.  group: member 0. */
+int vx_histogram(VxContext* ctx, const VxHistogramParams* params, uint64_t* counts, uint32_t ncounts, VxHistogramResult* out);
+/* The last vx_histogram: launches = the kernels it launched (1, or 2 with moments), kernel_ms[0 .. 1] = the HIP-event times
+ * of the histogram pass and of the moments' reduction; all 0 before the first call.  Any pointer may be NULL.  group:
+ * member 0. */
+int vx_histogram_stats(VxContext* ctx, uint32_t* launches, double* kernel_ms);
+
 /* ---- segment views (DESIGN.md section 2 "Segment views"): show only, or hide, the current segment.  With a view other than
  * OFF the covered calls -- vx_render_frame / vx_render_frames in VX_MODE_DVR, _DVR_PHONG, _MIP and _MINIP, and vx_isosurface
  * (hence picking) -- sample the masked volume: every decoded voxel v(i) reads +0.0f where it is hidden (ONLY: i is not in the

@@ -20,3 +20,5 @@ from .mesh import Mesh  # noqa: F401,E402
 from .renderer import Segment, SegmentComparison, SegmentDistance  # noqa: F401,E402
 from ._abi import VxDistanceParams, VxDistanceResult, VxMarginParams  # noqa: F401,E402
 from ._abi import VxCombineParams, VxCompareParams, VxCompareResult  # noqa: F401,E402
+from .renderer import Histogram  # noqa: F401,E402
+from ._abi import VxHistogramParams, VxHistogramResult  # noqa: F401,E402

@@ -63,6 +63,8 @@ VxMarginParams = struct_from_header("volxel_hip.h", "VxMarginParams")
 VxCombineParams = struct_from_header("volxel_hip.h", "VxCombineParams")
 VxCompareParams = struct_from_header("volxel_hip.h", "VxCompareParams")
 VxCompareResult = struct_from_header("volxel_hip.h", "VxCompareResult")
+VxHistogramParams = struct_from_header("volxel_hip.h", "VxHistogramParams")
+VxHistogramResult = struct_from_header("volxel_hip.h", "VxHistogramResult")
 VxMeshParams = struct_from_header("volxel_hip.h", "VxMeshParams")
 VxMeshResult = struct_from_header("volxel_hip.h", "VxMeshResult")
 
@@ -84,6 +86,9 @@ DISTANCE_SIDES = {"outside": 0, "inside": 1}            # enum VxDistanceSide
 MARGIN_OPS = {"grow": 0, "shrink": 1, "open": 2, "close": 3}   # enum VxMarginOp
 SEGMENT_SLOTS = 32                                     # VX_SEGMENT_SLOTS
 COMBINE_OPS = {"union": 0, "intersect": 1, "subtract": 2, "xor": 3, "invert": 4}   # enum VxCombineOp
+HIST_SOURCES = {"volume": 0, "segment": 1, "slot": 2}   # enum VxHistSource
+HIST_LINEAR, HIST_KEY = range(2)                       # enum VxHistRule
+HIST_MAX_BINS, HIST_MAX_KEY_BITS = 4096, 12            # VX_HIST_MAX_BINS, VX_HIST_MAX_KEY_BITS
 MESH_DENSITY, MESH_SEGMENT = range(2)                  # enum VxMeshSource
 
 
@@ -193,6 +198,8 @@ def load_library():
         "vx_segment_combine": ([vp, P(VxCombineParams), P(VxSegmentResult)], i32),
         "vx_segment_compare": ([vp, P(VxCompareParams), P(VxCompareResult)], i32),
         "vx_segments_labelmap": ([vp, P(u32), u32, vp, u64, P(u64)], i32),
+        "vx_histogram": ([vp, P(VxHistogramParams), vp, u32, P(VxHistogramResult)], i32),
+        "vx_histogram_stats": ([vp, P(u32), P(C.c_double)], i32),
         "vx_mesh_extract": ([vp, P(VxMeshParams), P(VxMeshResult)], i32),
         "vx_mesh_read": ([vp, vp, vp, vp], i32),
         "vx_mesh_stats": ([vp, P(u32), P(C.c_double)], i32),

@@ -89,6 +89,58 @@ def slots(ss) -> tuple:
     return t
 
 
+def hist_source(source) -> tuple:
+    """(VxHistSource, slot) of a histogram's `source`: "volume", "segment" or an int slot of the segment store"""
+    if isinstance(source, str) and source in ("volume", "segment"):
+        return _abi.HIST_SOURCES[source], 0
+    message = f"source must be 'volume', 'segment' or an integer slot 0 .. {_abi.SEGMENT_SLOTS - 1}, not {source!r}"
+    if isinstance(source, str):
+        raise ValueError(message)
+    return _abi.HIST_SOURCES["slot"], integer(source, 0, _abi.SEGMENT_SLOTS - 1, message, whole_floats=False)
+
+
+def hist_bins(bins) -> int:
+    return integer(bins, 1, _abi.HIST_MAX_BINS, f"bins must be an integer 1 .. {_abi.HIST_MAX_BINS}, not {bins!r}",
+                   whole_floats=False)
+
+
+def hist_range(r) -> tuple:
+    """(lo, hi) of a histogram's range as float32 with lo < hi, both finite"""
+    try:
+        lo, hi = (np.float32(a) for a in r)
+    except (TypeError, ValueError):
+        raise ValueError(f"range must be (lo, hi), two finite numbers with lo < hi, not {r!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"range must be (lo, hi), two finite numbers with lo < hi, not {r!r}")
+    return float(lo), float(hi)
+
+
+def ranks(ks, n=None) -> tuple:
+    """the 0-based ranks of an order statistic: a sequence of integers, 0 .. n - 1 once the size n of the region is known"""
+    try:
+        t = tuple(ks)
+    except TypeError:
+        raise ValueError(f"ranks must be a sequence of integers, not {ks!r}") from None
+    if n is None:
+        return tuple(integer(k, 0, 2 ** 64 - 1, f"ranks: every entry must be an integer >= 0, not {k!r}", whole_floats=False)
+                     for k in t)
+    return tuple(integer(k, 0, n - 1, f"ranks: every entry must be an integer 0 .. {n - 1} (the region has {n} voxels), "
+                                      f"not {k!r}", whole_floats=False) for k in t)
+
+
+def percentiles(q) -> tuple:
+    """(values, scalar) of a percentile argument: a number or a sequence of numbers in [0, 100]"""
+    scalar = isinstance(q, (int, float, np.integer, np.floating)) and not isinstance(q, bool)
+    try:
+        t = (q,) if scalar else tuple(q)
+    except TypeError:
+        t = (None,)
+    for a in t:
+        if isinstance(a, bool) or not isinstance(a, (int, float, np.integer, np.floating)) or not 0.0 <= float(a) <= 100.0:
+            raise ValueError(f"q must be a number or a sequence of numbers in [0, 100], not {q!r}")
+    return tuple(float(a) for a in t), scalar
+
+
 def box(b, ext):
     """(lo, hi) of box = ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices inside the index extent; None: all of it"""
     if b is None:

@@ -1,6 +1,6 @@
 // vx_api_segment.hip -- the segment unit of the host layer (units: DESIGN.md section 4.1): the segment chain -- seeded region
 // growing, the mask's read-back, slice overlay and view, the edits, the threshold, the islands, the distance field with the
-// millimetre margins, and the segment store with its set operations, comparison and label map.
+// millimetre margins, the segment store with its set operations, comparison and label map, and the histograms.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include "vx_islands.hpp"
 #include "vx_distance.hpp"
 #include "vx_segstore.hpp"
+#include "vx_histogram.hpp"
 #include "vx_context.hpp"
 
 using namespace vx;
@@ -333,6 +334,20 @@ static int launch_max_over(VxContext* c, const uint64_t* over, DstPartial* parti
   VX_HIP(c, hipGetLastError());
   c->dst_launches += 2;
   return VX_OK;
+}
+
+// ---- histograms (vx_histogram; kernels in vx_histogram.hpp) ------------------------------------------------------------------------
+// hst_bins for the resident layout and the two wave-uniform choices of the call
+static void launch_hst_bins(VxContext* c, const HstParams& h, bool moments, uint32_t blocks) {
+  const VxParams& p = c->params;
+  with_layout(slice_layout(c), [&](auto lay) {
+    with_bool(h.mask != nullptr, [&](auto masked) {
+      with_bool(moments, [&](auto mom) {
+        hipLaunchKernelGGL((hst_bins<decltype(lay)::value, decltype(masked)::value, decltype(mom)::value>), dim3(blocks), dim3(256), 0,
+                           c->stream, c->vol.dv, p.volume_density_scale, p.volume_inv_maj, h);
+      });
+    });
+  });
 }
 
 static int ensure_islands(VxContext* c) {
@@ -1078,6 +1093,116 @@ int vx_segments_labelmap(VxContext* c, const uint32_t* slots, uint32_t n, uint8_
   VX_HIP(c, hipMemcpyAsync(&over, multi, sizeof over, hipMemcpyDeviceToHost, c->stream));
   VX_HIP(c, hipStreamSynchronize(c->stream));
   if (overlaps) *overlaps = over;
+  return VX_OK;
+}
+
+// ---- histograms ------------------------------------------------------------------------------------------------------------------
+int vx_histogram(VxContext* c, const VxHistogramParams* hp, uint64_t* counts, uint32_t ncounts, VxHistogramResult* out) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_histogram(c->members[0], hp, counts, ncounts, out));
+  VX_DEV(c);
+  VoxelBox box;
+  if (int rc = check_ready(c, "vx_histogram", hp, "params")) return rc;
+  if (hp->source < VX_HIST_VOLUME || hp->source > VX_HIST_SLOT)
+    VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: source = %d is not a VxHistSource (0 .. 2)", hp->source);
+  if (hp->source == VX_HIST_SEGMENT)
+    if (int rc = check_current(c, "vx_histogram")) return rc;
+  if (hp->source == VX_HIST_SLOT)
+    if (int rc = check_slot(c, "vx_histogram", hp->slot, true)) return rc;
+  if (int rc = check_box(c, "vx_histogram", hp->box_lo, hp->box_hi, &box)) return rc;
+  HstParams h{};
+  if (hp->rule == VX_HIST_LINEAR) {
+    if (hp->bins < 1u || hp->bins > VX_HIST_MAX_BINS)
+      VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: bins = %u outside 1 .. %u", hp->bins, VX_HIST_MAX_BINS);
+    if (!std::isfinite(hp->lo)) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: lo is not finite");
+    if (!std::isfinite(hp->hi)) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: hi is not finite");
+    if (!(hp->lo < hp->hi)) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: lo = %g >= hi = %g", (double)hp->lo, (double)hp->hi);
+    // (this unit is built without contraction: one rounded difference, one rounded quotient)
+    const float width = hp->hi - hp->lo;
+    h.inv = (float)hp->bins / width;
+    if (!std::isfinite(h.inv))
+      VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: hi - lo = %g is too narrow for bins = %u (bins / (hi - lo) is not finite)", (double)width,
+              hp->bins);
+    h.bins = hp->bins;
+    h.lo = hp->lo;
+    h.hi = hp->hi;
+  } else if (hp->rule == VX_HIST_KEY) {
+    const uint32_t p = hp->prefix_bits, b = hp->key_bits;
+    if (b < 1u || b > VX_HIST_MAX_KEY_BITS) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: key_bits = %u outside 1 .. %u", b, VX_HIST_MAX_KEY_BITS);
+    if (p > 31u) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: prefix_bits = %u outside 0 .. 31", p);
+    if (p + b > 32u) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: prefix_bits + key_bits = %u + %u is more than the 32 bits of a key", p, b);
+    if ((uint64_t)hp->prefix >= (1ull << p))
+      VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: prefix = %u does not fit prefix_bits = %u", hp->prefix, p);
+    h.bins = 1u << b;
+    h.prefix = hp->prefix;
+    h.top_shift = 32u - p;
+    h.bin_shift = 32u - p - b;
+    h.bin_mask = h.bins - 1u;
+  } else {
+    VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: rule = %d is not a VxHistRule (0 .. 1)", hp->rule);
+  }
+  h.rule = hp->rule;
+  if (hp->moments != 0 && hp->moments != 1) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: moments = %d is not 0 or 1", hp->moments);
+  if (!counts) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: counts is NULL");
+  if (ncounts != h.bins) VX_FAIL(c, VX_ERR_INVALID, "vx_histogram: ncounts = %u, the call has %u bins", ncounts, h.bins);
+  const bool moments = hp->moments != 0;
+  // the brick grid from the volume itself: VX_HIST_VOLUME needs no segment, so SegDev may not be there
+  const uint32_t* bc = c->vol.dv.bc;
+  h.nb = bc[0] * bc[1] * bc[2];
+  for (int a = 0; a < 3; ++a) {
+    h.bc[a] = bc[a];
+    h.box_lo[a] = box.lo[a];
+    h.box_hi[a] = box.hi[a];
+  }
+  h.mask = hp->source == VX_HIST_SEGMENT ? c->vol.seg.seg : hp->source == VX_HIST_SLOT ? c->vol.slots[hp->slot].p : nullptr;
+  // (every earlier call has completed: each one synchronises)
+  if (int rc = c->vol.hst_bins.ensure(c, VX_HIST_MAX_BINS + 2u)) return rc;
+  if (moments)
+    if (int rc = c->vol.hst_partials.ensure(c, (size_t)h.nb + 1u)) return rc;
+  h.out = c->vol.hst_bins;
+  h.partial = moments ? c->vol.hst_partials.p : nullptr;
+  const size_t slots = (size_t)h.bins + 2u;
+  VX_HIP(c, hipMemsetAsync(h.out, 0, slots * sizeof(unsigned long long), c->stream));
+  if (int rc = c->hst_timer.mark(c, 0)) return rc;
+  launch_hst_bins(c, h, moments, std::min<uint32_t>((h.nb + 3u) / 4u, HST_MAX_BLOCKS));
+  VX_HIP(c, hipGetLastError());
+  if (int rc = c->hst_timer.mark(c, 1)) return rc;
+  if (moments) {
+    hipLaunchKernelGGL(hst_moments, dim3(1), dim3(1024), 0, c->stream, (const HstPartial*)h.partial, h.nb, h.partial + h.nb);
+    VX_HIP(c, hipGetLastError());
+  }
+  if (int rc = c->hst_timer.mark(c, 2)) return rc;
+  std::vector<unsigned long long> got(slots);
+  HstPartial total{};
+  VX_HIP(c, hipMemcpyAsync(got.data(), h.out, slots * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  if (moments) VX_HIP(c, hipMemcpyAsync(&total, h.partial + h.nb, sizeof total, hipMemcpyDeviceToHost, c->stream));
+  VX_HIP(c, hipStreamSynchronize(c->stream));
+  if (int rc = c->hst_timer.read(c)) return rc;
+  if (!moments) c->hst_timer.ms[1] = 0.0;   // (two events back to back still measure a few microseconds)
+  c->hst_launches = moments ? 2u : 1u;
+  VxHistogramResult r{};
+  r.below = got[h.bins];
+  r.above = got[h.bins + 1u];
+  r.count = r.below + r.above;
+  for (uint32_t k = 0; k < h.bins; ++k) {
+    counts[k] = got[k];
+    r.count += got[k];
+  }
+  if (moments && r.count) {
+    r.d_sum = total.sum;
+    r.d_sum2 = total.sum2;
+    r.d_min = total.mn;
+    r.d_max = total.mx;
+  }
+  if (out) *out = r;
+  return VX_OK;
+}
+
+int vx_histogram_stats(VxContext* c, uint32_t* launches, double* kernel_ms) {
+  if (!c) return VX_ERR_INVALID;
+  if (is_group(c)) return on_member0(c, vx_histogram_stats(c->members[0], launches, kernel_ms));
+  if (launches) *launches = c->hst_launches;
+  if (kernel_ms) std::copy_n(c->hst_timer.ms, 2, kernel_ms);
   return VX_OK;
 }
 

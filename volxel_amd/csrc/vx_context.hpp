@@ -136,6 +136,10 @@ struct VxContext : VxCore {   // (device, the stream the launches go to, the las
     DevBuf<SstCount> sst_partials;
     DevBuf<uint8_t> sst_labels;
     DevBuf<unsigned long long> sst_overlaps;
+    // histograms (vx_histogram): the 64-bit bins with `below` and `above` behind them, and the bricks' partial moments with
+    // their total behind them (24 B per brick), allocated by the first call that needs them
+    DevBuf<unsigned long long> hst_bins;
+    DevBuf<HstPartial> hst_partials;
     // meshes (vx_mesh_extract): one allocation for the inside words, the active words, the counts and their scans
     // (ensure_mesh); the vertex / cell buffers (3 values per vertex, grown together) and the triangles grow to the largest mesh
     DevBuf<void> mesh_alloc;
@@ -283,6 +287,9 @@ struct VxContext : VxCore {   // (device, the stream the launches go to, the las
   StageTimer<9> dst_timer;
   double dst_ms[4] = {};
   uint32_t dst_launches = 0;
+  // histograms: the histogram pass and the moments' reduction of the last vx_histogram
+  StageTimer<2> hst_timer;
+  uint32_t hst_launches = 0;
 };
 
 namespace vx __attribute__((visibility("hidden"))) {

@@ -174,6 +174,26 @@ struct SstSlots {
   uint32_t n;
 };
 
+// ---- the histogram (vx_histogram.hpp)
+// a brick's share of the moments: the float64 sums of d and d * d and the extreme densities over its voxels of the region
+// (0, 0, +inf, -inf for a brick without one); hst_moments reduces the bricks into element 0 of its output
+struct HstPartial {
+  double sum, sum2;
+  float mn, mx;
+};
+// what a launch of hst_bins needs beside the volume: the region, the bin rule and where the bins go
+struct HstParams {
+  const uint64_t* mask;      // nb * 8 words of the segment or the slot; nullptr: every voxel of the box
+  uint32_t box_lo[3], box_hi[3];
+  uint32_t bc[3], nb;
+  int32_t rule;              // VxHistRule
+  uint32_t bins;             // the number of bins, B or 2^b; `below` is counted at index bins, `above` at bins + 1
+  float lo, hi, inv;         // LINEAR
+  uint32_t prefix, top_shift, bin_shift, bin_mask;   // KEY: top_shift = 32 - p (32: no prefix), bin_shift = 32 - p - b
+  unsigned long long* out;   // bins + 2 counters, zeroed before the launch
+  HstPartial* partial;       // nb (MOMENTS only)
+};
+
 // ---- the islands (vx_islands.hpp)
 // one island while the table is built (device side; the host ranks the rows)
 struct IslRow {

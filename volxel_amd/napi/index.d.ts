@@ -15,6 +15,9 @@ export type SliceSpec = {
 };
 export declare const VolxelRenderMode: { default: 0; no_dda: 1; raymarch: 2; dvr: 3; dvr_phong: 4; mip: 5; minip: 6 };
 export declare function generateTransferFunction(colors: ColorStop[], generatedSteps?: number): { data: Float32Array; length: number };
+/** the region of a histogram call: source 'volume' (default: every voxel), 'segment' (the current segment) or a slot 0 .. 31 of the
+ *  segment store; box = [[x0, y0, z0], [x1, y1, z1]], inclusive voxel indices, null (default): the whole index extent */
+export type HistogramOptions = { source?: 'volume' | 'segment' | number; box?: [[number, number, number], [number, number, number]] | null };
 export declare class Camera {
   pos: number[]; view: number[];
   /** [build] null: the reference's perspective camera (scene.ts:65-72); a number: orthographic, image spans +-orthoHalfHeight world units vertically */
@@ -145,6 +148,26 @@ export declare class Volxel3DDicomRenderer {
   /** the uint8 label map over (z, y, x) of the listed slots, first listed first, and the number of voxels more than one of
    *  them holds (vx_segments_labelmap) */
   segmentsLabelmap(slots: number[] | Uint32Array): { labels: Uint8Array; overlaps: number };
+  /** the density histogram and the moments of a region on the GPU (vx_histogram): `bins` (1 .. 4096) bins of equal width over
+   *  range = [lo, hi] (default [0, 1]; a density equal to hi lands in the last bin); source 'volume' (default), 'segment' or a
+   *  slot of the segment store; box inclusive, null: the whole index extent.  edges are nominal (lo + k (hi - lo) / bins); below /
+   *  above count the voxels outside the range; the moments run over the whole region; mean and std (population) are NaN when it
+   *  is empty.  Changes nothing. */
+  histogram(opts?: HistogramOptions & { bins?: number; range?: [number, number] }):
+    { counts: Float64Array; edges: Float64Array; below: number; above: number; count: number; dMin: number; dMax: number;
+      dSum: number; dSum2: number; mean: number; std: number };
+  /** the exact k-th smallest densities of a region (0-based ranks), the bits a sort would give: a radix select in three
+   *  histogram passes per rank, the first shared by all ranks; an empty region is refused */
+  densityOrderStatistic(ranks: number[] | Uint32Array, opts?: HistogramOptions): Float32Array;
+  /** the exact q-th percentile(s), q in [0, 100]: the order statistic of rank floor(q / 100 * (n - 1)) (NumPy's method 'lower');
+   *  a number for a number, a Float32Array for a sequence */
+  densityPercentile(q: number, opts?: HistogramOptions): number;
+  densityPercentile(q: number[] | Float64Array, opts?: HistogramOptions): Float32Array;
+  /** Otsu's threshold from one histogram(opts): the upper edge of the bin that maximises the between-class variance, so that
+   *  threshold(t) is the bright class; fewer than two non-empty bins are refused */
+  otsuThreshold(opts?: HistogramOptions & { bins?: number; range?: [number, number] }): number;
+  /** the last histogram pass: kernels launched and the times of the histogram and of the moments' reduction */
+  histogramStats(): { launches: number; histogramMs: number; momentsMs: number };
   /** install a packed mask (the layout of segmentMask()) as the current segment (vx_segment_write_mask) */
   setSegmentMask(bits: Uint8Array):
     { count: number; bboxLo: [number, number, number]; bboxHi: [number, number, number]; dMin: number; dMax: number; dSum: number;

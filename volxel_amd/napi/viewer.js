@@ -14,6 +14,7 @@ const path = require('path');
 const native = require('./volxel_napi.node');
 const nativeDistance = require('./volxel_napi_distance.node');   // the addon of the distance calls, on native's handles
 const nativeSegments = require('./volxel_napi_segments.node');   // the addon of the segment store, on native's handles
+const nativeHistogram = require('./volxel_napi_histogram.node'); // the addon of the histograms, on native's handles
 
 const RenderMode = Object.freeze({ default: 0, no_dda: 1, raymarch: 2, dvr: 3, dvr_phong: 4, mip: 5, minip: 6 });
 const LOW_RES_DURATION = 5; // viewer.ts:132
@@ -43,6 +44,9 @@ const SLICE_LAYOUT = parseParamsLayout('VxSliceParams', native.sizeofSliceParams
 const ISO_LAYOUT = parseParamsLayout('VxIsoParams', native.sizeofIsoParams());
 const SEGMENT_LAYOUT = parseParamsLayout('VxSegmentParams', native.sizeofSegmentParams());
 const MESH_LAYOUT = parseParamsLayout('VxMeshParams', native.sizeofMeshParams());
+const HISTOGRAM_LAYOUT = parseParamsLayout('VxHistogramParams', nativeHistogram.sizeofHistogramParams());
+const HIST_MAX_BINS = 4096;                               // VX_HIST_MAX_BINS
+const RADIX_PASSES = [[0, 11], [11, 11], [22, 10]];       // [prefix_bits, key_bits] of the three passes of the radix select
 const MESH_SPACES = ['voxel', 'grid', 'world'];
 const SEGMENT_VIEWS = ['off', 'only', 'hide'];   // VX_SEGVIEW_OFF, _ONLY, _HIDE
 const SEGMENT_EDIT_OPS = ['dilate', 'erode', 'open', 'close', 'fill_holes'];   // VxSegmentEditOp, in order
@@ -331,6 +335,58 @@ function checkSlots(who, ss) {
   t.forEach(s => checkSlot(who, s, 'slots: every entry'));
   if (new Set(t).size !== t.length) throw new Error(`${who}: slots must not list a slot twice, as ${t} does`);
   return Uint32Array.from(t);
+}
+/** [VxHistSource, slot] of a histogram's source: 'volume', 'segment' or an integer slot of the segment store */
+function checkHistSource(who, source) {
+  if (source === 'volume') return [0, 0];
+  if (source === 'segment') return [1, 0];
+  if (!Number.isInteger(source) || source < 0 || source >= SEGMENT_SLOTS)
+    throw new Error(`${who}: source must be 'volume', 'segment' or an integer slot 0 .. ${SEGMENT_SLOTS - 1}, not ${source}`);
+  return [2, source];
+}
+function checkHistBins(who, bins) {
+  if (!Number.isInteger(bins) || bins < 1 || bins > HIST_MAX_BINS) throw new Error(`${who}: bins must be an integer 1 .. ${HIST_MAX_BINS}, not ${bins}`);
+  return bins;
+}
+/** [lo, hi] of a histogram's range as float32 with lo < hi, both finite */
+function checkHistRange(who, r) {
+  const t = Array.isArray(r) && r.length === 2 ? r.map(x => (typeof x === 'number' ? Math.fround(x) : NaN)) : [NaN, NaN];
+  if (!Number.isFinite(t[0]) || !Number.isFinite(t[1]) || !(t[0] < t[1])) throw new Error(`${who}: range must be (lo, hi), two finite numbers with lo < hi, not ${r}`);
+  return t;
+}
+/** the 0-based ranks of an order statistic over n values: a sequence of integers 0 .. n - 1 */
+function checkRanks(who, ks, n = null) {
+  const t = Array.isArray(ks) || ArrayBuffer.isView(ks) ? Array.from(ks) : null;
+  if (t === null) throw new Error(`${who}: ranks must be a sequence of integers, not ${ks}`);
+  for (const k of t) {
+    if (n === null && (!Number.isInteger(k) || k < 0)) throw new Error(`${who}: ranks: every entry must be an integer >= 0, not ${k}`);
+    if (n !== null && (!Number.isInteger(k) || k < 0 || k >= n)) throw new Error(`${who}: ranks: every entry must be an integer 0 .. ${n - 1} (the region has ${n} voxels), not ${k}`);
+  }
+  return t;
+}
+/** [values, scalar] of a percentile argument: a number or a sequence of numbers in [0, 100] */
+function checkPercentiles(who, q) {
+  const scalar = typeof q === 'number';
+  const t = scalar ? [q] : (Array.isArray(q) || ArrayBuffer.isView(q) ? Array.from(q) : [null]);
+  if (!t.every(x => typeof x === 'number' && x >= 0 && x <= 100)) throw new Error(`${who}: q must be a number or a sequence of numbers in [0, 100], not ${q}`);
+  return [t, scalar];
+}
+/** Otsu's split of a histogram: the k in 0 .. B - 2 that maximises w0 w1 (mu0 - mu1)^2 over the classes bins 0 .. k and
+ *  k + 1 .. B - 1, bin centres standing for the bins, ties to the lowest k; -1 with fewer than two non-empty bins (the Python
+ *  host's otsu_split, operation for operation) */
+function otsuSplit(counts, edges) {
+  const B = counts.length;
+  if (counts.reduce((n, c) => n + (c !== 0 ? 1 : 0), 0) < 2) return -1;
+  const cw = new Float64Array(B), cs = new Float64Array(B);
+  let w = 0, s = 0;
+  for (let k = 0; k < B; ++k) { w += counts[k]; s += counts[k] * ((edges[k] + edges[k + 1]) / 2); cw[k] = w; cs[k] = s; }
+  let best = 0, bestVar = -1;
+  for (let k = 0; k + 1 < B; ++k) {
+    const w0 = cw[k], w1 = cw[B - 1] - w0, s0 = cs[k], s1 = cs[B - 1] - s0;
+    const v = w0 > 0 && w1 > 0 ? w0 * w1 * (s0 / w0 - s1 / w1) ** 2 : 0;
+    if (v > bestVar) { best = k; bestVar = v; }
+  }
+  return best;
 }
 /** the VxSliceParams block of a slice spec with reduce = mean, no display and the window [0, 1] */
 function sliceParams(who, origin, du, dv, dn, [W, H], slabSamples) {
@@ -828,6 +884,96 @@ class Volxel3DDicomRenderer {
     const overlaps = nativeSegments.segmentsLabelmap(this.ctx, list, labels);
     return { labels, overlaps };
   }
+  _histogramParams(who, source, box) {
+    const e = this.sliceExtent();
+    const [src, slot] = checkHistSource(who, source), [blo, bhi] = checkBox(who, box, e);
+    const p = new ParamsBlock(HISTOGRAM_LAYOUT);
+    p.set('source', src); p.set('slot', slot); p.set('box_lo', blo); p.set('box_hi', bhi);
+    return p;
+  }
+  /** vx_histogram, LINEAR (DESIGN.md section 2 "Histograms"): the density histogram and the moments of a region on the GPU.
+   *  opts: { bins = 256 (1 .. 4096), range = [0, 1] ([lo, hi]; a density equal to hi lands in the last bin), source = 'volume' |
+   *  'segment' | an integer slot of the segment store, box = null ([[x0, y0, z0], [x1, y1, z1]], inclusive; null: the whole
+   *  index extent) } -> { counts: Float64Array, edges: Float64Array (nominal: lo + k (hi - lo) / bins), below, above, count,
+   *  dMin, dMax, dSum, dSum2, mean, std (population; NaN when the region is empty) }.  Binds the current uniforms first; changes
+   *  nothing. */
+  histogram({ bins = 256, range = [0, 1], source = 'volume', box = null } = {}) {
+    const p = this._histogramParams('histogram', source, box);
+    const B = checkHistBins('histogram', bins), [lo, hi] = checkHistRange('histogram', range);
+    p.set('rule', 0); p.set('bins', B); p.set('lo', lo); p.set('hi', hi); p.set('moments', 1);
+    this.bindUniforms();
+    const counts = new Float64Array(B);
+    const r = nativeHistogram.histogram(this.ctx, p.buffer, counts);
+    r.counts = counts;
+    r.edges = Float64Array.from({ length: B + 1 }, (_, k) => lo + k * (hi - lo) / B);
+    const n = r.count;
+    r.mean = n ? r.dSum / n : NaN;
+    r.std = n ? Math.sqrt(Math.max(0, (r.dSum2 - r.dSum * r.dSum / n) / n)) : NaN;
+    return r;
+  }
+  /** the radix select behind densityOrderStatistic and densityPercentile: ranksOf(n) -> the ranks, given the size of the region
+   *  from the first pass, which all ranks share (as they share every later pass with the same prefix) */
+  _orderStatistics(p, ranksOf) {
+    p.set('rule', 1); p.set('moments', 0);
+    this.bindUniforms();
+    const seen = new Map();
+    const countsOf = (pb, b, prefix) => {
+      const key = `${pb}:${prefix}`;
+      if (!seen.has(key)) {
+        p.set('prefix', prefix); p.set('prefix_bits', pb); p.set('key_bits', b);
+        const counts = new Float64Array(2 ** b);
+        const r = nativeHistogram.histogram(this.ctx, p.buffer, counts);
+        seen.set(key, { counts, below: r.below, count: r.count });
+      }
+      return seen.get(key);
+    };
+    const n = countsOf(RADIX_PASSES[0][0], RADIX_PASSES[0][1], 0).count;
+    const f = new DataView(new ArrayBuffer(4));
+    return ranksOf(n).map((k) => {
+      let prefix = 0;
+      for (const [pb, b] of RADIX_PASSES) {
+        // `below` holds every key under a smaller prefix: rank k of the region is rank k - below among this pass's bins
+        const h = countsOf(pb, b, prefix);
+        let j = 0;
+        for (let cum = h.counts[0]; cum <= k - h.below; cum += h.counts[++j]);
+        prefix = prefix * 2 ** b + j;
+      }
+      f.setUint32(0, prefix >= 2147483648 ? prefix - 2147483648 : 4294967295 - prefix);
+      return f.getFloat32(0);
+    });
+  }
+  /** the exact k-th smallest densities (0-based ranks) of a region, as float32 values: three vx_histogram KEY passes (11, 11
+   *  and 10 bits) per rank, the first shared by all ranks.  opts: { source, box } as histogram().  An empty region is refused. */
+  densityOrderStatistic(ranks, { source = 'volume', box = null } = {}) {
+    const p = this._histogramParams('densityOrderStatistic', source, box);
+    checkRanks('densityOrderStatistic', ranks);
+    return Float32Array.from(this._orderStatistics(p, (n) => {
+      if (n === 0) throw new Error('densityOrderStatistic: the region is empty');
+      return checkRanks('densityOrderStatistic', ranks, n);
+    }));
+  }
+  /** the q-th percentile(s) of the densities of a region, exact: the order statistic of rank floor(q / 100 * (n - 1)), NumPy's
+   *  method 'lower'.  q: a number (returns a number) or a sequence of numbers (returns a Float32Array) in [0, 100]. */
+  densityPercentile(q, { source = 'volume', box = null } = {}) {
+    const [qs, scalar] = checkPercentiles('densityPercentile', q);
+    const p = this._histogramParams('densityPercentile', source, box);
+    const v = this._orderStatistics(p, (n) => {
+      if (n === 0) throw new Error('densityPercentile: the region is empty');
+      return qs.map(a => Math.floor(a / 100 * (n - 1)));
+    });
+    return scalar ? v[0] : Float32Array.from(v);
+  }
+  /** Otsu's threshold of a region from one histogram(opts): the upper edge of the bin that maximises the between-class
+   *  variance, so that threshold(t) is the bright class; voxels below or above the range are ignored; fewer than two non-empty
+   *  bins are refused */
+  otsuThreshold(opts = {}) {
+    const h = this.histogram(opts);
+    const k = otsuSplit(h.counts, h.edges);
+    if (k < 0) throw new Error(`otsuThreshold: fewer than two non-empty bins among the ${h.counts.length}: nothing to split`);
+    return h.edges[k + 1];
+  }
+  /** the last histogram pass: kernels launched and the times of the histogram and of the moments' reduction */
+  histogramStats() { return nativeHistogram.histogramStats(this.ctx); }
   /** vx_segment_write_mask, the inverse of segmentMask(): installs a Uint8Array of X*Y*Z/8 bytes (one bit per voxel of
    *  (z, y, x) in C order, LSB first) as the current segment -> what segment() returns, for that mask */
   setSegmentMask(bits) {

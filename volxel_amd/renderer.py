@@ -33,7 +33,7 @@ from .settings import ViewerSettings, verify_settings
 from .transfer import default_transfer_function, generate_transfer_function
 from ._errors import VolxelError
 from .renderer_mesh import MeshMixin
-from .renderer_segment import (IslandSegment, Islands, Segment, SegmentComparison, SegmentDistance,  # noqa: F401
+from .renderer_segment import (Histogram, IslandSegment, Islands, Segment, SegmentComparison, SegmentDistance,  # noqa: F401
                                SegmentMixin)
 from .renderer_view import ViewMixin
 

@@ -111,6 +111,44 @@ class SegmentComparison:
     argmax_ba: tuple | None = None
 
 
+@dataclass(frozen=True)
+class Histogram:
+    """What Volxel3DRenderer.histogram returns (vx_histogram, LINEAR): `counts` (uint64, one per bin), `edges` (float64,
+    lo + k (hi - lo) / B for k = 0 .. B: nominal -- the fp32 rule of include/volxel_hip.h decides the bin), `below` / `above`
+    (voxels with d < lo / d > hi), `count` = below + above + counts.sum() = the voxels of the region, and over ALL of the
+    region: d_min, d_max, d_sum and d_sum2 (float64 sums of d and d * d), mean and std (population,
+    sqrt(max(0, (d_sum2 - d_sum^2 / n) / n)) in float64); mean and std are nan when the region is empty."""
+    counts: np.ndarray
+    edges: np.ndarray
+    below: int
+    above: int
+    count: int
+    d_min: float
+    d_max: float
+    d_sum: float
+    d_sum2: float
+    mean: float
+    std: float
+
+
+def otsu_split(counts, edges) -> int:
+    """Otsu's split of a histogram, on the host in float64: the k in 0 .. B - 2 that maximises the between-class variance
+    w0 w1 (mu0 - mu1)^2 of the classes bins 0 .. k and k + 1 .. B - 1, the bin centres (edges[k] + edges[k + 1]) / 2 standing for
+    the bins; ties go to the lowest k; a split that leaves a class empty has variance 0.  -1 with fewer than two non-empty
+    bins.  (Running sums in bin order, so that the JS host's loop gives the same bits.)"""
+    c = np.asarray(counts, dtype=np.float64)
+    if int(np.count_nonzero(c)) < 2:
+        return -1
+    e = np.asarray(edges, dtype=np.float64)
+    cw, cs = np.cumsum(c), np.cumsum(c * ((e[:-1] + e[1:]) / 2))
+    w0, s0 = cw[:-1], cs[:-1]
+    w1, s1 = cw[-1] - w0, cs[-1] - s0
+    ok = (w0 > 0) & (w1 > 0)
+    var = np.zeros_like(w0)
+    var[ok] = w0[ok] * w1[ok] * (s0[ok] / w0[ok] - s1[ok] / w1[ok]) ** 2
+    return int(np.argmax(var))   # (argmax returns the first of equal maxima)
+
+
 class SegmentMixin:
     def segment(self, seed, lo: float, hi: float = math.inf, connectivity: int = 6, box=None, max_rounds: int = 0):
         """Seeded region growing (vx_segment, DESIGN.md section 2 "Segmentation"): the connected component of
@@ -402,6 +440,111 @@ class SegmentMixin:
         self._check(self._lib.vx_segments_labelmap(self._ctx, (C.c_uint32 * len(t))(*t), len(t), out.ctypes.data, out.size,
                                                    C.byref(over)))
         return out, int(over.value)
+
+    # ---- histograms (DESIGN.md section 2 "Histograms") --------------------------------------------------------------------------
+    def _histogram_params(self, name: str, source, box):
+        ext = self._index_extent(name)
+        q = _abi.VxHistogramParams()
+        q.source, q.slot = _checks.hist_source(source)
+        q.box_lo[:], q.box_hi[:] = _checks.box(box, ext)
+        return q
+
+    def _histogram_call(self, q, nbins: int):
+        """vx_histogram under the uniforms already bound: (counts, VxHistogramResult)"""
+        counts = np.zeros(nbins, dtype=np.uint64)
+        res = _abi.VxHistogramResult()
+        self._check(self._lib.vx_histogram(self._ctx, C.byref(q), counts.ctypes.data, nbins, C.byref(res)))
+        return counts, res
+
+    def histogram(self, bins: int = 256, range=(0.0, 1.0), source="volume", box=None) -> Histogram:
+        """The density histogram and the moments of a region on the GPU (vx_histogram, DESIGN.md section 2 "Histograms").
+        source: "volume" (every voxel), "segment" (the current segment) or an int (that slot of the segment store); box =
+        ((x0, y0, z0), (x1, y1, z1)), inclusive voxel indices, or None for the whole index extent (padding included).  `bins`
+        bins of equal width over range = (lo, hi), the span the transfer function covers by default; a density equal to hi
+        lands in the last bin, as in np.histogram.  Binds the current uniforms first; changes nothing.  Returns a `Histogram`."""
+        q = self._histogram_params("histogram", source, box)
+        q.rule, q.bins = _abi.HIST_LINEAR, _checks.hist_bins(bins)
+        q.lo, q.hi = _checks.hist_range(range)
+        q.moments = 1
+        self.bind_uniforms()
+        counts, res = self._histogram_call(q, q.bins)
+        n, s1, s2 = int(res.count), float(res.d_sum), float(res.d_sum2)
+        lo, hi = float(q.lo), float(q.hi)
+        edges = lo + np.arange(q.bins + 1, dtype=np.float64) * (hi - lo) / q.bins
+        return Histogram(counts=counts, edges=edges, below=int(res.below), above=int(res.above), count=n, d_min=float(res.d_min),
+                         d_max=float(res.d_max), d_sum=s1, d_sum2=s2, mean=s1 / n if n else math.nan,
+                         std=math.sqrt(max(0.0, (s2 - s1 * s1 / n) / n)) if n else math.nan)
+
+    RADIX_PASSES = ((0, 11), (11, 11), (22, 10))   # (prefix_bits, key_bits) of the three passes of the select
+
+    def _order_statistics(self, q, ranks_of):
+        """the radix select behind density_order_statistic and density_percentile: ranks_of(n) -> the ranks, given the size of
+        the region from the first pass, which all ranks share (as they share every later pass with the same prefix)"""
+        q.rule, q.moments = _abi.HIST_KEY, 0
+        self.bind_uniforms()
+        seen = {}
+
+        def counts_of(p, b, prefix):
+            if (p, prefix) not in seen:
+                q.prefix, q.prefix_bits, q.key_bits = prefix, p, b
+                seen[(p, prefix)] = self._histogram_call(q, 1 << b)
+            return seen[(p, prefix)]
+
+        n = int(counts_of(*self.RADIX_PASSES[0], 0)[1].count)
+        out = []
+        for k in ranks_of(n):
+            prefix = 0
+            for p, b in self.RADIX_PASSES:
+                # `below` holds every key under a smaller prefix: rank k of the region is rank k - below among this pass's bins
+                c, res = counts_of(p, b, prefix)
+                j = int(np.searchsorted(np.cumsum(c.astype(np.int64)), k - int(res.below), side="right"))
+                prefix = (prefix << b) | j
+            key = prefix
+            u = key & 0x7fffffff if key & 0x80000000 else ~key & 0xffffffff
+            out.append(np.array([u], dtype=np.uint32).view(np.float32)[0])
+        return np.array(out, dtype=np.float32), n
+
+    def density_order_statistic(self, ranks, source="volume", box=None) -> np.ndarray:
+        """The exact k-th smallest densities (0-based ranks) of a region, as float32: the bits of np.sort(d[R])[k].  A radix
+        select over the order-preserving key of the densities in three histogram passes (11, 11 and 10 bits) per rank; the
+        first pass is shared by all ranks.  source and box as for histogram().  An empty region is refused."""
+        q = self._histogram_params("density_order_statistic", source, box)
+        _checks.ranks(ranks)
+
+        def ranks_of(n):
+            if n == 0:
+                raise VolxelError("density_order_statistic: the region is empty")
+            return _checks.ranks(ranks, n)
+        return self._order_statistics(q, ranks_of)[0]
+
+    def density_percentile(self, q, source="volume", box=None):
+        """The q-th percentile(s) of the densities of a region, exact: the order statistic of rank floor(q / 100 * (n - 1))
+        computed in float64 -- np.percentile(d[R], q, method="lower").  q: a number (returns a float) or a sequence of numbers
+        (returns a float32 array) in [0, 100].  source and box as for histogram().  An empty region is refused."""
+        qs, scalar = _checks.percentiles(q)
+        hp = self._histogram_params("density_percentile", source, box)
+
+        def ranks_of(n):
+            if n == 0:
+                raise VolxelError("density_percentile: the region is empty")
+            return [int(math.floor(a / 100.0 * (n - 1))) for a in qs]
+        v = self._order_statistics(hp, ranks_of)[0]
+        return float(v[0]) if scalar else v
+
+    def otsu_threshold(self, bins: int = 256, range=(0.0, 1.0), source="volume", box=None) -> float:
+        """Otsu's threshold of a region from one histogram() of `bins` bins over `range`: the upper edge of the bin k that
+        maximises the between-class variance (otsu_split), so that threshold(t) is the bright class.  Voxels below or above
+        the range are ignored.  Fewer than two non-empty bins are refused."""
+        h = self.histogram(bins, range, source, box)
+        k = otsu_split(h.counts, h.edges)
+        if k < 0:
+            raise VolxelError(f"otsu_threshold: fewer than two non-empty bins among the {h.counts.size} over {tuple(range)!r}: "
+                             "nothing to split")
+        return float(h.edges[k + 1])
+
+    def histogram_stats(self):
+        """(launches, histogram_ms, moments_ms) of the last histogram pass (vx_histogram_stats)"""
+        return self._out("vx_histogram_stats", C.c_uint32, C.c_double * 2)
 
     SEGMENT_VIEWS = ("off", "only", "hide")   # VX_SEGVIEW_OFF, _ONLY, _HIDE
 
